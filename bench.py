@@ -37,6 +37,7 @@ HBM_PEAK_GBS = 8000.0
 F16_ACT_MB = 253.7 / 2      # the f32 path's algorithmic activation bytes per frame, stored as halves
 F16_WEIGHT_MB = 24.0 / 2    # weights once per batch
 PROFILE_TAG = "r04"         # profiles/<tag>_*: the round's committed rocprofv3 summaries (tools/profile_bench.sh)
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the most it writes
 
 
 def kernel_source_hash() -> str:
@@ -494,6 +495,9 @@ def main() -> None:
                                                                "event timing loops, one repeat - so that every kernel's calls = frames x its launches per frame")
     ap.add_argument("--no-secondary", action="store_true", help="skip the VGG16-FCN (train/fcn_bbox) measurements reported under 'secondary'")
     ap.add_argument("--devices", default="", help="GPU id of every rank, comma separated (default 0..N-1; rehearsals on a one-GPU box: 0,0 with --no-train)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the LAST timed step of `value`'s region returned to its caller "
+                    "(rank 0's output blobs, NCHW float32) as DIR/<blob>.npy; the frame and the weights are seeded, so the same arguments give "
+                    "the same inputs in every run and two builds can be compared blob for blob")
     args = ap.parse_args()
 
     from fcn_object_detector_amd import dp      # (touches no GPU)
@@ -520,7 +524,9 @@ def main() -> None:
 
     msg = proto.parse_text(models.googlenet_detectnet_deploy(args.batch, 448, 448, 4))
     spec = NetSpec(msg, "TEST")
-    spec.infer()
+    shapes = spec.infer()
+    if args.dump_outputs and sum(4 * int(np.prod(shapes[k])) for k in spec.output_blobs()) > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs writes at most %d MB; the output blobs of --batch %d are larger" % (DUMP_MAX_BYTES >> 20, args.batch))
     params = fill_params(spec, seed=1234)
     depth = max(args.in_flight, 1)
     # (one frame in flight - the profiled single-stream mode - has no reason to cap the tiles' LDS footprint: the cap buys co-residency of
@@ -584,6 +590,18 @@ def main() -> None:
             cp.barrier()
             rep_s.append(cp.max(t_local))
     t_max = float(np.median(rep_s)) if rep_s else t_k
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # step K-1 of the last repeat ran on this replica (run_io / run_resident deal the steps round-robin) and nothing has touched it since:
+        # config 2's region has left its outputs in the replica's host arrays (what forward_end() returned), the kernels-only region in HBM
+        last = pipe.engines[(args.steps - 1) % depth]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {}
+        for k in last.outputs:
+            a = np.ascontiguousarray(last.read_blob(k), dtype=np.float32)
+            np.save(os.path.join(args.dump_outputs, k.replace("/", "_") + ".npy"), a)
+            dumped[k] = list(a.shape)
 
     out = None
     if rank == 0:
@@ -697,6 +715,8 @@ def main() -> None:
                                       "note": "conv FLOPs of a frame x frames/s over the wall clock of the K steps with frames in flight - kernels only "
                                               "(`value_kernels_only`) and, under `with_copies`, config 2's region (`value`); kernels of different frames overlap, so "
                                               "per-kernel durations are not comparable: profiles/%s_bench_inflight_kernel_stats.csv holds the kernel trace of this mode" % PROFILE_TAG}}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "step": "the last of the %d timed steps of the last repeat" % args.steps}
         if world == 1 and not args.no_cpu_baseline:
             base, ref_blobs = cpu_baseline(msg, params, x)
             out["cpu_baseline"] = base

@@ -1,13 +1,14 @@
 """Host logic: prototxt reader, shape rules, fillers, caffemodel codec (CPU only)."""
+import json
 import os
 
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from fcn_object_detector_amd import models, proto
 from fcn_object_detector_amd.netspec import NetSpec, bilinear_kernel, fill_params, pool_out
-
-REF = "/root/reference"
+from graph_signature import layer_digests, signature
 
 
 def test_text_format_features():
@@ -88,94 +89,54 @@ def test_caffemodel_roundtrip(tmp_path):
     assert it == 7 and np.array_equal(hist[0], layers[0][2][1])
 
 
-def _signature(msg, phase):
-    spec = NetSpec(msg, phase)
-    out = []
-    for l in spec.layers:
-        d = [l.type, l.name, tuple(l.bottoms), tuple(l.tops), tuple(l.lr_mult), tuple(l.decay_mult), tuple(l.loss_weight)]
-        for key in ("convolution_param", "pooling_param", "lrn_param", "power_param", "dropout_param", "eltwise_param"):
-            p = l.msg.get(key)
-            if p is None:
-                continue
-            items = []
-            for k, v in sorted(p.fields.items()):
-                vals = []
-                for x in v:
-                    if isinstance(x, proto.Msg):
-                        vals.append(tuple((kk, tuple(vv)) for kk, vv in sorted(x.fields.items()) if kk != "std"))
-                    else:
-                        vals.append(float(x) if isinstance(x, (int, float)) and not isinstance(x, bool) else x)
-                items.append((k, tuple(vals)))
-            d.append((key, tuple(items)))
-        out.append(tuple(d))
-    return spec.input_shapes, out
+def _assert_reference_graph(rel, text, n_layers):
+    """The builder's text must parse to the graph of the reference's file `rel`: same input shapes, same layers in the same
+    order (tests/golden/reference_graphs.json: one digest per layer, tests/golden/make_reference_graphs.py wrote them)."""
+    with open(os.path.join(GOLDEN, "reference_graphs.json")) as f:
+        ref = json.load(f)[rel]
+    inputs, layers = signature(proto.parse_text(text), ref["phase"])
+    assert {k: list(v) for k, v in inputs.items()} == ref["inputs"]
+    assert len(ref["layers"]) == len(layers) == n_layers
+    for i, (x, y) in enumerate(zip(ref["layers"], layer_digests(layers))):
+        assert x == y, "layer %d differs from the reference's: %r" % (i, layers[i])
+    return inputs
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_builder_equals_reference_deploy():
     """models.googlenet_detectnet_deploy() must parse to the same graph as the reference's models/deploy.prototxt."""
-    a = _signature(proto.parse_file(os.path.join(REF, "models/deploy.prototxt")), "TEST")
-    b = _signature(proto.parse_text(models.googlenet_detectnet_deploy()), "TEST")
-    assert a[0] == b[0]
-    assert len(a[1]) == len(b[1]) == 142
-    for x, y in zip(a[1], b[1]):
-        assert x == y
+    _assert_reference_graph("models/deploy.prototxt", models.googlenet_detectnet_deploy(), 142)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_builder_equals_reference_fcn_bbox_train():
     """models.vgg16_fcn_bbox_train() must parse to the same graph as the reference's train/fcn_bbox/train_val.prototxt."""
-    ref = proto.parse_file(os.path.join(REF, "train/fcn_bbox/train_val.prototxt"))
-    param_str = [l for l in ref.getall("layer") if l.get("type") == "Python"][0].get("python_param").get("param_str")
-    a = _signature(ref, "TRAIN")
-    b = _signature(proto.parse_text(models.vgg16_fcn_bbox_train("data_argumentation_layer", "DataArgumentationLayer", param_str)), "TRAIN")
-    assert len(a[1]) == len(b[1]) == 50
-    for x, y in zip(a[1], b[1]):
-        assert x == y
+    _assert_reference_graph("train/fcn_bbox/train_val.prototxt",
+                            models.vgg16_fcn_bbox_train("data_argumentation_layer", "DataArgumentationLayer", "unused"), 50)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_builder_equals_reference_bounding_box_train():
-    ref = proto.parse_file(os.path.join(REF, "train/bounding_box/train_val.prototxt"))
-    param_str = [l for l in ref.getall("layer") if l.get("type") == "Python"][0].get("python_param").get("param_str")
-    a = _signature(ref, "TRAIN")
-    b = _signature(proto.parse_text(models.vgg16_bounding_box_train("data_argumentation_layer", "DataArgumentationLayer", param_str)), "TRAIN")
-    assert len(a[1]) == len(b[1]) == 42
-    for x, y in zip(a[1], b[1]):
-        assert x == y
+    _assert_reference_graph("train/bounding_box/train_val.prototxt",
+                            models.vgg16_bounding_box_train("data_argumentation_layer", "DataArgumentationLayer", "unused"), 42)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_builder_equals_reference_models_train_val():
     """The LMDB-fronted training nets as shipped: models/train_val.prototxt and models/train_val2.prototxt (3-class heads)."""
     for rel, kw in (("models/train_val.prototxt", {}), ("models/train_val2.prototxt", {"head_classes": 3})):
-        a = _signature(proto.parse_file(os.path.join(REF, rel)), "TRAIN")
-        b = _signature(proto.parse_text(models.googlenet_detectnet_train_lmdb(**kw)), "TRAIN")
-        assert len(a[1]) == len(b[1]) == 152
-        for x, y in zip(a[1], b[1]):
-            assert x == y
+        _assert_reference_graph(rel, models.googlenet_detectnet_train_lmdb(**kw), 152)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
 def test_builder_equals_reference_bounding_box_deploy():
-    a = _signature(proto.parse_file(os.path.join(REF, "train/bounding_box/deploy.prototxt")), "TEST")
-    b = _signature(proto.parse_text(models.vgg16_bounding_box_deploy()), "TEST")
-    assert a[0] == b[0] == {"data": (10, 3, 448, 448)} and len(a[1]) == len(b[1]) == 51
-    for x, y in zip(a[1], b[1]):
-        assert x == y
+    inputs = _assert_reference_graph("train/bounding_box/deploy.prototxt", models.vgg16_bounding_box_deploy(), 51)
+    assert inputs == {"data": (10, 3, 448, 448)}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
-def test_all_reference_prototxts_parse():
-    for rel in ("models/deploy.prototxt", "models/train_val.prototxt", "models/train_val2.prototxt",
-                "train/fcn_bbox/train_val.prototxt", "train/bounding_box/train_val.prototxt",
-                "train/bounding_box/deploy.prototxt", "train/semantic_segmentation/train_val.prototxt",
-                "train/fcn_bbox/solver.prototxt", "train/bounding_box/solver.prototxt"):
-        m = proto.parse_file(os.path.join(REF, rel))
-        assert m.fields
-    s = proto.parse_file(os.path.join(REF, "train/bounding_box/solver.prototxt"))
+def test_solver_fields_and_fcn_bbox_train_shapes():
+    """Solver fields come out typed (the ones train/bounding_box/solver.prototxt sets), and shape inference over the graph of
+    the reference's train/fcn_bbox/train_val.prototxt (the builder's text: test_builder_equals_reference_fcn_bbox_train holds
+    it to that file layer by layer).  That every definition of the reference parses is checked where the files are:
+    tests/golden/make_reference_graphs.py."""
+    s = proto.parse_text('net: "train_val.prototxt"\nsolver_type: ADAM\nbase_lr: 1e-4\nlr_policy: "step"\nstepsize: 10000\n')
     assert s.get("solver_type") == "ADAM" and s.get("base_lr") == 1e-4 and s.get("stepsize") == 10000
-    tv = NetSpec(proto.parse_file(os.path.join(REF, "train/fcn_bbox/train_val.prototxt")), "TRAIN")
+    tv = NetSpec(proto.parse_text(models.vgg16_fcn_bbox_train("data_argumentation_layer", "DataArgumentationLayer", "unused")), "TRAIN")
     shapes = tv.infer({"data": (2, 3, 288, 288), "label": (2, 1, 288, 288), "bbox-label": (2, 44, 36, 36),
                        "size-block": (2, 44, 36, 36), "obj-block": (2, 44, 36, 36), "coverage-block": (2, 44, 36, 36)})
     assert shapes["upscore_pool5_bbox"] == (2, 44, 36, 36) and shapes["upscore_pool3"] == (2, 11, 288, 288)
