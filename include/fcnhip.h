@@ -142,7 +142,11 @@ int  fcn_conv2d_num_configs(void);
  * FCN_E_UNSUPPORTED when one is requested for a group it does not take (a tuner walking all configurations skips those):
  *   fcn_conv2d_first_layer_config()      conv_first7_kernel: a single 7x7 / stride 2 / pad 3 problem on 4-channel pixels with
  *                                        33..64 output channels (conv1/7x7_s2 of models/deploy.prototxt), ReLU optional; the
- *                                        built-in heuristic picks it for the problems it takes;
+ *                                        built-in heuristic picks it for the problems it takes.  It multiplies channels 0..2 ONLY:
+ *                                        channel 3 of every pixel of x and of every filter tap of w is the pad channel of a
+ *                                        3-channel image and is NOT READ (it may hold anything; a net with four real input
+ *                                        channels must keep this kernel off - FCN_CONV_FIRST7=0 - or give its first layer
+ *                                        another width).  tests/test_gpu_guarded.py::test_first_layer_kernel pins it;
  *   fcn_conv2d_first_layer_config() + 1  conv_dot1x1_kernel: groups of 1x1 / stride 1 / unpadded float32 problems over the same
  *                                        pixels with at most 32 output channels in all, counted in slices of 8 per problem (the
  *                                        detection heads cvg/classifier + bbox/regressor); ReLU and FCN_CONV_SIGMOID2 allowed. */
