@@ -1071,6 +1071,321 @@ __global__ __launch_bounds__(512) void pool_lrn5_conv1x1_f16_lds_kernel(const _F
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The remaining layers of the VGG16 nets on half blobs: AVE pooling, depthwise deconvolution, Eltwise, Softmax and the
+// channel copy of Dropout / Concat / Slice.  Same idiom as above - a lane owns 8 channels of a pixel (one 16-byte access),
+// arithmetic in f32, one round-to-nearest-even at the store - but C is the REAL channel count (11, 44, 3, 12 channels live in
+// 16- / 48-half strides): the lane of the last, partial group still loads its whole 16-byte segment (the pad channels of x
+// stay inside their own vector element and are never stored) and stores its C % 8 channels one by one, so exactly channels
+// y_coffset .. y_coffset + C - 1 of an output pixel are written.  out_f32 kernels store float32 (an output blob of the net).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cvt8(const h8_t v, float f[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+}
+
+// 8 consecutive channels at yp (halves, or floats when OUT_F32); nvalid < 8 in the last group of a C that is no multiple of 8
+template <bool OUT_F32>
+__device__ __forceinline__ void store8(void* y, size_t at, const float f[8], int nvalid) {
+    if (OUT_F32) {
+        float* yp = reinterpret_cast<float*>(y) + at;
+        if (nvalid >= 8) {
+            st4(yp, make_float4(f[0], f[1], f[2], f[3]));
+            st4(yp + 4, make_float4(f[4], f[5], f[6], f[7]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 7; ++e)
+                if (e < nvalid) yp[e] = f[e];
+        }
+    } else {
+        _Float16* yp = reinterpret_cast<_Float16*>(y) + at;
+        if (nvalid >= 8) {
+            h8_t o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (_Float16)f[e];
+            *reinterpret_cast<h8_t*>(yp) = o;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 7; ++e)
+                if (e < nvalid) yp[e] = (_Float16)f[e];
+        }
+    }
+}
+
+// AVE pooling, small windows: one lane per (output pixel, 8 channels), the window summed in raster order
+__global__ __launch_bounds__(256) void avepool_f16_kernel(const _Float16* __restrict__ x, _Float16* __restrict__ y, int N, int H, int W, int C,
+                                                          int x_cstride, int k, int stride, int pad, int OH, int OW, int y_cstride,
+                                                          int y_coffset) {
+    const int cg = (C + 7) / 8;
+    const long long total = (long long)N * OH * OW * cg;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int g = (int)(t % cg);
+        long long pix = t / cg;
+        const int ox = (int)(pix % OW);
+        pix /= OW;
+        const int oy = (int)(pix % OH);
+        const int n = (int)(pix / OH);
+        int hs = oy * stride - pad, ws = ox * stride - pad;
+        int he = min(hs + k, H + pad), we = min(ws + k, W + pad);
+        const float area = (float)((he - hs) * (we - ws));
+        hs = max(hs, 0);
+        ws = max(ws, 0);
+        he = min(he, H);
+        we = min(we, W);
+        const _Float16* xb = x + (size_t)n * H * W * x_cstride + g * 8;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int iy = hs; iy < he; ++iy)
+            for (int ix = ws; ix < we; ++ix) {
+                float f[8];
+                cvt8(*(const h8_t*)(xb + ((size_t)iy * W + ix) * x_cstride), f);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += f[e];
+            }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] /= area;
+        store8<false>(y, ((size_t)(n * OH + oy) * OW + ox) * y_cstride + y_coffset + g * 8, acc, C - g * 8);
+    }
+}
+
+// AVE pooling, large windows (the pyramid levels of train/bounding_box/deploy.prototxt: 56 / 28 / 14 / 8 on a 56 x 56 x 512 blob):
+// a workgroup owns ONE output pixel x GPB channel groups (GPB * 16 bytes = up to one 128-byte line of every input pixel), its
+// NT / GPB pixel lanes stride over the window in raster order and the partial sums meet in LDS in a fixed binary tree - the
+// order of the additions depends on the geometry alone, so two runs give the same bits (no atomics).
+template <int NT>
+__global__ __launch_bounds__(NT) void avepool_f16_coop_kernel(const _Float16* __restrict__ x, _Float16* __restrict__ y, int H, int W, int C,
+                                                              int x_cstride, int k, int stride, int pad, int OH, int OW, int y_cstride,
+                                                              int y_coffset, int gpb_log2) {
+    __shared__ float red[8 * NT];
+    const int tid = threadIdx.x;
+    const int gpb = 1 << gpb_log2, lanes = NT >> gpb_log2;
+    const int gl = tid & (gpb - 1), p = tid >> gpb_log2;
+    const int cg = (C + 7) / 8;
+    const int g = blockIdx.x * gpb + gl;
+    const int ox = blockIdx.y % OW, oy = blockIdx.y / OW, n = blockIdx.z;
+    int hs = oy * stride - pad, ws = ox * stride - pad;
+    int he = min(hs + k, H + pad), we = min(ws + k, W + pad);
+    const float area = (float)((he - hs) * (we - ws));
+    hs = max(hs, 0);
+    ws = max(ws, 0);
+    he = min(he, H);
+    we = min(we, W);
+    const int ww = we - ws, count = (he - hs) * ww;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (g < cg) {
+        const _Float16* xb = x + (size_t)n * H * W * x_cstride + g * 8;
+#pragma unroll 4
+        for (int i = p; i < count; i += lanes) {
+            const int iy = hs + i / ww, ix = ws + i % ww;
+            float f[8];
+            cvt8(*(const h8_t*)(xb + ((size_t)iy * W + ix) * x_cstride), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += f[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[e * NT + tid] = acc[e];
+    __syncthreads();
+    for (int s = lanes >> 1; s >= 1; s >>= 1) {
+        if (p < s) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                acc[e] += red[e * NT + tid + (s << gpb_log2)];
+                red[e * NT + tid] = acc[e];
+            }
+        }
+        __syncthreads();
+    }
+    if (p == 0 && g < cg) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] /= area;
+        store8<false>(y, ((size_t)(n * OH + oy) * OW + ox) * y_cstride + y_coffset + g * 8, acc, C - g * 8);
+    }
+}
+
+// Depthwise transposed convolution on half activations (gather form, see deconv_dw_kernel): float32 taps [C][k][k] and bias.
+// A lane owns 8 channels of the output pixels (oy0 + j * stride, ox), j < rows: they share the phase (oy + pad) % stride and
+// (ox + pad) % stride, so the at most T x T taps that reach them - 8 channels each - are loaded once, in front of the row loop.
+// Consecutive lanes hold consecutive channel groups, then consecutive ox: a wave stores whole runs of output pixels.
+// T = ceil(k / stride) taps per axis; T = 0 is the form for any geometry, whose taps are read inside the loops.
+template <int T, bool OUT_F32>
+__global__ __launch_bounds__(256) void deconv_dw_f16_kernel(const _Float16* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, void* __restrict__ y, int N, int H, int W, int C,
+                                                            int x_cstride, int k, int stride, int pad, int OH, int OW, int y_cstride,
+                                                            int y_coffset, int rows) {
+    const int cg = (C + 7) / 8;
+    const int chunks = (OH + stride * rows - 1) / (stride * rows);      // row chunks per phase
+    const long long total = (long long)N * chunks * stride * OW * cg;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int g = (int)(t % cg);
+        long long rest = t / cg;
+        const int ox = (int)(rest % OW);
+        rest /= OW;
+        const int oy0 = (int)(rest % stride);
+        rest /= stride;
+        const int chunk = (int)(rest % chunks);
+        const int n = (int)(rest / chunks);
+        const int nvalid = C - g * 8;
+        const int pr = (oy0 + pad) % stride, pq = (ox + pad) % stride;
+        const int bx = (ox + pad) / stride;
+        float b8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) b8[e] = bias && e < nvalid ? bias[g * 8 + e] : 0.f;
+        const float* wg = w + (size_t)g * 8 * k * k;
+        const _Float16* xb = x + (size_t)n * H * W * x_cstride + g * 8;
+        float wt[T > 0 ? T * T : 1][8];
+        if (T > 0) {
+#pragma unroll
+            for (int a = 0; a < T; ++a)
+#pragma unroll
+                for (int b = 0; b < T; ++b) {
+                    const int r = pr + a * stride, q = pq + b * stride;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) wt[a * T + b][e] = r < k && q < k && e < nvalid ? wg[(size_t)e * k * k + r * k + q] : 0.f;
+                }
+        }
+        for (int j = 0; j < rows; ++j) {
+            const int oy = oy0 + (chunk * rows + j) * stride;
+            if (oy >= OH) break;
+            const int by = (oy + pad) / stride;
+            float acc[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = b8[e];
+            if (T > 0) {
+#pragma unroll
+                for (int a = 0; a < T; ++a) {
+                    const int iy = by - a;
+                    if (pr + a * stride >= k || iy < 0 || iy >= H) continue;
+#pragma unroll
+                    for (int b = 0; b < T; ++b) {
+                        const int ix = bx - b;
+                        if (pq + b * stride >= k || ix < 0 || ix >= W) continue;
+                        float f[8];
+                        cvt8(*(const h8_t*)(xb + ((size_t)iy * W + ix) * x_cstride), f);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) acc[e] += f[e] * wt[a * T + b][e];
+                    }
+                }
+            } else {
+                for (int r = pr, iy = by; r < k; r += stride, --iy) {
+                    if (iy < 0 || iy >= H) continue;
+                    for (int q = pq, ix = bx; q < k; q += stride, --ix) {
+                        if (ix < 0 || ix >= W) continue;
+                        float f[8];
+                        cvt8(*(const h8_t*)(xb + ((size_t)iy * W + ix) * x_cstride), f);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e)
+                            if (e < nvalid) acc[e] += f[e] * wg[(size_t)e * k * k + r * k + q];
+                    }
+                }
+            }
+            store8<OUT_F32>(y, ((size_t)(n * OH + oy) * OW + ox) * y_cstride + y_coffset + g * 8, acc, nvalid);
+        }
+    }
+}
+
+// y = a (op) b over whole strided rows of halves; y may be a (the engine chains a three-input Eltwise through its top)
+__global__ __launch_bounds__(256) void eltwise_f16_kernel(const _Float16* a, const _Float16* b, _Float16* y, size_t groups, int op, float ca,
+                                                          float cb) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += stride) {
+        float u[8], v[8];
+        cvt8(*(const h8_t*)(a + i * 8), u);
+        cvt8(*(const h8_t*)(b + i * 8), v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) u[e] = op == FCN_ELT_PROD ? u[e] * v[e] : op == FCN_ELT_SUM ? ca * u[e] + cb * v[e] : fmaxf(u[e], v[e]);
+        store8<false>(y, i * 8, u, 8);
+    }
+}
+
+// Softmax over the C channels of a pixel, one lane per pixel.  G > 0: C <= 8 G, the pixel is read once (G 16-byte loads) and its
+// exponentials stay in registers - one exp per element; G = 0 (C > 32) walks the pixel three times.  Pad channels of x are masked
+// out of the maximum and the sum, those of y are not written.
+template <int G, bool OUT_F32>
+__global__ __launch_bounds__(256) void softmax_f16_kernel(const _Float16* __restrict__ x, void* __restrict__ y, long long pixels, int C,
+                                                          int x_cstride, int y_cstride) {
+    for (long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x; pix < pixels; pix += (long long)gridDim.x * blockDim.x) {
+        const _Float16* xp = x + (size_t)pix * x_cstride;
+        if (G > 0) {
+            float v[G > 0 ? G : 1][8];
+            float m = -INFINITY;
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g * 8 < C) {
+                    cvt8(*(const h8_t*)(xp + g * 8), v[g]);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (g * 8 + e < C) m = fmaxf(m, v[g][e]);
+                }
+            float sum = 0.f;
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (g * 8 + e < C) {
+                        v[g][e] = expf(v[g][e] - m);
+                        sum += v[g][e];
+                    }
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g * 8 < C) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[g][e] /= sum;
+                    store8<OUT_F32>(y, (size_t)pix * y_cstride + g * 8, v[g], C - g * 8);
+                }
+        } else {
+            const int cg = (C + 7) / 8;
+            float m = -INFINITY;
+            for (int g = 0; g < cg; ++g) {
+                float f[8];
+                cvt8(*(const h8_t*)(xp + g * 8), f);
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (g * 8 + e < C) m = fmaxf(m, f[e]);
+            }
+            float sum = 0.f;
+            for (int g = 0; g < cg; ++g) {
+                float f[8];
+                cvt8(*(const h8_t*)(xp + g * 8), f);
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (g * 8 + e < C) sum += expf(f[e] - m);
+            }
+            for (int g = 0; g < cg; ++g) {
+                float f[8];
+                cvt8(*(const h8_t*)(xp + g * 8), f);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) f[e] = expf(f[e] - m) / sum;
+                store8<OUT_F32>(y, (size_t)pix * y_cstride + g * 8, f, C - g * 8);
+            }
+        }
+    }
+}
+
+// Channel copy between strided half buffers.  VEC: both offsets are multiples of 8 - whole groups move as 16 bytes, the last
+// C % 8 channels one by one; otherwise one lane per element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void copy_channels_f16_kernel(const _Float16* __restrict__ src, _Float16* __restrict__ dst, long long pixels,
+                                                                int C, int src_cstride, int src_coffset, int dst_cstride, int dst_coffset) {
+    const int per = VEC ? (C + 7) / 8 : C;
+    const long long total = pixels * per;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(t % per);
+        const long long pix = t / per;
+        const _Float16* sp = src + (size_t)pix * src_cstride + src_coffset;
+        _Float16* dp = dst + (size_t)pix * dst_cstride + dst_coffset;
+        if (!VEC) {
+            dp[c] = sp[c];
+        } else if (c * 8 + 8 <= C) {
+            *(h8_t*)(dp + c * 8) = *(const h8_t*)(sp + c * 8);
+        } else {
+            const h8_t v = *(const h8_t*)(sp + c * 8);
+#pragma unroll
+            for (int e = 0; e < 7; ++e)
+                if (c * 8 + e < C) dp[c * 8 + e] = v[e];
+        }
+    }
+}
+
 extern "C" {
 
 int fcn_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int dst_cstride, int dst_coffset, float shift,
@@ -1449,6 +1764,121 @@ int fcn_lrn_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, in
         hipLaunchKernelGGL(lrn5_f16_kernel<false>, lgrid, dim3(256), 0, as_stream(s), reinterpret_cast<const _Float16*>(x), reinterpret_cast<_Float16*>(y),
                            (long long)pixels, C, x_cstride, y_cstride, alpha / (float)local_size, beta, k);
     FCN_LAUNCH_CHECK("lrn_f16");
+    return 0;
+}
+
+// ---- the VGG16 nets' other layers on half blobs (see the kernels: C is the real channel count, strides / offsets count whole
+// 16-byte segments).  Every check precedes the first HIP call.
+int fcn_avepool_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int k, int stride, int pad, int OH, int OW,
+                        int y_cstride, int y_coffset, fcn_stream_t s) {
+    FCN_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && pad < k && OH > 0 && OW > 0, FCN_E_ARG,
+                "avepool_f16: bad args");
+    FCN_REQUIRE((OH - 1) * stride - pad < H && (OW - 1) * stride - pad < W, FCN_E_ARG, "avepool_f16: last window starts outside the image");
+    FCN_REQUIRE(x_cstride >= C && y_coffset >= 0 && y_cstride >= y_coffset + C, FCN_E_ARG, "avepool_f16: channel slice out of range");
+    FCN_REQUIRE(x_cstride % 8 == 0 && y_cstride % 8 == 0 && y_coffset % 8 == 0 && aligned16(x) && aligned16(y), FCN_E_ALIGN,
+                "avepool_f16: strides / offset must be multiples of 8 halves, pointers of 16 bytes");
+    const _Float16* xh = reinterpret_cast<const _Float16*>(x);
+    _Float16* yh = reinterpret_cast<_Float16*>(y);
+    const int cg = cdiv(C, 8);
+    const int kk = min(k, H + pad) * min(k, W + pad);      // pixels of the largest window
+    if (kk >= 64 && (long long)OH * OW <= 65535 && N <= 65535) {
+        int gl2 = 0;                                       // channel groups per workgroup: up to 8 (one 128-byte line per input pixel)
+        while (gl2 < 3 && (1 << gl2) < cg) ++gl2;
+        const dim3 grid(cdiv(cg, 1 << gl2), OH * OW, N);
+        if (kk >= 1024)
+            hipLaunchKernelGGL(avepool_f16_coop_kernel<1024>, grid, dim3(1024), 0, as_stream(s), xh, yh, H, W, C, x_cstride, k, stride, pad, OH, OW,
+                               y_cstride, y_coffset, gl2);
+        else
+            hipLaunchKernelGGL(avepool_f16_coop_kernel<256>, grid, dim3(256), 0, as_stream(s), xh, yh, H, W, C, x_cstride, k, stride, pad, OH, OW,
+                               y_cstride, y_coffset, gl2);
+    } else {
+        hipLaunchKernelGGL(avepool_f16_kernel, dim3(stream_grid((long long)N * OH * OW * cg, 256)), dim3(256), 0, as_stream(s), xh, yh, N, H, W, C,
+                           x_cstride, k, stride, pad, OH, OW, y_cstride, y_coffset);
+    }
+    FCN_LAUNCH_CHECK("avepool_f16");
+    return 0;
+}
+
+int fcn_deconv_depthwise_fwd_f16(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C, int x_cstride, int k,
+                                 int stride, int pad, int OH, int OW, int y_cstride, int y_coffset, int out_f32, fcn_stream_t s) {
+    FCN_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && OH > 0 && OW > 0, FCN_E_ARG,
+                "deconv_depthwise_f16: bad args");
+    FCN_REQUIRE(OH == stride * (H - 1) + k - 2 * pad && OW == stride * (W - 1) + k - 2 * pad, FCN_E_ARG,
+                "deconv_depthwise_f16: OH/OW do not match s(H-1)+k-2p");
+    FCN_REQUIRE(x_cstride >= C && y_coffset >= 0 && y_cstride >= y_coffset + C, FCN_E_ARG, "deconv_depthwise_f16: channel slice out of range");
+    const int yseg = out_f32 ? 4 : 8;
+    FCN_REQUIRE(x_cstride % 8 == 0 && y_cstride % yseg == 0 && y_coffset % yseg == 0 && aligned16(x) && aligned16(y), FCN_E_ALIGN,
+                "deconv_depthwise_f16: strides / offset must be whole 16-byte segments (8 halves, 4 floats), pointers 16-byte aligned");
+    const _Float16* xh = reinterpret_cast<const _Float16*>(x);
+    const int cg = cdiv(C, 8);
+    // rows of one phase per lane: as many as leave 512 workgroups (the taps of a lane are loaded once per launch of its rows)
+    int rows = 8;
+    while (rows > 1 && (long long)N * cdiv(OH, stride * rows) * stride * OW * cg < 512 * 256) rows >>= 1;
+    const dim3 grid(stream_grid((long long)N * cdiv(OH, stride * rows) * stride * OW * cg, 256));
+    const int taps = cdiv(k, stride);
+#define FCN_DECONV_F16(T, F)                                                                                                                   \
+    hipLaunchKernelGGL((deconv_dw_f16_kernel<T, F>), grid, dim3(256), 0, as_stream(s), xh, w, bias, y, N, H, W, C, x_cstride, k, stride, pad, \
+                       OH, OW, y_cstride, y_coffset, rows)
+    if (taps == 1 && out_f32) FCN_DECONV_F16(1, true);
+    else if (taps == 1) FCN_DECONV_F16(1, false);
+    else if (taps == 2 && out_f32) FCN_DECONV_F16(2, true);
+    else if (taps == 2) FCN_DECONV_F16(2, false);
+    else if (out_f32) FCN_DECONV_F16(0, true);
+    else FCN_DECONV_F16(0, false);
+#undef FCN_DECONV_F16
+    FCN_LAUNCH_CHECK("deconv_depthwise_f16");
+    return 0;
+}
+
+int fcn_eltwise_fwd_f16(const void* a, const void* b, void* y, size_t count, int op, float ca, float cb, fcn_stream_t s) {
+    FCN_REQUIRE(a && b && y && count > 0, FCN_E_ARG, "eltwise_f16: null pointer or empty range");
+    FCN_REQUIRE(op == FCN_ELT_PROD || op == FCN_ELT_SUM || op == FCN_ELT_MAX, FCN_E_ARG, "eltwise_f16: bad op %d", op);
+    FCN_REQUIRE(count % 8 == 0 && aligned16(a) && aligned16(b) && aligned16(y), FCN_E_ALIGN,
+                "eltwise_f16: count must be a multiple of 8 halves, pointers of 16 bytes");
+    hipLaunchKernelGGL(eltwise_f16_kernel, dim3(stream_grid((long long)(count / 8), 256)), dim3(256), 0, as_stream(s),
+                       reinterpret_cast<const _Float16*>(a), reinterpret_cast<const _Float16*>(b), reinterpret_cast<_Float16*>(y), count / 8, op, ca, cb);
+    FCN_LAUNCH_CHECK("eltwise_f16");
+    return 0;
+}
+
+int fcn_softmax_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, int y_cstride, int out_f32, fcn_stream_t s) {
+    FCN_REQUIRE(x && y && pixels > 0 && C > 0 && x_cstride >= C && y_cstride >= C, FCN_E_ARG, "softmax_f16: bad args");
+    FCN_REQUIRE(x_cstride % 8 == 0 && y_cstride % (out_f32 ? 4 : 8) == 0 && aligned16(x) && aligned16(y), FCN_E_ALIGN,
+                "softmax_f16: strides must be whole 16-byte segments (8 halves, 4 floats), pointers 16-byte aligned");
+    const _Float16* xh = reinterpret_cast<const _Float16*>(x);
+    const dim3 grid(stream_grid(pixels, 256));
+#define FCN_SOFTMAX_F16(G)                                                                                                                    \
+    do {                                                                                                                                      \
+        if (out_f32)                                                                                                                          \
+            hipLaunchKernelGGL((softmax_f16_kernel<G, true>), grid, dim3(256), 0, as_stream(s), xh, y, (long long)pixels, C, x_cstride, y_cstride); \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((softmax_f16_kernel<G, false>), grid, dim3(256), 0, as_stream(s), xh, y, (long long)pixels, C, x_cstride, y_cstride); \
+    } while (0)
+    if (C <= 8) FCN_SOFTMAX_F16(1);
+    else if (C <= 16) FCN_SOFTMAX_F16(2);
+    else if (C <= 32) FCN_SOFTMAX_F16(4);
+    else FCN_SOFTMAX_F16(0);
+#undef FCN_SOFTMAX_F16
+    FCN_LAUNCH_CHECK("softmax_f16");
+    return 0;
+}
+
+int fcn_copy_channels_f16(const void* src, void* dst, int pixels, int C, int src_cstride, int src_coffset, int dst_cstride, int dst_coffset,
+                          fcn_stream_t s) {
+    FCN_REQUIRE(src && dst && pixels > 0 && C > 0, FCN_E_ARG, "copy_channels_f16: bad args");
+    FCN_REQUIRE(src_coffset >= 0 && dst_coffset >= 0 && src_cstride >= src_coffset + C && dst_cstride >= dst_coffset + C, FCN_E_ARG,
+                "copy_channels_f16: slice out of range");
+    FCN_REQUIRE(src_cstride % 8 == 0 && dst_cstride % 8 == 0 && aligned16(src) && aligned16(dst), FCN_E_ALIGN,
+                "copy_channels_f16: strides must be multiples of 8 halves, pointers of 16 bytes");
+    const _Float16* sh = reinterpret_cast<const _Float16*>(src);
+    _Float16* dh = reinterpret_cast<_Float16*>(dst);
+    if (src_coffset % 8 == 0 && dst_coffset % 8 == 0)
+        hipLaunchKernelGGL(copy_channels_f16_kernel<true>, dim3(stream_grid((long long)pixels * cdiv(C, 8), 256)), dim3(256), 0, as_stream(s), sh, dh,
+                           (long long)pixels, C, src_cstride, src_coffset, dst_cstride, dst_coffset);
+    else
+        hipLaunchKernelGGL(copy_channels_f16_kernel<false>, dim3(stream_grid((long long)pixels * C, 256)), dim3(256), 0, as_stream(s), sh, dh,
+                           (long long)pixels, C, src_cstride, src_coffset, dst_cstride, dst_coffset);
+    FCN_LAUNCH_CHECK("copy_channels_f16");
     return 0;
 }
 }  // extern "C"

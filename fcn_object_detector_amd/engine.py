@@ -246,7 +246,8 @@ class Engine:
         if self.f16:
             for name in self.shapes:
                 if esize[name] == 4 and len(self.shapes[name]) == 4 and name not in data_tops:
-                    bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power")]
+                    # (Softmax and Deconvolution read halves and store float32: the out_f32 forms of their half kernels)
+                    bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution")]
                     if bad:
                         raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 
@@ -1145,8 +1146,16 @@ class Engine:
         B, lib, t = self.blobs, L.load(), l.type
         out: List[Op] = []
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN"):
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
+
+        def copy_op(name: str, sb: Blob, so: int, db: Blob, do: int, pixels: int, c: int) -> Op:
+            """`c` channels of every pixel from channel `so` of sb's buffer to channel `do` of db's (Dropout at TEST, copied Concat / Slice)."""
+            if sb.esize != db.esize:
+                raise NotImplementedError("f16 engine: %s copies between half and float32 blobs" % name)
+            fn = lib.fcn_copy_channels_f16 if sb.esize == 2 else lib.fcn_copy_channels_f32
+            return Op("copy", name, lambda st: L.check(fn(sb.buf.ptr, db.buf.ptr, pixels, c, sb.cstride, so, db.cstride, do, st)),
+                      0.0, 2.0 * sb.esize * pixels * c)
         if t == "Pooling":
             xb, yb = B[l.bottoms[0]], B[l.tops[0]]
             pp = l.sub("pooling_param")
@@ -1158,8 +1167,12 @@ class Engine:
                 k, s, pad = kernel_stride_pad(pp)
             byts = float(xb.esize) * (xb.pixels * c + yb.pixels * c)
             if halves:
-                if str(pp.get("pool", "MAX")) != "MAX" or xb.esize != 2 or yb.esize != 2:
+                if xb.esize != 2 or yb.esize != 2:
                     raise NotImplementedError("f16 engine: pooling %s" % l.name)
+                if str(pp.get("pool", "MAX")) != "MAX":
+                    out.append(Op("avepool", l.name, lambda st: L.check(lib.fcn_avepool_fwd_f16(
+                        xb.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
+                    return out
                 out.append(Op("maxpool", l.name, lambda st: L.check(lib.fcn_maxpool_fwd_f16(
                     xb.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
             elif str(pp.get("pool", "MAX")) == "MAX":
@@ -1213,6 +1226,9 @@ class Engine:
         elif t == "Dropout":
             xb, yb = B[l.bottoms[0]], B[l.tops[0]]
             if self.spec.phase == "TEST":
+                if halves:
+                    out.append(copy_op(l.name, xb, xb.coffset, yb, yb.coffset, xb.pixels, xb.channels))
+                    return out
                 out.append(Op("copy", l.name, lambda st: L.check(lib.fcn_copy_channels_f32(
                     xb.buf.ptr, yb.buf.ptr, xb.pixels, xb.channels, xb.cstride, xb.coffset, yb.cstride, yb.coffset, st))))
             else:
@@ -1237,6 +1253,13 @@ class Engine:
             xb, yb = B[l.bottoms[0]], B[l.tops[0]]
             if int(l.sub("softmax_param").get("axis", 1)) != 1:
                 raise NotImplementedError("Softmax over an axis other than channels (layer %s)" % l.name)
+            if halves:
+                if xb.esize != 2 or xb.coffset % 8 or yb.coffset % (16 // yb.esize):
+                    raise NotImplementedError("f16 engine: Softmax %s from a float32 blob / on an unaligned channel slice" % l.name)
+                out.append(Op("softmax", l.name, lambda st: L.check(lib.fcn_softmax_fwd_f16(
+                    xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, 1 if yb.esize == 4 else 0, st)),
+                    0.0, float(xb.esize + yb.esize) * xb.pixels * xb.channels))
+                return out
             out.append(Op("softmax", l.name, lambda st: L.check(lib.fcn_softmax_fwd_f32(
                 xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, st)), 0.0, 8.0 * xb.pixels * xb.channels))
         elif t == "SoftmaxWithLoss":
@@ -1260,6 +1283,10 @@ class Engine:
             for tn in l.tops:
                 yb = B[tn]
                 o = off
+                if halves:
+                    out.append(copy_op(l.name + ":" + tn, xb, xb.coffset + o, yb, yb.coffset, yb.pixels, yb.channels))
+                    off += yb.channels
+                    continue
                 out.append(Op("copy", l.name + ":" + tn, lambda st, yb=yb, o=o: L.check(lib.fcn_copy_channels_f32(
                     xb.buf.ptr, yb.buf.ptr, yb.pixels, yb.channels, xb.cstride, xb.coffset + o, yb.cstride, yb.coffset, st)),
                     0.0, 8.0 * yb.pixels * yb.channels))
@@ -1270,6 +1297,10 @@ class Engine:
             for bn in l.bottoms:
                 xb = B[bn]
                 o = off
+                if halves:
+                    out.append(copy_op(l.name + ":" + bn, xb, xb.coffset, yb, yb.coffset + o, xb.pixels, xb.channels))
+                    off += xb.channels
+                    continue
                 out.append(Op("copy", l.name + ":" + bn, lambda st, xb=xb, o=o: L.check(lib.fcn_copy_channels_f32(
                     xb.buf.ptr, yb.buf.ptr, xb.pixels, xb.channels, xb.cstride, xb.coffset, yb.cstride, yb.coffset + o, st)),
                     0.0, 8.0 * xb.pixels * xb.channels))
@@ -1281,6 +1312,8 @@ class Engine:
             coeff = [float(c) for c in p.getall("coeff")] or [1.0] * len(l.bottoms)
             yb = B[l.tops[0]]
             srcs = [B[b] for b in l.bottoms]
+            if halves and len(halves) != len(l.bottoms) + 1:
+                raise NotImplementedError("f16 engine: Eltwise %s mixes half and float32 blobs" % l.name)
             for b in srcs + [yb]:
                 if not (b.coffset == 0 and b.cstride == yb.cstride):
                     raise NotImplementedError("Eltwise on channel slices (layer %s)" % l.name)
@@ -1288,8 +1321,9 @@ class Engine:
             a = srcs[0]
             for i, b in enumerate(srcs[1:], start=1):
                 ca = coeff[0] if i == 1 else 1.0
-                out.append(Op("eltwise", l.name, lambda st, a=a, b=b, ca=ca, cb=coeff[i]: L.check(lib.fcn_eltwise_fwd_f32(
-                    a.ptr, b.ptr, yb.ptr, count, op, ca, cb, st)), 0.0, 12.0 * count))
+                fn = lib.fcn_eltwise_fwd_f16 if halves else lib.fcn_eltwise_fwd_f32
+                out.append(Op("eltwise", l.name, lambda st, a=a, b=b, ca=ca, cb=coeff[i]: L.check(fn(
+                    a.ptr, b.ptr, yb.ptr, count, op, ca, cb, st)), 0.0, 3.0 * yb.esize * count))
                 a = yb
         elif t == "Deconvolution":
             p = l.sub("convolution_param")
@@ -1301,6 +1335,14 @@ class Engine:
                 raise NotImplementedError("Deconvolution %s: only group == channels == num_output" % l.name)
             wdev = self.params_dev[l.name][0].ptr
             bdev = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
+            if halves:
+                if xb.esize != 2 or xb.coffset % 8:
+                    raise NotImplementedError("f16 engine: Deconvolution %s from a float32 blob / an unaligned channel slice" % l.name)
+                out.append(Op("deconv", l.name, lambda st: L.check(lib.fcn_deconv_depthwise_fwd_f16(
+                    xb.ptr, wdev, bdev, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset,
+                    1 if yb.esize == 4 else 0, st)),
+                    2.0 * yb.pixels * c * (k / s) ** 2, float(xb.esize * xb.pixels + yb.esize * yb.pixels) * c))
+                return out
             out.append(Op("deconv", l.name, lambda st: L.check(lib.fcn_deconv_depthwise_fwd_f32(
                 xb.ptr, wdev, bdev, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)),
                 2.0 * yb.pixels * c * (k / s) ** 2, 4.0 * (xb.pixels + yb.pixels) * c))

@@ -171,6 +171,11 @@ PROTOTYPES = {
     "fcn_nhwc_f16_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fcn_maxpool_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_lrn_fwd_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "fcn_avepool_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
+    "fcn_deconv_depthwise_fwd_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_eltwise_fwd_f16": (_i, [_vp, _vp, _vp, _sz, _i, _f, _f, _vp]),
+    "fcn_softmax_fwd_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fcn_copy_channels_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fcn_preprocess_bgr8_batch": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "fcn_preprocess_bgr8_rois": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "fcn_preprocess_bgr8_f16": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp]),

@@ -273,6 +273,28 @@ int  fcn_lrn_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, i
  * (tests/test_gpu_f16.py asserts exactly that bound); every other geometry is bit-identical to the two launches. */
 int  fcn_maxpool_lrn5_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int k, int stride, int pad,
                               int OH, int OW, int y_cstride, int lrn_first, float alpha, float beta, float lrn_k, fcn_stream_t s);
+/* The other layers of the VGG16 nets (train/fcn_bbox, train/bounding_box/deploy.prototxt) on half blobs: twins of fcn_avepool_fwd_f32,
+ * fcn_deconv_depthwise_fwd_f32, fcn_eltwise_fwd_f32, fcn_softmax_fwd_f32 and fcn_copy_channels_f32.  A lane moves 8 channels (16 bytes),
+ * sums in float32 and rounds once (to nearest even) at the store.  Common contract: pointers 16-byte aligned, x_cstride / y_cstride /
+ * y_coffset multiples of 8 halves (of 4 floats for a float32 output) else FCN_E_ALIGN; null pointers and non-positive extents FCN_E_ARG;
+ * every check precedes the first HIP call.  C is the REAL channel count and need not be a multiple of 8: exactly channels
+ * y_coffset .. y_coffset + C - 1 of every output pixel are written, no w / bias element beyond C is read, and the pad channels of x up to
+ * the next multiple of 8 may be read but never reach a written value.  Results do not depend on the run (no atomics).
+ * out_f32 = 1: y holds float32 (an output blob of an f16 engine, which the decode kernels read). */
+/* Caffe divisor (window clipped to H + pad), sum over the part inside the image.  Windows of 64 pixels and more are summed by a whole
+ * workgroup per output pixel (pixel lanes stride over the window, partial sums meet in LDS in a fixed tree); smaller ones by one lane. */
+int  fcn_avepool_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int k, int stride, int pad, int OH, int OW,
+                         int y_cstride, int y_coffset, fcn_stream_t s);
+/* x halves; w float32 [C][k][k] and bias float32 [C] (may be NULL), as fcn_deconv_depthwise_fwd_f32 takes them */
+int  fcn_deconv_depthwise_fwd_f16(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C, int x_cstride,
+                                  int k, int stride, int pad, int OH, int OW, int y_cstride, int y_coffset, int out_f32, fcn_stream_t s);
+/* over `count` contiguous halves, count a positive multiple of 8 (whole strided rows, pad channels included); y may be a */
+int  fcn_eltwise_fwd_f16(const void* a, const void* b, void* y, size_t count, int op, float ca, float cb, fcn_stream_t s);
+/* channels 0 .. C-1 of every pixel; one exp per element while C <= 32 */
+int  fcn_softmax_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, int y_cstride, int out_f32, fcn_stream_t s);
+/* strides multiples of 8 halves; offsets that are both multiples of 8 move 16 bytes per lane, any other offset one half per lane */
+int  fcn_copy_channels_f16(const void* src, void* dst, int pixels, int C, int src_cstride, int src_coffset, int dst_cstride,
+                           int dst_coffset, fcn_stream_t s);
 /* n windows of ONE frame -> the n images of an N x H x W x dst_cstride blob: the node's multi-window path
  * (scripts/fcn_object_detector.py run_detector2 :198-211 with detection_window_roi :257-277) demeans and normalises the WHOLE frame
  * (min / max over the frame), crops stride x stride windows plus a central one, and resizes each to the net's input.  h_rois: n x

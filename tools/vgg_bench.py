@@ -1,6 +1,9 @@
 #!/usr/bin/env python
-"""GPU: the reference's secondary VGG16 nets — forward of the train/fcn_bbox deploy form at 448x448 and one training step of
-train/fcn_bbox at its native configuration (288x288, stride 8, 11 classes; batch 24 in the reference's param_str)."""
+"""GPU: the reference's secondary VGG16 nets.  `vgg_bench.py [batch] [f32|f16]`: forward of the two deploy nets (train/fcn_bbox's
+inference form and train/bounding_box/deploy.prototxt) at 448x448 in the chosen element type - three repeats of 20 resident
+forwards after warm-up, the eight slowest launches and the time of every pointwise kernel family with its bytes per second from
+Engine.time_ops - and, for f32 only, one training step of train/fcn_bbox at its native configuration (288x288, stride 8, 11 classes;
+batch 24 in the reference's param_str unless a batch is given)."""
 import os
 import sys
 import time
@@ -27,23 +30,43 @@ def conv_flops(spec, shapes):
     return f
 
 
-def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-    L.call("fcn_init", 0)
-    msg = proto.parse_text(models.vgg16_fcn_bbox_deploy(1, 448, 448, 11))
+def forward_bench(title, txt, batch, dtype):
+    msg = proto.parse_text(txt)
     spec = NetSpec(msg, "TEST")
     shapes = spec.infer()
-    eng = Engine(NetSpec(msg, "TEST"), params=fill_params(spec, seed=1), device=0)
-    eng.host_array("data")[...] = np.random.default_rng(0).random((1, 3, 448, 448), dtype=np.float32)
+    eng = Engine(NetSpec(msg, "TEST"), params=fill_params(spec, seed=1), device=0, dtype=dtype)
+    eng.host_array("data")[...] = np.random.default_rng(0).random((batch, 3, 448, 448), dtype=np.float32)
     eng.upload_inputs()
-    eng.forward_resident(3)
-    ms = eng.forward_resident(20) / 20
-    fl = conv_flops(spec, shapes)
-    print("fcn_bbox deploy 448x448 b1: %.3f ms/frame, %.1f frames/s, %.2f GFLOP/frame, %.1f TF/s" % (ms, 1e3 / ms, fl / 1e9, fl / ms / 1e9))
+    eng.forward_resident(5)
+    runs = sorted(eng.forward_resident(20) / 20 / batch for _ in range(3))      # ms per frame, three repeats of 20 forwards
+    ms = runs[1]
+    fl = conv_flops(spec, shapes) / batch
+    print("%s 448x448 b%d %s: %.3f ms/frame (min %.3f max %.3f of 3 x 20 forwards), %.1f frames/s, %.2f GFLOP/frame, %.1f TF/s" % (
+        title, batch, dtype, ms, runs[0], runs[2], 1e3 / ms, fl / 1e9, fl / ms / 1e9))
     rows = eng.time_ops(5)
     for kind, name, t, f, b in sorted(rows, key=lambda r: -r[2])[:8]:
         print("   %-10s %-50s %8.1f us %6.1f TF/s" % (kind, name[:50], t * 1e3, f / t / 1e9 if t else 0))
+    by = {}
+    for kind, name, t, f, b in rows:
+        if not kind.startswith("conv"):
+            by.setdefault(kind, []).append((name, t, b))
+    for kind, items in sorted(by.items()):
+        print("   family %-8s x%-2d %8.1f us: " % (kind, len(items), 1e3 * sum(t for _n, t, _b in items)) +
+              ", ".join("%s %.1f us %.2f TB/s" % (nm[-24:], t * 1e3, b / t / 1e9 if t else 0) for nm, t, b in items))
     eng.close()
+
+
+def main():
+    args = [a for a in sys.argv[1:] if a not in ("f32", "f16")]
+    dtype = "f16" if "f16" in sys.argv[1:] else "f32"
+    fwd_batch = int(args[0]) if args else 1
+    batch = int(args[0]) if args else 24
+    print("GPU_MAX_HW_QUEUES=%s" % os.environ.get("GPU_MAX_HW_QUEUES", "(unset)"))
+    L.call("fcn_init", 0)
+    forward_bench("fcn_bbox deploy", models.vgg16_fcn_bbox_deploy(fwd_batch, 448, 448, 11), fwd_batch, dtype)
+    forward_bench("bounding_box deploy", models.vgg16_bounding_box_deploy(fwd_batch, 448, 448, 20), fwd_batch, dtype)
+    if dtype != "f32":
+        return      # training is float32 only
 
     n, size, classes = batch, 288, 11
     msg = proto.parse_text(models.vgg16_fcn_bbox_train("synthetic", "Boxes", "288,288,8,11,%d,none" % n, num_classes=classes))
