@@ -103,7 +103,12 @@ int  fcn_nhwc_to_nchw_multi_f32(const fcn_layout_desc* h_descs, int n, fcn_strea
 #define FCN_CONV_IMAGE_ONES 128 /* with FCN_CONV_F16 on an 8-half pixel image (the first layer of an f16 net): the caller promises that channels 3
                                 * and 4 of x hold the constant 1 at every pixel and channels 5..7 contribute nothing (zero pixels or zero
                                 * weights) - the folded Power shift of models/deploy.prototxt:8-16.  Their products are then added
-                                * as per-tap constants (f32) instead of being multiplied; pixels outside the image count as 0, as ever */
+                                * as per-tap constants (f32) instead of being multiplied; pixels outside the image count as 0, as ever.
+                                * What the half first-layer kernels READ (tests/test_gpu_guarded_f16.py pins it): with this flag
+                                * (conv_first7_f16x4_kernel) halves 0..3 of every pixel and halves 0..4 of every filter tap - halves 4..7
+                                * of a pixel and 5..7 of a tap are NOT READ and may hold anything; without it (conv_first7_f16_kernel, and
+                                * the tiled kernels) all eight halves of pixel and tap are loaded and MULTIPLIED, so the pad channels must
+                                * be the caller's zeros (a NaN times zero is a NaN).  Cout: a multiple of 8 in 40 .. 64 */
 #define FCN_CONV_OUT_F32   8   /* with FCN_CONV_F16: y is float32 (the detection heads feed the f32 decode kernel)   */
 #define FCN_CONV_OUT_F16  32   /* float32 x and w, y stored as half floats: the first layer of an f16 net keeps its input in
                                 * float32 (models/deploy.prototxt shifts a [0,1] image by -127: 16 half-float levels)   */

@@ -189,6 +189,10 @@ class GuardedBuffer:
         bad = np.nonzero(diff)[0]
         return None if bad.size == 0 else (int(bad[0]) - self.offset, int(bad[-1]) - self.offset)
 
+    def unchanged(self) -> bool:
+        """True when the WHOLE allocation - payload and both red zones - is bit-identical to what was uploaded (a refused call)."""
+        return bool(np.array_equal(self.mem.download(self.handle, 0, self.total), self._image))
+
     def check(self):
         m = self.modified()
         if m is not None:
@@ -268,3 +272,12 @@ def poison_free(a: np.ndarray, poison="nan") -> bool:
     if not np.all(np.isfinite(a)):
         return False
     return poison != "huge" or bool(np.all(np.abs(a.astype(np.float64)) < 0.25 * float(poison_value("huge", a.dtype))))
+
+
+def channels_untouched(full: np.ndarray, written: np.ndarray, poison="nan") -> bool:
+    """slice_untouched for several slices of one buffer: every channel of `full` (.., cstride) whose entry in the boolean vector `written`
+    is False still holds the poison, bit for bit (any element type: the comparison goes through an integer view)."""
+    written = np.asarray(written, bool)
+    assert written.shape == (full.shape[-1],)
+    want = _bits(np.array([poison_value(poison, full.dtype)]))[0]
+    return bool(np.all(_bits(full)[..., ~written] == want))

@@ -249,3 +249,106 @@ def adam_update(w, g, m, v, rate, beta1, beta2, delta, weight_decay, lr_mult, de
     v2 = beta2 * f64(v) + (1 - beta2) * gg * gg
     corr = np.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
     return f64(w) - rate * lr_mult * corr * m2 / (np.sqrt(v2) + delta), m2, v2
+
+
+# ---- half-float kernels: the same definitions with the roundings a kernel makes where it STORES halves ---------------------------
+def to_f16_then_f64(a):
+    """Round to the nearest half (ties to even, as the hardware conversion does) and return the rounded values as float64."""
+    return np.asarray(a, np.float64).astype(np.float16).astype(np.float64)
+
+
+def f16_ulp(a):
+    """Spacing of the halves at |a| (the subnormal spacing 2^-24 below 2^-14): ONE f16 ulp of every element."""
+    a = np.abs(np.asarray(a, np.float64))
+    e = np.floor(np.log2(np.maximum(a, 2.0 ** -14)))
+    return 2.0 ** (e - 10)
+
+
+def max_pool_values(x, k, stride, pad):
+    """The values of max_pool by a second route: the image padded with -inf (the largest NEGATIVE value stands for 'outside', so an
+    all-negative image keeps its own maxima), then the maximum over the k x k shifted, strided views.  Caffe's ceil-mode output size;
+    a window that hangs over the bottom / right edge is clipped the same way (the padding there is -inf too)."""
+    x = f64(x)
+    n, c, h, w = x.shape
+    oh, ow = pool_out(h, k, pad, stride), pool_out(w, k, pad, stride)
+    hp, wp = (oh - 1) * stride + k, (ow - 1) * stride + k
+    xp = np.full((n, c, max(hp, h + pad), max(wp, w + pad)), -np.inf)
+    xp[:, :, pad:pad + h, pad:pad + w] = x
+    y = np.full((n, c, oh, ow), -np.inf)
+    for r in range(k):
+        for q in range(k):
+            y = np.maximum(y, xp[:, :, r:r + (oh - 1) * stride + 1:stride, q:q + (ow - 1) * stride + 1:stride])
+    return y
+
+
+def lrn_f16(x, local_size, alpha, beta, k=1.0, round_out=True):
+    """LRN of a half blob as the half kernels define it: the operands are the halves as given, the arithmetic is exact here (float32 in
+    the kernel), and the ONE rounding is the store of y as a half (round_out=False leaves it out: the value the kernel rounds)."""
+    y, _ = lrn(x, local_size, alpha, beta, k)
+    return to_f16_then_f64(y) if round_out else y
+
+
+def lrn_f16_allow(y64, local_size, beta):
+    """Allowed |y - y64| of a half LRN output against the UNROUNDED float64 value: half an f16 ulp for the store (U16 |y|, or half the
+    subnormal spacing) plus the float32 arithmetic in front of it, as lrn_allow of the float32 kernels derives it - (local_size + 2) u on
+    the sum of squares -> beta (local_size + 2) u on the factor, 6 u for the power, the product and the conversion."""
+    return U16 * np.abs(y64) + 2.0 ** -25 + (beta * (local_size + 2) + 6) * U32 * np.abs(y64)
+
+
+def pool_lrn_f16(x, k, stride, pad, lrn_first, alpha, beta, lrn_k=1.0, round_out=True):
+    """fcn_maxpool_lrn5_fwd_f16 from the definitions: LRN(maxpool(x)) or maxpool(LRN(x)) with local_size 5.  The maximum of halves is
+    a half (exact); rounding is monotonic, so the maximum of rounded values is the rounded maximum: one rounding, at the end, either way."""
+    if lrn_first:
+        y = max_pool_values(lrn(x, 5, alpha, beta, lrn_k)[0], k, stride, pad)
+    else:
+        y = lrn(max_pool_values(x, k, stride, pad), 5, alpha, beta, lrn_k)[0]
+    return to_f16_then_f64(y) if round_out else y
+
+
+def pool_lrn_conv1x1_f16(x, w, b, k, stride, pad, alpha, beta, lrn_k=1.0, relu=False):
+    """(y64, allowance) of fcn_maxpool_lrn5_conv1x1_fwd_f16: pool (exact) -> LRN -> 1x1 convolution + bias (+ ReLU).  The kernel
+    STORES the normalised tile as halves (the matrix cores multiply halves), so the reference rounds there too, multiplies in float64 and
+    leaves the final rounding to the allowance:
+        dot_bound_f16(C, mag, y64)                           float32 accumulation of C products + the one rounding of y
+      + 2 * (one f16 ulp of the largest |w_c mid_c|)          the kernel's float32 LRN lands on the other side of a rounding tie on about one
+                                                              normalised value in 700 (12 u32 / u16); such a value differs by ONE f16 ulp, and
+                                                              an output may see a flipped value in its largest products twice.
+    w: [Cout, C] or [Cout, C, 1, 1]."""
+    w = f64(w).reshape(w.shape[0], -1)
+    mid = to_f16_then_f64(lrn(max_pool_values(x, k, stride, pad), 5, alpha, beta, lrn_k)[0])
+    y64 = np.einsum("nchw,oc->nohw", mid, w)
+    mag = np.einsum("nchw,oc->nohw", np.abs(mid), np.abs(w))
+    if b is not None:
+        y64 = y64 + f64(b)[None, :, None, None]
+        mag = mag + np.abs(f64(b))[None, :, None, None]
+    top = np.zeros_like(y64)
+    for c in range(mid.shape[1]):      # largest single product of every output, one input channel at a time
+        top = np.maximum(top, np.abs(w[:, c])[None, :, None, None] * np.abs(mid[:, c])[:, None])
+    allow = dot_bound_f16(mid.shape[1], mag, y64) + 2 * 2.0 * U16 * top
+    return (np.maximum(y64, 0) if relu else y64), allow
+
+
+def conv2d_image_ones(x3, w, b, pad, stride):
+    """(y64, mag, border) of the first layer on an image whose channels 3 and 4 are the constant 1 (FCN_CONV_IMAGE_ONES).  x3: the
+    three real channels [N, 3, H, W]; w: [Cout, >= 5, k, k] whose channels 3 and 4 are the filters of the two constant channels.
+    The constant channels count ONLY over the taps that lie inside the image (outside it the padded image is 0, not 1):
+        y[n,o,i,j] = b[o] + sum_{c<3,r,q} x3[...] w[o,c,r,q] + sum_{(r,q) inside} (w[o,3,r,q] + w[o,4,r,q]).
+    border: boolean [OH, OW], True where some tap of the window falls outside the image."""
+    x3, w = f64(x3), f64(w)
+    n, _, h, wd = x3.shape
+    co, _, kh, kw = w.shape
+    oh, ow = conv_out(h, kh, pad, stride), conv_out(wd, kw, pad, stride)
+    y = conv2d(x3, w[:, :3], b, pad, stride)
+    mag = conv2d_mag(x3, w[:, :3], b, pad, stride)
+    shift = w[:, 3] + w[:, 4]
+    ashift = np.abs(w[:, 3]) + np.abs(w[:, 4])
+    border = np.zeros((oh, ow), bool)
+    for i in range(oh):
+        for j in range(ow):
+            r0, q0 = i * stride - pad, j * stride - pad
+            rs = [r for r in range(kh) if 0 <= r0 + r < h]
+            qs = [q for q in range(kw) if 0 <= q0 + q < wd]
+            border[i, j] = len(rs) < kh or len(qs) < kw
+            y[:, :, i, j] += shift[:, rs][:, :, qs].sum(axis=(1, 2))[None]
+            mag[:, :, i, j] += ashift[:, rs][:, :, qs].sum(axis=(1, 2))[None]
+    return y, mag, border
