@@ -1323,6 +1323,141 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const 
     }
 }
 
+// One kernel for every solver type (fcn_solver_update_f32), the type and the regulariser as template parameters.  With L2 and
+// clip == 1 the SGD / ADAM instances perform the operations of sgd_kernel / adam_kernel in the same order (g * 1.0f is exact), so
+// their results are bit-identical to those kernels'.  d_clip: device word written by clip_final_kernel, or nullptr (1.0).
+template <int KIND, bool L1>
+__global__ __launch_bounds__(256) void solver_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ h1, float* __restrict__ h2,
+                                                     const SolverSeg* __restrict__ segs, int nseg, float rate, float a, float b, float delta,
+                                                     float decay, float grad_scale, const float* __restrict__ d_clip) {
+    const int s = blockIdx.y;
+    if (s >= nseg) return;
+    const SolverSeg seg = segs[s];
+    if (seg.lr_mult == 0.f) return;
+    const float lr = rate * seg.lr_mult, wd = decay * seg.decay_mult;
+    const float gs = d_clip ? grad_scale * *d_clip : grad_scale;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < seg.count; i += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long o = seg.offset + i;
+        const float wi = w[o];
+        const float gi = g[o] * gs + wd * (L1 ? (float)((wi > 0.f) - (wi < 0.f)) : wi);
+        if constexpr (KIND == FCN_SOLVER_SGD) {
+            const float h = a * h1[o] + lr * gi;
+            h1[o] = h;
+            w[o] = wi - h;
+        } else if constexpr (KIND == FCN_SOLVER_NESTEROV) {
+            const float h_old = h1[o];
+            const float h = a * h_old + lr * gi;
+            h1[o] = h;
+            w[o] = wi - ((1.f + a) * h - a * h_old);
+        } else if constexpr (KIND == FCN_SOLVER_ADAGRAD) {
+            const float h = h1[o] + gi * gi;
+            h1[o] = h;
+            w[o] = wi - lr * gi / (sqrtf(h) + delta);
+        } else if constexpr (KIND == FCN_SOLVER_RMSPROP) {
+            const float h = a * h1[o] + (1.f - a) * gi * gi;
+            h1[o] = h;
+            w[o] = wi - lr * gi / (sqrtf(h) + delta);
+        } else if constexpr (KIND == FCN_SOLVER_ADADELTA) {
+            const float hg = a * h1[o] + (1.f - a) * gi * gi;
+            const float u = gi * sqrtf((h2[o] + delta) / (hg + delta));
+            h1[o] = hg;
+            h2[o] = a * h2[o] + (1.f - a) * u * u;
+            w[o] = wi - lr * u;
+        } else {      // FCN_SOLVER_ADAM: rate already carries sqrt(1 - b2^t) / (1 - b1^t)
+            const float mi = a * h1[o] + (1.f - a) * gi;
+            const float vi = b * h2[o] + (1.f - b) * gi * gi;
+            h1[o] = mi;
+            h2[o] = vi;
+            w[o] = wi - lr * mi / (sqrtf(vi) + delta);
+        }
+    }
+}
+
+// gradient clipping: sum of squares over the segments of the flat gradient buffer as a fixed-order two-stage tree (no atomics).
+// Stage 1: SUMSQ_BLOCKS workgroups walk every segment grid-stride with 16-byte loads (up to three scalar elements in front of
+// and behind the aligned body of a segment) and leave one double each in the workspace; stage 2: one workgroup adds those in
+// index order.  The grid does not depend on the data or the segment layout: the same inputs give the same bits on every run.
+constexpr int SUMSQ_BLOCKS = 1024, SUMSQ_THREADS = 256;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// sum over the workgroup, valid in thread 0 (the waves' sums are added in wave order)
+__device__ __forceinline__ double block_sum(double v) {
+    __shared__ double wave_part[SUMSQ_THREADS / 64];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < SUMSQ_THREADS / 64; ++i) t += wave_part[i];
+    return t;
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void sumsq_partial_kernel(const float* __restrict__ g, const SolverSeg* __restrict__ segs, int nseg,
+                                                                       double* __restrict__ partial) {
+    const unsigned long long tid = (unsigned long long)blockIdx.x * SUMSQ_THREADS + threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * SUMSQ_THREADS;
+    double acc = 0.0;
+    for (int s = 0; s < nseg; ++s) {
+        const SolverSeg seg = segs[s];
+        const float* p = g + seg.offset;
+        unsigned long long head = (4 - (seg.offset & 3)) & 3;      // g itself is 16-byte aligned
+        if (head > seg.count) head = seg.count;
+        const unsigned long long nvec = (seg.count - head) >> 2, tail = seg.count - head - 4 * nvec;
+        const v4f* pv = reinterpret_cast<const v4f*>(p + head);
+        for (unsigned long long i = tid; i < nvec; i += stride) {
+            const v4f v = pv[i];
+            acc += (double)v.x * (double)v.x + (double)v.y * (double)v.y + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
+        }
+        if (tid < head) acc += (double)p[tid] * (double)p[tid];
+        if (tid < tail) {
+            const float t = p[head + 4 * nvec + tid];
+            acc += (double)t * (double)t;
+        }
+    }
+    const double t = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void clip_final_kernel(const double* __restrict__ partial, int n, float clip_gradients, float norm_scale,
+                                                                    float* __restrict__ d_clip, float* __restrict__ d_sumsq) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += SUMSQ_THREADS) acc += partial[i];
+    const double t = block_sum(acc);
+    if (threadIdx.x == 0) {
+        if (d_sumsq) *d_sumsq = (float)t;
+        const double norm = sqrt(t) * fabs((double)norm_scale);
+        *d_clip = norm > (double)clip_gradients ? (float)((double)clip_gradients / norm) : 1.f;
+    }
+}
+
+// acc = first ? g : acc + g over a flat buffer, 16 bytes per lane
+__global__ __launch_bounds__(256) void accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, unsigned long long count, int first) {
+    const unsigned long long nvec = count >> 2;
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (unsigned long long)gridDim.x * blockDim.x;
+    v4f* av = reinterpret_cast<v4f*>(acc);
+    const v4f* gv = reinterpret_cast<const v4f*>(g);
+    for (unsigned long long i = tid; i < nvec; i += stride) av[i] = first ? gv[i] : av[i] + gv[i];
+    const unsigned long long o = 4 * nvec + tid;
+    if (o < count) acc[o] = first ? g[o] : acc[o] + g[o];
+}
+
+template <int KIND>
+void launch_solver(bool l1, dim3 grid, hipStream_t st, float* w, const float* g, float* h1, float* h2, const SolverSeg* segs, int nseg,
+                          float rate, float a, float b, float delta, float decay, float grad_scale, const float* d_clip) {
+    if (l1)
+        hipLaunchKernelGGL((solver_kernel<KIND, true>), grid, dim3(256), 0, st, w, g, h1, h2, segs, nseg, rate, a, b, delta, decay, grad_scale, d_clip);
+    else
+        hipLaunchKernelGGL((solver_kernel<KIND, false>), grid, dim3(256), 0, st, w, g, h1, h2, segs, nseg, rate, a, b, delta, decay, grad_scale, d_clip);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool unit_interval(float v) { return v >= 0.f && v < 1.f; }      // (false for a NaN)
+
 unsigned magic32(unsigned d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)((0x100000000ull + d - 1) / d); }
 
 }  // namespace
@@ -1933,6 +2068,65 @@ int fcn_adam_update_f32(float* w, const float* g, float* m, float* v, const fcn_
     hipLaunchKernelGGL(adam_kernel, dim3(64, nseg), dim3(256), 0, as_stream(s), w, g, m, v, reinterpret_cast<const SolverSeg*>(d_segs), nseg,
                        (float)(rate * corr), beta1, beta2, delta, weight_decay, grad_scale);
     FCN_LAUNCH_CHECK("adam_update");
+    return 0;
+}
+
+int fcn_solver_update_f32(int kind, float* w, const float* g, float* h1, float* h2, const fcn_solver_seg* d_segs, int nseg, float rate,
+                          float momentum, float momentum2, float rms_decay, float delta, float weight_decay, int regularization, int t,
+                          float grad_scale, const float* d_clip, fcn_stream_t s) {
+    FCN_REQUIRE(kind >= FCN_SOLVER_SGD && kind <= FCN_SOLVER_ADAM, FCN_E_ARG, "solver_update: unknown solver kind %d", kind);
+    const bool two = kind == FCN_SOLVER_ADADELTA || kind == FCN_SOLVER_ADAM;
+    FCN_REQUIRE(w && g && h1 && (h2 || !two) && d_segs, FCN_E_ARG, "solver_update: null pointer");
+    FCN_REQUIRE(nseg > 0 && nseg <= 65535, FCN_E_ARG, "solver_update: nseg %d outside 1 .. 65535", nseg);
+    FCN_REQUIRE(regularization == FCN_REG_L2 || regularization == FCN_REG_L1, FCN_E_ARG, "solver_update: unknown regularization %d", regularization);
+    FCN_REQUIRE(unit_interval(momentum), FCN_E_ARG, "solver_update: momentum %g outside [0, 1)", (double)momentum);
+    FCN_REQUIRE(unit_interval(rms_decay), FCN_E_ARG, "solver_update: rms_decay %g outside [0, 1)", (double)rms_decay);
+    FCN_REQUIRE(kind != FCN_SOLVER_ADAM || (unit_interval(momentum2) && t >= 1), FCN_E_ARG, "solver_update: Adam needs momentum2 in [0, 1) and t >= 1");
+    FCN_REQUIRE(aligned16(w) && aligned16(g) && aligned16(h1) && aligned16(h2) && aligned16(d_segs) && ((uintptr_t)d_clip & 3) == 0, FCN_E_ALIGN,
+                "solver_update: buffers must be 16-byte aligned (the clip word 4-byte)");
+    const SolverSeg* segs = reinterpret_cast<const SolverSeg*>(d_segs);
+    const dim3 grid(64, nseg);
+    const bool l1 = regularization == FCN_REG_L1;
+    hipStream_t st = as_stream(s);
+    switch (kind) {
+        case FCN_SOLVER_SGD: launch_solver<FCN_SOLVER_SGD>(l1, grid, st, w, g, h1, h2, segs, nseg, rate, momentum, 0.f, delta, weight_decay, grad_scale, d_clip); break;
+        case FCN_SOLVER_NESTEROV: launch_solver<FCN_SOLVER_NESTEROV>(l1, grid, st, w, g, h1, h2, segs, nseg, rate, momentum, 0.f, delta, weight_decay, grad_scale, d_clip); break;
+        case FCN_SOLVER_ADAGRAD: launch_solver<FCN_SOLVER_ADAGRAD>(l1, grid, st, w, g, h1, h2, segs, nseg, rate, 0.f, 0.f, delta, weight_decay, grad_scale, d_clip); break;
+        case FCN_SOLVER_RMSPROP: launch_solver<FCN_SOLVER_RMSPROP>(l1, grid, st, w, g, h1, h2, segs, nseg, rate, rms_decay, 0.f, delta, weight_decay, grad_scale, d_clip); break;
+        case FCN_SOLVER_ADADELTA: launch_solver<FCN_SOLVER_ADADELTA>(l1, grid, st, w, g, h1, h2, segs, nseg, rate, momentum, 0.f, delta, weight_decay, grad_scale, d_clip); break;
+        default: {
+            const double corr = sqrt(1.0 - pow((double)momentum2, t)) / (1.0 - pow((double)momentum, t));
+            launch_solver<FCN_SOLVER_ADAM>(l1, grid, st, w, g, h1, h2, segs, nseg, (float)(rate * corr), momentum, momentum2, delta, weight_decay, grad_scale, d_clip);
+        }
+    }
+    FCN_LAUNCH_CHECK("solver_update");
+    return 0;
+}
+
+size_t fcn_grad_clip_workspace_bytes(void) { return SUMSQ_BLOCKS * sizeof(double); }
+
+int fcn_grad_clip_f32(const float* g, const fcn_solver_seg* d_segs, int nseg, float clip_gradients, float norm_scale, float* d_clip, float* d_sumsq,
+                      void* d_workspace, fcn_stream_t s) {
+    FCN_REQUIRE(g && d_segs && d_clip && d_workspace, FCN_E_ARG, "grad_clip: null pointer");
+    FCN_REQUIRE(nseg > 0, FCN_E_ARG, "grad_clip: nseg %d", nseg);
+    FCN_REQUIRE(clip_gradients > 0.f && norm_scale > 0.f, FCN_E_ARG, "grad_clip: clip_gradients and norm_scale must be positive");
+    FCN_REQUIRE(aligned16(g) && aligned16(d_segs) && aligned16(d_workspace) && (((uintptr_t)d_clip | (uintptr_t)d_sumsq) & 3) == 0, FCN_E_ALIGN,
+                "grad_clip: g, segments and workspace must be 16-byte aligned (the result words 4-byte)");
+    hipStream_t st = as_stream(s);
+    double* partial = reinterpret_cast<double*>(d_workspace);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(SUMSQ_BLOCKS), dim3(SUMSQ_THREADS), 0, st, g, reinterpret_cast<const SolverSeg*>(d_segs), nseg, partial);
+    FCN_LAUNCH_CHECK("grad_clip (partial sums)");
+    hipLaunchKernelGGL(clip_final_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, st, partial, SUMSQ_BLOCKS, clip_gradients, norm_scale, d_clip, d_sumsq);
+    FCN_LAUNCH_CHECK("grad_clip (final sum)");
+    return 0;
+}
+
+int fcn_grad_accumulate_f32(float* acc, const float* g, size_t count, int first, fcn_stream_t s) {
+    FCN_REQUIRE(acc && g && count > 0, FCN_E_ARG, "grad_accumulate: bad args");
+    FCN_REQUIRE(aligned16(acc) && aligned16(g), FCN_E_ALIGN, "grad_accumulate: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(accumulate_kernel, dim3(stream_grid((long long)((count + 3) / 4), 256)), dim3(256), 0, as_stream(s), acc, g,
+                       (unsigned long long)count, first);
+    FCN_LAUNCH_CHECK("grad_accumulate");
     return 0;
 }
 

@@ -88,6 +88,8 @@ class DetectParams(C.Structure):
 CONV_RELU, CONV_SIGMOID2, CONV_ACCUM, CONV_OUT_F32, CONV_F16, CONV_OUT_F16, CONV_MASK = 1, 2, 4, 8, 16, 32, 64
 CONV_IMAGE_ONES = 128      # half image whose channels 3 and 4 are the constant 1 (the folded Power shift): see include/fcnhip.h
 ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
+SOLVER_KINDS = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADADELTA": 4, "ADAM": 5}      # FCN_SOLVER_*
+REG_L2, REG_L1 = 0, 1
 RECT_ROUND_NEAREST_EVEN, RECT_ROUND_TRUNCATE = 0, 1
 
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -205,6 +207,10 @@ PROTOTYPES = {
     "fcn_loss_f32": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "fcn_sgd_update_f32": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _vp]),
     "fcn_adam_update_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp]),
+    "fcn_solver_update_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _f, _i, _i, _f, _vp, _vp]),
+    "fcn_grad_clip_workspace_bytes": (_sz, []),
+    "fcn_grad_clip_f32": (_i, [_vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
+    "fcn_grad_accumulate_f32": (_i, [_vp, _vp, _sz, _i, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

@@ -285,3 +285,4 @@ def get_solver(solver_file, **kw):
 
 SGDSolver = get_solver
 AdamSolver = get_solver
+NesterovSolver = AdaGradSolver = RMSPropSolver = AdaDeltaSolver = get_solver      # (the type comes from the solver file, as in get_solver)

@@ -88,6 +88,8 @@ class TrainNet(object):
 
 
 class Solver(object):
+    TYPE_NAMES = {"SGD": "SGD", "NESTEROV": "Nesterov", "ADAGRAD": "AdaGrad", "RMSPROP": "RMSProp", "ADADELTA": "AdaDelta", "ADAM": "Adam"}
+
     def __init__(self, solver_file: str, device: int = 0, comm=None, rank: int = 0, log: Optional[Callable[[str], None]] = _log,
                  autotune: bool = True):
         if not os.path.isfile(str(solver_file)):
@@ -124,6 +126,9 @@ class Solver(object):
                 self._device_label_tops[id(inst)] = tuple(t.name for t in tops[1:6])
         self.log("Solver: %s, net %s, %d learnable floats, world %d" % (
             self.param.kind, self.net_file, self.engine.param_count, comm.world if comm is not None else 1))
+        p = self.param
+        self.log('Initializing solver from parameters: type: "%s" lr_policy: "%s" base_lr: %g regularization_type: "%s" iter_size: %d '
+                 'clip_gradients: %g' % (self.TYPE_NAMES[p.kind], p.lr_policy, p.base_lr, p.regularization_type, p.iter_size, p.clip_gradients))
 
     @property
     def iter(self) -> int:
@@ -162,16 +167,17 @@ class Solver(object):
         pipelined = pipeline and self._all_device_fed()
         while self.iter < stop:
             it = self.iter
-            if not self._fed:
-                self._feed()
-            self._fed = False
-            self.engine.step_begin()
-            if pipelined and it + 1 < p.max_iter:
-                # the renders of the next batch queue up behind this iteration on the stream; its planning (host RNG and
-                # box bookkeeping) overlaps the device work
-                self._feed()
-                self._fed = True
-            out = self.engine.step_end()
+            for j in range(p.iter_size):      # iter_size passes, each on a fresh batch; the engine updates after the last one
+                if not self._fed:
+                    self._feed()
+                self._fed = False
+                self.engine.step_begin()
+                if pipelined and (j + 1 < p.iter_size or it + 1 < p.max_iter):
+                    # the renders of the next batch queue up behind this iteration on the stream; its planning (host RNG and
+                    # box bookkeeping) overlaps the device work
+                    self._feed()
+                    self._fed = True
+                out = self.engine.step_end()
             self._losses.append(out["total_loss"])
             if p.display and it % p.display == 0:
                 self.log("Iteration %d, loss = %g" % (it, sum(self._losses) / len(self._losses)))
@@ -216,9 +222,9 @@ class Solver(object):
             raise IOError("solver state not found: %s" % state_file)
         with open(state_file, "rb") as f:
             it, history, learned = proto.unpack_solverstate(f.read(), with_learned_net=True)
+        self.engine.upload_history(history)      # (first: a state written by another solver type is refused before anything is loaded)
         if learned:
             self.net.copy_from(_resolve(learned, state_file))
-        self.engine.upload_history(history)
         self.engine.iter = int(it)
         self.log("Restoring previous solver status from %s (iteration %d)" % (state_file, it))
 
@@ -228,6 +234,7 @@ class Solver(object):
 
 SGDSolver = Solver
 AdamSolver = Solver
+NesterovSolver = AdaGradSolver = RMSPropSolver = AdaDeltaSolver = Solver
 
 
 def get_solver(solver_file: str, **kw) -> Solver:

@@ -2,8 +2,8 @@
 
 Stands in for `caffe train` (reference: train/train.sh:25-28) over the DetectNet training net
 (reference: models/train_val.prototxt with the Python data layer's tops, README.md:57-76) and the
-solver settings of the reference's solver.prototxt files (SGD with momentum, Adam, fixed / step
-learning-rate policy, L2 weight decay, per-blob lr_mult / decay_mult).
+settings a solver.prototxt may carry: every solver type and learning-rate policy of Caffe's
+SolverParameter, L1 / L2 weight decay, clip_gradients, iter_size, per-blob lr_mult / decay_mult.
 
 Data layout: every blob that receives a gradient has a gradient buffer with the SAME NHWC view
 geometry as its activation (so Concat / Slice / Dropout views need no backward kernel); all
@@ -28,7 +28,21 @@ F32 = np.float32
 
 
 class SolverParams:
-    """The subset of Caffe's SolverParameter the reference's solver.prototxt files use."""
+    """Caffe's SolverParameter as far as `caffe train` on one training net needs it: every solver type, every lr_policy, L1 / L2
+    regularisation, clip_gradients and iter_size (test nets are not run).
+
+        type          histories  update (g' = normalised, clipped gradient + regularisation; lr = rate(iter) * lr_mult)
+        SGD           1          h = momentum*h + lr*g' ; w -= h
+        Nesterov      1          h_old = h ; h = momentum*h + lr*g' ; w -= (1+momentum)*h - momentum*h_old
+        AdaGrad       1          h += g'^2 ; w -= lr*g' / (sqrt(h) + delta)                            (momentum must be 0)
+        RMSProp       1          h = rms_decay*h + (1-rms_decay)*g'^2 ; w -= lr*g' / (sqrt(h) + delta)  (momentum must be 0)
+        AdaDelta      2          h1 = momentum*h1 + (1-momentum)*g'^2 ; u = g'*sqrt((h2+delta)/(h1+delta)) ;
+                                 h2 = momentum*h2 + (1-momentum)*u^2 ; w -= lr*u
+        Adam          2          m, v moments ; w -= lr*sqrt(1-momentum2^t)/(1-momentum^t) * m / (sqrt(v) + delta)
+    """
+
+    KINDS = ("SGD", "NESTEROV", "ADAGRAD", "RMSPROP", "ADADELTA", "ADAM")
+    POLICIES = ("fixed", "step", "exp", "inv", "multistep", "poly", "sigmoid")
 
     def __init__(self, msg: Optional[proto.Msg] = None, **kw):
         g = (lambda k, d=None: msg.get(k, d)) if msg is not None else (lambda k, d=None: d)
@@ -36,28 +50,68 @@ class SolverParams:
         self.base_lr = float(kw.get("base_lr", g("base_lr", 0.01)))
         self.momentum = float(kw.get("momentum", g("momentum", 0.0)))
         self.momentum2 = float(kw.get("momentum2", g("momentum2", 0.999)))
+        self.rms_decay = float(kw.get("rms_decay", g("rms_decay", 0.99)))
         self.delta = float(kw.get("delta", g("delta", 1e-8)))
         self.weight_decay = float(kw.get("weight_decay", g("weight_decay", 0.0)))
+        self.regularization_type = str(kw.get("regularization_type", g("regularization_type", "L2")))
+        self.clip_gradients = float(kw.get("clip_gradients", g("clip_gradients", -1.0)))
         self.lr_policy = str(kw.get("lr_policy", g("lr_policy", "fixed")))
         self.gamma = float(kw.get("gamma", g("gamma", 0.1)))
+        self.power = float(kw.get("power", g("power", 0.0)))
         self.stepsize = int(kw.get("stepsize", g("stepsize", 1)))
+        self.stepvalue = sorted(int(v) for v in kw.get("stepvalue", msg.getall("stepvalue") if msg is not None else ()))
         self.max_iter = int(kw.get("max_iter", g("max_iter", 1)))
         self.iter_size = int(kw.get("iter_size", g("iter_size", 1)))
         self.display = int(kw.get("display", g("display", 0)))
         self.average_loss = int(kw.get("average_loss", g("average_loss", 1)))
         self.snapshot = int(kw.get("snapshot", g("snapshot", 0)))
         self.snapshot_prefix = str(kw.get("snapshot_prefix", g("snapshot_prefix", "snapshot")))
-        kind = kw.get("solver_type", g("solver_type", g("type", "SGD")))
+        # `type: "Nesterov"` (a string, any case) or the older enum `solver_type: NESTEROV`
+        kind = kw.get("solver_type", kw.get("type", g("solver_type", g("type", "SGD"))))
         self.kind = str(kind).upper()
-        if self.kind not in ("SGD", "ADAM"):
-            raise NotImplementedError("solver type %s (the reference uses SGD and ADAM)" % self.kind)
-        if self.lr_policy not in ("fixed", "step"):
-            raise NotImplementedError("lr_policy %s (the reference uses fixed and step)" % self.lr_policy)
+        if self.kind not in self.KINDS:
+            raise ValueError("type: unknown solver type %r (one of SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam)" % str(kind))
+        if self.lr_policy not in self.POLICIES:
+            raise ValueError("lr_policy: unknown policy %r (one of %s)" % (self.lr_policy, ", ".join(self.POLICIES)))
+        if self.regularization_type not in ("L1", "L2"):
+            raise ValueError("regularization_type: %r is neither \"L1\" nor \"L2\"" % self.regularization_type)
+        if self.kind in ("ADAGRAD", "RMSPROP") and self.momentum != 0.0:
+            raise ValueError("momentum: cannot be used with %s (it must be 0)" % {"ADAGRAD": "AdaGrad", "RMSPROP": "RMSProp"}[self.kind])
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError("momentum: %g is outside [0, 1)" % self.momentum)
+        if not 0.0 <= self.rms_decay < 1.0:
+            raise ValueError("rms_decay: %g is outside [0, 1)" % self.rms_decay)
+        if self.lr_policy == "multistep" and not self.stepvalue:
+            raise ValueError("stepvalue: lr_policy \"multistep\" needs at least one")
+        if self.lr_policy == "poly" and self.max_iter <= 0:
+            raise ValueError("max_iter: lr_policy \"poly\" needs max_iter > 0")
+        if self.lr_policy in ("step", "sigmoid") and self.stepsize <= 0:
+            raise ValueError("stepsize: lr_policy \"%s\" needs stepsize > 0" % self.lr_policy)
+        if self.iter_size < 1:
+            raise ValueError("iter_size: %d is not positive" % self.iter_size)
+
+    @property
+    def histories(self) -> int:
+        """History buffers per learnable blob (what a .solverstate of this type carries per blob)."""
+        return 2 if self.kind in ("ADAM", "ADADELTA") else 1
 
     def rate(self, it: int) -> float:
-        if self.lr_policy == "fixed":
-            return self.base_lr
-        return self.base_lr * self.gamma ** (it // self.stepsize)
+        """SGDSolver::GetLearningRate; multistep counts the stepvalues passed instead of carrying current_step, so a resumed run
+        needs no extra state."""
+        p, b = self.lr_policy, self.base_lr
+        if p == "fixed":
+            return b
+        if p == "step":
+            return b * self.gamma ** (it // self.stepsize)
+        if p == "exp":
+            return b * self.gamma ** it
+        if p == "inv":
+            return b * (1.0 + self.gamma * it) ** (-self.power)
+        if p == "multistep":
+            return b * self.gamma ** sum(1 for v in self.stepvalue if v <= it)
+        if p == "poly":
+            return b * (1.0 - float(it) / self.max_iter) ** self.power
+        return b / (1.0 + math.exp(-self.gamma * (it - self.stepsize)))
 
 
 class TrainEngine(Engine):
@@ -125,7 +179,16 @@ class TrainEngine(Engine):
         n = max(self.param_count, 4)
         self.grad_flat = DeviceBuffer(n * 4, zero=True)
         self.hist = DeviceBuffer(n * 4, zero=True)
-        self.hist2 = DeviceBuffer(n * 4, zero=True) if self.solver.kind == "ADAM" else None
+        self.hist2 = DeviceBuffer(n * 4, zero=True) if self.solver.histories == 2 else None
+        # iter_size > 1: every pass overwrites grad_flat; fcn_grad_accumulate_f32 sums the passes here, and the update reads this
+        self.acc_flat = DeviceBuffer(n * 4, zero=True) if self.solver.iter_size > 1 else None
+        self._pass = 0
+        self._pass_losses: List[Dict[str, float]] = []
+        # clip_gradients: the factor is computed and consumed on the device (no read-back inside a step)
+        self.clip_dev = self.clip_ws = None
+        if self.solver.clip_gradients > 0:
+            self.clip_dev = DeviceBuffer(16, zero=True)      # word 0: the factor, word 1: the sum of squares (for read_clip())
+            self.clip_ws = DeviceBuffer(int(L.load().fcn_grad_clip_workspace_bytes()), zero=False)
         segs = (L.SolverSeg * len(self.param_layout))(*[
             L.SolverSeg(e["offset"], e["count"], e["lr_mult"], e["decay_mult"]) for e in self.param_layout])
         self._segs_host = segs
@@ -689,21 +752,33 @@ class TrainEngine(Engine):
         L.check(lib.fcn_gen_targets_nhwc(t["rects"].ptr, t["labels"].ptr, t["offs"].ptr, n, c, gy, gx, t["stride"], t["thresh"],
                                          fg.ptr, fg.cstride, bb.ptr, sz.ptr, ob.ptr, cv.ptr, bb.cstride, self.stream))
 
-    def step(self, seed: Optional[int] = None, upload: bool = True) -> Dict[str, float]:
+    def step(self, seed: Optional[int] = None, upload: bool = True, feed: Optional[Callable[[int], None]] = None) -> Dict[str, float]:
         """Solver::Step for one iteration.  Inputs come from the input blobs' host arrays (upload=True), except label
         blobs staged with set_targets(), which are generated on the device; upload=False reuses what is already in HBM.
         Returns {loss blob: value} plus 'total_loss' = sum of loss_weight * value (what `caffe train` prints; also under
-        'loss' when no blob has that name)."""
-        self.step_begin(seed, upload)
-        return self.step_end()
+        'loss' when no blob has that name).
+        With iter_size k > 1 the iteration is k forward / backward passes whose gradients are summed before one update;
+        feed(j), when given, is called before pass j to put that pass's batch into the host arrays (without it every pass sees
+        what the caller filled in).  The losses returned are the means over the passes."""
+        out: Dict[str, float] = {}
+        for j in range(self.solver.iter_size):
+            if feed is not None:
+                feed(j)
+            self.step_begin(seed, upload)
+            out = self.step_end()
+        return out
 
     def step_begin(self, seed: Optional[int] = None, upload: bool = True) -> None:
         """Enqueue a whole iteration (inputs, targets, forward, backward, all-reduce, update, loss read-back) and return
-        without waiting: the caller may prepare the next batch while the device works (step_end() collects the losses)."""
+        without waiting: the caller may prepare the next batch while the device works (step_end() collects the losses).
+        With iter_size k > 1 one call is one of the k passes of the iteration: forward, backward and the accumulation of its
+        gradients; the last pass adds the all-reduce of the accumulated buffer, clipping and the update."""
         lib = L.load()
         with self.lock:
             L.call("fcn_init", self.device)
-            self.dropout_seed = int(seed if seed is not None else self.iter) & 0xFFFFFFFF
+            k = self.solver.iter_size
+            last = self._pass == k - 1
+            self.dropout_seed = int(seed if seed is not None else self.iter * k + self._pass) & 0xFFFFFFFF
             dev_targets = getattr(self, "_tgt", None) is not None and self._tgt.get("pending")
             fed = set(self.device_fed)      # inputs some producer already wrote in HBM (device scene renderer)
             if upload:
@@ -737,6 +812,8 @@ class TrainEngine(Engine):
                     L.check(lib.fcn_stream_wait_event(side, ev))
                     op.run(side)
                     side_used = True
+                elif k > 1:
+                    continue        # (the ranks exchange the ACCUMULATED buffer, once, after the last pass)
                 else:
                     for b in item:
                         # this bucket's gradients are final: sum them across ranks on the side stream
@@ -757,12 +834,22 @@ class TrainEngine(Engine):
                         elif world > 1:
                             self._replicas_diverged = True
                         L.check(lib.fcn_event_record(b["done"], self.comm_stream))
-            for b in self.buckets:
-                L.check(lib.fcn_stream_wait_event(self.stream, b["done"]))
+            if k == 1:
+                for b in self.buckets:
+                    L.check(lib.fcn_stream_wait_event(self.stream, b["done"]))
             if side_used:
                 L.check(lib.fcn_event_record(self._side_done, side))
                 L.check(lib.fcn_stream_wait_event(self.stream, self._side_done))
-            self.apply_update(1.0 / (world * self.solver.iter_size))
+            if k > 1:
+                L.check(lib.fcn_grad_accumulate_f32(self.acc_flat.ptr, self.grad_flat.ptr, max(self.param_count, 4), int(self._pass == 0),
+                                                    self.stream))
+                if last and self.comm is not None and world > 1:
+                    if getattr(self, "comm_dry", False):
+                        self._replicas_diverged = True
+                    else:
+                        self.comm.all_reduce_sum(self.acc_flat.ptr, max(self.param_count, 4), self.stream)
+            if last:
+                self.apply_update(1.0 / (world * k), 1.0 / world)
             for name, arr in self.loss_host.items():
                 L.check(lib.fcn_memcpy_d2h_async(arr.ctypes.data, self.blobs[name].buf.ptr, 4, self.stream))
             if getattr(self, "_step_done", None) is None:
@@ -810,9 +897,19 @@ class TrainEngine(Engine):
             for nm in self._in_flight:
                 self.blobs[nm].host_valid = False          # generated in HBM, never on the host
             out = {k: float(v[0]) for k, v in self.loss_host.items()}
+            if self.solver.iter_size > 1:
+                # one pass of an accumulated iteration: what is displayed and averaged is the mean over its passes, and the
+                # iteration counter moves with the update, after the last of them
+                self._pass_losses.append(out)
+                out = {k: float(sum(p[k] for p in self._pass_losses) / len(self._pass_losses)) for k in out}
+                self._pass += 1
+                if self._pass == self.solver.iter_size:
+                    self._pass, self._pass_losses = 0, []
+                    self.iter += 1
+            else:
+                self.iter += 1
             out["total_loss"] = float(sum(self.loss_blobs[k] * out[k] for k in self.loss_blobs))
             out.setdefault("loss", out["total_loss"])      # shorthand, unless a blob is itself called "loss" (train/fcn_bbox)
-            self.iter += 1
             return out
 
     # kinds whose launch arguments change from step to step (the dropout seed): they stay ordinary launches
@@ -912,16 +1009,40 @@ class TrainEngine(Engine):
             self._side_stream = None
         super().close()
 
-    def apply_update(self, grad_scale: float) -> None:
+    def apply_update(self, grad_scale: float, norm_scale: float = 1.0) -> None:
+        """ClipGradients + Normalize + Regularize + ComputeUpdateValue + Update of Caffe's solvers on the flat buffers.
+        grad_scale: 1 / (ranks * iter_size); norm_scale: 1 / ranks (clipping sees the gradient summed over iter_size, averaged
+        over the ranks).  SGD and Adam with L2 and without clipping take the two original entry points."""
         sp, lib = self.solver, L.load()
         rate = sp.rate(self.iter)
         n = len(self.param_layout)
-        if sp.kind == "ADAM":
-            L.check(lib.fcn_adam_update_f32(self.param_flat.ptr, self.grad_flat.ptr, self.hist.ptr, self.hist2.ptr, self.segs_dev.ptr, n, rate,
+        g = self.acc_flat if self.acc_flat is not None else self.grad_flat
+        l1 = sp.regularization_type == "L1"
+        clip = None
+        if self.clip_dev is not None:
+            clip = self.clip_dev.ptr
+            L.check(lib.fcn_grad_clip_f32(g.ptr, self.segs_dev.ptr, n, sp.clip_gradients, norm_scale, clip, clip + 4, self.clip_ws.ptr,
+                                          self.stream))
+        if sp.kind == "ADAM" and not l1 and clip is None:
+            L.check(lib.fcn_adam_update_f32(self.param_flat.ptr, g.ptr, self.hist.ptr, self.hist2.ptr, self.segs_dev.ptr, n, rate,
                                             sp.momentum, sp.momentum2, sp.delta, sp.weight_decay, self.iter + 1, grad_scale, self.stream))
-        else:
-            L.check(lib.fcn_sgd_update_f32(self.param_flat.ptr, self.grad_flat.ptr, self.hist.ptr, self.segs_dev.ptr, n, rate, sp.momentum,
+        elif sp.kind == "SGD" and not l1 and clip is None:
+            L.check(lib.fcn_sgd_update_f32(self.param_flat.ptr, g.ptr, self.hist.ptr, self.segs_dev.ptr, n, rate, sp.momentum,
                                            sp.weight_decay, grad_scale, self.stream))
+        else:
+            L.check(lib.fcn_solver_update_f32(L.SOLVER_KINDS[sp.kind], self.param_flat.ptr, g.ptr, self.hist.ptr,
+                                              self.hist2.ptr if self.hist2 is not None else None, self.segs_dev.ptr, n, rate, sp.momentum,
+                                              sp.momentum2, sp.rms_decay, sp.delta, sp.weight_decay, L.REG_L1 if l1 else L.REG_L2,
+                                              self.iter + 1, grad_scale, clip, self.stream))
+
+    def read_clip(self) -> Tuple[float, float]:
+        """(clip factor, sum of squares of the gradient) of the last update, or (1.0, nan) when clip_gradients is off (debug / tests)."""
+        if self.clip_dev is None:
+            return 1.0, float("nan")
+        out = np.empty(2, F32)
+        L.call("fcn_memcpy_d2h_async", out.ctypes.data, self.clip_dev.ptr, out.nbytes, self.stream)
+        L.call("fcn_stream_sync", self.stream)
+        return float(out[0]), float(out[1])
 
     # ------------------------------------------------------------------ parameters back to Caffe layout
     def download_params(self) -> Dict[str, List[np.ndarray]]:
@@ -932,8 +1053,10 @@ class TrainEngine(Engine):
         return self._unpack(flat)
 
     def download_grads(self) -> Dict[str, List[np.ndarray]]:
+        """Parameter gradients of the last iteration: with iter_size > 1 their sum over its passes (not divided by iter_size)."""
         flat = np.empty(max(self.param_count, 4), F32)
-        L.call("fcn_memcpy_d2h_async", flat.ctypes.data, self.grad_flat.ptr, flat.nbytes, self.stream)
+        src = self.acc_flat if self.acc_flat is not None else self.grad_flat
+        L.call("fcn_memcpy_d2h_async", flat.ctypes.data, src.ptr, flat.nbytes, self.stream)
         L.call("fcn_stream_sync", self.stream)
         return self._unpack(flat)
 
@@ -965,7 +1088,8 @@ class TrainEngine(Engine):
         return flat
 
     def download_history(self) -> List[np.ndarray]:
-        """Solver history in Caffe's order: one blob per learnable parameter (SGD momentum / Adam m), then Adam's v blobs."""
+        """Solver history in Caffe's order: one blob per learnable parameter (SGD / Nesterov momentum, the AdaGrad / RMSProp sums,
+        Adam's m, AdaDelta's gradient history), then for Adam and AdaDelta as many again (v / the update history)."""
         out: List[np.ndarray] = []
         for buf in (self.hist, self.hist2):
             if buf is None:
@@ -982,7 +1106,16 @@ class TrainEngine(Engine):
         bufs = [b for b in (self.hist, self.hist2) if b is not None]
         per_buf = sum(len(self.params_host[l.name]) for l in self.spec.param_layers())
         if len(history) != per_buf * len(bufs):
-            raise ValueError("solver state holds %d history blobs, this solver needs %d" % (len(history), per_buf * len(bufs)))
+            raise ValueError("solver state holds %d history blobs, a %s solver over this net needs %d" % (
+                len(history), self.solver.kind, per_buf * len(bufs)))
+        k = 0
+        for _ in bufs:
+            for l in self.spec.param_layers():
+                for a in self.params_host[l.name]:
+                    if np.asarray(history[k]).size != a.size:
+                        raise ValueError("solver state: history blob %d has %d values, blob of layer %s has %d" % (
+                            k, np.asarray(history[k]).size, l.name, a.size))
+                    k += 1
         it = iter(history)
         for buf in bufs:
             per = {l.name: [next(it) for _ in self.params_host[l.name]] for l in self.spec.param_layers()}

@@ -509,6 +509,40 @@ int  fcn_sgd_update_f32(float* w, const float* g, float* hist, const fcn_solver_
 /* Adam (Caffe AdamSolver): m,v moments, w -= rate*lr_mult*sqrt(1-b2^t)/(1-b1^t) * m/(sqrt(v)+delta) */
 int  fcn_adam_update_f32(float* w, const float* g, float* m, float* v, const fcn_solver_seg* d_segs, int nseg, float rate,
                          float beta1, float beta2, float delta, float weight_decay, int t, float grad_scale, fcn_stream_t s);
+/* Every solver type of Caffe's SolverParameter in one entry point (public BVLC Caffe sgd_solvers, restated).  Per element of a segment,
+ * with clip = *d_clip (1.0 when d_clip is NULL), lr = rate*lr_mult and
+ *   g' = g*grad_scale*clip + weight_decay*decay_mult * (w for FCN_REG_L2, sign(w) for FCN_REG_L1):
+ *   SGD       h1 = momentum*h1 + lr*g' ;  w -= h1
+ *   NESTEROV  h_old = h1 ; h1 = momentum*h1 + lr*g' ;  w -= (1+momentum)*h1 - momentum*h_old
+ *   ADAGRAD   h1 += g'^2 ;  w -= lr*g' / (sqrt(h1) + delta)
+ *   RMSPROP   h1 = rms_decay*h1 + (1-rms_decay)*g'^2 ;  w -= lr*g' / (sqrt(h1) + delta)
+ *   ADADELTA  h1 = momentum*h1 + (1-momentum)*g'^2 ; u = g'*sqrt((h2+delta)/(h1+delta)) ; h2 = momentum*h2 + (1-momentum)*u^2 ;  w -= lr*u
+ *   ADAM      as fcn_adam_update_f32 with beta1 = momentum, beta2 = momentum2, step t
+ * h2 is read for ADADELTA and ADAM only (NULL otherwise).  Segments with lr_mult == 0 and the elements outside every segment are
+ * neither read into a result nor written.  With FCN_REG_L2 and d_clip == NULL, SGD and ADAM give the bits of fcn_sgd_update_f32 /
+ * fcn_adam_update_f32.  FCN_E_ARG: null pointer, nseg outside 1 .. 65535, unknown kind / regularization, momentum or rms_decay
+ * outside [0, 1) (ADAM: momentum2 too, t < 1); FCN_E_ALIGN: w, g, h1, h2 or d_segs not 16-byte aligned.  Checked before any HIP call. */
+#define FCN_SOLVER_SGD      0
+#define FCN_SOLVER_NESTEROV 1
+#define FCN_SOLVER_ADAGRAD  2
+#define FCN_SOLVER_RMSPROP  3
+#define FCN_SOLVER_ADADELTA 4
+#define FCN_SOLVER_ADAM     5
+#define FCN_REG_L2 0
+#define FCN_REG_L1 1
+int  fcn_solver_update_f32(int kind, float* w, const float* g, float* h1, float* h2, const fcn_solver_seg* d_segs, int nseg, float rate,
+                           float momentum, float momentum2, float rms_decay, float delta, float weight_decay, int regularization, int t,
+                           float grad_scale, const float* d_clip, fcn_stream_t s);
+/* Gradient clipping (Caffe's clip_gradients) without a host read-back: *d_clip = min(1, clip_gradients / (norm_scale * sqrt(sumsq))),
+ * sumsq = the sum of g^2 over every segment (also written to *d_sumsq unless NULL); exactly 1.0 when the norm does not exceed the
+ * threshold.  norm_scale: what the buffer is a multiple of (1 / ranks after a summing all-reduce).  The sum is a fixed-order
+ * two-stage tree in float64 (per-workgroup partials in d_workspace, fcn_grad_clip_workspace_bytes() bytes, 16-byte aligned, then
+ * one workgroup in index order; no atomics): the same inputs give the same bits on every run.  Elements outside the segments are not read. */
+size_t fcn_grad_clip_workspace_bytes(void);
+int  fcn_grad_clip_f32(const float* g, const fcn_solver_seg* d_segs, int nseg, float clip_gradients, float norm_scale, float* d_clip,
+                       float* d_sumsq, void* d_workspace, fcn_stream_t s);
+/* Gradient accumulation of iter_size > 1: acc = first ? g : acc + g over count floats (both 16-byte aligned), one launch */
+int  fcn_grad_accumulate_f32(float* acc, const float* g, size_t count, int first, fcn_stream_t s);
 
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
