@@ -1,9 +1,11 @@
 #!/usr/bin/python3
 """`caffe` command-line tool over the MI355X engine — the binary the reference's training script runs
 (reference: train/train.sh:25-28, `$CAFFE_ROOT/build/tools/caffe train --solver=... --gpu=0 --weights=...`).
-Point CAFFE_ROOT at <repo>/fcn_object_detector_amd and that script works unchanged.
+The build installs this file as <repo>/fcn_object_detector_amd/build/tools/caffe (csrc/Makefile, beside libfcnhip.so, which the
+tool cannot run without): point CAFFE_ROOT at <repo>/fcn_object_detector_amd and that script works unchanged.
 
     caffe train --solver=solver.prototxt [--weights=a.caffemodel[,b.caffemodel]] [--snapshot=x.solverstate] [--gpu=0|0,1,..|all]
+    caffe test --model=train_val.prototxt --weights=a.caffemodel [--iterations=50] [--gpu=0]
     caffe time --model=deploy.prototxt [--iterations=50] [--gpu=0]
     caffe device_query [--gpu=0]
 
@@ -14,8 +16,9 @@ import os
 import subprocess
 import sys
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_REPO = os.path.dirname(os.path.dirname(os.path.dirname(_HERE)))
+_REPO = os.path.dirname(os.path.abspath(__file__))      # (the installed copy lies three levels below the repository, this file one)
+while not os.path.isdir(os.path.join(_REPO, "fcn_object_detector_amd", "python")) and os.path.dirname(_REPO) != _REPO:
+    _REPO = os.path.dirname(_REPO)
 for p in (_REPO, os.path.join(_REPO, "fcn_object_detector_amd", "python")):
     if p not in sys.path:
         sys.path.insert(0, p)
@@ -99,6 +102,45 @@ def spawn_ranks(gpus):
     return dp.spawn_ranks(__file__, sys.argv[1:], gpus, {})
 
 
+def cmd_test(flags):
+    """Score a snapshot: `iterations` batches of the model's TEST phase, every output blob summed on the device (the solver's test
+    pass), Caffe's lines per batch and for the means.  $FCN_AUTOTUNE=0 keeps the default launch plan (repeatable bits)."""
+    if "model" not in flags:
+        sys.stderr.write("Need a model definition to score.\n")
+        return 1
+    if "weights" not in flags:
+        sys.stderr.write("Need model weights to score.\n")
+        return 1
+    for f in (flags["model"], flags["weights"]):
+        if not os.path.isfile(f):
+            sys.stderr.write("file not found: %s\n" % f)
+            return 1
+    from fcn_object_detector_amd import lib as L
+    from fcn_object_detector_amd.solver import TestNet, _log
+    iters = int(flags.get("iterations", 50))
+    device = gpu_list(flags.get("gpu"))[0]
+    L.call("fcn_init", device)
+    net = TestNet(flags["model"], device=device, autotune=os.environ.get("FCN_AUTOTUNE", "1") != "0")
+    net.copy_from(flags["weights"], log=_log)
+    _log("Running for %d iterations." % iters)
+    weights = net.engine.loss_blobs
+    loss = [0.0]
+
+    def per_batch(k, out):
+        for nm in net.outputs:
+            for v in out[nm].reshape(-1):
+                _log("Batch %d, %s = %g" % (k, nm, v))
+            if nm in weights:
+                loss[0] += weights[nm] * float(out[nm].sum())
+
+    sums = net.run_pass(iters, per_batch)
+    _log("Loss: %g" % (loss[0] / iters))
+    for line in net.lines(sums, iters, "%.0s%s = %g"):
+        _log(line)
+    net.close()
+    return 0
+
+
 def cmd_time(flags):
     import numpy as np
     from fcn_object_detector_amd import lib as L, proto
@@ -137,10 +179,10 @@ def cmd_device_query(flags):
 
 def main(argv):
     pos, flags = parse_flags(argv)
-    if not pos or pos[0] not in ("train", "time", "device_query"):
+    if not pos or pos[0] not in ("train", "test", "time", "device_query"):
         sys.stderr.write("usage:\n" + USAGE + "\n")
         return 1
-    return {"train": cmd_train, "time": cmd_time, "device_query": cmd_device_query}[pos[0]](flags)
+    return {"train": cmd_train, "test": cmd_test, "time": cmd_time, "device_query": cmd_device_query}[pos[0]](flags)
 
 
 if __name__ == "__main__":

@@ -155,9 +155,21 @@ class Engine:
     def __init__(self, spec: NetSpec, data_shapes: Optional[Dict[str, Tuple[int, ...]]] = None,
                  params: Optional[Dict[str, List[np.ndarray]]] = None, device: int = 0,
                  fuse: bool = True, group_convs: bool = True, autotune: bool = True, dtype: str = "f32",
-                 tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None, tune_streams: Optional[int] = None):
+                 tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None, tune_streams: Optional[int] = None,
+                 share_params: Optional["Engine"] = None, score_outputs: bool = False):
+        """share_params: Net::ShareTrainedLayersWith - every parameter layer whose name the given engine also has reads that
+        engine's flat parameter buffer in place (no copy; a solver step is visible to the next forward of this engine).
+        score_outputs: the engine is built for scoring (Solver::Test, `caffe test`): every forward also adds each output blob
+        to a device accumulator (score_begin() / forward_score() / score_read())."""
         if dtype not in ("f32", "f16"):
             raise ValueError("dtype must be 'f32' or 'f16'")
+        if share_params is not None and (dtype != "f32" or share_params.f16):
+            raise NotImplementedError("share_params: only between float32 engines (a half-float engine packs its weights differently)")
+        self._share_from = share_params
+        self.shared_layers: set = set()
+        self.score_outputs = bool(score_outputs)
+        self.score_acc: Dict[str, DeviceBuffer] = {}
+        self.graph_score: Optional[int] = None
         if dtype == "f16" and spec.phase != "TEST":
             raise NotImplementedError("the half-float path is inference only (BASELINE configs[4])")
         self.dtype, self.f16 = dtype, dtype == "f16"      # f16: activations / weights stored as halves, f32 accumulation
@@ -316,7 +328,7 @@ class Engine:
                 blob.buf = DeviceBuffer(blob.pixels * blob.cstride * blob.esize)
             else:
                 blob.cstride = 1
-                blob.buf = DeviceBuffer(16)
+                blob.buf = DeviceBuffer(max(16, 4 * int(np.prod(blob.shape)) if blob.shape else 16))
         for name in alias:
             root, off = name, 0
             total_shift = 0.0
@@ -355,7 +367,24 @@ class Engine:
             params = fill_params(self.spec, seed=0)
         self.param_layout: List[dict] = []
         off = 0
+        src = self._share_from
+        if src is not None:
+            # shared layers: views INTO the source's flat buffer (the packed bytes of a float32 layer do not depend on the phase:
+            # OHWI with Cin padded to 4 / the depthwise deconvolution's filters as they are).  Holding the source's DeviceBuffers
+            # keeps the storage alive whichever engine is closed or collected first; this engine never writes or frees it.
+            self._shared_keep = [src.param_flat] + list(getattr(src, "_shared_keep", []))
+            for l in self.spec.param_layers():
+                if l.name not in src.params_dev:
+                    continue
+                mine, theirs = [tuple(x) for x in self.spec.param_shapes[l.name]], [tuple(x) for x in src.spec.param_shapes[l.name]]
+                if mine != theirs:
+                    raise ValueError("share_params: layer %s has blobs %s here and %s in the source net" % (l.name, mine, theirs))
+                self.shared_layers.add(l.name)
+                self.params_host[l.name] = src.params_host[l.name]
+                self.params_dev[l.name] = [DevView(v.ptr, v.nbytes) for v in src.params_dev[l.name]]
         for l in self.spec.param_layers():
+            if l.name in self.shared_layers:
+                continue
             shapes = self.spec.param_shapes[l.name]
             blobs = params.get(l.name)
             if blobs is None:
@@ -382,7 +411,8 @@ class Engine:
         for e in self.param_layout:
             self.params_dev.setdefault(e["layer"], []).append(DevView(self.param_flat.ptr + 4 * e["offset"], e["nbytes"]))
         for l in self.spec.param_layers():
-            self._upload_params(l)
+            if l.name not in self.shared_layers:
+                self._upload_params(l)
 
     def _packed_weight(self, l: Layer) -> np.ndarray:
         w = self.params_host[l.name][0]
@@ -407,6 +437,8 @@ class Engine:
         raise NotImplementedError(l.type)
 
     def _upload_params(self, l: Layer) -> None:
+        if l.name in self.shared_layers:
+            raise RuntimeError("layer %s reads the parameters of another engine (share_params): set them there" % l.name)
         host = self.params_host[l.name]
         packed = [self._packed_weight(l)] + [np.ascontiguousarray(h) for h in host[1:]]
         devs = self.params_dev[l.name]
@@ -417,9 +449,25 @@ class Engine:
     def set_params(self, layer: str, blobs: Sequence[np.ndarray]) -> None:
         """Replace a layer's parameter blobs (Caffe layouts: conv OIHW + bias) and re-upload."""
         lay = next(l for l in self.spec.layers if l.name == layer)
+        if layer in self.shared_layers:
+            raise RuntimeError("layer %s reads the parameters of another engine (share_params): set them there" % layer)
         shapes = self.spec.param_shapes[layer]
         self.params_host[layer] = [np.ascontiguousarray(b, dtype=F32).reshape(s).copy() for b, s in zip(blobs, shapes)]
         self._upload_params(lay)
+
+    def read_param(self, layer: str, index: int) -> np.ndarray:
+        """Caffe-layout host copy (conv: OIHW, bias) of one parameter blob as the device holds it now - for a shared layer, the
+        source engine's current weights."""
+        with self.lock:
+            v, shp = self.params_dev[layer][index], self.params_host[layer][index].shape
+            raw = np.empty(v.nbytes // 4, F32)
+            L.call("fcn_memcpy_d2h_async", raw.ctypes.data, v.ptr, raw.nbytes, self.stream)
+            L.call("fcn_stream_sync", self.stream)
+        lay = next(l for l in self.spec.layers if l.name == layer)
+        if index == 0 and lay.type == "Convolution":
+            co, ci, kh, kw = shp
+            return np.ascontiguousarray(raw.reshape(co, kh, kw, -1)[..., :ci].transpose(0, 3, 1, 2))
+        return raw.reshape(shp).copy()
 
     # ------------------------------------------------------------------ plan
     def _conv_desc(self, l: Layer, fused_relu: bool, sig_top: Optional[str]) -> L.ConvDesc:
@@ -610,6 +658,26 @@ class Engine:
                 self.ops.extend(tasks[i]["ops"])
         emit_convs(pending, pending_pools)
         self.levels = max(levels) + 1 if levels else 0
+        if self.score_outputs:
+            self._emit_score_ops()
+
+    def _emit_score_ops(self) -> None:
+        """Solver::Test's `test_score[idx] += result`, on the device: one accumulator per output blob (NCHW order, float32) and one
+        fcn_score_accumulate_f32 launch per blob behind the last layer, inside whatever graph the forward is captured into."""
+        lib = L.load()
+        for nm in self.outputs:
+            b = self.blobs[nm]
+            if b.esize != 4 or b.lazy_shift:
+                raise NotImplementedError("score_outputs: output blob %s is not a plain float32 blob" % nm)
+            count = int(np.prod(b.shape)) if b.shape else 1
+            acc = DeviceBuffer(max(4 * count, 16), zero=True)
+            self.score_acc[nm] = acc
+            if len(b.shape) == 4:
+                n, c, h, w = b.shape
+                args = (acc.ptr, b.buf.ptr, n, h * w, c, b.cstride, b.coffset)
+            else:
+                args = (acc.ptr, b.ptr, 1, 1, count, count, 0)
+            self.ops.append(Op("score", "score:" + nm, lambda st, a=args: L.check(lib.fcn_score_accumulate_f32(*a, st)), 0.0, 12.0 * count))
 
     def _plan_tail(self, tasks: List[dict], levels: List[int], hit) -> Optional[dict]:
         """The detection heads (cvg/classifier + bbox/regressor of models/deploy.prototxt: 4 + 16 outputs over inception_5b/output) as the
@@ -1277,6 +1345,22 @@ class Engine:
             out.append(Op("loss", l.name, lambda st: L.check(lib.fcn_softmax_loss_f32(
                 xb.ptr, lab.ptr, da, lb.buf.ptr, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, normalize,
                 0 if ign is None else 1, 0 if ign is None else int(ign), weight, ws.ptr, st)), 0.0, 8.0 * xb.pixels * xb.channels))
+        elif t == "Accuracy":
+            if self.f16:
+                raise NotImplementedError("f16 engine: layer type Accuracy (%s) has no half-float kernel" % l.name)
+            xb, lab, ab = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
+            if lab.channels != 1 or lab.pixels != xb.pixels:
+                raise NotImplementedError("Accuracy %s: needs one label per pixel of the score blob" % l.name)
+            ap = l.sub("accuracy_param")
+            if int(ap.get("axis", 1)) != 1:
+                raise NotImplementedError("Accuracy over an axis other than channels (layer %s)" % l.name)
+            top_k, ign = int(ap.get("top_k", 1)), ap.get("ignore_label", None)
+            per_class = B[l.tops[1]].ptr if len(l.tops) > 1 else None
+            ws = DeviceBuffer(int(lib.fcn_accuracy_workspace_bytes()), zero=True)
+            self._keep.append(ws)
+            out.append(Op("accuracy", l.name, lambda st: L.check(lib.fcn_accuracy_f32(
+                xb.ptr, lab.ptr, ab.ptr, per_class, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, top_k,
+                0 if ign is None else 1, 0 if ign is None else int(ign), ws.ptr, st)), 0.0, 4.0 * xb.pixels * (xb.channels + 1)))
         elif t == "Slice":
             off = 0
             xb = B[l.bottoms[0]]
@@ -1452,12 +1536,114 @@ class Engine:
                 b.host_valid = True
             return host
 
+    # ------------------------------------------------------------------ label grids generated on the device
+    # blob names of the DetectNet label tops, in the order DataArgumentationLayer emits them (data_argumentation_layer.py:67-72)
+    LABEL_TOPS = ("coverage-label", "bbox-label", "size-block", "obj-block", "coverage-block")
+
+    def set_targets(self, rects: Sequence[Sequence[Sequence[int]]], labels: Sequence[Sequence[int]], stride: int,
+                    iou_thresh: float = 0.1, tops: Sequence[str] = LABEL_TOPS) -> None:
+        """Stage the ground-truth boxes of the next step; the label blobs are then generated ON THE DEVICE inside step() / forward_score()
+        (fcn_gen_targets_nhwc: bounding_box_parameterized_labels of the reference) instead of being uploaded."""
+        fg = self.blobs[tops[0]]
+        n, c, gy, gx = fg.shape
+        if len(rects) != n or len(labels) != n:
+            raise ValueError("need boxes for %d images" % n)
+        offs = np.zeros(n + 1, np.int32)
+        flat_r, flat_l = [], []
+        for i, (rs, ls) in enumerate(zip(rects, labels)):
+            for r, lab in zip(rs, ls):
+                if not 0 <= int(lab) < c:
+                    raise IndexError("label %d outside [0, %d)" % (lab, c))
+                flat_r.append([int(v) for v in r])
+                flat_l.append(int(lab))
+            offs[i + 1] = len(flat_r)
+        if not hasattr(self, "_tgt"):
+            cap = max(64 * n, 256)
+            self._tgt = dict(cap=cap, rects=DeviceBuffer(cap * 16, zero=True), labels=DeviceBuffer(cap * 4, zero=True),
+                             offs=DeviceBuffer((n + 1) * 4, zero=True))
+        if len(flat_r) > self._tgt["cap"]:
+            raise ValueError("too many boxes in one batch (%d > %d)" % (len(flat_r), self._tgt["cap"]))
+        self._tgt.update(h_rects=np.asarray(flat_r, np.int32).reshape(-1, 4), h_labels=np.asarray(flat_l, np.int32), h_offs=offs,
+                         stride=int(stride), thresh=float(iou_thresh), tops=tuple(tops), pending=True)
+
+    def _enqueue_targets(self) -> None:
+        t, lib = self._tgt, L.load()
+        if t["h_rects"].size:
+            L.check(lib.fcn_memcpy_h2d_async(t["rects"].ptr, t["h_rects"].ctypes.data, t["h_rects"].nbytes, self.stream))
+            L.check(lib.fcn_memcpy_h2d_async(t["labels"].ptr, t["h_labels"].ctypes.data, t["h_labels"].nbytes, self.stream))
+        L.check(lib.fcn_memcpy_h2d_async(t["offs"].ptr, t["h_offs"].ctypes.data, t["h_offs"].nbytes, self.stream))
+        fg, bb, sz, ob, cv = (self.blobs[nm] for nm in t["tops"])
+        n, c, gy, gx = fg.shape
+        for b in (bb, sz, ob, cv):
+            if b.coffset or b.cstride != bb.cstride:
+                raise NotImplementedError("label blobs must be plain buffers of one geometry")
+        L.check(lib.fcn_gen_targets_nhwc(t["rects"].ptr, t["labels"].ptr, t["offs"].ptr, n, c, gy, gx, t["stride"], t["thresh"],
+                                         fg.ptr, fg.cstride, bb.ptr, sz.ptr, ob.ptr, cv.ptr, bb.cstride, self.stream))
+
+
+    # ------------------------------------------------------------------ scoring (Solver::Test, `caffe test`)
+    def score_begin(self, io: bool = False) -> None:
+        """Start of a test pass: zero every accumulator (one fcn_memset_async each) on the engine's stream.  The forward graph is
+        captured first: its warm-up launches would otherwise land in the accumulators.  io=True: the pass will run through
+        forward() (outputs downloaded per batch, what `caffe test` prints) instead of forward_score()."""
+        if not self.score_outputs:
+            raise RuntimeError("engine was not built with score_outputs=True")
+        with self.lock:
+            L.call("fcn_init", self.device)
+            for nm in self.inputs:
+                if nm not in self.device_fed:
+                    self.host_array(nm)
+                    if len(self.blobs[nm].shape) == 4:
+                        self._stage(nm)
+            if os.environ.get("FCN_NO_GRAPH", "0") in ("", "0"):
+                if io and self.graph_io is None:
+                    for nm in self.outputs:
+                        self.host_array(nm)
+                    self.graph_io = self._capture(with_io=True)
+                elif not io and self.graph_score is None:
+                    self.graph_score = self._capture(with_io=True, download=False)
+            for acc in self.score_acc.values():
+                L.call("fcn_memset_async", acc.ptr, 0, acc.nbytes, self.stream)
+            self.score_forwards = 0
+
+    def forward_score(self, uploaded_event=None) -> None:
+        """One forward of a test pass, enqueued without waiting: copies of the host-fed inputs, staged label grids, then ONE graph launch
+        (layout kernels of the inputs, every layer, the accumulation of every output blob).  Nothing is read back.  uploaded_event is
+        recorded behind the input copies: the host arrays may be refilled once it has passed."""
+        with self.lock:
+            for nm in self.inputs:      # (label tops generated by set_targets() belong in device_fed, like rendered scenes)
+                if nm not in self.device_fed:
+                    self._upload_copy(nm, self.stream)
+            if uploaded_event is not None:
+                L.call("fcn_event_record", uploaded_event, self.stream)
+            if getattr(self, "_tgt", None) is not None and self._tgt.get("pending"):
+                self._enqueue_targets()
+            if self.graph_score is not None:
+                L.call("fcn_graph_launch", self.graph_score, self.stream)
+            else:
+                for nm in self.inputs:
+                    if nm not in self.device_fed:
+                        self._upload_convert(nm, self.stream)
+                self.run_ops(self.stream)
+            for b in self.blobs.values():
+                b.host_valid = False
+            self.score_forwards += 1
+
+    def score_read(self) -> Dict[str, np.ndarray]:
+        """End of a test pass: the one read-back.  {output blob: float32 sums over the forwards since score_begin(), blob shape}."""
+        with self.lock:
+            out = {nm: np.empty(self.blobs[nm].shape, F32) for nm in self.outputs}
+            for nm, a in out.items():
+                L.call("fcn_memcpy_d2h_async", a.ctypes.data, self.score_acc[nm].ptr, a.nbytes, self.stream)
+            L.call("fcn_stream_sync", self.stream)
+            return out
+
     # ------------------------------------------------------------------ execution
     def run_ops(self, stream: Optional[int]) -> None:
         for op in self.ops:
             op.run(stream)
 
-    def _capture(self, with_io: bool) -> int:
+    def _capture(self, with_io: bool, download: bool = True) -> int:
         if with_io:                      # nothing may allocate while the stream is capturing
             for nm in list(self.inputs) + list(self.outputs):
                 self.host_array(nm)
@@ -1486,7 +1672,7 @@ class Engine:
                     if nm not in self.device_fed:
                         self._upload_convert(nm, self.stream)
             self.run_ops(self.stream)
-            if with_io:
+            if with_io and download:
                 self._download_convert_all(self.stream)
         finally:
             g = C.c_void_p()
@@ -1678,10 +1864,10 @@ class Engine:
     def close(self) -> None:
         with self.lock:
             lib = L.load()
-            for g in (self.graph_io, self.graph_core):
+            for g in (self.graph_io, self.graph_core, self.graph_score):
                 if g:
                     lib.fcn_graph_destroy(g)
-            self.graph_io = self.graph_core = None
+            self.graph_io = self.graph_core = self.graph_score = None
             if self.stream:
                 lib.fcn_stream_sync(self.stream)
                 lib.fcn_stream_destroy(self.stream)

@@ -211,6 +211,9 @@ PROTOTYPES = {
     "fcn_grad_clip_workspace_bytes": (_sz, []),
     "fcn_grad_clip_f32": (_i, [_vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "fcn_grad_accumulate_f32": (_i, [_vp, _vp, _sz, _i, _vp]),
+    "fcn_score_accumulate_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fcn_accuracy_workspace_bytes": (_sz, []),
+    "fcn_accuracy_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

@@ -129,12 +129,24 @@ def googlenet_detectnet_deploy(batch: int = 1, height: int = 448, width: int = 4
     return w.text()
 
 
-def googlenet_detectnet_train(module: str, layer: str, param_str: str, num_classes: int = 1) -> str:
-    """Training net: Python data layer (6 tops) -> GoogLeNet body -> masked/normalised L1 + Euclidean losses."""
+def _python_data_layers(w: _Writer, name: str, tops: List[str], module: str, layer: str, param_str: str,
+                        test_param_str: Optional[str]) -> None:
+    """The Python data layer; with test_param_str twice, `include { phase: TRAIN }` with param_str and `include { phase: TEST }`
+    with test_param_str - the validation copy with its own geometry of train/bounding_box/train_val.prototxt lines 1-36."""
+    body = "  python_param {\n    module: '%s'\n    layer: '%s'\n    param_str: '%s'\n  }"
+    if test_param_str is None:
+        w.layer(name, "Python", [], tops, body % (module, layer, param_str), quote="'")
+        return
+    for phase, ps in (("TRAIN", param_str), ("TEST", test_param_str)):
+        w.layer(name, "Python", [], tops, body % (module, layer, ps) + "\n  include { phase: %s }" % phase, quote="'")
+
+
+def googlenet_detectnet_train(module: str, layer: str, param_str: str, num_classes: int = 1, test_param_str: Optional[str] = None) -> str:
+    """Training net: Python data layer (6 tops) -> GoogLeNet body -> masked/normalised L1 + Euclidean losses.  test_param_str adds a
+    TEST-phase copy of the data layer (the solver's test net)."""
     w = _Writer()
     tops = ["data", "coverage-label", "bbox-label", "size-block", "obj-block", "coverage-block"]
-    body = "  python_param {\n    module: '%s'\n    layer: '%s'\n    param_str: '%s'\n  }" % (module, layer, param_str)
-    w.layer("data", "Python", [], tops, body, quote="'")
+    _python_data_layers(w, "data", tops, module, layer, param_str, test_param_str)
     prod = "  eltwise_param { operation: PROD }"
     w.layer("bb-label-norm", "Eltwise", ["bbox-label", "size-block"], ["bbox-label-norm"], prod)
     w.layer("bb-obj-norm", "Eltwise", ["bbox-label-norm", "obj-block"], ["bbox-obj-label-norm"], prod)
@@ -257,14 +269,14 @@ def vgg16_fcn_bbox_deploy(batch: int = 1, height: int = 448, width: int = 448, n
     return w.text()
 
 
-def vgg16_bounding_box_train(module: str, layer: str, param_str: str, num_classes: int = 11) -> str:
+def vgg16_bounding_box_train(module: str, layer: str, param_str: str, num_classes: int = 11, test_param_str: Optional[str] = None) -> str:
     """The reference's train/bounding_box/train_val.prototxt (solver: ADAM, step policy): VGG16 with conv1_1..conv3_3
     frozen (lr_mult 0), no ReLU after conv5_3, a frozen x2 bilinear deconvolution back to stride 8, dropout, the
-    DetectNet coverage / bbox heads and their L1 + Euclidean losses."""
+    DetectNet coverage / bbox heads and their L1 + Euclidean losses.  test_param_str adds the TEST-phase copy of the data
+    layer (the reference's reads val.txt at 448 x 448, stride 16, batch 10)."""
     w = _Writer()
     tops = ["data", "coverage-label", "bbox-label", "size-block", "obj-block", "coverage-block"]
-    body = "  python_param {\n    module: '%s'\n    layer: '%s'\n    param_str: '%s'\n  }" % (module, layer, param_str)
-    w.layer("Argumentation", "Python", [], tops, body, quote="'")
+    _python_data_layers(w, "Argumentation", tops, module, layer, param_str, test_param_str)
     prod = "  eltwise_param { operation: PROD }"
     w.layer("bb-label-norm", "Eltwise", ["bbox-label", "size-block"], ["bbox-label-norm"], prod)
     w.layer("bb-obj-norm", "Eltwise", ["bbox-label-norm", "obj-block"], ["bbox-obj-label-norm"], prod)

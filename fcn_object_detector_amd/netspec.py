@@ -188,6 +188,18 @@ class NetSpec:
                     shapes[tp] = (n, b - a, h, w)
             elif t in LOSS_TYPES:
                 shapes[l.tops[0]] = ()
+            elif t == "Accuracy":
+                # Caffe's AccuracyLayer over the channel axis: top0 the scalar accuracy, optional top1 the per-class accuracies
+                ap = l.sub("accuracy_param")
+                if int(ap.get("axis", 1)) != 1:
+                    raise NotImplementedError("Accuracy over axis %d (layer %s): only the channel axis" % (int(ap.get("axis", 1)), l.name))
+                if len(bots) != 2 or len(bots[0]) != 4 or not 1 <= len(l.tops) <= 2:
+                    raise ValueError("layer %s: Accuracy takes a 4-d score blob and a label blob, and has one or two tops" % l.name)
+                if int(ap.get("top_k", 1)) < 1 or int(ap.get("top_k", 1)) > bots[0][1]:
+                    raise ValueError("layer %s: top_k %d is outside [1, %d]" % (l.name, int(ap.get("top_k", 1)), bots[0][1]))
+                shapes[l.tops[0]] = ()
+                if len(l.tops) > 1:
+                    shapes[l.tops[1]] = (bots[0][1],)
             elif t in ("ReLU", "Sigmoid", "Power", "LRN", "Dropout", "Softmax", "TanH"):
                 shapes[l.tops[0]] = bots[0]
             elif t == "Eltwise":

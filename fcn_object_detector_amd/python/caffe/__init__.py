@@ -172,8 +172,10 @@ class Net(object):
             spec.infer({**spec.input_shapes, **shapes})
             params = _fill_params(spec, seed=0)
         self._spec = spec
+        src = getattr(self, "_share_src", None)
         self._engine = _Engine(spec, data_shapes=shapes, params=params, device=self._device,
-                               dtype=self._dtype if self._phase == "TEST" else "f32")
+                               dtype=self._dtype if self._phase == "TEST" else "f32",
+                               share_params=src._engine if src is not None else None)
         self.blobs = OrderedDict((name, _Blob(self, name)) for name in self._engine.shapes)
         self.params = OrderedDict(
             (l.name, [_Param(self, l.name, i) for i in range(len(self._engine.params_host[l.name]))])
@@ -214,6 +216,20 @@ class Net(object):
             raise IOError("weights file not found: %s" % weights_path)
         _proto.copy_trained_layers(weights_path, self._engine.params_host, self._engine.set_params)
 
+    def share_with(self, other: "Net") -> None:
+        """Net::ShareTrainedLayersWith: every parameter layer whose name `other` also has reads other's device storage in place from
+        now on (float32 nets; blob shapes must agree).  Edits through either net's ``params`` reach both."""
+        with self._lock:
+            params = {k: [a.copy() for a in v] for k, v in self._engine.params_host.items()}
+            self._engine.close()
+            self._share_src = other
+            try:
+                self._build(initial_params=params)
+            except Exception:
+                self._share_src = None
+                self._build(initial_params=params)
+                raise
+
     def save(self, path: str) -> None:
         layers = [(l.name, l.type, self._engine.params_host[l.name]) for l in self._spec.param_layers()]
         _proto.write_caffemodel(path, layers, self._spec.name)
@@ -226,7 +242,11 @@ class Net(object):
             _L.call("fcn_init", self._device)
             eng = self._engine
             for lname in list(self._params_touched):
-                eng.set_params(lname, eng.params_host[lname])
+                if lname in eng.shared_layers:      # the storage belongs to the net this one shares with: upload through it
+                    owner = self._share_src._engine
+                    owner.set_params(lname, owner.params_host[lname])
+                else:
+                    eng.set_params(lname, eng.params_host[lname])
             self._params_touched.clear()
             for k, v in kwargs.items():
                 if k not in eng.inputs:

@@ -29,7 +29,8 @@ F32 = np.float32
 
 class SolverParams:
     """Caffe's SolverParameter as far as `caffe train` on one training net needs it: every solver type, every lr_policy, L1 / L2
-    regularisation, clip_gradients and iter_size (test nets are not run).
+    regularisation, clip_gradients and iter_size, and the test-net schedule (test_iter / test_interval / test_net,
+    Solver::InitTestNets: `test_instances` lists what the solver scores, `test_due(it)` says when).
 
         type          histories  update (g' = normalised, clipped gradient + regularisation; lr = rate(iter) * lr_mult)
         SGD           1          h = momentum*h + lr*g' ; w -= h
@@ -89,11 +90,43 @@ class SolverParams:
             raise ValueError("stepsize: lr_policy \"%s\" needs stepsize > 0" % self.lr_policy)
         if self.iter_size < 1:
             raise ValueError("iter_size: %d is not positive" % self.iter_size)
+        # ---- test nets (Solver::InitTestNets): the test_net files in order, then the `net:` file in TEST phase once for every
+        # test_iter entry left over; one test_iter per instance; test_interval > 0 as soon as there is one
+        rep = (lambda k: list(kw[k]) if k in kw else (list(msg.getall(k)) if msg is not None else []))
+        for k in ("test_state", "net_param", "train_net_param", "test_net_param"):
+            if k in kw or (msg is not None and msg.getall(k)):
+                raise ValueError("%s: not supported (name the nets by file: net / train_net / test_net)" % k)
+        self.train_net = kw.get("train_net", g("train_net"))
+        self.test_iter = [int(v) for v in rep("test_iter")]
+        self.test_net = [str(v) for v in rep("test_net")]
+        self.test_interval = int(kw.get("test_interval", g("test_interval", 0)))
+        self.test_initialization = bool(kw.get("test_initialization", g("test_initialization", True)))
+        self.test_compute_loss = bool(kw.get("test_compute_loss", g("test_compute_loss", False)))
+        if any(v <= 0 for v in self.test_iter):
+            raise ValueError("test_iter: every entry must be positive")
+        has_net = g("net") is not None or "net" in kw
+        generic = len(self.test_iter) - len(self.test_net) if has_net else 0
+        if len(self.test_net) > len(self.test_iter):
+            raise ValueError("test_iter: %d given for %d test_net files (one test_iter per test net)" % (len(self.test_iter), len(self.test_net)))
+        if len(self.test_net) + generic != len(self.test_iter):
+            raise ValueError("test_iter: %d given but only %d test nets (test_net files, plus `net` in TEST phase)" % (
+                len(self.test_iter), len(self.test_net) + generic))
+        net = kw.get("net", g("net"))
+        # [(file, test_iter)]: what Solver builds, in Caffe's order
+        self.test_instances: List[Tuple[str, int]] = list(zip(self.test_net + [str(net)] * generic, self.test_iter))
+        if self.test_instances and self.test_interval <= 0:
+            raise ValueError("test_interval: must be > 0 when a test net is given (%d)" % self.test_interval)
+        if self.test_interval < 0:
+            raise ValueError("test_interval: %d is negative" % self.test_interval)
 
     @property
     def histories(self) -> int:
         """History buffers per learnable blob (what a .solverstate of this type carries per blob)."""
         return 2 if self.kind in ("ADAM", "ADADELTA") else 1
+
+    def test_due(self, it: int) -> bool:
+        """Solver::Step's test condition at the top of iteration `it`."""
+        return self.test_interval > 0 and it % self.test_interval == 0 and (it > 0 or self.test_initialization)
 
     def rate(self, it: int) -> float:
         """SGDSolver::GetLearningRate; multistep counts the stepvalues passed instead of carrying current_step, so a resumed run
@@ -388,6 +421,8 @@ class TrainEngine(Engine):
                 if t == "Slice" and l.name in self.copy_slices and any(tp in G for tp in l.tops):
                     raise NotImplementedError("backward through the copied Slice %s" % l.name)
                 continue
+            if t == "Accuracy":
+                continue                     # a metric: no gradient, no entry in loss_blobs
             if t in ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss"):
                 g = G.get(l.bottoms[0])
                 if g is None:
@@ -709,49 +744,6 @@ class TrainEngine(Engine):
         return self._fused_relu_cache
 
     # ------------------------------------------------------------------ one solver iteration
-    # blob names of the DetectNet label tops, in the order DataArgumentationLayer emits them (data_argumentation_layer.py:67-72)
-    LABEL_TOPS = ("coverage-label", "bbox-label", "size-block", "obj-block", "coverage-block")
-
-    def set_targets(self, rects: Sequence[Sequence[Sequence[int]]], labels: Sequence[Sequence[int]], stride: int,
-                    iou_thresh: float = 0.1, tops: Sequence[str] = LABEL_TOPS) -> None:
-        """Stage the ground-truth boxes of the next step; the label blobs are then generated ON THE DEVICE inside step()
-        (fcn_gen_targets_nhwc: bounding_box_parameterized_labels of the reference) instead of being uploaded."""
-        fg = self.blobs[tops[0]]
-        n, c, gy, gx = fg.shape
-        if len(rects) != n or len(labels) != n:
-            raise ValueError("need boxes for %d images" % n)
-        offs = np.zeros(n + 1, np.int32)
-        flat_r, flat_l = [], []
-        for i, (rs, ls) in enumerate(zip(rects, labels)):
-            for r, lab in zip(rs, ls):
-                if not 0 <= int(lab) < c:
-                    raise IndexError("label %d outside [0, %d)" % (lab, c))
-                flat_r.append([int(v) for v in r])
-                flat_l.append(int(lab))
-            offs[i + 1] = len(flat_r)
-        if not hasattr(self, "_tgt"):
-            cap = max(64 * n, 256)
-            self._tgt = dict(cap=cap, rects=DeviceBuffer(cap * 16, zero=True), labels=DeviceBuffer(cap * 4, zero=True),
-                             offs=DeviceBuffer((n + 1) * 4, zero=True))
-        if len(flat_r) > self._tgt["cap"]:
-            raise ValueError("too many boxes in one batch (%d > %d)" % (len(flat_r), self._tgt["cap"]))
-        self._tgt.update(h_rects=np.asarray(flat_r, np.int32).reshape(-1, 4), h_labels=np.asarray(flat_l, np.int32), h_offs=offs,
-                         stride=int(stride), thresh=float(iou_thresh), tops=tuple(tops), pending=True)
-
-    def _enqueue_targets(self) -> None:
-        t, lib = self._tgt, L.load()
-        if t["h_rects"].size:
-            L.check(lib.fcn_memcpy_h2d_async(t["rects"].ptr, t["h_rects"].ctypes.data, t["h_rects"].nbytes, self.stream))
-            L.check(lib.fcn_memcpy_h2d_async(t["labels"].ptr, t["h_labels"].ctypes.data, t["h_labels"].nbytes, self.stream))
-        L.check(lib.fcn_memcpy_h2d_async(t["offs"].ptr, t["h_offs"].ctypes.data, t["h_offs"].nbytes, self.stream))
-        fg, bb, sz, ob, cv = (self.blobs[nm] for nm in t["tops"])
-        n, c, gy, gx = fg.shape
-        for b in (bb, sz, ob, cv):
-            if b.coffset or b.cstride != bb.cstride:
-                raise NotImplementedError("label blobs must be plain buffers of one geometry")
-        L.check(lib.fcn_gen_targets_nhwc(t["rects"].ptr, t["labels"].ptr, t["offs"].ptr, n, c, gy, gx, t["stride"], t["thresh"],
-                                         fg.ptr, fg.cstride, bb.ptr, sz.ptr, ob.ptr, cv.ptr, bb.cstride, self.stream))
-
     def step(self, seed: Optional[int] = None, upload: bool = True, feed: Optional[Callable[[int], None]] = None) -> Dict[str, float]:
         """Solver::Step for one iteration.  Inputs come from the input blobs' host arrays (upload=True), except label
         blobs staged with set_targets(), which are generated on the device; upload=False reuses what is already in HBM.

@@ -544,6 +544,25 @@ int  fcn_grad_clip_f32(const float* g, const fcn_solver_seg* d_segs, int nseg, f
 /* Gradient accumulation of iter_size > 1: acc = first ? g : acc + g over count floats (both 16-byte aligned), one launch */
 int  fcn_grad_accumulate_f32(float* acc, const float* g, size_t count, int first, fcn_stream_t s);
 
+/* ---- validation pass (Solver::Test, `caffe test`) ---- */
+/* Running sum of an output blob over the forwards of a test pass: acc[n][c][p] += x[n][p][x_coffset + c].  x: base of an NHWC
+ * buffer with channel stride x_cstride (N images of `pixels` = H*W pixels; x_coffset selects the view's first channel); acc:
+ * N*C*pixels floats in NCHW order, what Caffe's test_score[] holds.  Float32, exactly one add per element per call, so after k
+ * calls the bits equal a host float32 running sum in call order.  N = pixels = C = 1 is a loss scalar.  16-byte loads when x is
+ * 16-byte aligned and x_cstride, x_coffset are multiples of 4; channels outside [x_coffset, x_coffset + C) are neither read nor
+ * written.  Zero acc with fcn_memset_async at the start of a pass. */
+int  fcn_score_accumulate_f32(float* acc, const float* x, int N, int pixels, int C, int x_cstride, int x_coffset, fcn_stream_t s);
+/* Accuracy (BVLC Caffe master's AccuracyLayer over the channel axis), arguments as fcn_softmax_loss_f32: x NHWC scores (view base,
+ * `pixels` = N*H*W), label one float per pixel.  A pixel whose label equals ignore_label (has_ignore != 0) is skipped; a labelled
+ * pixel is correct iff fewer than top_k channels j != label have x[j] >= x[label] (ties count against the label); a label outside
+ * [0, C) counts as valid and wrong and never indexes x.  *d_acc = valid ? correct / valid : 0; d_per_class (may be NULL, C floats,
+ * C <= 128) [c] = n_c ? correct_c / n_c : 0.  Integer counts: per-workgroup partials in d_workspace (fcn_accuracy_workspace_bytes()
+ * bytes, 4-byte aligned), then one workgroup in index order; no atomics on floats, the same bits on every run.  16-byte loads
+ * when x is 16-byte aligned and x_cstride is a multiple of 4; channels >= C are never read. */
+size_t fcn_accuracy_workspace_bytes(void);
+int  fcn_accuracy_f32(const float* x, const float* label, float* d_acc, float* d_per_class, int N, int pixels, int C, int x_cstride,
+                      int label_cstride, int top_k, int has_ignore, int ignore_label, void* d_workspace, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
