@@ -431,10 +431,29 @@ class Engine:
             return out
         if l.type == "Deconvolution":
             c, cog, kh, kw = w.shape
-            if cog != 1:
-                raise NotImplementedError("Deconvolution %s: only group == channels (one filter per channel)" % l.name)
+            if self._deconv_dense(l):
+                # group 1: [Cin][kh][kw][Cout padded to 4] - an OHWI bank of Cin outputs over Cout inputs, which is what the layer's data
+                # gradient (a forward convolution of dY) and its weight gradient (roles swapped) read as it stands
+                out = np.zeros((c, kh, kw, _r4(cog)), F32)
+                out[..., :cog] = w.transpose(0, 2, 3, 1)
+                return out
             return np.ascontiguousarray(w.reshape(c, kh, kw))
         raise NotImplementedError(l.type)
+
+    def _deconv_dense(self, l: Layer) -> bool:
+        """True: a group-1 Deconvolution (the transposed-convolution kernel); False: group == channels == num_output (the depthwise
+        kernels).  Every other grouping is refused, by name."""
+        p = l.sub("convolution_param")
+        g, co = int(p.get("group", 1)), int(p.get("num_output"))
+        c = self.spec.param_shapes[l.name][0][0]
+        if g == c and co == c:
+            return False
+        if g == 1:
+            if self.f16:
+                raise NotImplementedError("f16 engine: layer type Deconvolution with group 1 (%s) has no half-float kernel" % l.name)
+            return True
+        raise NotImplementedError("Deconvolution %s: group %d with %d -> %d channels (only group 1 and group == channels == num_output)"
+                                  % (l.name, g, c, co))
 
     def _upload_params(self, l: Layer) -> None:
         if l.name in self.shared_layers:
@@ -467,6 +486,9 @@ class Engine:
         if index == 0 and lay.type == "Convolution":
             co, ci, kh, kw = shp
             return np.ascontiguousarray(raw.reshape(co, kh, kw, -1)[..., :ci].transpose(0, 3, 1, 2))
+        if index == 0 and lay.type == "Deconvolution" and self._deconv_dense(lay):
+            ci, co, kh, kw = shp
+            return np.ascontiguousarray(raw.reshape(ci, kh, kw, -1)[..., :co].transpose(0, 3, 1, 2))
         return raw.reshape(shp).copy()
 
     # ------------------------------------------------------------------ plan
@@ -1415,10 +1437,29 @@ class Engine:
             xb, yb = B[l.bottoms[0]], B[l.tops[0]]
             n, c, h, w = xb.shape
             _, co, oh, ow = yb.shape
-            if int(p.get("group", 1)) != c or co != c:
-                raise NotImplementedError("Deconvolution %s: only group == channels == num_output" % l.name)
             wdev = self.params_dev[l.name][0].ptr
             bdev = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
+            if self._deconv_dense(l):
+                # group 1: the transposed convolution on the matrix cores.  Its bank is re-packed from the blob in front of every
+                # launch (one small launch): the blob may have been stepped by a solver, set through net.params or belong to
+                # another engine (share_params) since the last forward.
+                if xb.coffset % 4 or xb.cstride % 4:
+                    raise NotImplementedError("Deconvolution %s: input view is not 16-byte aligned" % l.name)
+                bank = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(c, co, k, k)), 4) * 4, zero=True)
+                d = L.TConvDesc()
+                d.a, d.w, d.bias, d.b = xb.ptr, bank.ptr, bdev, yb.buf.ptr
+                d.N, d.H, d.W, d.Ca, d.a_cstride = n, h, w, c, xb.cstride
+                d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = co, k, k, pad, s, oh, ow
+                d.b_cstride, d.b_coffset, d.flags = yb.cstride, yb.coffset, 0
+                tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+                plan = L.TConvPlan()
+                L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(plan))
+                self._keep.extend([bank, d, tws, plan])
+                out.append(Op("tconv_pack", l.name, lambda st: L.check(lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, c, co, _r4(co), k, k, st)),
+                              0.0, 8.0 * c * co * k * k))
+                out.append(Op("tconv", l.name, lambda st: L.check(lib.fcn_tconv2d_f32(C.byref(plan), st)),
+                              2.0 * n * h * w * c * co * k * k, 4.0 * (xb.pixels * c + yb.pixels * co)))
+                return out
             if halves:
                 if xb.esize != 2 or xb.coffset % 8:
                     raise NotImplementedError("f16 engine: Deconvolution %s from a float32 blob / an unaligned channel slice" % l.name)

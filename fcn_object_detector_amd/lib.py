@@ -45,6 +45,23 @@ class ConvGroup(C.Structure):
     _fields_ = [("d_probs", C.c_void_p), ("n", C.c_int32), ("cfg", C.c_int32), ("total_tiles", C.c_int32)]
 
 
+class TConvDesc(C.Structure):
+    """fcn_tconv_desc: transposed convolution (group-1 Deconvolution forward / data gradient of a strided Convolution)."""
+    _fields_ = [
+        ("a", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("b", C.c_void_p), ("y2", C.c_void_p),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ca", C.c_int32), ("a_cstride", C.c_int32),
+        ("Cb", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("pad", C.c_int32), ("stride", C.c_int32),
+        ("OH", C.c_int32), ("OW", C.c_int32),
+        ("b_cstride", C.c_int32), ("b_coffset", C.c_int32), ("y2_cstride", C.c_int32), ("y2_coffset", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
+class TConvPlan(C.Structure):
+    _fields_ = [("d_probs", C.c_void_p), ("n", C.c_int32), ("cfg", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
+                ("total_tiles", C.c_int32)]
+
+
 class SolverSeg(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("count", C.c_uint64), ("lr_mult", C.c_float), ("decay_mult", C.c_float)]
 
@@ -214,6 +231,13 @@ PROTOTYPES = {
     "fcn_score_accumulate_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fcn_accuracy_workspace_bytes": (_sz, []),
     "fcn_accuracy_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "fcn_tconv2d_num_configs": (_i, []),
+    "fcn_tconv2d_workspace_bytes": (_sz, [C.POINTER(TConvDesc), _i]),
+    "fcn_tconv2d_prepare": (_i, [C.POINTER(TConvDesc), _i, _vp, _i, C.POINTER(TConvPlan)]),
+    "fcn_tconv2d_f32": (_i, [C.POINTER(TConvPlan), _vp]),
+    "fcn_tconv_bank_floats": (_sz, [_i, _i, _i, _i]),
+    "fcn_tconv_bank_pack_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fcn_channel_sum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

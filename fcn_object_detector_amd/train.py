@@ -306,7 +306,47 @@ class TrainEngine(Engine):
             L.call("fcn_device_sync")
             ops.append(Op("flip", "%d filter banks" % len(flip_segs), lambda st, n=len(flip_segs): L.check(lib.fcn_conv_weights_flip_batch_f32(
                 self.param_flat.ptr, self._flip_flat.ptr, self._flip_segs_dev.ptr, n, st))))
+        # Strided convolutions whose input needs a gradient: the transposed-convolution kernel reads the layer's own OHWI bank
+        # re-packed tap-major ([kh][kw][Cin][Cout4]), refreshed from the current weights at the start of every backward pass
+        tbank: Dict[str, DeviceBuffer] = {}
+        for l in spec.layers:
+            if l.type != "Convolution" or G.get(l.bottoms[0]) is None or G.get(l.tops[0]) is None:
+                continue
+            k, s_, _pad = kernel_stride_pad(l.sub("convolution_param"))
+            if s_ == 1:
+                continue
+            cin, cout = B[l.bottoms[0]].shape[1], B[l.tops[0]].shape[1]
+            tbank[l.name] = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(cout, cin, k, k)), 4) * 4, zero=True)
+            ops.append(Op("tconv_pack", l.name, lambda st, wdev=self.params_dev[l.name][0].ptr, bank=tbank[l.name], g=(cout, cin, _r4(cin), k):
+                          L.check(lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, g[0], g[1], g[2], g[3], g[3], st))))
+        self._tbank = tbank
         skip_sigmoid_of = {m["sigmoid_top"]: name for name, m in self._conv_layer_meta.items() if m.get("sigmoid_top")}
+
+        def emit_tdgrad(l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> dict:
+            """Data gradient of the strided convolution l: the transposed convolution of dY, written at the size of the layer's input
+            (rows / columns of it that lay under no window get zeros).  Prepared in finish_dgrads like the grouped launches, because
+            the ReLU mask of the layer below may still be folded into its epilogue."""
+            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
+            n, cin, h, w = xb.shape
+            _, cout, oh, ow = yb.shape
+            if gtop.coffset % 4 or gtop.cstride - gtop.coffset < _r4(cout):
+                raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
+            if pad >= k:
+                raise NotImplementedError("data gradient of the strided convolution %s with pad %d >= kernel %d" % (l.name, pad, k))
+            d = L.TConvDesc()
+            d.a, d.w, d.bias, d.b = gtop.ptr, tbank[l.name].ptr, None, gbot.buf.ptr
+            d.N, d.H, d.W, d.Ca, d.a_cstride = n, oh, ow, cout, gtop.cstride
+            d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = cin, k, k, pad, s, h, w
+            d.b_cstride, d.b_coffset = gbot.cstride, gbot.coffset
+            d.flags = L.CONV_ACCUM if accumulate else 0
+            rec = dict(name=l.name, descs=[d], targets=[l.bottoms[0]], tconv=L.TConvPlan())
+            rec["op"] = Op("tconv_dgrad", l.name, lambda st, pl=rec["tconv"]: L.check(lib.fcn_tconv2d_f32(C.byref(pl), st)),
+                           2.0 * n * cout * oh * ow * cin * k * k)
+            ops.append(rec["op"])
+            dgrad_records.append(rec)
+            self._keep.append(d)
+            return rec
 
         def dgrad_desc(l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Tuple[L.ConvDesc, float]:
             """Data gradient of convolution l = the forward kernel on dY with the flipped / transposed bank."""
@@ -315,7 +355,7 @@ class TrainEngine(Engine):
             n, cin, h, w = xb.shape
             _, cout, oh, ow = yb.shape
             if s != 1:
-                raise NotImplementedError("data gradient of the strided convolution %s" % l.name)
+                raise RuntimeError("dgrad_desc is the stride-1 path; strided layers go through emit_tdgrad (%s)" % l.name)
             cin_dg = _r4(cout)      # the flipped bank reads Cout4 input channels: the gradient view must expose them contiguously
             if gtop.cstride - gtop.coffset < cin_dg:
                 raise NotImplementedError("gradient view of %s too narrow for the data-gradient pass" % l.tops[0])
@@ -360,6 +400,13 @@ class TrainEngine(Engine):
                 d.flags |= L.CONV_MASK
                 ops.remove(rop)
             for rec in dgrad_records:
+                if "tconv" in rec:
+                    d = rec["descs"][0]
+                    tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+                    L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(rec["tconv"]))
+                    self._keep.extend([tws, rec["tconv"]])
+                    rec["op"].name = "%s [%dwg]" % (rec["name"], rec["tconv"].total_tiles)
+                    continue
                 n_ = len(rec["descs"])
                 arr = (L.ConvDesc * n_)(*rec["descs"])
                 gws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(n_)), zero=False)
@@ -414,6 +461,52 @@ class TrainEngine(Engine):
                 op.layers = names
                 ops.append(op)
                 wgrad_done.update(names)
+
+        def emit_dense_deconv_bwd(l: Layer, gtop: Blob, gbot: Optional[Blob]) -> None:
+            """Backward of a group-1 Deconvolution whose blob is kept as [Cin][kh][kw][Cout4], an OHWI bank of Cin outputs:
+            db = per-channel sum of dY; dW = the weight-gradient kernel with the roles swapped (its x is dY, its y the layer's input);
+            dX = the forward convolution of dY at the layer's stride."""
+            nonlocal ws_floats
+            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
+            n, c, h, w = xb.shape
+            _, co, oh, ow = yb.shape
+            if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(co):
+                raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
+
+            def swapped() -> L.ConvDesc:
+                d = L.ConvDesc()
+                d.x = gtop.ptr
+                d.N, d.H, d.W, d.Cin, d.x_cstride = n, oh, ow, _r4(co), gtop.cstride
+                d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = c, k, k, pad, s, h, w
+                self._keep.append(d)
+                return d
+            if self._learns(l) and l.name not in wgrad_done:
+                if len(self.params_dev[l.name]) > 1:
+                    db = self._grad_view(l.name, 1)
+                    ops.append(Op("channel_sum", l.name, lambda st, a=gtop, db=db, co=co: L.check(lib.fcn_channel_sum_f32(
+                        a.buf.ptr, db.ptr, a.pixels, co, a.cstride, a.coffset, st)), 0.0, 4.0 * gtop.pixels * co))
+                if xb.coffset % 4 or xb.cstride % 4:
+                    raise NotImplementedError("input view of %s is not 16-byte aligned" % l.name)
+                d = swapped()
+                d.y, d.y_cstride, d.y_coffset = xb.buf.ptr, xb.cstride, xb.coffset
+                dw = self._grad_view(l.name, 0)
+                sel = {"cfg": -1}
+                cfgs = [-1] + (list(range(int(lib.fcn_conv2d_wgrad_num_configs()))) if self.autotune else [])
+                ws_floats = max([ws_floats] + [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), cf, None)) for cf in cfgs])
+                op = Op("wgrad", l.name, lambda st, d=d, dw=dw, sel=sel: L.check(lib.fcn_conv2d_wgrad_cfg_f32(
+                    C.byref(d), dw.ptr, None, self._ws.ptr, sel["cfg"], st)), 2.0 * n * c * h * w * co * k * k)
+                op.sel = sel
+                op.layers = [l.name]
+                ops.append(op)
+                wgrad_done.add(l.name)
+            if gbot is not None:
+                d = swapped()
+                d.w, d.bias, d.y = self.params_dev[l.name][0].ptr, None, gbot.buf.ptr
+                d.y_cstride, d.y_coffset = gbot.cstride, gbot.coffset
+                d.flags = L.CONV_ACCUM if state(gbot) == "full" else 0
+                rec = emit_dgrads(l.name, [(d, 2.0 * n * c * h * w * co * k * k)], [l.bottoms[0]])
+                mark(gbot, rec)
 
         for l in reversed(spec.layers):
             t = l.type
@@ -521,7 +614,10 @@ class TrainEngine(Engine):
                 emit_wgrads([l], [gtop])
                 gbot = G.get(l.bottoms[0])
                 if gbot is not None and l.name not in dgrad_done:
-                    rec = emit_dgrads(l.name, [dgrad_desc(l, gtop, gbot, state(gbot) == "full")], [l.bottoms[0]])
+                    if s != 1:
+                        rec = emit_tdgrad(l, gtop, gbot, state(gbot) == "full")
+                    else:
+                        rec = emit_dgrads(l.name, [dgrad_desc(l, gtop, gbot, state(gbot) == "full")], [l.bottoms[0]])
                     mark(gbot, rec)
                 continue
             if t == "Eltwise" and str(l.sub("eltwise_param").get("operation", "SUM")) == "SUM":
@@ -542,6 +638,10 @@ class TrainEngine(Engine):
                         ops.append(Op("eltwise_bwd", l.name + ":" + bn, lambda st, a=gtop, b=gb: L.check(lib.fcn_copy_channels_f32(
                             a.buf.ptr, b.buf.ptr, a.pixels, a.channels, a.cstride, a.coffset, b.cstride, b.coffset, st))))
                     mark(gb)
+                continue
+            if t == "Deconvolution" and self._deconv_dense(l):
+                gbot = G.get(l.bottoms[0])
+                emit_dense_deconv_bwd(l, gtop, gbot)
                 continue
             gbot = G.get(l.bottoms[0]) if l.bottoms else None
             if gbot is None:
@@ -597,7 +697,8 @@ class TrainEngine(Engine):
                     a.ptr, o.ptr, b.ptr, n, L.ELT_PROD, 1.0, 1.0, st))))
             elif t == "Deconvolution":
                 if any(m != 0.0 for m in l.lr_mult) or not l.lr_mult:
-                    raise NotImplementedError("learnable Deconvolution %s (the reference freezes its bilinear upsampling, lr_mult 0)" % l.name)
+                    raise NotImplementedError("learnable depthwise Deconvolution %s (group == channels): only group 1 learns; the reference "
+                                              "freezes its bilinear upsampling, lr_mult 0" % l.name)
                 p = l.sub("convolution_param")
                 k, s, pad = kernel_stride_pad(p)
                 xb, yb = B[l.bottoms[0]], B[l.tops[0]]
@@ -1061,7 +1162,11 @@ class TrainEngine(Engine):
                 host_shape = self.params_host[e["layer"]][0].shape
                 a = a[..., :host_shape[1]].transpose(0, 3, 1, 2)
             elif e["index"] == 0 and types[e["layer"]] == "Deconvolution":
-                a = a.reshape(self.params_host[e["layer"]][0].shape)
+                host_shape = self.params_host[e["layer"]][0].shape
+                if a.ndim == 4:      # group 1: [Cin][kh][kw][Cout padded to 4] on the device
+                    a = a[..., :host_shape[1]].transpose(0, 3, 1, 2)
+                else:
+                    a = a.reshape(host_shape)
             out.setdefault(e["layer"], []).append(np.ascontiguousarray(a))
         return out
 
@@ -1075,6 +1180,11 @@ class TrainEngine(Engine):
                 co, ci, kh, kw = self.params_host[e["layer"]][0].shape
                 d = np.zeros(e["shape"], F32)
                 d[..., :ci] = a.reshape(co, ci, kh, kw).transpose(0, 2, 3, 1)
+                a = d
+            elif e["index"] == 0 and types[e["layer"]] == "Deconvolution" and len(e["shape"]) == 4:
+                ci, co, kh, kw = self.params_host[e["layer"]][0].shape
+                d = np.zeros(e["shape"], F32)
+                d[..., :co] = a.reshape(ci, co, kh, kw).transpose(0, 2, 3, 1)
                 a = d
             flat[e["offset"]:e["offset"] + e["count"]] = a.reshape(-1)
         return flat

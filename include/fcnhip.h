@@ -563,6 +563,57 @@ size_t fcn_accuracy_workspace_bytes(void);
 int  fcn_accuracy_f32(const float* x, const float* label, float* d_acc, float* d_per_class, int N, int pixels, int C, int x_cstride,
                       int label_cstride, int top_k, int has_ignore, int ignore_label, void* d_workspace, fcn_stream_t s);
 
+/* ---- transposed (fractionally-strided) convolution: Caffe DeconvolutionLayer::Forward_gpu with group 1, and the bottom diff of
+ *      a strided ConvolutionLayer::Backward_gpu.  NHWC float32, exact f32 on the matrix cores (v_mfma_f32_32x32x2_f32).
+ *        b[n, oy, ox, cb] = bias[cb] + sum over ca, r, q, iy, ix with oy + pad - r == stride*iy, ox + pad - q == stride*ix,
+ *                                      0 <= iy < H, 0 <= ix < W  of  w[ca][cb][r][q] * a[n, iy, ix, ca]
+ *      OH / OW are explicit: any value in [stride*(H-1) + kh - 2 pad, that + stride - 1] (the data gradient of a convolution whose
+ *      last rows / columns lay under no window: those outputs get bias / zero).  The outputs are evaluated phase by phase
+ *      ((oy + pad) mod stride, (ox + pad) mod stride): each phase is a stride-1 correlation with its own sub-filter, no structural
+ *      zero is multiplied, and all phases of all problems of a plan run in ONE launch.  Every output element is written by exactly
+ *      one lane and the contraction is never split: the same bits on every run.
+ *      flags: FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK with the meaning (and order: accumulate, ReLU, mask) they have in
+ *      fcn_conv_desc; y2 is only read (FCN_CONV_MASK).  Channels Ca .. round4(Ca)-1 of `a` are padding and are never multiplied
+ *      (they may hold anything); channels of b outside [b_coffset, b_coffset + Cb) are not touched.  16-byte stores when
+ *      b (y2) is 16-byte aligned with strides / offsets in multiples of 4, scalar stores otherwise and for a last partial group.
+ *      Refused on the host before any launch: FCN_E_ARG (null pointer, non-positive extent, OH / OW outside the range above,
+ *      slice wider than its stride, FCN_CONV_MASK without y2), FCN_E_ALIGN (a_cstride not a multiple of 4 or below round4(Ca);
+ *      a / w not 16-byte aligned), FCN_E_UNSUPPORTED (stride > 64, pad >= kh or kw, other flags, tensors past 2^31 elements). ---- */
+typedef struct fcn_tconv_desc {
+    const float* a;      /* NHWC input, channel stride a_cstride (a multiple of 4, >= round4(Ca))               */
+    const float* w;      /* bank packed by fcn_tconv_bank_pack_f32: [kh][kw][Cb][round4(Ca)]                     */
+    const float* bias;   /* [Cb] or NULL                                                                         */
+    float*       b;      /* NHWC output; channel cb of pixel m at b[m*b_cstride + b_coffset + cb]                */
+    float*       y2;     /* FCN_CONV_MASK: the activation whose sign masks the result (same indexing via y2_*)   */
+    int32_t N, H, W, Ca, a_cstride;
+    int32_t Cb, kh, kw, pad, stride, OH, OW;
+    int32_t b_cstride, b_coffset, y2_cstride, y2_coffset;
+    int32_t flags;
+} fcn_tconv_desc;
+typedef struct fcn_tconv_plan {
+    void*   d_probs;
+    int32_t n;
+    int32_t cfg;          /* tile configuration chosen by prepare() */
+    int32_t grid_x, grid_y;
+    int32_t total_tiles;
+} fcn_tconv_plan;
+/* number of tile configurations (cfg_request: -1 = built-in choice, 0 .. count-1); one today: 64 pixels x 64 channels x 16 k */
+int    fcn_tconv2d_num_configs(void);
+size_t fcn_tconv2d_workspace_bytes(const fcn_tconv_desc* h_descs, int n);
+/* validates and uploads n problems into d_workspace with a synchronous copy (plan time, not inside a graph capture); the
+ * workspace must stay alive as long as the plan is used */
+int    fcn_tconv2d_prepare(const fcn_tconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_tconv_plan* h_out);
+/* one pure kernel launch for all problems and phases of the plan: capturable */
+int    fcn_tconv2d_f32(const fcn_tconv_plan* h_plan, fcn_stream_t s);
+/* packed[(r*kw + q)*Cb + cb][ca] = w[ca][r][q][cb], zero for Ca <= ca < round4(Ca).  w is [Ca][kh][kw][w_cstride] (cb contiguous):
+ * the OHWI bank of a Convolution read for its data gradient (Ca = Cout, Cb = Cin, w_cstride = round4(Cin)), and the device layout of a
+ * group-1 Deconvolution blob (Ca = Cin, Cb = Cout, w_cstride = round4(Cout)).  fcn_tconv_bank_floats(): floats of `packed`. */
+size_t fcn_tconv_bank_floats(int Ca, int Cb, int kh, int kw);
+int    fcn_tconv_bank_pack_f32(const float* w, float* packed, int Ca, int Cb, int w_cstride, int kh, int kw, fcn_stream_t s);
+/* db[c] = sum over pixels of dy[pixel*cstride + coffset + c], c < C: the bias gradient of a Deconvolution (the weight-gradient kernel
+ * sums ITS y, which after the role swap is the layer's input).  One workgroup per channel, fixed order: bit-reproducible. */
+int    fcn_channel_sum_f32(const float* dy, float* db, int pixels, int C, int cstride, int coffset, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
