@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the fcn_object_detector hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: it builds and tunes the engines, warms up, times the K steps
+(`value`, `ms_per_step`), writes --dump-outputs and prints the line.  --full adds every other measurement and check of this
+file to the same line, behind the same headline: the single-stream latency and the kernels-only figure in front of the timed
+steps, the one-frame-at-a-time region, the per-launch roofline, the CPU baseline with its parity check, the detector per camera
+frame, the training step, the batch-8 / batch-32 / half-float forwards and the VGG16-FCN net after them.
 
 A "step" is one forward pass of the DetectNet GoogLeNet stack + coverage/bbox heads (the graph of the
 reference's models/deploy.prototxt, BASELINE.json configs[1]) over one synthetic 448x448x3 frame that
@@ -474,17 +480,117 @@ def bench_vgg(steps: int = 5):
     return out
 
 
+def forward_details(args, eng, depth, dev_ms, serial_s, frames, value, t_k, rep_k, rep_s):
+    """--full: what rides beside the headline about the same batch-1 forward - the kernels-only figure (timed by the caller in front of the
+    headline's steps, as is the single-stream latency), config 2's region one frame at a time and the per-launch roofline (both timed here,
+    after the headline's steps).  Returns the entries it adds to the line."""
+    value_k = frames / t_k
+    # the same region one frame at a time (the latency form of config 2)
+    n_io = max(min(args.steps, 200), 10) if not args.trace_clean else 5
+    io_one = [] if not args.no_io_region else [0.0]
+    for _ in range(5 if not args.no_io_region else 0):
+        eng.forward()
+    for _ in range(max(args.repeats, 1) if not args.no_io_region else 0):
+        t1 = time.perf_counter()
+        for _ in range(n_io):
+            eng.forward()
+        io_one.append(n_io * args.batch / (time.perf_counter() - t1))
+    pcie_fps = float(np.median(io_one))
+
+    # dominant kernel family = the MFMA implicit-GEMM convolution: per-launch HIP-event timing on the engine's stream
+    # `roofline.achieved`: HIP events on the engine's stream around each launch repeated back to back (20 reps: the launch floor and the
+    # event cost amortise away).  rocprofv3's per-kernel durations of whole forwards are 1-4 % longer (in a forward the filters of a launch
+    # are cold in L2, back to back they are warm): `from_profile` holds that figure, derived from the committed kernel trace alone by
+    # tools/roofline_from_profile.py.  (Timing each launch once, in sequence, between two events - Engine.time_ops_in_sequence - reads
+    # 2-4 us of event handling per launch on top: kept as `in_sequence_events` for reference, not used.)
+    if args.trace_clean:      # (no event-timed launches in a clean trace: `roofline` of this run is a placeholder)
+        ops = ops_seq = [(o.kind, o.name, 1e-6, o.flops, o.bytes) for o in eng.ops]
+    else:
+        ops = eng.time_ops(reps=20)
+        ops_seq = eng.time_ops_in_sequence(reps=5)
+    conv = [(k, n, ms, fl, by) for (k, n, ms, fl, by) in ops if k.startswith("conv")]
+    conv_ms = sum(o[2] for o in conv)
+    conv_flops = sum(o[3] for o in conv)
+    conv_ms_seq = sum(o[2] for o in ops_seq if o[0].startswith("conv"))
+    all_ms = sum(o[2] for o in ops)
+    if args.per_op:
+        for (k, n, ms, fl, by), w in zip(ops, ops_seq):
+            sys.stderr.write("%-10s %-60s %8.2f us (in sequence, with event cost %7.2f) %7.2f TF/s %7.1f GB/s\n" % (k, n[:160], ms * 1e3, w[2] * 1e3, fl / ms / 1e9 if ms else 0,
+                                                                                                                  by / ms / 1e6 if ms else 0))
+    live = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms else 0.0
+    tr = profile_traffic(PROFILE_TAG + "_bench")      # HBM bytes per conv launch from the committed PMC passes (stamped with the sources' hash)
+    traffic = tr["bytes_per_launch"] if tr else None
+    prof_roof = profile_json("bench_roofline")        # the family's time per frame from the committed kernel trace alone (tools/roofline_from_profile.py)
+    if prof_roof is not None:
+        prof_roof = {k: prof_roof[k] for k in ("frac", "achieved_tflops", "conv_us_per_frame", "mfma_busy_frac", "clock_ghz_assumed", "source", "stale") if k in prof_roof}
+    live_d = {"achieved": round(live, 3), "frac": round(live / F32_MFMA_PEAK_TFLOPS, 4), "conv_us_per_frame": round(conv_ms * 1e3, 2),
+              "note": "HIP events on the engine's stream around each launch repeated back to back (20 reps): the launch's filters are warm in L2, "
+                      "inside a forward they are cold - 1-4 % faster than the kernel trace of whole forwards"}
+    if args.trace_clean:
+        roofline = {"placeholder": True, "note": "--trace-clean: a kernel-trace pass times no launch by itself; the roofline of this command is derived "
+                                                 "from the trace (tools/roofline_from_profile.py)"}
+    else:
+        fresh = prof_roof is not None and not prof_roof.get("stale", True)
+        achieved = prof_roof["achieved_tflops"] if fresh else live
+        roofline = {"bound": "mfma", "kernel": "conv_fwd_group + conv_first7 (f32 MFMA convolution family; %d launches covering the 59 convolutions)" % len(conv),
+                    "achieved": round(achieved, 3), "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(achieved / F32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                    "source": ("profiles/%s_bench_kernel_stats.csv: rocprofv3 --kernel-trace --stats of this command with one frame in flight, the family's "
+                               "TotalDurationNs / frames (tools/roofline_from_profile.py)" % PROFILE_TAG) if fresh else
+                              "live back-to-back launches (the committed kernel trace is %s)" % ("stale: kernel sources changed since" if prof_roof else "missing"),
+                    "traffic_source": tr, "algorithmic_bytes_per_launch": round(sum(o[4] for o in conv) / max(len(conv), 1)),
+                    "traffic_note": "HBM bytes per conv launch = 2*FETCH_SIZE + WRITE_SIZE from separate rocprofv3 --pmc passes of this "
+                                    "command; 'stale' = the kernel sources changed since that profile",
+                    "frames_in_flight": 1,
+                    "conv_us_per_frame": prof_roof["conv_us_per_frame"] if fresh else round(conv_ms * 1e3, 2),
+                    "live_back_to_back": live_d,
+                    "in_sequence_events": {"conv_us_per_frame": round(conv_ms_seq * 1e3, 2), "event_pair_floor_us": round(getattr(eng, "event_pair_floor_ms", 0.0) * 1e3, 2),
+                                           "note": "each launch once, in the cache state of a forward, between two events: includes event handling "
+                                                   "(an empty pair reads event_pair_floor_us); reference only"},
+                    "from_profile": prof_roof,
+                    "avg_launch_us": round(conv_ms * 1e3 / max(len(conv), 1), 2), "launches_per_step": len(ops),
+                    "sum_kernel_ms_per_step": round(all_ms, 4),
+                    "measured_on": "one stream; kernel durations are not comparable once frames overlap",
+                    "whole_step_tflops": round(FWD_GFLOP * args.batch / (dev_ms / args.steps), 3)}
+    return {"value_kernels_only": round(value_k, 2),
+            "kernels_only": {"frames_per_s": round(value_k, 2), "ms_per_step": round(t_k * 1e3 / args.steps, 4), "frames_in_flight": depth,
+                             "repeats": [round(frames / t, 1) for t in rep_k],
+                             "includes": "all kernels of the forward, inputs resident in HBM, outputs left in HBM (no copies in the timed region)"},
+            "config2_frames_per_s": round(pcie_fps, 2),
+            "config2_frames_per_s_in_flight": round(value, 2) if rep_s else None,
+            "config2_timed_region": {"frames_per_s": round(pcie_fps, 2), "ms_per_frame": round(1e3 / pcie_fps, 4) if pcie_fps else None,
+                                     "frames_per_s_in_flight": round(value, 2) if rep_s else None, "frames_in_flight": depth,
+                                     "repeats": {"one_at_a_time": [round(v, 1) for v in io_one]},
+                                     "includes": "SURVEY 8(d) config 2: H2D of the (3,448,448) f32 frame (pinned host memory) + layout change + all kernels + "
+                                                 "D2H of the two head blobs; one frame at a time here, with frames in flight it is `value`"},
+            "single_stream": {"frames_per_s": round(args.steps * args.batch / serial_s, 2),
+                              "latency_ms_per_frame": round(serial_s * 1e3 / args.steps, 4),
+                              "device_ms_per_step": round(dev_ms / args.steps, 4)},
+            "pcie_inclusive_fps": round(pcie_fps, 2),
+            "roofline": roofline,
+            "roofline_in_flight": {"bound": "mfma", "frames_in_flight": depth, "achieved": round(FWD_GFLOP * value_k / 1e3, 3), "peak": F32_MFMA_PEAK_TFLOPS,
+                                   "unit": "TFLOP/s", "frac": round(FWD_GFLOP * value_k / 1e3 / F32_MFMA_PEAK_TFLOPS, 4),
+                                   "with_copies": {"achieved": round(FWD_GFLOP * value / 1e3, 3), "frac": round(FWD_GFLOP * value / 1e3 / F32_MFMA_PEAK_TFLOPS, 4)},
+                                   "note": "conv FLOPs of a frame x frames/s over the wall clock of the K steps with frames in flight - kernels only "
+                                           "(`value_kernels_only`) and, under `with_copies`, config 2's region (`value`); kernels of different frames overlap, so "
+                                           "per-kernel durations are not comparable: profiles/%s_bench_inflight_kernel_stats.csv holds the kernel trace of this mode" % PROFILE_TAG}}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1, help="frames per step (BASELINE config 2 uses 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step measurement reported under 'train'")
+    ap.add_argument("--full", action="store_true", help="beside the headline, measure and check everything else this file knows: single-stream latency, "
+                    "kernels-only and one-frame-at-a-time figures, per-launch roofline, CPU baseline + parity, detector per camera frame, training step, "
+                    "batch-8 / batch-32 / half-float forwards, VGG16-FCN (half a minute instead of a second; --no-cpu-baseline, --no-train and --no-secondary "
+                    "take single parts out again).  Without it only `value` and `ms_per_step` are measured")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check against it")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the training-step measurement reported under 'train'")
     ap.add_argument("--train-batch", type=int, default=8, help="images per GPU per training step (BASELINE configs[2]/[3])")
     ap.add_argument("--train-steps", type=int, default=0, help="timed training steps (default: min(steps, 30))")
-    ap.add_argument("--per-op", action="store_true", help="print the per-launch table to stderr")
+    ap.add_argument("--per-op", action="store_true", help="--full: print the per-launch table to stderr")
     ap.add_argument("--in-flight", type=int, default=4, help="frames in flight: replicas of the batch-1 engine on their own streams "
                                                              "(1 = one stream, launches strictly serial)")
     ap.add_argument("--repeats", type=int, default=5, help="the K-step timing is repeated this many times inside the run: `value` is the median, "
@@ -493,12 +599,15 @@ def main() -> None:
                     "`value` is then the kernels-only figure")
     ap.add_argument("--trace-clean", action="store_true", help="kernel-trace passes of tools/profile_bench.sh: whole forwards only - no per-launch "
                                                                "event timing loops, one repeat - so that every kernel's calls = frames x its launches per frame")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the VGG16-FCN (train/fcn_bbox) measurements reported under 'secondary'")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the detector per camera frame, the batch-8 / batch-32 forwards and the VGG16-FCN "
+                                                                "(train/fcn_bbox) measurements reported under 'secondary'")
     ap.add_argument("--devices", default="", help="GPU id of every rank, comma separated (default 0..N-1; rehearsals on a one-GPU box: 0,0 with --no-train)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the LAST timed step of `value`'s region returned to its caller "
                     "(rank 0's output blobs, NCHW float32) as DIR/<blob>.npy; the frame and the weights are seeded, so the same arguments give "
                     "the same inputs in every run and two builds can be compared blob for blob")
     args = ap.parse_args()
+    if args.per_op and not args.full:
+        ap.error("--per-op prints the per-launch timings, which only a --full run takes")
 
     from fcn_object_detector_amd import dp      # (touches no GPU)
     if args.gpus > 1 and not dp.launched_as_rank():
@@ -544,15 +653,18 @@ def main() -> None:
         e.host_array("data")[...] = x
         e.upload_inputs()
 
-    # single stream first: the latency of one frame and the per-launch kernel times behind `roofline`
-    eng.forward_resident(max(args.warmup, 1))
-    L.call("fcn_device_sync")
-    t0 = time.perf_counter()
-    dev_ms = eng.forward_resident(args.steps)
-    L.call("fcn_device_sync")
-    serial_s = time.perf_counter() - t0
+    dev_ms = serial_s = 0.0
+    if args.full:
+        # single stream first: the latency of one frame and the per-launch kernel times behind `roofline`
+        eng.forward_resident(max(args.warmup, 1))
+        L.call("fcn_device_sync")
+        t0 = time.perf_counter()
+        dev_ms = eng.forward_resident(args.steps)
+        L.call("fcn_device_sync")
+        serial_s = time.perf_counter() - t0
 
     # kernels only, inputs resident in HBM: the same K batch-1 steps with `depth` frames in flight (replica engines on their own streams), repeated R times
+    # (timed by --full, and where `value` is this figure: --no-io-region; the warm-up and the choice of the depth belong to every run)
     pipe.run_resident(max(args.warmup, 1))                        # W untimed warm-up steps (also captures the hipGraphs)
     depth = pipe.calibrate((depth - 1, depth)) if depth > 1 else 1    # untimed: 3 or 4 replicas, whichever packs better here
     if args.trace_clean:
@@ -562,7 +674,7 @@ def main() -> None:
         args.repeats = 1
         args.no_io_region = True
     rep_k = []
-    for _ in range(max(args.repeats, 1)):
+    for _ in range(max(args.repeats, 1) if args.full or args.no_io_region else 0):
         L.call("fcn_device_sync")
         cp.barrier()
         t0 = time.perf_counter()
@@ -571,7 +683,7 @@ def main() -> None:
         t_local = time.perf_counter() - t0
         cp.barrier()
         rep_k.append(cp.max(t_local))
-    t_k = float(np.median(rep_k))
+    t_k = float(np.median(rep_k)) if rep_k else None
 
     # headline (round 4): SURVEY 8(d) config 2's own timed region - H2D of the (3,448,448) f32 frame from pinned host
     # memory + layout change + all kernels + D2H of the two head blobs - with `depth` frames in flight: a frame's copies ride on its
@@ -608,116 +720,29 @@ def main() -> None:
         ms_per_step = t_max * 1e3 / args.steps
         frames = args.steps * args.batch * world
         value = frames / t_max
-        value_k = frames / t_k
-        # the same region one frame at a time (the latency form of config 2)
-        n_io = max(min(args.steps, 200), 10) if not args.trace_clean else 5
-        io_one = [] if not args.no_io_region else [0.0]
-        for _ in range(5 if not args.no_io_region else 0):
-            eng.forward()
-        for _ in range(max(args.repeats, 1) if not args.no_io_region else 0):
-            t1 = time.perf_counter()
-            for _ in range(n_io):
-                eng.forward()
-            io_one.append(n_io * args.batch / (time.perf_counter() - t1))
-        pcie_fps = float(np.median(io_one))
-
-        # dominant kernel family = the MFMA implicit-GEMM convolution: per-launch HIP-event timing on the engine's stream
-        # `roofline.achieved`: HIP events on the engine's stream around each launch repeated back to back (20 reps: the launch floor and the
-        # event cost amortise away).  rocprofv3's per-kernel durations of whole forwards are 1-4 % longer (in a forward the filters of a launch
-        # are cold in L2, back to back they are warm): `from_profile` holds that figure, derived from the committed kernel trace alone by
-        # tools/roofline_from_profile.py.  (Timing each launch once, in sequence, between two events - Engine.time_ops_in_sequence - reads
-        # 2-4 us of event handling per launch on top: kept as `in_sequence_events` for reference, not used.)
-        if args.trace_clean:      # (no event-timed launches in a clean trace: `roofline` of this run is a placeholder)
-            ops = ops_seq = [(o.kind, o.name, 1e-6, o.flops, o.bytes) for o in eng.ops]
-        else:
-            ops = eng.time_ops(reps=20)
-            ops_seq = eng.time_ops_in_sequence(reps=5)
-        conv = [(k, n, ms, fl, by) for (k, n, ms, fl, by) in ops if k.startswith("conv")]
-        conv_ms = sum(o[2] for o in conv)
-        conv_flops = sum(o[3] for o in conv)
-        conv_ms_seq = sum(o[2] for o in ops_seq if o[0].startswith("conv"))
-        all_ms = sum(o[2] for o in ops)
-        if args.per_op:
-            for (k, n, ms, fl, by), w in zip(ops, ops_seq):
-                sys.stderr.write("%-10s %-60s %8.2f us (in sequence, with event cost %7.2f) %7.2f TF/s %7.1f GB/s\n" % (k, n[:160], ms * 1e3, w[2] * 1e3, fl / ms / 1e9 if ms else 0,
-                                                                                                                      by / ms / 1e6 if ms else 0))
-        live = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms else 0.0
-        tr = profile_traffic(PROFILE_TAG + "_bench")      # HBM bytes per conv launch from the committed PMC passes (stamped with the sources' hash)
-        traffic = tr["bytes_per_launch"] if tr else None
-        prof_roof = profile_json("bench_roofline")        # the family's time per frame from the committed kernel trace alone (tools/roofline_from_profile.py)
-        if prof_roof is not None:
-            prof_roof = {k: prof_roof[k] for k in ("frac", "achieved_tflops", "conv_us_per_frame", "mfma_busy_frac", "clock_ghz_assumed", "source", "stale") if k in prof_roof}
-        live_d = {"achieved": round(live, 3), "frac": round(live / F32_MFMA_PEAK_TFLOPS, 4), "conv_us_per_frame": round(conv_ms * 1e3, 2),
-                  "note": "HIP events on the engine's stream around each launch repeated back to back (20 reps): the launch's filters are warm in L2, "
-                          "inside a forward they are cold - 1-4 % faster than the kernel trace of whole forwards"}
-        if args.trace_clean:
-            roofline = {"placeholder": True, "note": "--trace-clean: a kernel-trace pass times no launch by itself; the roofline of this command is derived "
-                                                     "from the trace (tools/roofline_from_profile.py)"}
-        else:
-            fresh = prof_roof is not None and not prof_roof.get("stale", True)
-            achieved = prof_roof["achieved_tflops"] if fresh else live
-            roofline = {"bound": "mfma", "kernel": "conv_fwd_group + conv_first7 (f32 MFMA convolution family; %d launches covering the 59 convolutions)" % len(conv),
-                        "achieved": round(achieved, 3), "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(achieved / F32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                        "source": ("profiles/%s_bench_kernel_stats.csv: rocprofv3 --kernel-trace --stats of this command with one frame in flight, the family's "
-                                   "TotalDurationNs / frames (tools/roofline_from_profile.py)" % PROFILE_TAG) if fresh else
-                                  "live back-to-back launches (the committed kernel trace is %s)" % ("stale: kernel sources changed since" if prof_roof else "missing"),
-                        "traffic_source": tr, "algorithmic_bytes_per_launch": round(sum(o[4] for o in conv) / max(len(conv), 1)),
-                        "traffic_note": "HBM bytes per conv launch = 2*FETCH_SIZE + WRITE_SIZE from separate rocprofv3 --pmc passes of this "
-                                        "command; 'stale' = the kernel sources changed since that profile",
-                        "frames_in_flight": 1,
-                        "conv_us_per_frame": prof_roof["conv_us_per_frame"] if fresh else round(conv_ms * 1e3, 2),
-                        "live_back_to_back": live_d,
-                        "in_sequence_events": {"conv_us_per_frame": round(conv_ms_seq * 1e3, 2), "event_pair_floor_us": round(getattr(eng, "event_pair_floor_ms", 0.0) * 1e3, 2),
-                                               "note": "each launch once, in the cache state of a forward, between two events: includes event handling "
-                                                       "(an empty pair reads event_pair_floor_us); reference only"},
-                        "from_profile": prof_roof,
-                        "avg_launch_us": round(conv_ms * 1e3 / max(len(conv), 1), 2), "launches_per_step": len(ops),
-                        "sum_kernel_ms_per_step": round(all_ms, 4),
-                        "measured_on": "one stream; kernel durations are not comparable once frames overlap",
-                        "whole_step_tflops": round(FWD_GFLOP * args.batch / (dev_ms / args.steps), 3)}
         region = ("SURVEY 8(d) config 2: H2D of the (3,448,448) f32 frame from pinned host memory + layout change + all kernels + D2H of the two head "
                   "blobs") if rep_s else "kernels only (--no-io-region)"
         rep_v = rep_s or rep_k
         out = {"metric": "frames/sec forward 448x448 @1 GPU; train imgs/sec @1/2/4/8 GPUs", "value": round(value, 2),
                "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32", "data": "synthetic",
+               "dtype": "f32", "data": "synthetic", "full": args.full,
                "config": {"workload": "configs[1]: single-GPU forward, DetectNet GoogLeNet conv stack + coverage/bbox heads "
                                       "(graph of models/deploy.prototxt), batch=%d, 448x448, random-init weights" % args.batch,
                           "global_batch": args.batch * world, "parallelism": "replicas x%d" % world, "frames_in_flight": depth,
                           "timed_region": "`value`: %s, hipGraph replay, %d frames in flight (a frame's copies ride on its replica's stream and overlap "
-                                          "the other replicas' kernels), median of %d repeats of K steps; `value_kernels_only`: the same K steps on inputs "
-                                          "already resident in HBM (rounds 1-3's `value`); `config2_frames_per_s`: the region one frame at a time"
-                                          % (region, depth, len(rep_v))},
+                                          "the other replicas' kernels), median of %d repeats of K steps%s"
+                                          % (region, depth, len(rep_v), "; `value_kernels_only`: the same K steps on inputs already resident in HBM "
+                                             "(rounds 1-3's `value`); `config2_frames_per_s`: the region one frame at a time" if args.full else
+                                             "; nothing else is measured without --full")},
                "repeats": {"R": len(rep_v), "frames_per_s": [round(frames / t, 1) for t in rep_v],
                            "min": round(frames / max(rep_v), 1), "max": round(frames / min(rep_v), 1),
-                           "spread_pct": round(100.0 * (max(rep_v) - min(rep_v)) / t_max, 2)},
-               "value_kernels_only": round(value_k, 2),
-               "kernels_only": {"frames_per_s": round(value_k, 2), "ms_per_step": round(t_k * 1e3 / args.steps, 4), "frames_in_flight": depth,
-                                "repeats": [round(frames / t, 1) for t in rep_k],
-                                "includes": "all kernels of the forward, inputs resident in HBM, outputs left in HBM (no copies in the timed region)"},
-               "config2_frames_per_s": round(pcie_fps, 2),
-               "config2_frames_per_s_in_flight": round(value, 2) if rep_s else None,
-               "config2_timed_region": {"frames_per_s": round(pcie_fps, 2), "ms_per_frame": round(1e3 / pcie_fps, 4) if pcie_fps else None,
-                                        "frames_per_s_in_flight": round(value, 2) if rep_s else None, "frames_in_flight": depth,
-                                        "repeats": {"one_at_a_time": [round(v, 1) for v in io_one]},
-                                        "includes": "SURVEY 8(d) config 2: H2D of the (3,448,448) f32 frame (pinned host memory) + layout change + all kernels + "
-                                                    "D2H of the two head blobs; one frame at a time here, with frames in flight it is `value`"},
-               "single_stream": {"frames_per_s": round(args.steps * args.batch / serial_s, 2),
-                                 "latency_ms_per_frame": round(serial_s * 1e3 / args.steps, 4),
-                                 "device_ms_per_step": round(dev_ms / args.steps, 4)},
-               "pcie_inclusive_fps": round(pcie_fps, 2),
-               "roofline": roofline,
-               "roofline_in_flight": {"bound": "mfma", "frames_in_flight": depth, "achieved": round(FWD_GFLOP * value_k / 1e3, 3), "peak": F32_MFMA_PEAK_TFLOPS,
-                                      "unit": "TFLOP/s", "frac": round(FWD_GFLOP * value_k / 1e3 / F32_MFMA_PEAK_TFLOPS, 4),
-                                      "with_copies": {"achieved": round(FWD_GFLOP * value / 1e3, 3), "frac": round(FWD_GFLOP * value / 1e3 / F32_MFMA_PEAK_TFLOPS, 4)},
-                                      "note": "conv FLOPs of a frame x frames/s over the wall clock of the K steps with frames in flight - kernels only "
-                                              "(`value_kernels_only`) and, under `with_copies`, config 2's region (`value`); kernels of different frames overlap, so "
-                                              "per-kernel durations are not comparable: profiles/%s_bench_inflight_kernel_stats.csv holds the kernel trace of this mode" % PROFILE_TAG}}
+                           "spread_pct": round(100.0 * (max(rep_v) - min(rep_v)) / t_max, 2)}}
+        if args.full:
+            out.update(forward_details(args, eng, depth, dev_ms, serial_s, frames, value, t_k, rep_k, rep_s))
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "step": "the last of the %d timed steps of the last repeat" % args.steps}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, ref_blobs = cpu_baseline(msg, params, x)
             out["cpu_baseline"] = base
             res = eng.forward()
@@ -726,15 +751,16 @@ def main() -> None:
             if max(errs.values()) >= 1e-3:
                 raise SystemExit("bench: GPU output differs from the oracle: %s" % errs)
             out["speedup_vs_cpu"] = round(value / base["value"], 1)      # (config 2's region with frames in flight against the CPU port's forward)
-            out["speedup_vs_cpu_kernels_only"] = round(value_k / base["value"], 1)
+            out["speedup_vs_cpu_kernels_only"] = round(frames / t_k / base["value"], 1)
     cp.barrier()
     pipe.close()
-    if out is not None and world == 1 and not args.no_secondary:
+    secondary = args.full and out is not None and world == 1 and not args.no_secondary
+    if secondary:
         # measured right after the headline's replicas are gone: the runtime deals streams to its hardware queues in creation
         # order and replica streams that share a queue do not overlap (with 8 queues and other engines' streams alive: 2550
         # instead of 3450 frames/s; lib.load() asks for 16)
         out["detector_batch1"] = bench_detector_stream(local, msg, params)
-    if not args.no_train:
+    if args.full and not args.no_train:
         tsteps = args.train_steps or max(min(args.steps, 30), 1)
         watchdog = None
         if world > 1:
@@ -760,7 +786,7 @@ def main() -> None:
             watchdog.cancel()
         if out is not None:
             out["train"] = tr
-    if out is not None and world == 1 and not args.no_secondary:
+    if secondary:
         # the same DetectNet forward at batch 8 (not the headline configuration): M is 8x larger, launches stop being latency-bound
         msg8 = proto.parse_text(models.googlenet_detectnet_deploy(8, 448, 448, 4))
         spec8 = NetSpec(msg8, "TEST")

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export FCN_TUNE_CACHE=$OUT/${TAG}_tune.json
-ARGS="--steps 50 --warmup 5 --no-cpu-baseline --no-secondary $*"
+ARGS="--full --steps 50 --warmup 5 --no-cpu-baseline --no-secondary $*"      # --full: the passes below profile the single-stream forward, the per-launch timings and the training step too
 cd "$ROOT"
 python3 bench.py $ARGS > "$OUT/${TAG}_bench_plain.json"            # fills the tune cache: profiled runs replay the plan
 # ... and the plan of the one-frame-in-flight mode (no LDS cap: its own cache keys).  The tuner decides by timing and two tunings of the same
@@ -19,7 +19,7 @@ BASE_CACHE=$FCN_TUNE_CACHE
 best=""; best_ms=""
 for i in 1 2 3; do
     cp "$BASE_CACHE" "$OUT/${TAG}_tune1_$i.cache.json"
-    FCN_TUNE_CACHE="$OUT/${TAG}_tune1_$i.cache.json" python3 bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-secondary $* --in-flight 1 --no-train --no-io-region > "$OUT/${TAG}_tune1_$i.json"
+    FCN_TUNE_CACHE="$OUT/${TAG}_tune1_$i.cache.json" python3 bench.py --full --steps 200 --warmup 5 --no-cpu-baseline --no-secondary $* --in-flight 1 --no-train --no-io-region > "$OUT/${TAG}_tune1_$i.json"
     ms=$(python3 -c "import json,sys; print(json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['single_stream']['device_ms_per_step'])" "$OUT/${TAG}_tune1_$i.json")
     echo "one-frame-in-flight tuning $i: $ms ms per frame"
     if [ -z "$best" ] || python3 -c "import sys; sys.exit(0 if float(sys.argv[1]) < float(sys.argv[2]) else 1)" "$ms" "$best_ms"; then best=$i; best_ms=$ms; fi
@@ -39,7 +39,7 @@ prof() {      # prof <dir> <rocprofv3 options...> -- <program...>   (the program
 ONE="$ARGS --in-flight 1"      # ONE frame in flight: per-kernel durations only mean something when launches do not overlap
 # kernel-trace passes run 4 x the frames of the counter passes: rocprofv3's per-kernel AVERAGES (what roofline_from_profile.py divides)
 # carry the first frames of a process (clock ramp, cold code) - 1.8 % above the median at 50 steps, within 0.5 % at 200
-TRACE="--steps 200 --warmup 5 --no-cpu-baseline --no-secondary $*"
+TRACE="--full --steps 200 --warmup 5 --no-cpu-baseline --no-secondary $*"
 export PYTHONFAULTHANDLER=1
 export FCN_NO_GRAPH=1          # plain launches: the training step, the counter passes, and a kernel trace of the forward
 prof ${TAG}_pstats --stats -- python3 "$ROOT/bench.py" $TRACE --in-flight 1 --no-train --trace-clean > "$OUT/${TAG}_bench_plain_under_rocprof.json"

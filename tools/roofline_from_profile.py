@@ -80,7 +80,7 @@ def main():
 
 def train_roofline(tag, batch):
     """bench.py's `train.roofline` from the kernel trace of the REAL two-stream training step (profiles/<tag>_train_kernel_stats.csv, a
-    `bench.py --trace-clean` pass: whole steps only): the weight-gradient family = conv_wgrad_* + reduce_partials_* kernels, steps = calls of
+    `bench.py --full --trace-clean` pass: whole steps only): the weight-gradient family = conv_wgrad_* + reduce_partials_* kernels, steps = calls of
     the solver kernel (one per step), FLOPs of a step = 2 * Cout * K * M over the 59 convolutions = 15.608 GFLOP x batch."""
     stats = os.path.join(ROOT, "profiles", tag + "_train_kernel_stats.csv")
     if not os.path.isfile(stats):
