@@ -1,0 +1,548 @@
+"""Plan of the backward pass of a TrainEngine: layer list in reverse -> the launches of Net::Backward.
+
+Runs once, when the engine is built.  One method per layer type (BackwardPlanner.emitters / .one_bottom); what they share is the
+write state of every gradient view - state() / mark() - because a gradient that already holds a value must be accumulated
+into, and because the LAST data-gradient pass that writes a view may take the ReLU mask of the layer below into its epilogue
+(_finish_dgrads).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
+
+from . import lib as L
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, tconv_desc
+from .netspec import DATA_TYPES, Layer
+
+
+@dataclass
+class Dgrad:
+    """One data-gradient launch, prepared once the whole plan is known: a group of stride-1 passes that write different buffers
+    (ConvDesc, launch: L.ConvGroup) or the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan).
+    targets[i]: the blob descs[i] writes."""
+    name: str
+    descs: list
+    targets: List[str]
+    launch: object
+    op: Optional[Op] = None
+
+
+@dataclass
+class PoolBwd:
+    """A MAX pooling backward writing the gradient of `blob`; mask = (activation buffer, cstride, coffset) once the ReLU backward
+    of that blob is folded into it."""
+    blob: str
+    mask: Tuple[Optional[int], int, int] = (None, 0, 0)
+
+
+class BackwardPlanner:
+    def __init__(self, eng) -> None:
+        self.e, self.spec, self.B, self.G, self.lib = eng, eng.spec, eng.blobs, eng.grad_blobs, L.load()
+        self.ops: List[Op] = []
+        self.ws_floats = 1                                   # workspace of the weight-gradient launches: the largest any of them needs
+        self.written: Dict[int, List[Tuple[int, int]]] = {}  # gradient buffer -> channel ranges already holding a gradient
+        self.writers: Dict[str, List[object]] = {}           # gradient blob -> what wrote it, in order (a dgrad / pooling record or None)
+        self.concat_members: Dict[str, List[str]] = {}       # Concat output -> its member blobs
+        self.concat_relu: Dict[str, str] = {}                # member blob -> the Concat output one ReLU mask launch covers
+        self.relu_done, self.dgrad_done, self.wgrad_done = set(), set(), set()
+        self.sibling_reduces: Dict[str, List[Layer]] = {}    # reduce layer -> the reduce layers of its module (ready together)
+        self.flip_layout: Dict[str, int] = {}                # stride-1 convolution -> offset of its bank in flip_flat (floats)
+        self.flip_segs_dev: Optional[DeviceBuffer] = None
+        self.tbank: Dict[str, DeviceBuffer] = {}
+        self.dgrad_records: List[Dgrad] = []
+        self.relu_ops: Dict[str, Op] = {}                    # gradient blob whose ReLU backward is the op (candidates for the fused mask)
+        self.skip_sigmoid_of = {m["sigmoid_top"]: name for name, m in eng._conv_layer_meta.items() if m.get("sigmoid_top")}
+        nothing = lambda l: None
+        # layer types that look at the plan state themselves ...
+        self.emitters = {"Convolution": self._convolution, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
+                         "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": nothing,
+                         "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
+                         "Accuracy": nothing,      # a metric: no gradient, no entry in loss_blobs
+                         **{t: nothing for t in DATA_TYPES}}
+        # ... and the ones _one_bottom hands (layer, dY, dX, accumulate)
+        self.one_bottom = {"Pooling": self._pooling, "LRN": self._lrn, "Dropout": self._dropout, "Eltwise": self._eltwise_prod,
+                           "Deconvolution": self._depthwise_deconv, "Sigmoid": self._sigmoid_plain, "ReLU": self._relu_plain,
+                           "Power": lambda l, gtop, gbot, acc: None}      # input transform: nothing upstream learns
+
+    def run(self) -> None:
+        self._find_concat_relu()
+        self._plan_banks()
+        for l in reversed(self.spec.layers):
+            (self.emitters.get(l.type) or self._one_bottom)(l)
+        self._finish_dgrads()
+        self.ws = DeviceBuffer(self.ws_floats * 4, zero=False)
+
+    # ------------------------------------------------------------------ write state of the gradient views
+    def state(self, g: Blob) -> str:
+        """'none' | 'full' for the channel range of view g (partial overlap is a planning error)."""
+        lo, hi = g.coffset, g.coffset + g.channels
+        cov = 0
+        for a, b in self.written.get(g.buf.ptr, []):
+            o = min(hi, b) - max(lo, a)
+            if o > 0:
+                cov += o
+        if cov == 0:
+            return "none"
+        if cov >= hi - lo:
+            return "full"
+        raise NotImplementedError("gradient of %s is partially written" % g.name)
+
+    def mark(self, g: Blob, writer: object = None) -> None:
+        self.written.setdefault(g.buf.ptr, []).append((g.coffset, g.coffset + g.channels))
+        self.writers.setdefault(g.name, []).append(writer)
+
+    def last_writer(self, name: str) -> object:
+        w = self.writers.get(name)
+        return w[-1] if w else None
+
+    def _arrived(self, l: Layer) -> Optional[Blob]:
+        """dY of the layer's first top, or None when no gradient reaches this layer."""
+        g = self.G.get(l.tops[0]) if l.tops else None
+        return g if g is not None and self.state(g) != "none" else None
+
+    # ------------------------------------------------------------------ before the layers
+    def _conv_of(self, blob: str) -> Layer:
+        return [q for q in self.e.producers.get(blob, []) if q.type == "Convolution"][0]
+
+    def _find_concat_relu(self) -> None:
+        """Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch."""
+        e, B = self.e, self.B
+        for child, (parent, _off) in e.alias.items():
+            if any(q.type == "Concat" and parent in q.tops for q in e.producers.get(parent, [])):
+                self.concat_members.setdefault(parent, []).append(child)
+        for parent, members in self.concat_members.items():
+            prods = [[q for q in e.producers.get(m, []) if q.type == "Convolution"] for m in members]
+            if all(len(pr) == 1 and e._conv_layer_meta.get(pr[0].name, {}).get("relu") for pr in prods) and \
+                    sum(B[m].channels for m in members) == B[parent].channels and B[parent].coffset == 0:
+                for m in members:
+                    self.concat_relu[m] = parent
+
+    def _plan_banks(self) -> None:
+        """Filter banks of the data-gradient passes, refreshed from the current weights at the start of every backward pass.
+        Stride 1: flipped / transposed banks, slices of ONE flat buffer that a single launch refreshes (58 launches otherwise).
+        Strided convolutions: the transposed-convolution kernel reads the layer's own OHWI bank re-packed tap-major
+        ([kh][kw][Cin][Cout4])."""
+        e, lib = self.e, self.lib
+        flip_segs: List[L.FlipSeg] = []
+        flip_floats = 0
+        packs: List[Op] = []
+        for l in self.spec.layers:
+            if l.type != "Convolution" or self.G.get(l.bottoms[0]) is None or self.G.get(l.tops[0]) is None:
+                continue
+            g = e._geom(l)
+            cin, cout, k = g.cin, g.cout, g.k
+            wdev = e.params_dev[l.name][0].ptr
+            if g.s == 1:
+                self.flip_layout[l.name] = flip_floats
+                flip_segs.append(L.FlipSeg((wdev - e.param_flat.ptr) // 4, flip_floats, cout, k, k, cin, _r4(cin), _r4(cout)))
+                flip_floats += _r4(cin * k * k * _r4(cout))
+            else:
+                bank = self.tbank[l.name] = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(cout, cin, k, k)), 4) * 4, zero=True)
+                packs.append(Op("tconv_pack", l.name, lambda st, wdev=wdev, bank=bank, cout=cout, cin=cin, k=k: L.check(
+                    lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, cout, cin, _r4(cin), k, k, st))))
+        self.flip_flat = DeviceBuffer(max(flip_floats, 4) * 4, zero=True)
+        if flip_segs:
+            seg_arr = (L.FlipSeg * len(flip_segs))(*flip_segs)
+            self.flip_segs_dev = DeviceBuffer(C.sizeof(seg_arr), zero=False)
+            L.call("fcn_memcpy_h2d_async", self.flip_segs_dev.ptr, C.addressof(seg_arr), C.sizeof(seg_arr), None)
+            L.call("fcn_device_sync")
+            self.ops.append(Op("flip", "%d filter banks" % len(flip_segs), lambda st, n=len(flip_segs): L.check(lib.fcn_conv_weights_flip_batch_f32(
+                e.param_flat.ptr, e._flip_flat.ptr, e._flip_segs_dev.ptr, n, st))))
+        self.ops.extend(packs)
+
+    # ------------------------------------------------------------------ data gradients
+    def emit_tdgrad(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Dgrad:
+        """Data gradient of the strided convolution l: the transposed convolution of dY, written at the size of the layer's input
+        (rows / columns of it that lay under no window get zeros).  Prepared in _finish_dgrads like the grouped launches, because
+        the ReLU mask of the layer below may still be folded into its epilogue."""
+        g, lib = self.e._geom(l), self.lib
+        if gtop.coffset % 4 or gtop.cstride - gtop.coffset < _r4(g.cout):
+            raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
+        if g.pad >= g.k:
+            raise NotImplementedError("data gradient of the strided convolution %s with pad %d >= kernel %d" % (l.name, g.pad, g.k))
+        d = tconv_desc(gtop, gbot, g.swapped(), self.tbank[l.name].ptr, flags=L.CONV_ACCUM if accumulate else 0)
+        rec = Dgrad(l.name, [d], [l.bottoms[0]], L.TConvPlan())
+        rec.op = Op("tconv_dgrad", l.name, lambda st, pl=rec.launch: L.check(lib.fcn_tconv2d_f32(C.byref(pl), st)), g.flops)
+        self.ops.append(rec.op)
+        self.dgrad_records.append(rec)
+        self.e._keep.append(d)
+        return rec
+
+    def dgrad_desc(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Tuple[L.ConvDesc, float]:
+        """Data gradient of convolution l = the forward kernel on dY with the flipped / transposed bank."""
+        g = self.e._geom(l)
+        if g.s != 1:
+            raise RuntimeError("dgrad_desc is the stride-1 path; strided layers go through emit_tdgrad (%s)" % l.name)
+        cin_dg = _r4(g.cout)      # the flipped bank reads Cout4 input channels: the gradient view must expose them contiguously
+        if gtop.cstride - gtop.coffset < cin_dg:
+            raise NotImplementedError("gradient view of %s too narrow for the data-gradient pass" % l.tops[0])
+        wt = DevView(self.flip_flat.ptr + 4 * self.flip_layout[l.name], g.cin * g.k * g.k * cin_dg * 4)
+        dd = conv_desc(gtop, gbot, g.swapped()._replace(cin=cin_dg, s=1, pad=g.k - 1 - g.pad), wt.ptr,
+                       flags=L.CONV_ACCUM if accumulate else 0)
+        self.e._keep.append(dd)
+        return dd, g.flops
+
+    def emit_dgrads(self, name: str, items: List[Tuple[L.ConvDesc, float]], targets: List[str]) -> Dgrad:
+        """One grouped launch for data-gradient passes that write different buffers.  The group is prepared (and
+        autotuned) after the whole backward plan is known, because the LAST writer of a gradient may still get the ReLU
+        mask of the layer below folded into its epilogue (_finish_dgrads)."""
+        lib = self.lib
+        rec = Dgrad(name, [d for d, _ in items], list(targets), L.ConvGroup())
+        rec.op = Op("dgrad", name, lambda st, g=rec.launch: L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(g), st)), sum(fl for _, fl in items))
+        self.ops.append(rec.op)
+        self.dgrad_records.append(rec)
+        return rec
+
+    def _finish_dgrads(self) -> None:
+        e, B, lib = self.e, self.B, self.lib
+        # fold "ReLU backward of blob X" into the last data-gradient pass that writes dX, when that is what wrote it last
+        for x, rop in self.relu_ops.items():
+            rec = self.last_writer(x)
+            if rec is None or rop not in self.ops:
+                continue
+            if isinstance(rec, PoolBwd):        # the last writer is a pooling backward of exactly this blob
+                if rec.blob == x:
+                    rec.mask = (B[x].buf.ptr, B[x].cstride, B[x].coffset)
+                    self.ops.remove(rop)
+                continue
+            d = rec.descs[rec.targets.index(x)]
+            act = B[x]
+            d.y2, d.y2_cstride, d.y2_coffset = act.buf.ptr, act.cstride, act.coffset
+            d.flags |= L.CONV_MASK
+            self.ops.remove(rop)
+        for rec in self.dgrad_records:
+            if isinstance(rec.launch, L.TConvPlan):
+                d = rec.descs[0]
+                tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+                L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(rec.launch))
+                e._keep.extend([tws, rec.launch])
+                rec.op.name = "%s [%dwg]" % (rec.name, rec.launch.total_tiles)
+                continue
+            n_ = len(rec.descs)
+            arr = (L.ConvDesc * n_)(*rec.descs)
+            gws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(n_)), zero=False)
+            cfg = e._tuned_cfg("dgrad:" + rec.name, arr, n_, gws) if e.autotune else -1
+            L.call("fcn_conv2d_group_prepare", arr, n_, gws.ptr, cfg, C.byref(rec.launch))
+            e._keep.extend([arr, gws, rec.launch])
+            e._group_workspaces.append(gws)
+            rec.op.name = "%s [cfg%d %dwg]" % (rec.name, rec.launch.cfg, rec.launch.total_tiles)
+
+    # ------------------------------------------------------------------ weight gradients, ReLU masks
+    def relu_bwd_op(self, name: str, y: Blob, dy: Blob, dx: Optional[Blob] = None) -> Op:
+        """dX = dY where the activation y is positive, else 0.  dx None: in place on dY, the mask of a ReLU fused into its
+        convolution (its traffic is booked; the ReLU layer's own never was)."""
+        lib, byts = self.lib, 12.0 * y.pixels * y.channels if dx is None else 0.0
+        dx = dy if dx is None else dx
+        op = Op("relu_bwd", name, lambda st: L.check(lib.fcn_relu_bwd_f32(dy.ptr, y.ptr, dx.ptr, y.pixels, y.channels, y.cstride, st)), 0.0, byts)
+        self.ops.append(op)
+        return op
+
+    def _book_wgrad(self, op: Op, sel: dict, names: List[str], ws_floats: List[int]) -> None:
+        self.ws_floats = max([self.ws_floats] + ws_floats)
+        op.sel = sel
+        op.layers = names
+        self.ops.append(op)
+        self.wgrad_done.update(names)
+
+    def _wgrad_cfgs(self) -> List[int]:
+        return [-1] + (list(range(int(self.lib.fcn_conv2d_wgrad_num_configs()))) if self.e.autotune else [])
+
+    def wgrad_op(self, name: str, d: L.ConvDesc, dw: DevView, db: Optional[DevView], flops: float) -> None:
+        """The weight (and bias) gradient of one problem: d.x the layer's input, d.y its dY."""
+        e, lib = self.e, self.lib
+        sel = {"cfg": -1}      # -1: the library's heuristic; _tune_wgrads() replaces it once the workspace exists
+        op = Op("wgrad", name, lambda st: L.check(lib.fcn_conv2d_wgrad_cfg_f32(
+            C.byref(d), dw.ptr, db.ptr if db else None, e._ws.ptr, sel["cfg"], st)), flops)
+        self._book_wgrad(op, sel, [name], [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), c, None)) for c in self._wgrad_cfgs()])
+
+    def wgrad_item(self, l: Layer, gtop: Blob) -> Tuple[L.ConvDesc, DevView, Optional[DevView], float]:
+        """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns."""
+        e, g, xb = self.e, self.e._geom(l), self.B[l.bottoms[0]]
+        if gtop.coffset % 4 or gtop.cstride % 4:
+            raise NotImplementedError("gradient view of %s is not 16-byte aligned" % l.tops[0])
+        d = conv_desc(xb, gtop, g._replace(cin=_r4(g.cin)))
+        e._keep.append(d)
+        dw = e._grad_view(l.name, 0)
+        db = e._grad_view(l.name, 1) if len(e.params_dev[l.name]) > 1 else None
+        return d, dw, db, g.flops
+
+    def emit_wgrads(self, layers_: List[Layer], gtops: List[Blob]) -> None:
+        """Weight (and bias) gradients of layers that are ready together: one launch + one reduction for up to four."""
+        e, lib = self.e, self.lib
+        todo = [(l_, g_) for l_, g_ in zip(layers_, gtops) if e._learns(l_) and l_.name not in self.wgrad_done]
+        for base in range(0, len(todo), 4):
+            chunk = todo[base:base + 4]
+            its = [self.wgrad_item(l_, g_) for l_, g_ in chunk]
+            names = [l_.name for l_, _ in chunk]
+            if len(its) == 1:
+                self.wgrad_op(names[0], *its[0])
+                continue
+            descs, dws, dbs, flops = zip(*its)
+            m = len(its)
+            sel = {"cfg": -1}
+            arr = (L.ConvDesc * m)(*descs)
+            pdw = (C.c_void_p * m)(*[dw.ptr for dw in dws])
+            pdb = (C.c_void_p * m)(*[(db.ptr if db is not None else None) for db in dbs])
+            e._keep.extend([arr, pdw, pdb])
+            op = Op("wgrad", "+".join(names), lambda st, arr=arr, pdw=pdw, pdb=pdb, m=m, sel=sel: L.check(
+                lib.fcn_conv2d_wgrad_group_cfg_f32(arr, pdw, pdb, m, e._ws.ptr, sel["cfg"], st)), sum(flops))
+            self._book_wgrad(op, sel, names, [int(lib.fcn_conv2d_wgrad_group_workspace_floats_cfg(arr, m, c)) for c in self._wgrad_cfgs()])
+
+    # ------------------------------------------------------------------ Convolution
+    def _convolution(self, l: Layer) -> None:
+        gtop = self._arrived(l)
+        if gtop is None:
+            return
+        e, G, top = self.e, self.G, l.tops[0]
+        if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
+            whole = self.concat_relu.get(top)
+            if whole is not None and whole in G and self.state(G[whole]) == "full":
+                self._concat_module(whole)
+            else:
+                rop = self.relu_bwd_op(l.name, self.B[top], gtop)
+                if top not in e.alias:
+                    self.relu_ops[top] = rop
+                self.relu_done.add(top)
+        self._sibling_wgrads(l)
+        self.emit_wgrads([l], [gtop])
+        gbot = G.get(l.bottoms[0])
+        if gbot is not None and l.name not in self.dgrad_done:
+            if e._geom(l).s != 1:
+                rec = self.emit_tdgrad(l, gtop, gbot, self.state(gbot) == "full")
+            else:
+                rec = self.emit_dgrads(l.name, [self.dgrad_desc(l, gtop, gbot, self.state(gbot) == "full")], [l.bottoms[0]])
+            self.mark(gbot, rec)
+
+    def _concat_module(self, whole: str) -> None:
+        """Every member of this Concat is a convolution with an in-place ReLU and the gradient of the whole concatenation is
+        final: ONE contiguous launch masks all members (an inception module: 4 -> 1); then their data gradients, their weight
+        gradients, and which of the layers below become ready together."""
+        members = self.concat_members[whole]
+        self.relu_ops[whole] = self.relu_bwd_op(whole, self.B[whole], self.G[whole])
+        self.relu_done.update(members)
+        self._member_dgrads(members)
+        # ... and their weight gradients need nothing else either: one grouped launch
+        mem_layers = [self._conv_of(m) for m in members]
+        self.emit_wgrads(mem_layers, [self.G[m] for m in members])
+        self._find_sibling_reduces(mem_layers)
+
+    def _member_dgrads(self, members: List[str]) -> None:
+        """The members' data gradients only need the masked gradient of the concatenation and write four different buffers (the
+        module input and the outputs of the reduce / pool layers): one grouped launch at the top of the module's backward
+        instead of four scattered ones."""
+        G = self.G
+        items, names, targets, tnames = [], [], [], []
+        for m in members:
+            lm = self._conv_of(m)
+            gb = G.get(lm.bottoms[0])
+            if gb is None or lm.name not in self.flip_layout or self.state(gb) != "none" or any(gb.buf.ptr == tb for tb in targets):
+                continue
+            items.append(self.dgrad_desc(lm, G[m], gb, False))
+            names.append(lm.name)
+            targets.append(gb.buf.ptr)
+            tnames.append(lm.bottoms[0])
+        if len(items) > 1:
+            rec = self.emit_dgrads("+".join(names), items, tnames)
+            for nm, tn in zip(names, tnames):
+                self.dgrad_done.add(nm)
+                self.mark(G[tn], rec)
+
+    def _find_sibling_reduces(self, mem_layers: List[Layer]) -> None:
+        """The layers feeding the members (3x3_reduce, 5x5_reduce) get their whole gradient from the members' dgrad launch: they
+        become ready together too."""
+        e = self.e
+        sibs = []
+        for lm in mem_layers:
+            if lm.name not in self.dgrad_done:
+                continue
+            prods = [q for q in e.producers.get(lm.bottoms[0], []) if q.type == "Convolution"]
+            cons = [q for q in e.consumers.get(lm.bottoms[0], []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)]
+            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in e.alias and lm.bottoms[0] in self.G:
+                sibs.append(prods[0])
+        if len(sibs) > 1:
+            for q in sibs:
+                self.sibling_reduces[q.name] = sibs
+
+    def _sibling_wgrads(self, l: Layer) -> None:
+        """l is the first of its module's reduce layers to be visited: mask and take the weight gradients of all of them now."""
+        G = self.G
+        sibs = self.sibling_reduces.get(l.name)
+        if not (sibs and l.name not in self.wgrad_done and all(self.state(G[q.tops[0]]) == "full" for q in sibs)):
+            return
+        for q in sibs:
+            if q.tops[0] not in self.relu_done and self.e._conv_layer_meta[q.name].get("relu"):
+                self.relu_ops[q.tops[0]] = self.relu_bwd_op(q.name, self.B[q.tops[0]], G[q.tops[0]])
+                self.relu_done.add(q.tops[0])
+        self.emit_wgrads(sibs, [G[q.tops[0]] for q in sibs])
+
+    # ------------------------------------------------------------------ the other layers that look at the plan state themselves
+    def _slice(self, l: Layer) -> None:
+        if l.name in self.e.copy_slices and any(tp in self.G for tp in l.tops):
+            raise NotImplementedError("backward through the copied Slice %s" % l.name)
+
+    def _loss(self, l: Layer) -> None:
+        g = self.G.get(l.bottoms[0])
+        if g is None:
+            return
+        if l.bottoms[1] in self.e.need_grad:
+            raise NotImplementedError("loss layer %s: gradient w.r.t. the second bottom" % l.name)
+        if self.state(g) != "none":
+            raise NotImplementedError("loss gradient would have to accumulate into %s" % l.bottoms[0])
+        self.mark(g)                      # written by the forward loss kernel (da)
+
+    def _sigmoid(self, l: Layer) -> None:
+        if l.tops[0] not in self.skip_sigmoid_of:
+            return self._one_bottom(l)
+        # fused into the conv epilogue in forward; backward is its own small kernel
+        yb, gtop, gbot = self.B[l.tops[0]], self.G.get(l.tops[0]), self.G.get(l.bottoms[0])
+        if gtop is None or gbot is None or self.state(gtop) == "none":
+            return
+        lib, acc = self.lib, 1 if self.state(gbot) == "full" else 0
+        count = yb.pixels * yb.cstride
+        if yb.coffset or gtop.coffset or gbot.coffset or yb.cstride != gbot.cstride:
+            raise NotImplementedError("sigmoid backward on channel slices")
+        self.ops.append(Op("sigmoid_bwd", l.name, lambda st: L.check(lib.fcn_sigmoid_bwd_f32(yb.ptr, gtop.ptr, gbot.ptr, count, acc, st))))
+        self.mark(gbot)
+
+    def _relu(self, l: Layer) -> None:
+        if l.name not in self.e._fused_relu_layers():
+            self._one_bottom(l)
+
+    def _eltwise(self, l: Layer) -> None:
+        p = l.sub("eltwise_param")
+        if str(p.get("operation", "SUM")) != "SUM":
+            return self._one_bottom(l)
+        gtop = self._arrived(l)
+        if gtop is None:
+            return
+        # d(bottom_i) = dY for every bottom (train/fcn_bbox fuse_pool4 / fuse_pool3: skip connections)
+        if any(float(c) != 1.0 for c in p.getall("coeff")):
+            raise NotImplementedError("Eltwise SUM backward with coefficients (%s)" % l.name)
+        lib = self.lib
+        for bn in l.bottoms:
+            gb = self.G.get(bn)
+            if gb is None:
+                continue
+            if self.state(gb) == "full":
+                if gtop.coffset or gb.coffset or gb.cstride != gtop.cstride:
+                    raise NotImplementedError("Eltwise SUM backward accumulating into a channel slice")
+                run = lambda st, a=gtop, b=gb: L.check(lib.fcn_eltwise_fwd_f32(a.ptr, b.ptr, b.ptr, a.pixels * a.cstride, L.ELT_SUM, 1.0, 1.0, st))
+            else:
+                run = lambda st, a=gtop, b=gb: L.check(lib.fcn_copy_channels_f32(
+                    a.buf.ptr, b.buf.ptr, a.pixels, a.channels, a.cstride, a.coffset, b.cstride, b.coffset, st))
+            self.ops.append(Op("eltwise_bwd", l.name + ":" + bn, run))
+            self.mark(gb)
+
+    def _deconvolution(self, l: Layer) -> None:
+        if not self.e._deconv_dense(l):
+            return self._one_bottom(l)
+        gtop = self._arrived(l)
+        if gtop is not None:
+            self._dense_deconv(l, gtop, self.G.get(l.bottoms[0]))
+
+    def _dense_deconv(self, l: Layer, gtop: Blob, gbot: Optional[Blob]) -> None:
+        """Backward of a group-1 Deconvolution whose blob is kept as [Cin][kh][kw][Cout4], an OHWI bank of Cin outputs:
+        db = per-channel sum of dY; dW = the weight-gradient kernel with the roles swapped (its x is dY, its y the layer's input);
+        dX = the forward convolution of dY at the layer's stride."""
+        e, lib, xb = self.e, self.lib, self.B[l.bottoms[0]]
+        g = e._geom(l)
+        co = g.cout
+        if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(co):
+            raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
+        gs = g.swapped()._replace(cin=_r4(co))
+        flops = 2.0 * g.n * g.cin * g.h * g.w * co * g.k * g.k
+        if e._learns(l) and l.name not in self.wgrad_done:
+            if len(e.params_dev[l.name]) > 1:
+                db = e._grad_view(l.name, 1)
+                self.ops.append(Op("channel_sum", l.name, lambda st: L.check(lib.fcn_channel_sum_f32(
+                    gtop.buf.ptr, db.ptr, gtop.pixels, co, gtop.cstride, gtop.coffset, st)), 0.0, 4.0 * gtop.pixels * co))
+            if xb.coffset % 4 or xb.cstride % 4:
+                raise NotImplementedError("input view of %s is not 16-byte aligned" % l.name)
+            d = conv_desc(gtop, xb, gs)
+            e._keep.append(d)
+            self.wgrad_op(l.name, d, e._grad_view(l.name, 0), None, flops)
+        if gbot is not None:
+            d = conv_desc(gtop, gbot, gs, e.params_dev[l.name][0].ptr, flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
+            e._keep.append(d)
+            self.mark(gbot, self.emit_dgrads(l.name, [(d, flops)], [l.bottoms[0]]))
+
+    # ------------------------------------------------------------------ one bottom, one top, one launch dY -> dX
+    def _one_bottom(self, l: Layer) -> None:
+        gtop = self._arrived(l)
+        gbot = self.G.get(l.bottoms[0]) if gtop is not None and l.bottoms else None
+        if gbot is None:
+            return
+        acc = 1 if self.state(gbot) == "full" else 0
+        emit = self.one_bottom.get(l.type)
+        if emit is None:
+            raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
+        emit(l, gtop, gbot, acc)
+
+    def _pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        if str(l.sub("pooling_param").get("pool", "MAX")) != "MAX":
+            raise NotImplementedError("backward of AVE pooling (%s)" % l.name)
+        g, lib, idx = self.e._geom(l), self.lib, self.e.aux_dev[l.name]
+        rec = PoolBwd(l.bottoms[0])      # _finish_dgrads may fold a ReLU backward into this pass
+        self.ops.append(Op("maxpool_bwd", l.name, lambda st: L.check(lib.fcn_maxpool_bwd_mask_f32(
+            gtop.buf.ptr, idx.ptr, gbot.buf.ptr, g.n, g.h, g.w, g.cin, gbot.cstride, gbot.coffset, g.k, g.s, g.pad, g.oh, g.ow,
+            gtop.cstride, gtop.coffset, acc, rec.mask[0], rec.mask[1], rec.mask[2], st))))
+        self.mark(gbot, rec)
+
+    def _lrn(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        xb, yb = self.B[l.bottoms[0]], self.B[l.tops[0]]
+        p = l.sub("lrn_param")
+        ls, al, be = int(p.get("local_size", 5)), float(p.get("alpha", 1.0)), float(p.get("beta", 0.75))
+        lib, sc = self.lib, self.e.aux_dev[l.name]
+        if gtop.coffset or gbot.coffset or xb.coffset or yb.coffset:
+            raise NotImplementedError("LRN backward on channel slices")
+        self.ops.append(Op("lrn_bwd", l.name, lambda st: L.check(lib.fcn_lrn_bwd_f32(
+            xb.ptr, yb.ptr, sc.ptr, gtop.ptr, gbot.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, acc, st))))
+        self.mark(gbot)
+
+    def _dropout(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        if acc:
+            raise NotImplementedError("dropout backward into an already written gradient")
+        e, lib = self.e, self.lib
+        ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
+        n, c, h, w = self.B[l.bottoms[0]].shape
+        self.ops.append(Op("dropout_bwd", l.name, lambda st: L.check(lib.fcn_dropout_f32(
+            gtop.buf.ptr, gbot.buf.ptr, n, c, h, w, gtop.cstride, gtop.coffset, gbot.cstride, gbot.coffset, ratio, e.dropout_seed,
+            e.dropout_index_offset, st))))
+        self.mark(gbot)
+
+    def _eltwise_prod(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        opname = str(l.sub("eltwise_param").get("operation", "SUM"))
+        if opname != "PROD" or len(l.bottoms) != 2:
+            raise NotImplementedError("backward of Eltwise %s" % l.name)
+        if l.bottoms[1] in self.e.need_grad:
+            raise NotImplementedError("Eltwise PROD backward w.r.t. both bottoms (%s)" % l.name)
+        if acc:
+            raise NotImplementedError("Eltwise backward into an already written gradient")
+        lib, other = self.lib, self.B[l.bottoms[1]]
+        count = gtop.pixels * gtop.cstride
+        if gtop.coffset or gbot.coffset or other.coffset or other.cstride != gtop.cstride:
+            raise NotImplementedError("Eltwise backward on channel slices")
+        self.ops.append(Op("eltwise_bwd", l.name, lambda st: L.check(lib.fcn_eltwise_fwd_f32(
+            gtop.ptr, other.ptr, gbot.ptr, count, L.ELT_PROD, 1.0, 1.0, st))))
+        self.mark(gbot)
+
+    def _depthwise_deconv(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        if any(m != 0.0 for m in l.lr_mult) or not l.lr_mult:
+            raise NotImplementedError("learnable depthwise Deconvolution %s (group == channels): only group 1 learns; the reference "
+                                      "freezes its bilinear upsampling, lr_mult 0" % l.name)
+        g, lib = self.e._geom(l), self.lib
+        wdev = self.e.params_dev[l.name][0].ptr
+        self.ops.append(Op("deconv_bwd", l.name, lambda st: L.check(lib.fcn_deconv_depthwise_bwd_f32(
+            gtop.buf.ptr, wdev, gbot.ptr, g.n, g.h, g.w, g.cin, gbot.cstride, g.k, g.s, g.pad, g.oh, g.ow, gtop.cstride, gtop.coffset, acc, st))))
+        self.mark(gbot)
+
+    def _sigmoid_plain(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        lib, yb = self.lib, self.B[l.tops[0]]
+        self.ops.append(Op("sigmoid_bwd", l.name, lambda st: L.check(lib.fcn_sigmoid_bwd_f32(
+            yb.ptr, gtop.ptr, gbot.ptr, yb.pixels * yb.cstride, acc, st))))
+        self.mark(gbot)
+
+    def _relu_plain(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        self.relu_bwd_op(l.name, self.B[l.tops[0]], gtop, gbot)
+        self.mark(gbot)

@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from collections import namedtuple
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -39,6 +40,50 @@ def _ra(c: int, esize: int) -> int:
     """Channel count rounded up to whole 16-byte segments of `esize`-byte elements (4 floats / 8 halves)."""
     eps = 16 // esize
     return (c + eps - 1) // eps * eps
+
+
+def graphs_enabled() -> bool:
+    """False under FCN_NO_GRAPH=1: plain launches instead of hipGraphs (e.g. under a profiler).  Reads the environment at every
+    call - tests and tools set the variable after import."""
+    return os.environ.get("FCN_NO_GRAPH", "0") in ("", "0")
+
+
+class ConvGeom(namedtuple("ConvGeom", "n cin h w cout oh ow k s pad")):
+    """The convolution-shaped geometry of one layer (Convolution, Deconvolution, Pooling): input n x cin x h x w, output
+    n x cout x oh x ow, square kernel k at stride s with padding pad."""
+    __slots__ = ()
+
+    @property
+    def flops(self) -> float:
+        return 2.0 * self.n * self.cout * self.oh * self.ow * self.cin * self.k * self.k
+
+    def swapped(self) -> "ConvGeom":
+        """The same layer seen from its output: input and output trade places (data-gradient passes, Deconvolution backward)."""
+        return self._replace(cin=self.cout, h=self.oh, w=self.ow, cout=self.cin, oh=self.h, ow=self.w)
+
+
+def conv_desc(x: "Blob", y: "Blob", g: ConvGeom, w: Optional[int] = None, bias: Optional[int] = None, flags: int = 0) -> L.ConvDesc:
+    """fcn_conv_desc of the problem `g` as the kernel sees it (the caller has rounded Cin and swapped roles where it must) reading
+    the view x and writing the view y - activations or gradients."""
+    d = L.ConvDesc()
+    d.x, d.w, d.bias, d.y = x.ptr, w, bias, y.buf.ptr
+    d.N, d.H, d.W, d.Cin, d.x_cstride = g.n, g.h, g.w, g.cin, x.cstride
+    d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
+    d.y_cstride, d.y_coffset = y.cstride, y.coffset
+    d.flags = flags
+    return d
+
+
+def tconv_desc(a: "Blob", b: "Blob", g: ConvGeom, bank: int, bias: Optional[int] = None, flags: int = 0) -> L.TConvDesc:
+    """fcn_tconv_desc: the transposed convolution that reads the view a (n x cin x h x w of g) through the tap-major bank and
+    writes the view b (n x cout x oh x ow)."""
+    d = L.TConvDesc()
+    d.a, d.w, d.bias, d.b = a.ptr, bank, bias, b.buf.ptr
+    d.N, d.H, d.W, d.Ca, d.a_cstride = g.n, g.h, g.w, g.cin, a.cstride
+    d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
+    d.b_cstride, d.b_coffset = b.cstride, b.coffset
+    d.flags = flags
+    return d
 
 
 class DeviceBuffer:
@@ -492,60 +537,74 @@ class Engine:
         return raw.reshape(shp).copy()
 
     # ------------------------------------------------------------------ plan
+    def _geom(self, l: Layer, ksp: Optional[Tuple[int, int, int]] = None) -> ConvGeom:
+        """Geometry of a Convolution / Deconvolution / Pooling layer from its blobs and its kernel_size / stride / pad (`ksp`
+        overrides the three: global pooling)."""
+        n, cin, h, w = self.blobs[l.bottoms[0]].shape
+        _, cout, oh, ow = self.blobs[l.tops[0]].shape
+        k, s, pad = ksp or kernel_stride_pad(l.sub("pooling_param" if l.type == "Pooling" else "convolution_param"))
+        return ConvGeom(n, cin, h, w, cout, oh, ow, k, s, pad)
+
     def _conv_desc(self, l: Layer, fused_relu: bool, sig_top: Optional[str]) -> L.ConvDesc:
-        p = l.sub("convolution_param")
-        k, s, pad = kernel_stride_pad(p)
-        if int(p.get("group", 1)) != 1:
+        g = self._geom(l)
+        if int(l.sub("convolution_param").get("group", 1)) != 1:
             raise NotImplementedError("grouped Convolution (layer %s) is not used by the reference nets" % l.name)
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        n, cin, h, w = xb.shape
-        _, cout, oh, ow = yb.shape
         eps = 16 // xb.esize
         if xb.coffset % eps or xb.cstride % eps:
             raise NotImplementedError("conv input view of %s is not 16-byte aligned" % l.name)
-        d = L.ConvDesc()
-        d.x, d.w = xb.ptr, self.params_dev[l.name][0].ptr
-        d.bias = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
-        d.y = yb.buf.ptr
-        d.N, d.H, d.W, d.Cin, d.x_cstride = n, h, w, _ra(cin, xb.esize), xb.cstride
-        d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = cout, k, k, pad, s, oh, ow
-        d.y_cstride, d.y_coffset = yb.cstride, yb.coffset
         flags = 0
         if xb.esize == 2:
             flags |= L.CONV_F16 | (L.CONV_OUT_F32 if yb.esize == 4 else 0)
             # the half image of _half_inputs: channels 3 and 4 are the constant 1 (written once, _plan_buffers), 5..7 stay zero and
             # _packed_weight puts the folded shift into the filters' channels 3 and 4 - the first-layer kernel may take them as constants
-            if any(l.bottoms[0] == t and sh for t, sh in getattr(self, "_half_inputs", {}).values()) and _ra(cin, 2) == 8 and xb.cstride == 8:
+            if any(l.bottoms[0] == t and sh for t, sh in getattr(self, "_half_inputs", {}).values()) and _ra(g.cin, 2) == 8 and xb.cstride == 8:
                 flags |= L.CONV_IMAGE_ONES
         elif yb.esize != 4:
             flags |= L.CONV_OUT_F16      # first layer of an f16 net: float32 image in, halves out
         if fused_relu:
             flags |= L.CONV_RELU
         if sig_top:
+            flags |= L.CONV_SIGMOID2
+        pd = self.params_dev[l.name]
+        d = conv_desc(xb, yb, g._replace(cin=_ra(g.cin, xb.esize)), pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, flags)
+        if sig_top:
             sb = self.blobs[sig_top]
             if sb.esize != 4:
                 raise NotImplementedError("sigmoid output %s must be float32" % sig_top)
             d.y2, d.y2_cstride, d.y2_coffset = sb.buf.ptr, sb.cstride, sb.coffset
-            flags |= L.CONV_SIGMOID2
-        d.flags = flags
-        d.in_shift = 0.0
         return d
 
     def _range(self, name: str) -> Tuple[int, int, int]:
         b = self.blobs[name]
         return (b.buf.ptr, b.coffset, b.coffset + max(b.channels, 1))
 
-    def _build_ops(self) -> None:
-        """Layer list -> tasks with read/write sets -> dependency levels -> launches.
+    def _fused_after(self, li: int, l: Layer, skip: set) -> Tuple[bool, Optional[str]]:
+        """(an in-place ReLU directly after convolution l rides in its epilogue, the top of a Sigmoid that does) - the layers so
+        absorbed join `skip`."""
+        layers, top = self.spec.layers, l.tops[0]
+        if not self.fuse:
+            return False, None
+        for nxt in layers[li + 1:]:          # in-place ReLU directly after this conv
+            if top in nxt.bottoms or top in nxt.tops:
+                if nxt.type == "ReLU" and nxt.bottoms == [top] and nxt.tops == [top] and \
+                        float(nxt.sub("relu_param").get("negative_slope", 0.0)) == 0.0:
+                    skip.add(nxt.name)
+                    return True, None
+                break
+        cons = self.consumers.get(top, [])
+        if len(cons) == 1 and cons[0].type == "Sigmoid" and cons[0].tops[0] != top and len(self.producers.get(top, [])) == 1:
+            skip.add(cons[0].name)
+            return False, cons[0].tops[0]
+        return False, None
 
-        Tasks on one level are mutually independent; all convolutions of a level share ONE grouped launch
-        (an inception module becomes {1x1, 3x3_reduce, 5x5_reduce} then {3x3, 5x5, pool_proj})."""
-        spec, B = self.spec, self.blobs
-        layers = spec.layers
-        lib = L.load()
-        skip = set()
+    def _collect_tasks(self) -> List[dict]:
+        """Layer list -> tasks with read/write sets: one per convolution (a descriptor for the grouped launches) and one per
+        other layer that launches anything (its ops)."""
+        spec = self.spec
+        skip: set = set()
         tasks: List[dict] = []
-        for li, l in enumerate(layers):
+        for li, l in enumerate(spec.layers):
             if l.name in skip:
                 continue
             t = l.type
@@ -553,28 +612,11 @@ class Engine:
                 continue
             if t == "Convolution":
                 top = l.tops[0]
-                fused_relu, sig_top = False, None
-                if self.fuse:
-                    for nxt in layers[li + 1:]:          # in-place ReLU directly after this conv
-                        if top in nxt.bottoms or top in nxt.tops:
-                            if nxt.type == "ReLU" and nxt.bottoms == [top] and nxt.tops == [top] and \
-                                    float(nxt.sub("relu_param").get("negative_slope", 0.0)) == 0.0:
-                                fused_relu = True
-                                skip.add(nxt.name)
-                            break
-                    if not fused_relu:
-                        cons = self.consumers.get(top, [])
-                        if len(cons) == 1 and cons[0].type == "Sigmoid" and cons[0].tops[0] != top and \
-                                len(self.producers.get(top, [])) == 1:
-                            sig_top = cons[0].tops[0]
-                            skip.add(cons[0].name)
-                desc = self._conv_desc(l, fused_relu, sig_top)
-                n, cin, h, w = B[l.bottoms[0]].shape
-                _, cout, oh, ow = B[top].shape
-                k = desc.kh
-                tasks.append(dict(kind="conv", layer=l, desc=desc,
-                                  flops=2.0 * n * cout * oh * ow * cin * k * k,
-                                  bytes=4.0 * (n * cin * h * w + n * cout * oh * ow + cout * cin * k * k + cout),
+                fused_relu, sig_top = self._fused_after(li, l, skip)
+                g = self._geom(l)
+                tasks.append(dict(kind="conv", layer=l, desc=self._conv_desc(l, fused_relu, sig_top),
+                                  flops=g.flops,
+                                  bytes=4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout),
                                   reads=[self._range(l.bottoms[0])],
                                   writes=[self._range(top)] + ([self._range(sig_top)] if sig_top else [])))
                 self._conv_layer_meta[l.name] = dict(relu=fused_relu, sigmoid_top=sig_top)
@@ -590,8 +632,15 @@ class Engine:
             ops = self._emit_simple(l)
             tasks.append(dict(kind="op", layer=l, ops=ops, reads=[self._range(b) for b in l.bottoms],
                               writes=[self._range(tp) for tp in l.tops], pool_desc=self._fusable_pool_desc(l)))
+        return tasks
 
-        if self.fuse and spec.phase == "TEST" and os.environ.get("FCN_FUSE_POOL_LRN", "1") != "0":
+    def _build_ops(self) -> None:
+        """Layer list -> tasks with read/write sets -> dependency levels -> launches.
+
+        Tasks on one level are mutually independent; all convolutions of a level share ONE grouped launch
+        (an inception module becomes {1x1, 3x3_reduce, 5x5_reduce} then {3x3, 5x5, pool_proj})."""
+        tasks = self._collect_tasks()
+        if self.fuse and self.spec.phase == "TEST" and os.environ.get("FCN_FUSE_POOL_LRN", "1") != "0":
             tasks = self._fuse_pool_lrn(tasks)
 
         def hit(a, b) -> bool:
@@ -611,64 +660,12 @@ class Engine:
         self._move_floaters(tasks, levels, hit)
         tail = self._plan_tail(tasks, levels, hit)
         order = sorted(range(len(tasks)), key=lambda i: (levels[i], 0 if tasks[i]["kind"] == "op" else 1, i))
-
-        def emit_group(chunk: List[dict], fused: List[dict]) -> None:
-            """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""
-            name = "+".join(it["layer"].name for it in chunk)
-            flops = sum(it["flops"] for it in chunk)
-            byts = sum(it["bytes"] for it in chunk)
-            arr = (L.ConvDesc * len(chunk))(*[it["desc"] for it in chunk])
-            ws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(len(chunk))), zero=False)
-            self._group_workspaces.append(ws)
-            grp = L.ConvGroup()
-            parr = (L.PoolDesc * max(len(fused), 1))(*[pt["pool_desc"] for pt in fused])
-            tune_key = name + ("{+%d pool}" % len(fused) if fused else "")
-            tailed = tail is not None and any(id(it) in tail["producers"] for it in chunk)
-            if tailed:      # this launch writes (part of) the blob the narrow heads read: it carries them as its tail
-                fin = 1 if any(tail["producers"][id(it)] == tail["final_level"] for it in chunk if id(it) in tail["producers"]) else 0
-                tail["desc"].finalize = fin
-                L.call("fcn_conv2d_group_attach_tail", ws.ptr, C.byref(tail["desc"]))
-                tune_key += "{+tail%d}" % fin
-                if fin:
-                    flops += sum(ht["flops"] for ht in tail["heads"])
-                    byts += sum(4.0 * ht["desc"].Cout * (ht["desc"].N * ht["desc"].OH * ht["desc"].OW + ht["desc"].Cin) for ht in tail["heads"])
-            cfg = self._tuned_cfg(tune_key, arr, len(chunk), ws, parr, len(fused)) if self.autotune else -1
-            L.call("fcn_conv2d_group_prepare_fused", arr, len(chunk), parr, len(fused), ws.ptr, cfg, C.byref(grp))
-            self._keep.extend([arr, parr, ws, grp])
-            kind = "conv_group" if len(chunk) > 1 else "conv"
-            label = "%s [cfg%d %dwg]" % (name, grp.cfg, grp.total_tiles)
-            if fused:
-                label = "%s {+%s}" % (label, "+".join(pt["layer"].name for pt in fused))
-                byts += sum(pt["ops"][0].bytes for pt in fused)
-            if tailed:
-                label = "%s {%s %s}" % (label, "tail:" if tail["desc"].finalize else "partial sums of", "+".join(ht["layer"].name for ht in tail["heads"]))
-            self.ops.append(Op(kind, label, lambda st, g=grp: L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(g), st)), flops, byts))
-
-        def emit_convs(items: List[dict], pools: List[dict]) -> None:
-            """One grouped launch per 16 convolutions of a level; the level's fusable MAX poolings ride in the first one.  Half-float
-            engines may cut a level in two launches - its 3x3 / 5x5 convolutions and its 1x1 convolutions - when the autotuner
-            finds the pair faster (the streaming kernel's configurations are shaped for one kind or the other)."""
-            for base in range(0, len(items), 16):
-                chunk = items[base:base + 16]
-                fused = pools[:2] if base == 0 and len(chunk) <= 8 else []
-                parts = [chunk]
-                if self.f16 and self.autotune and not fused and len(chunk) > 1:
-                    parts = self._split_level(chunk)
-                for part in parts:
-                    emit_group(part, fused)
-                    fused = []
-                if base == 0 and len(chunk) <= 8:
-                    del pools[:2]
-            for pt in pools:            # no convolution launch at this level to ride in
-                self.ops.extend(pt["ops"])
-            pools.clear()
-
         pending: List[dict] = []
         pending_pools: List[dict] = []
         cur = None
         for i in order:
             if levels[i] != cur:
-                emit_convs(pending, pending_pools)
+                self._emit_convs(pending, pending_pools, tail)
                 pending, cur = [], levels[i]
             if tail is not None and any(tasks[i] is ht for ht in tail["heads"]):
                 continue      # evaluated by the launches that produce its input
@@ -678,10 +675,62 @@ class Engine:
                 pending_pools.append(tasks[i])
             else:
                 self.ops.extend(tasks[i]["ops"])
-        emit_convs(pending, pending_pools)
+        self._emit_convs(pending, pending_pools, tail)
         self.levels = max(levels) + 1 if levels else 0
         if self.score_outputs:
             self._emit_score_ops()
+
+    def _emit_group(self, chunk: List[dict], fused: List[dict], tail: Optional[dict]) -> None:
+        """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""
+        lib = L.load()
+        name = "+".join(it["layer"].name for it in chunk)
+        flops = sum(it["flops"] for it in chunk)
+        byts = sum(it["bytes"] for it in chunk)
+        arr = (L.ConvDesc * len(chunk))(*[it["desc"] for it in chunk])
+        ws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(len(chunk))), zero=False)
+        self._group_workspaces.append(ws)
+        grp = L.ConvGroup()
+        parr = (L.PoolDesc * max(len(fused), 1))(*[pt["pool_desc"] for pt in fused])
+        tune_key = name + ("{+%d pool}" % len(fused) if fused else "")
+        tailed = tail is not None and any(id(it) in tail["producers"] for it in chunk)
+        if tailed:      # this launch writes (part of) the blob the narrow heads read: it carries them as its tail
+            fin = 1 if any(tail["producers"][id(it)] == tail["final_level"] for it in chunk if id(it) in tail["producers"]) else 0
+            tail["desc"].finalize = fin
+            L.call("fcn_conv2d_group_attach_tail", ws.ptr, C.byref(tail["desc"]))
+            tune_key += "{+tail%d}" % fin
+            if fin:
+                flops += sum(ht["flops"] for ht in tail["heads"])
+                byts += sum(4.0 * ht["desc"].Cout * (ht["desc"].N * ht["desc"].OH * ht["desc"].OW + ht["desc"].Cin) for ht in tail["heads"])
+        cfg = self._tuned_cfg(tune_key, arr, len(chunk), ws, parr, len(fused)) if self.autotune else -1
+        L.call("fcn_conv2d_group_prepare_fused", arr, len(chunk), parr, len(fused), ws.ptr, cfg, C.byref(grp))
+        self._keep.extend([arr, parr, ws, grp])
+        kind = "conv_group" if len(chunk) > 1 else "conv"
+        label = "%s [cfg%d %dwg]" % (name, grp.cfg, grp.total_tiles)
+        if fused:
+            label = "%s {+%s}" % (label, "+".join(pt["layer"].name for pt in fused))
+            byts += sum(pt["ops"][0].bytes for pt in fused)
+        if tailed:
+            label = "%s {%s %s}" % (label, "tail:" if tail["desc"].finalize else "partial sums of", "+".join(ht["layer"].name for ht in tail["heads"]))
+        self.ops.append(Op(kind, label, lambda st, g=grp: L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(g), st)), flops, byts))
+
+    def _emit_convs(self, items: List[dict], pools: List[dict], tail: Optional[dict]) -> None:
+        """One grouped launch per 16 convolutions of a level; the level's fusable MAX poolings ride in the first one.  Half-float
+        engines may cut a level in two launches - its 3x3 / 5x5 convolutions and its 1x1 convolutions - when the autotuner
+        finds the pair faster (the streaming kernel's configurations are shaped for one kind or the other)."""
+        for base in range(0, len(items), 16):
+            chunk = items[base:base + 16]
+            fused = pools[:2] if base == 0 and len(chunk) <= 8 else []
+            parts = [chunk]
+            if self.f16 and self.autotune and not fused and len(chunk) > 1:
+                parts = self._split_level(chunk)
+            for part in parts:
+                self._emit_group(part, fused, tail)
+                fused = []
+            if base == 0 and len(chunk) <= 8:
+                del pools[:2]
+        for pt in pools:            # no convolution launch at this level to ride in
+            self.ops.extend(pt["ops"])
+        pools.clear()
 
     def _emit_score_ops(self) -> None:
         """Solver::Test's `test_score[idx] += result`, on the device: one accumulator per output blob (NCHW order, float32) and one
@@ -1233,247 +1282,236 @@ class Engine:
         return None
 
     def _emit_simple(self, l: Layer) -> List[Op]:
-        B, lib, t = self.blobs, L.load(), l.type
-        out: List[Op] = []
+        """The launches of one layer that is not a convolution."""
+        B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
         if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
-
-        def copy_op(name: str, sb: Blob, so: int, db: Blob, do: int, pixels: int, c: int) -> Op:
-            """`c` channels of every pixel from channel `so` of sb's buffer to channel `do` of db's (Dropout at TEST, copied Concat / Slice)."""
-            if sb.esize != db.esize:
-                raise NotImplementedError("f16 engine: %s copies between half and float32 blobs" % name)
-            fn = lib.fcn_copy_channels_f16 if sb.esize == 2 else lib.fcn_copy_channels_f32
-            return Op("copy", name, lambda st: L.check(fn(sb.buf.ptr, db.buf.ptr, pixels, c, sb.cstride, so, db.cstride, do, st)),
-                      0.0, 2.0 * sb.esize * pixels * c)
-        if t == "Pooling":
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            pp = l.sub("pooling_param")
-            n, c, h, w = xb.shape
-            _, _, oh, ow = yb.shape
-            if bool(pp.get("global_pooling", False)):
-                k, s, pad = h, 1, 0
-            else:
-                k, s, pad = kernel_stride_pad(pp)
-            byts = float(xb.esize) * (xb.pixels * c + yb.pixels * c)
-            if halves:
-                if xb.esize != 2 or yb.esize != 2:
-                    raise NotImplementedError("f16 engine: pooling %s" % l.name)
-                if str(pp.get("pool", "MAX")) != "MAX":
-                    out.append(Op("avepool", l.name, lambda st: L.check(lib.fcn_avepool_fwd_f16(
-                        xb.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
-                    return out
-                out.append(Op("maxpool", l.name, lambda st: L.check(lib.fcn_maxpool_fwd_f16(
-                    xb.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
-            elif str(pp.get("pool", "MAX")) == "MAX":
-                idx_ptr = None
-                if self.spec.phase == "TRAIN":      # backward routes the gradient to the argmax
-                    ib = DeviceBuffer(yb.pixels * c * 4, zero=False)
-                    self.aux_dev[l.name] = ib
-                    idx_ptr = ib.ptr
-                out.append(Op("maxpool", l.name, lambda st: L.check(lib.fcn_maxpool_fwd_f32(
-                    xb.ptr, yb.buf.ptr, idx_ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
-            else:
-                out.append(Op("avepool", l.name, lambda st: L.check(lib.fcn_avepool_fwd_f32(
-                    xb.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)), 0.0, byts))
-        elif t == "LRN":
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            p = l.sub("lrn_param")
-            if str(p.get("norm_region", "ACROSS_CHANNELS")) != "ACROSS_CHANNELS":
-                raise NotImplementedError("LRN WITHIN_CHANNEL")
-            if yb.coffset != 0:
-                raise NotImplementedError("LRN into a channel slice")
-            ls, al, be, kk = int(p.get("local_size", 5)), float(p.get("alpha", 1.0)), float(p.get("beta", 0.75)), float(p.get("k", 1.0))
-            scale_ptr = None
-            if self.spec.phase == "TRAIN":
-                sb = DeviceBuffer(xb.pixels * xb.channels * 4, zero=False)
-                self.aux_dev[l.name] = sb
-                scale_ptr = sb.ptr
-            if halves:
-                if xb.esize != 2 or yb.esize != 2 or xb.coffset:
-                    raise NotImplementedError("f16 engine: LRN %s" % l.name)
-                out.append(Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f16(
-                    xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, kk, st)), 0.0, 4.0 * xb.pixels * xb.channels))
-                return out
-            out.append(Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f32(
-                xb.ptr, yb.ptr, scale_ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, kk, st)),
-                0.0, 8.0 * xb.pixels * xb.channels))
-        elif t in ("ReLU", "Sigmoid", "Power"):
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            if xb.coffset or yb.coffset or xb.cstride != yb.cstride:
-                raise NotImplementedError("%s on a channel slice (layer %s)" % (t, l.name))
-            count = xb.pixels * xb.cstride
-            if t == "ReLU":
-                ns = float(l.sub("relu_param").get("negative_slope", 0.0))
-                fn = lambda st: L.check(lib.fcn_relu_fwd_f32(xb.ptr, yb.ptr, count, ns, st))
-            elif t == "Sigmoid":
-                fn = lambda st: L.check(lib.fcn_sigmoid_fwd_f32(xb.ptr, yb.ptr, count, st))
-            else:
-                p = l.sub("power_param")
-                pw, sc, sh = float(p.get("power", 1.0)), float(p.get("scale", 1.0)), float(p.get("shift", 0.0))
-                fn = lambda st: L.check(lib.fcn_power_fwd_f32(xb.ptr, yb.ptr, count, pw, sc, sh, st))
-            out.append(Op(t.lower(), l.name, fn, 0.0, 8.0 * count))
-        elif t == "Dropout":
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            if self.spec.phase == "TEST":
-                if halves:
-                    out.append(copy_op(l.name, xb, xb.coffset, yb, yb.coffset, xb.pixels, xb.channels))
-                    return out
-                out.append(Op("copy", l.name, lambda st: L.check(lib.fcn_copy_channels_f32(
-                    xb.buf.ptr, yb.buf.ptr, xb.pixels, xb.channels, xb.cstride, xb.coffset, yb.cstride, yb.coffset, st))))
-            else:
-                ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
-                n, c, h, w = xb.shape
-                out.append(Op("dropout", l.name, lambda st: L.check(lib.fcn_dropout_f32(
-                    xb.buf.ptr, yb.buf.ptr, n, c, h, w, xb.cstride, xb.coffset, yb.cstride, yb.coffset, ratio, self.dropout_seed,
-                    self.dropout_index_offset, st)),
-                    0.0, 8.0 * xb.pixels * c))
-        elif t in ("L1Loss", "EuclideanLoss"):
-            ab, bb, lb = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
-            if ab.shape != bb.shape or ab.coffset or bb.coffset or ab.cstride != bb.cstride:
-                raise NotImplementedError("loss layer %s on mismatched / sliced blobs" % l.name)
-            kind = 0 if t == "L1Loss" else 1
-            weight = l.loss_weight[0] if l.loss_weight else 1.0
-            da = self._loss_grad_ptr(l.bottoms[0])
-            self.loss_blobs[l.tops[0]] = float(weight)
-            out.append(Op("loss", l.name, lambda st: L.check(lib.fcn_loss_f32(
-                kind, ab.ptr, bb.ptr, da, lb.buf.ptr, ab.pixels, ab.channels, ab.cstride, ab.shape[0], weight, st)),
-                0.0, 8.0 * ab.pixels * ab.channels))
-        elif t == "Softmax":
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            if int(l.sub("softmax_param").get("axis", 1)) != 1:
-                raise NotImplementedError("Softmax over an axis other than channels (layer %s)" % l.name)
-            if halves:
-                if xb.esize != 2 or xb.coffset % 8 or yb.coffset % (16 // yb.esize):
-                    raise NotImplementedError("f16 engine: Softmax %s from a float32 blob / on an unaligned channel slice" % l.name)
-                out.append(Op("softmax", l.name, lambda st: L.check(lib.fcn_softmax_fwd_f16(
-                    xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, 1 if yb.esize == 4 else 0, st)),
-                    0.0, float(xb.esize + yb.esize) * xb.pixels * xb.channels))
-                return out
-            out.append(Op("softmax", l.name, lambda st: L.check(lib.fcn_softmax_fwd_f32(
-                xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, st)), 0.0, 8.0 * xb.pixels * xb.channels))
-        elif t == "SoftmaxWithLoss":
-            xb, lab, lb = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
-            if lab.channels != 1 or lab.pixels != xb.pixels or xb.coffset:
-                raise NotImplementedError("SoftmaxWithLoss %s: needs one label per pixel of an unsliced score blob" % l.name)
-            lp = l.sub("loss_param")
-            normalize = 1 if bool(lp.get("normalize", True)) else 0
-            ign = lp.get("ignore_label", None)
-            weight = l.loss_weight[0] if l.loss_weight else 1.0
-            da = self._loss_grad_ptr(l.bottoms[0])
-            self.loss_blobs[l.tops[0]] = float(weight)
-            ws = DeviceBuffer(int(lib.fcn_softmax_loss_workspace_bytes()), zero=True)
-            self._keep.append(ws)
-            out.append(Op("loss", l.name, lambda st: L.check(lib.fcn_softmax_loss_f32(
-                xb.ptr, lab.ptr, da, lb.buf.ptr, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, normalize,
-                0 if ign is None else 1, 0 if ign is None else int(ign), weight, ws.ptr, st)), 0.0, 8.0 * xb.pixels * xb.channels))
-        elif t == "Accuracy":
-            if self.f16:
-                raise NotImplementedError("f16 engine: layer type Accuracy (%s) has no half-float kernel" % l.name)
-            xb, lab, ab = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
-            if lab.channels != 1 or lab.pixels != xb.pixels:
-                raise NotImplementedError("Accuracy %s: needs one label per pixel of the score blob" % l.name)
-            ap = l.sub("accuracy_param")
-            if int(ap.get("axis", 1)) != 1:
-                raise NotImplementedError("Accuracy over an axis other than channels (layer %s)" % l.name)
-            top_k, ign = int(ap.get("top_k", 1)), ap.get("ignore_label", None)
-            per_class = B[l.tops[1]].ptr if len(l.tops) > 1 else None
-            ws = DeviceBuffer(int(lib.fcn_accuracy_workspace_bytes()), zero=True)
-            self._keep.append(ws)
-            out.append(Op("accuracy", l.name, lambda st: L.check(lib.fcn_accuracy_f32(
-                xb.ptr, lab.ptr, ab.ptr, per_class, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, top_k,
-                0 if ign is None else 1, 0 if ign is None else int(ign), ws.ptr, st)), 0.0, 4.0 * xb.pixels * (xb.channels + 1)))
-        elif t == "Slice":
-            off = 0
-            xb = B[l.bottoms[0]]
-            for tn in l.tops:
-                yb = B[tn]
-                o = off
-                if halves:
-                    out.append(copy_op(l.name + ":" + tn, xb, xb.coffset + o, yb, yb.coffset, yb.pixels, yb.channels))
-                    off += yb.channels
-                    continue
-                out.append(Op("copy", l.name + ":" + tn, lambda st, yb=yb, o=o: L.check(lib.fcn_copy_channels_f32(
-                    xb.buf.ptr, yb.buf.ptr, yb.pixels, yb.channels, xb.cstride, xb.coffset + o, yb.cstride, yb.coffset, st)),
-                    0.0, 8.0 * yb.pixels * yb.channels))
-                off += yb.channels
-        elif t == "Concat":
-            off = 0
-            yb = B[l.tops[0]]
-            for bn in l.bottoms:
-                xb = B[bn]
-                o = off
-                if halves:
-                    out.append(copy_op(l.name + ":" + bn, xb, xb.coffset, yb, yb.coffset + o, xb.pixels, xb.channels))
-                    off += xb.channels
-                    continue
-                out.append(Op("copy", l.name + ":" + bn, lambda st, xb=xb, o=o: L.check(lib.fcn_copy_channels_f32(
-                    xb.buf.ptr, yb.buf.ptr, xb.pixels, xb.channels, xb.cstride, xb.coffset, yb.cstride, yb.coffset + o, st)),
-                    0.0, 8.0 * xb.pixels * xb.channels))
-                off += xb.channels
-        elif t == "Eltwise":
-            p = l.sub("eltwise_param")
-            opname = str(p.get("operation", "SUM"))
-            op = {"PROD": L.ELT_PROD, "SUM": L.ELT_SUM, "MAX": L.ELT_MAX}[opname]
-            coeff = [float(c) for c in p.getall("coeff")] or [1.0] * len(l.bottoms)
-            yb = B[l.tops[0]]
-            srcs = [B[b] for b in l.bottoms]
-            if halves and len(halves) != len(l.bottoms) + 1:
-                raise NotImplementedError("f16 engine: Eltwise %s mixes half and float32 blobs" % l.name)
-            for b in srcs + [yb]:
-                if not (b.coffset == 0 and b.cstride == yb.cstride):
-                    raise NotImplementedError("Eltwise on channel slices (layer %s)" % l.name)
-            count = yb.pixels * yb.cstride
-            a = srcs[0]
-            for i, b in enumerate(srcs[1:], start=1):
-                ca = coeff[0] if i == 1 else 1.0
-                fn = lib.fcn_eltwise_fwd_f16 if halves else lib.fcn_eltwise_fwd_f32
-                out.append(Op("eltwise", l.name, lambda st, a=a, b=b, ca=ca, cb=coeff[i]: L.check(fn(
-                    a.ptr, b.ptr, yb.ptr, count, op, ca, cb, st)), 0.0, 3.0 * yb.esize * count))
-                a = yb
-        elif t == "Deconvolution":
-            p = l.sub("convolution_param")
-            k, s, pad = kernel_stride_pad(p)
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            n, c, h, w = xb.shape
-            _, co, oh, ow = yb.shape
-            wdev = self.params_dev[l.name][0].ptr
-            bdev = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
-            if self._deconv_dense(l):
-                # group 1: the transposed convolution on the matrix cores.  Its bank is re-packed from the blob in front of every
-                # launch (one small launch): the blob may have been stepped by a solver, set through net.params or belong to
-                # another engine (share_params) since the last forward.
-                if xb.coffset % 4 or xb.cstride % 4:
-                    raise NotImplementedError("Deconvolution %s: input view is not 16-byte aligned" % l.name)
-                bank = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(c, co, k, k)), 4) * 4, zero=True)
-                d = L.TConvDesc()
-                d.a, d.w, d.bias, d.b = xb.ptr, bank.ptr, bdev, yb.buf.ptr
-                d.N, d.H, d.W, d.Ca, d.a_cstride = n, h, w, c, xb.cstride
-                d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = co, k, k, pad, s, oh, ow
-                d.b_cstride, d.b_coffset, d.flags = yb.cstride, yb.coffset, 0
-                tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
-                plan = L.TConvPlan()
-                L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(plan))
-                self._keep.extend([bank, d, tws, plan])
-                out.append(Op("tconv_pack", l.name, lambda st: L.check(lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, c, co, _r4(co), k, k, st)),
-                              0.0, 8.0 * c * co * k * k))
-                out.append(Op("tconv", l.name, lambda st: L.check(lib.fcn_tconv2d_f32(C.byref(plan), st)),
-                              2.0 * n * h * w * c * co * k * k, 4.0 * (xb.pixels * c + yb.pixels * co)))
-                return out
-            if halves:
-                if xb.esize != 2 or xb.coffset % 8:
-                    raise NotImplementedError("f16 engine: Deconvolution %s from a float32 blob / an unaligned channel slice" % l.name)
-                out.append(Op("deconv", l.name, lambda st: L.check(lib.fcn_deconv_depthwise_fwd_f16(
-                    xb.ptr, wdev, bdev, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset,
-                    1 if yb.esize == 4 else 0, st)),
-                    2.0 * yb.pixels * c * (k / s) ** 2, float(xb.esize * xb.pixels + yb.esize * yb.pixels) * c))
-                return out
-            out.append(Op("deconv", l.name, lambda st: L.check(lib.fcn_deconv_depthwise_fwd_f32(
-                xb.ptr, wdev, bdev, yb.buf.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, yb.cstride, yb.coffset, st)),
-                2.0 * yb.pixels * c * (k / s) ** 2, 4.0 * (xb.pixels + yb.pixels) * c))
-        else:
+        emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
+                "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
+                "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
+                "Slice": self._fwd_slice, "Concat": self._fwd_concat, "Eltwise": self._fwd_eltwise,
+                "Deconvolution": self._fwd_deconvolution}.get(t)
+        if emit is None:
             raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
+        return emit(l, halves)
+
+    def _copy_op(self, name: str, sb: Blob, so: int, db: Blob, do: int, pixels: int, c: int) -> Op:
+        """`c` channels of every pixel from channel `so` of sb's buffer to channel `do` of db's (Dropout at TEST, copied Concat / Slice)."""
+        if sb.esize != db.esize:
+            raise NotImplementedError("f16 engine: %s copies between half and float32 blobs" % name)
+        lib = L.load()
+        fn = lib.fcn_copy_channels_f16 if sb.esize == 2 else lib.fcn_copy_channels_f32
+        return Op("copy", name, lambda st: L.check(fn(sb.buf.ptr, db.buf.ptr, pixels, c, sb.cstride, so, db.cstride, do, st)),
+                  0.0, 2.0 * sb.esize * pixels * c)
+
+    def _fwd_pooling(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        pp = l.sub("pooling_param")
+        g = self._geom(l, (xb.shape[2], 1, 0) if bool(pp.get("global_pooling", False)) else None)
+        c = g.cin
+        byts = float(xb.esize) * (xb.pixels * c + yb.pixels * c)
+        is_max = str(pp.get("pool", "MAX")) == "MAX"
+        if halves and (xb.esize != 2 or yb.esize != 2):
+            raise NotImplementedError("f16 engine: pooling %s" % l.name)
+        if is_max and not halves:
+            idx_ptr = None
+            if self.spec.phase == "TRAIN":      # backward routes the gradient to the argmax
+                ib = DeviceBuffer(yb.pixels * c * 4, zero=False)
+                self.aux_dev[l.name] = ib
+                idx_ptr = ib.ptr
+            run = lambda st: L.check(lib.fcn_maxpool_fwd_f32(
+                xb.ptr, yb.buf.ptr, idx_ptr, g.n, g.h, g.w, c, xb.cstride, g.k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, st))
+        else:
+            fn = (lib.fcn_maxpool_fwd_f16 if is_max else lib.fcn_avepool_fwd_f16) if halves else lib.fcn_avepool_fwd_f32
+            run = lambda st: L.check(fn(
+                xb.ptr, yb.buf.ptr, g.n, g.h, g.w, c, xb.cstride, g.k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, st))
+        return [Op("maxpool" if is_max else "avepool", l.name, run, 0.0, byts)]
+
+    def _fwd_lrn(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        p = l.sub("lrn_param")
+        if str(p.get("norm_region", "ACROSS_CHANNELS")) != "ACROSS_CHANNELS":
+            raise NotImplementedError("LRN WITHIN_CHANNEL")
+        if yb.coffset != 0:
+            raise NotImplementedError("LRN into a channel slice")
+        ls, al, be, kk = int(p.get("local_size", 5)), float(p.get("alpha", 1.0)), float(p.get("beta", 0.75)), float(p.get("k", 1.0))
+        scale_ptr = None
+        if self.spec.phase == "TRAIN":
+            sb = DeviceBuffer(xb.pixels * xb.channels * 4, zero=False)
+            self.aux_dev[l.name] = sb
+            scale_ptr = sb.ptr
+        if halves:
+            if xb.esize != 2 or yb.esize != 2 or xb.coffset:
+                raise NotImplementedError("f16 engine: LRN %s" % l.name)
+            return [Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f16(
+                xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, kk, st)), 0.0, 4.0 * xb.pixels * xb.channels)]
+        return [Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f32(
+            xb.ptr, yb.ptr, scale_ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, kk, st)),
+            0.0, 8.0 * xb.pixels * xb.channels)]
+
+    def _fwd_pointwise(self, l: Layer, halves: List[str]) -> List[Op]:
+        """ReLU, Sigmoid and Power as layers of their own."""
+        lib, t = L.load(), l.type
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.coffset or yb.coffset or xb.cstride != yb.cstride:
+            raise NotImplementedError("%s on a channel slice (layer %s)" % (t, l.name))
+        count = xb.pixels * xb.cstride
+        if t == "ReLU":
+            ns = float(l.sub("relu_param").get("negative_slope", 0.0))
+            fn = lambda st: L.check(lib.fcn_relu_fwd_f32(xb.ptr, yb.ptr, count, ns, st))
+        elif t == "Sigmoid":
+            fn = lambda st: L.check(lib.fcn_sigmoid_fwd_f32(xb.ptr, yb.ptr, count, st))
+        else:
+            p = l.sub("power_param")
+            pw, sc, sh = float(p.get("power", 1.0)), float(p.get("scale", 1.0)), float(p.get("shift", 0.0))
+            fn = lambda st: L.check(lib.fcn_power_fwd_f32(xb.ptr, yb.ptr, count, pw, sc, sh, st))
+        return [Op(t.lower(), l.name, fn, 0.0, 8.0 * count)]
+
+    def _fwd_dropout(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if self.spec.phase == "TEST":
+            return [self._copy_op(l.name, xb, xb.coffset, yb, yb.coffset, xb.pixels, xb.channels)]
+        ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
+        n, c, h, w = xb.shape
+        return [Op("dropout", l.name, lambda st: L.check(lib.fcn_dropout_f32(
+            xb.buf.ptr, yb.buf.ptr, n, c, h, w, xb.cstride, xb.coffset, yb.cstride, yb.coffset, ratio, self.dropout_seed,
+            self.dropout_index_offset, st)),
+            0.0, 8.0 * xb.pixels * c)]
+
+    def _fwd_loss(self, l: Layer, halves: List[str]) -> List[Op]:
+        """L1Loss / EuclideanLoss; in a training engine the same launch writes the gradient of the first bottom."""
+        lib = L.load()
+        ab, bb, lb = self.blobs[l.bottoms[0]], self.blobs[l.bottoms[1]], self.blobs[l.tops[0]]
+        if ab.shape != bb.shape or ab.coffset or bb.coffset or ab.cstride != bb.cstride:
+            raise NotImplementedError("loss layer %s on mismatched / sliced blobs" % l.name)
+        kind = 0 if l.type == "L1Loss" else 1
+        weight = l.loss_weight[0] if l.loss_weight else 1.0
+        da = self._loss_grad_ptr(l.bottoms[0])
+        self.loss_blobs[l.tops[0]] = float(weight)
+        return [Op("loss", l.name, lambda st: L.check(lib.fcn_loss_f32(
+            kind, ab.ptr, bb.ptr, da, lb.buf.ptr, ab.pixels, ab.channels, ab.cstride, ab.shape[0], weight, st)),
+            0.0, 8.0 * ab.pixels * ab.channels)]
+
+    def _fwd_softmax(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if int(l.sub("softmax_param").get("axis", 1)) != 1:
+            raise NotImplementedError("Softmax over an axis other than channels (layer %s)" % l.name)
+        if halves and (xb.esize != 2 or xb.coffset % 8 or yb.coffset % (16 // yb.esize)):
+            raise NotImplementedError("f16 engine: Softmax %s from a float32 blob / on an unaligned channel slice" % l.name)
+        # the half-float kernel takes one more argument: whether it writes float32 (a net output) or halves
+        fn, out_f32 = (lib.fcn_softmax_fwd_f16, (1 if yb.esize == 4 else 0,)) if halves else (lib.fcn_softmax_fwd_f32, ())
+        return [Op("softmax", l.name, lambda st: L.check(fn(xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, *out_f32, st)),
+                   0.0, float(xb.esize + yb.esize) * xb.pixels * xb.channels)]
+
+    def _fwd_softmax_loss(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        xb, lab, lb = self.blobs[l.bottoms[0]], self.blobs[l.bottoms[1]], self.blobs[l.tops[0]]
+        if lab.channels != 1 or lab.pixels != xb.pixels or xb.coffset:
+            raise NotImplementedError("SoftmaxWithLoss %s: needs one label per pixel of an unsliced score blob" % l.name)
+        lp = l.sub("loss_param")
+        normalize = 1 if bool(lp.get("normalize", True)) else 0
+        ign = lp.get("ignore_label", None)
+        weight = l.loss_weight[0] if l.loss_weight else 1.0
+        da = self._loss_grad_ptr(l.bottoms[0])
+        self.loss_blobs[l.tops[0]] = float(weight)
+        ws = DeviceBuffer(int(lib.fcn_softmax_loss_workspace_bytes()), zero=True)
+        self._keep.append(ws)
+        return [Op("loss", l.name, lambda st: L.check(lib.fcn_softmax_loss_f32(
+            xb.ptr, lab.ptr, da, lb.buf.ptr, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, normalize,
+            0 if ign is None else 1, 0 if ign is None else int(ign), weight, ws.ptr, st)), 0.0, 8.0 * xb.pixels * xb.channels)]
+
+    def _fwd_accuracy(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib, B = L.load(), self.blobs
+        if self.f16:
+            raise NotImplementedError("f16 engine: layer type Accuracy (%s) has no half-float kernel" % l.name)
+        xb, lab, ab = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
+        if lab.channels != 1 or lab.pixels != xb.pixels:
+            raise NotImplementedError("Accuracy %s: needs one label per pixel of the score blob" % l.name)
+        ap = l.sub("accuracy_param")
+        if int(ap.get("axis", 1)) != 1:
+            raise NotImplementedError("Accuracy over an axis other than channels (layer %s)" % l.name)
+        top_k, ign = int(ap.get("top_k", 1)), ap.get("ignore_label", None)
+        per_class = B[l.tops[1]].ptr if len(l.tops) > 1 else None
+        ws = DeviceBuffer(int(lib.fcn_accuracy_workspace_bytes()), zero=True)
+        self._keep.append(ws)
+        return [Op("accuracy", l.name, lambda st: L.check(lib.fcn_accuracy_f32(
+            xb.ptr, lab.ptr, ab.ptr, per_class, xb.shape[0], xb.pixels, xb.channels, xb.cstride, lab.cstride, top_k,
+            0 if ign is None else 1, 0 if ign is None else int(ign), ws.ptr, st)), 0.0, 4.0 * xb.pixels * (xb.channels + 1))]
+
+    def _fwd_slice(self, l: Layer, halves: List[str]) -> List[Op]:
+        out, off, xb = [], 0, self.blobs[l.bottoms[0]]
+        for tn in l.tops:
+            yb = self.blobs[tn]
+            out.append(self._copy_op(l.name + ":" + tn, xb, xb.coffset + off, yb, yb.coffset, yb.pixels, yb.channels))
+            off += yb.channels
         return out
+
+    def _fwd_concat(self, l: Layer, halves: List[str]) -> List[Op]:
+        out, off, yb = [], 0, self.blobs[l.tops[0]]
+        for bn in l.bottoms:
+            xb = self.blobs[bn]
+            out.append(self._copy_op(l.name + ":" + bn, xb, xb.coffset, yb, yb.coffset + off, xb.pixels, xb.channels))
+            off += xb.channels
+        return out
+
+    def _fwd_eltwise(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib, out = L.load(), []
+        p = l.sub("eltwise_param")
+        opname = str(p.get("operation", "SUM"))
+        op = {"PROD": L.ELT_PROD, "SUM": L.ELT_SUM, "MAX": L.ELT_MAX}[opname]
+        coeff = [float(c) for c in p.getall("coeff")] or [1.0] * len(l.bottoms)
+        yb = self.blobs[l.tops[0]]
+        srcs = [self.blobs[b] for b in l.bottoms]
+        if halves and len(halves) != len(l.bottoms) + 1:
+            raise NotImplementedError("f16 engine: Eltwise %s mixes half and float32 blobs" % l.name)
+        for b in srcs + [yb]:
+            if not (b.coffset == 0 and b.cstride == yb.cstride):
+                raise NotImplementedError("Eltwise on channel slices (layer %s)" % l.name)
+        count = yb.pixels * yb.cstride
+        fn = lib.fcn_eltwise_fwd_f16 if halves else lib.fcn_eltwise_fwd_f32
+        a = srcs[0]
+        for i, b in enumerate(srcs[1:], start=1):
+            ca = coeff[0] if i == 1 else 1.0
+            out.append(Op("eltwise", l.name, lambda st, a=a, b=b, ca=ca, cb=coeff[i]: L.check(fn(
+                a.ptr, b.ptr, yb.ptr, count, op, ca, cb, st)), 0.0, 3.0 * yb.esize * count))
+            a = yb
+        return out
+
+    def _fwd_deconvolution(self, l: Layer, halves: List[str]) -> List[Op]:
+        lib = L.load()
+        g = self._geom(l)
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        c, co, k = g.cin, g.cout, g.k
+        wdev = self.params_dev[l.name][0].ptr
+        bdev = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
+        if self._deconv_dense(l):
+            # group 1: the transposed convolution on the matrix cores.  Its bank is re-packed from the blob in front of every
+            # launch (one small launch): the blob may have been stepped by a solver, set through net.params or belong to
+            # another engine (share_params) since the last forward.
+            if xb.coffset % 4 or xb.cstride % 4:
+                raise NotImplementedError("Deconvolution %s: input view is not 16-byte aligned" % l.name)
+            bank = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(c, co, k, k)), 4) * 4, zero=True)
+            d = tconv_desc(xb, yb, g, bank.ptr, bdev)
+            tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+            plan = L.TConvPlan()
+            L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(plan))
+            self._keep.extend([bank, d, tws, plan])
+            return [Op("tconv_pack", l.name, lambda st: L.check(lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, c, co, _r4(co), k, k, st)),
+                       0.0, 8.0 * c * co * k * k),
+                    Op("tconv", l.name, lambda st: L.check(lib.fcn_tconv2d_f32(C.byref(plan), st)),
+                       2.0 * g.n * g.h * g.w * c * co * k * k, 4.0 * (xb.pixels * c + yb.pixels * co))]
+        if halves and (xb.esize != 2 or xb.coffset % 8):
+            raise NotImplementedError("f16 engine: Deconvolution %s from a float32 blob / an unaligned channel slice" % l.name)
+        # depthwise (group == channels); the half-float kernel takes one more argument: whether it writes float32 or halves
+        fn, out_f32 = (lib.fcn_deconv_depthwise_fwd_f16, (1 if yb.esize == 4 else 0,)) if halves else (lib.fcn_deconv_depthwise_fwd_f32, ())
+        return [Op("deconv", l.name, lambda st: L.check(fn(
+            xb.ptr, wdev, bdev, yb.buf.ptr, g.n, g.h, g.w, c, xb.cstride, k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, *out_f32, st)),
+            2.0 * yb.pixels * c * (k / g.s) ** 2, float(xb.esize * xb.pixels + yb.esize * yb.pixels) * c)]
 
     # ------------------------------------------------------------------ host <-> device
     def _stage(self, name: str) -> DeviceBuffer:
@@ -1636,7 +1674,7 @@ class Engine:
                     self.host_array(nm)
                     if len(self.blobs[nm].shape) == 4:
                         self._stage(nm)
-            if os.environ.get("FCN_NO_GRAPH", "0") in ("", "0"):
+            if graphs_enabled():
                 if io and self.graph_io is None:
                     for nm in self.outputs:
                         self.host_array(nm)
@@ -1733,7 +1771,7 @@ class Engine:
 
     def forward(self, use_graph: bool = True) -> Dict[str, np.ndarray]:
         """Upload inputs, run every layer, download the output blobs (synchronous, like Net.forward())."""
-        use_graph = use_graph and os.environ.get("FCN_NO_GRAPH", "0") in ("", "0")
+        use_graph = use_graph and graphs_enabled()
         with self.lock:
             L.call("fcn_init", self.device)
             for nm in self.inputs:
@@ -1769,7 +1807,7 @@ class Engine:
             L.call("fcn_init", self.device)
             for nm in list(self.inputs) + list(self.outputs):
                 self.host_array(nm)
-            if os.environ.get("FCN_NO_GRAPH", "0") in ("", "0"):
+            if graphs_enabled():
                 self._launch_io()
             else:
                 for nm in self.inputs:
@@ -1804,7 +1842,7 @@ class Engine:
     def forward_enqueue(self) -> None:
         """The layer stack once on inputs already in HBM, enqueued on the engine's stream without waiting."""
         with self.lock:
-            if os.environ.get("FCN_NO_GRAPH", "0") in ("", "0"):
+            if graphs_enabled():
                 if self.graph_core is None:
                     self.graph_core = self._capture(with_io=False)
                 L.call("fcn_graph_launch", self.graph_core, self.stream)
@@ -1816,7 +1854,7 @@ class Engine:
 
     def forward_resident(self, iters: int = 1, use_graph: bool = True) -> float:
         """Run the layer stack ``iters`` times on inputs already in HBM; returns HIP-event ms for all iterations."""
-        use_graph = use_graph and os.environ.get("FCN_NO_GRAPH", "0") in ("", "0")      # plain launches (e.g. under a profiler)
+        use_graph = use_graph and graphs_enabled()      # plain launches (e.g. under a profiler)
         with self.lock:
             L.call("fcn_init", self.device)
             if use_graph and self.graph_core is None:
@@ -2039,7 +2077,7 @@ class ForwardPipeline:
             if e.graph_core is None:
                 e.forward_resident(1)
             L.call("fcn_stream_sync", e.stream)
-        no_graph = os.environ.get("FCN_NO_GRAPH", "0") not in ("", "0")
+        no_graph = not graphs_enabled()
         t0 = time.perf_counter()
         for i in range(iters):
             e = engines[i % len(engines)]

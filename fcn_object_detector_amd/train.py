@@ -21,8 +21,9 @@ import numpy as np
 
 from . import lib as L
 from . import proto
-from .engine import Blob, DevView, DeviceBuffer, Engine, Op, PinnedArray, _r4
-from .netspec import DATA_TYPES, LOSS_TYPES, Layer, NetSpec, kernel_stride_pad
+from .backward import BackwardPlanner
+from .engine import Blob, DevView, DeviceBuffer, Engine, Op, PinnedArray, _r4, graphs_enabled
+from .netspec import DATA_TYPES, Layer, NetSpec
 
 F32 = np.float32
 
@@ -241,489 +242,10 @@ class TrainEngine(Engine):
 
     # ------------------------------------------------------------------ backward plan
     def _build_backward(self) -> None:
-        spec, B, G, lib = self.spec, self.blobs, self.grad_blobs, L.load()
-        written: Dict[int, List[Tuple[int, int]]] = {}      # gradient buffer -> channel ranges already holding a gradient
-
-        def state(g: Blob) -> str:
-            """'none' | 'full' for the channel range of view g (partial overlap is a planning error)."""
-            lo, hi = g.coffset, g.coffset + g.channels
-            cov = 0
-            for a, b in written.get(g.buf.ptr, []):
-                o = min(hi, b) - max(lo, a)
-                if o > 0:
-                    cov += o
-            if cov == 0:
-                return "none"
-            if cov >= hi - lo:
-                return "full"
-            raise NotImplementedError("gradient of %s is partially written" % g.name)
-
-        writers: Dict[str, List[object]] = {}      # gradient blob -> what wrote it, in order (a dgrad record or None)
-
-        def mark(g: Blob, writer: object = None) -> None:
-            written.setdefault(g.buf.ptr, []).append((g.coffset, g.coffset + g.channels))
-            writers.setdefault(g.name, []).append(writer)
-
-        ws_floats = 1
-        ops: List[Op] = []
-        # Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch
-        concat_members: Dict[str, List[str]] = {}
-        for child, (parent, _off) in self.alias.items():
-            if any(q.type == "Concat" and parent in q.tops for q in self.producers.get(parent, [])):
-                concat_members.setdefault(parent, []).append(child)
-        concat_relu: Dict[str, str] = {}
-        for parent, members in concat_members.items():
-            prods = [[q for q in self.producers.get(m, []) if q.type == "Convolution"] for m in members]
-            if all(len(pr) == 1 and self._conv_layer_meta.get(pr[0].name, {}).get("relu") for pr in prods) and \
-                    sum(B[m].channels for m in members) == B[parent].channels and B[parent].coffset == 0:
-                for m in members:
-                    concat_relu[m] = parent
-        relu_done: set = set()
-        dgrad_done: set = set()
-        wgrad_done: set = set()
-        sibling_reduces: Dict[str, List[Layer]] = {}      # reduce layer -> the reduce layers of its module (ready together)
-        # Flipped / transposed filter banks of the data-gradient passes: slices of ONE flat buffer that a single launch
-        # refreshes from the current weights at the start of every backward pass (58 launches otherwise).
-        flip_layout: Dict[str, int] = {}
-        flip_segs: List[L.FlipSeg] = []
-        flip_floats = 0
-        for l in spec.layers:
-            if l.type != "Convolution" or G.get(l.bottoms[0]) is None or G.get(l.tops[0]) is None:
-                continue
-            k, s_, _pad = kernel_stride_pad(l.sub("convolution_param"))
-            if s_ != 1:
-                continue
-            cin, cout = B[l.bottoms[0]].shape[1], B[l.tops[0]].shape[1]
-            flip_layout[l.name] = flip_floats
-            flip_segs.append(L.FlipSeg((self.params_dev[l.name][0].ptr - self.param_flat.ptr) // 4, flip_floats, cout, k, k, cin,
-                                       _r4(cin), _r4(cout)))
-            flip_floats += _r4(cin * k * k * _r4(cout))
-        self._flip_flat = DeviceBuffer(max(flip_floats, 4) * 4, zero=True)
-        if flip_segs:
-            seg_arr = (L.FlipSeg * len(flip_segs))(*flip_segs)
-            self._flip_segs_dev = DeviceBuffer(C.sizeof(seg_arr), zero=False)
-            L.call("fcn_memcpy_h2d_async", self._flip_segs_dev.ptr, C.addressof(seg_arr), C.sizeof(seg_arr), None)
-            L.call("fcn_device_sync")
-            ops.append(Op("flip", "%d filter banks" % len(flip_segs), lambda st, n=len(flip_segs): L.check(lib.fcn_conv_weights_flip_batch_f32(
-                self.param_flat.ptr, self._flip_flat.ptr, self._flip_segs_dev.ptr, n, st))))
-        # Strided convolutions whose input needs a gradient: the transposed-convolution kernel reads the layer's own OHWI bank
-        # re-packed tap-major ([kh][kw][Cin][Cout4]), refreshed from the current weights at the start of every backward pass
-        tbank: Dict[str, DeviceBuffer] = {}
-        for l in spec.layers:
-            if l.type != "Convolution" or G.get(l.bottoms[0]) is None or G.get(l.tops[0]) is None:
-                continue
-            k, s_, _pad = kernel_stride_pad(l.sub("convolution_param"))
-            if s_ == 1:
-                continue
-            cin, cout = B[l.bottoms[0]].shape[1], B[l.tops[0]].shape[1]
-            tbank[l.name] = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(cout, cin, k, k)), 4) * 4, zero=True)
-            ops.append(Op("tconv_pack", l.name, lambda st, wdev=self.params_dev[l.name][0].ptr, bank=tbank[l.name], g=(cout, cin, _r4(cin), k):
-                          L.check(lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, g[0], g[1], g[2], g[3], g[3], st))))
-        self._tbank = tbank
-        skip_sigmoid_of = {m["sigmoid_top"]: name for name, m in self._conv_layer_meta.items() if m.get("sigmoid_top")}
-
-        def emit_tdgrad(l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> dict:
-            """Data gradient of the strided convolution l: the transposed convolution of dY, written at the size of the layer's input
-            (rows / columns of it that lay under no window get zeros).  Prepared in finish_dgrads like the grouped launches, because
-            the ReLU mask of the layer below may still be folded into its epilogue."""
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
-            n, cin, h, w = xb.shape
-            _, cout, oh, ow = yb.shape
-            if gtop.coffset % 4 or gtop.cstride - gtop.coffset < _r4(cout):
-                raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
-            if pad >= k:
-                raise NotImplementedError("data gradient of the strided convolution %s with pad %d >= kernel %d" % (l.name, pad, k))
-            d = L.TConvDesc()
-            d.a, d.w, d.bias, d.b = gtop.ptr, tbank[l.name].ptr, None, gbot.buf.ptr
-            d.N, d.H, d.W, d.Ca, d.a_cstride = n, oh, ow, cout, gtop.cstride
-            d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = cin, k, k, pad, s, h, w
-            d.b_cstride, d.b_coffset = gbot.cstride, gbot.coffset
-            d.flags = L.CONV_ACCUM if accumulate else 0
-            rec = dict(name=l.name, descs=[d], targets=[l.bottoms[0]], tconv=L.TConvPlan())
-            rec["op"] = Op("tconv_dgrad", l.name, lambda st, pl=rec["tconv"]: L.check(lib.fcn_tconv2d_f32(C.byref(pl), st)),
-                           2.0 * n * cout * oh * ow * cin * k * k)
-            ops.append(rec["op"])
-            dgrad_records.append(rec)
-            self._keep.append(d)
-            return rec
-
-        def dgrad_desc(l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Tuple[L.ConvDesc, float]:
-            """Data gradient of convolution l = the forward kernel on dY with the flipped / transposed bank."""
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
-            n, cin, h, w = xb.shape
-            _, cout, oh, ow = yb.shape
-            if s != 1:
-                raise RuntimeError("dgrad_desc is the stride-1 path; strided layers go through emit_tdgrad (%s)" % l.name)
-            cin_dg = _r4(cout)      # the flipped bank reads Cout4 input channels: the gradient view must expose them contiguously
-            if gtop.cstride - gtop.coffset < cin_dg:
-                raise NotImplementedError("gradient view of %s too narrow for the data-gradient pass" % l.tops[0])
-            wt = DevView(self._flip_flat.ptr + 4 * flip_layout[l.name], cin * k * k * cin_dg * 4)
-            dd = L.ConvDesc()
-            dd.x, dd.w, dd.bias, dd.y = gtop.ptr, wt.ptr, None, gbot.buf.ptr
-            dd.N, dd.H, dd.W, dd.Cin, dd.x_cstride = n, oh, ow, cin_dg, gtop.cstride
-            dd.Cout, dd.kh, dd.kw, dd.pad, dd.stride, dd.OH, dd.OW = cin, k, k, k - 1 - pad, 1, h, w
-            dd.y_cstride, dd.y_coffset = gbot.cstride, gbot.coffset
-            dd.flags = L.CONV_ACCUM if accumulate else 0
-            self._keep.append(dd)
-            return dd, 2.0 * n * cout * oh * ow * cin * k * k
-
-        dgrad_records: List[dict] = []
-        relu_ops: Dict[str, Op] = {}       # gradient blob whose ReLU backward is the op (candidates for the fused mask)
-
-        def emit_dgrads(name: str, items: List[Tuple[L.ConvDesc, float]], targets: List[str]) -> dict:
-            """One grouped launch for data-gradient passes that write different buffers.  The group is prepared (and
-            autotuned) after the whole backward plan is known, because the LAST writer of a gradient may still get the ReLU
-            mask of the layer below folded into its epilogue (finish_dgrads)."""
-            rec = dict(name=name, descs=[it[0] for it in items], targets=list(targets), grp=L.ConvGroup())
-            rec["op"] = Op("dgrad", name, lambda st, g=rec["grp"]: L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(g), st)), sum(it[1] for it in items))
-            ops.append(rec["op"])
-            dgrad_records.append(rec)
-            return rec
-
-        def finish_dgrads() -> None:
-            # fold "ReLU backward of blob X" into the last data-gradient pass that writes dX, when that is what wrote it last
-            for x, rop in relu_ops.items():
-                w = writers.get(x, [])
-                rec = w[-1] if w else None
-                if not isinstance(rec, dict) or rop not in ops:
-                    continue
-                if "pool" in rec:        # the last writer is a pooling backward of exactly this blob
-                    if rec["pool"] == x:
-                        rec["mask"] = (B[x].buf.ptr, B[x].cstride, B[x].coffset)
-                        ops.remove(rop)
-                    continue
-                d = rec["descs"][rec["targets"].index(x)]
-                act = B[x]
-                d.y2, d.y2_cstride, d.y2_coffset = act.buf.ptr, act.cstride, act.coffset
-                d.flags |= L.CONV_MASK
-                ops.remove(rop)
-            for rec in dgrad_records:
-                if "tconv" in rec:
-                    d = rec["descs"][0]
-                    tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
-                    L.call("fcn_tconv2d_prepare", C.byref(d), 1, tws.ptr, -1, C.byref(rec["tconv"]))
-                    self._keep.extend([tws, rec["tconv"]])
-                    rec["op"].name = "%s [%dwg]" % (rec["name"], rec["tconv"].total_tiles)
-                    continue
-                n_ = len(rec["descs"])
-                arr = (L.ConvDesc * n_)(*rec["descs"])
-                gws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(n_)), zero=False)
-                cfg = self._tuned_cfg("dgrad:" + rec["name"], arr, n_, gws) if self.autotune else -1
-                L.call("fcn_conv2d_group_prepare", arr, n_, gws.ptr, cfg, C.byref(rec["grp"]))
-                self._keep.extend([arr, gws, rec["grp"]])
-                self._group_workspaces.append(gws)
-                rec["op"].name = "%s [cfg%d %dwg]" % (rec["name"], rec["grp"].cfg, rec["grp"].total_tiles)
-
-        def wgrad_item(l: Layer, gtop: Blob):
-            """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns."""
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
-            n, cin, h, w = xb.shape
-            _, cout, oh, ow = yb.shape
-            if gtop.coffset % 4 or gtop.cstride % 4:
-                raise NotImplementedError("gradient view of %s is not 16-byte aligned" % l.tops[0])
-            d = L.ConvDesc()
-            d.x, d.y = xb.ptr, gtop.buf.ptr
-            d.N, d.H, d.W, d.Cin, d.x_cstride = n, h, w, _r4(cin), xb.cstride
-            d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = cout, k, k, pad, s, oh, ow
-            d.y_cstride, d.y_coffset = gtop.cstride, gtop.coffset
-            self._keep.append(d)
-            dw = self._grad_view(l.name, 0)
-            db = self._grad_view(l.name, 1) if len(self.params_dev[l.name]) > 1 else None
-            return d, dw, db, 2.0 * n * cout * oh * ow * cin * k * k
-
-        def emit_wgrads(layers_: List[Layer], gtops: List[Blob]) -> None:
-            """Weight (and bias) gradients of layers that are ready together: one launch + one reduction for up to four."""
-            nonlocal ws_floats
-            todo = [(l_, g_) for l_, g_ in zip(layers_, gtops) if self._learns(l_) and l_.name not in wgrad_done]
-            for base in range(0, len(todo), 4):
-                chunk = todo[base:base + 4]
-                its = [wgrad_item(l_, g_) for l_, g_ in chunk]
-                names = [l_.name for l_, _ in chunk]
-                sel = {"cfg": -1}      # -1: the library's heuristic; _tune_wgrads() replaces it once the workspace exists
-                cfgs = [-1] + (list(range(int(lib.fcn_conv2d_wgrad_num_configs()))) if self.autotune else [])
-                if len(its) == 1:
-                    d, dw, db, fl = its[0]
-                    ws_floats = max([ws_floats] + [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), c, None)) for c in cfgs])
-                    op = Op("wgrad", names[0], lambda st, d=d, dw=dw, db=db, sel=sel: L.check(lib.fcn_conv2d_wgrad_cfg_f32(
-                        C.byref(d), dw.ptr, db.ptr if db else None, self._ws.ptr, sel["cfg"], st)), fl)
-                else:
-                    arr = (L.ConvDesc * len(its))(*[it[0] for it in its])
-                    pdw = (C.c_void_p * len(its))(*[it[1].ptr for it in its])
-                    pdb = (C.c_void_p * len(its))(*[(it[2].ptr if it[2] is not None else None) for it in its])
-                    ws_floats = max([ws_floats] + [int(lib.fcn_conv2d_wgrad_group_workspace_floats_cfg(arr, len(its), c)) for c in cfgs])
-                    self._keep.extend([arr, pdw, pdb])
-                    op = Op("wgrad", "+".join(names), lambda st, arr=arr, pdw=pdw, pdb=pdb, m=len(its), sel=sel: L.check(
-                        lib.fcn_conv2d_wgrad_group_cfg_f32(arr, pdw, pdb, m, self._ws.ptr, sel["cfg"], st)), sum(it[3] for it in its))
-                op.sel = sel
-                op.layers = names
-                ops.append(op)
-                wgrad_done.update(names)
-
-        def emit_dense_deconv_bwd(l: Layer, gtop: Blob, gbot: Optional[Blob]) -> None:
-            """Backward of a group-1 Deconvolution whose blob is kept as [Cin][kh][kw][Cout4], an OHWI bank of Cin outputs:
-            db = per-channel sum of dY; dW = the weight-gradient kernel with the roles swapped (its x is dY, its y the layer's input);
-            dX = the forward convolution of dY at the layer's stride."""
-            nonlocal ws_floats
-            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-            k, s, pad = kernel_stride_pad(l.sub("convolution_param"))
-            n, c, h, w = xb.shape
-            _, co, oh, ow = yb.shape
-            if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(co):
-                raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
-
-            def swapped() -> L.ConvDesc:
-                d = L.ConvDesc()
-                d.x = gtop.ptr
-                d.N, d.H, d.W, d.Cin, d.x_cstride = n, oh, ow, _r4(co), gtop.cstride
-                d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = c, k, k, pad, s, h, w
-                self._keep.append(d)
-                return d
-            if self._learns(l) and l.name not in wgrad_done:
-                if len(self.params_dev[l.name]) > 1:
-                    db = self._grad_view(l.name, 1)
-                    ops.append(Op("channel_sum", l.name, lambda st, a=gtop, db=db, co=co: L.check(lib.fcn_channel_sum_f32(
-                        a.buf.ptr, db.ptr, a.pixels, co, a.cstride, a.coffset, st)), 0.0, 4.0 * gtop.pixels * co))
-                if xb.coffset % 4 or xb.cstride % 4:
-                    raise NotImplementedError("input view of %s is not 16-byte aligned" % l.name)
-                d = swapped()
-                d.y, d.y_cstride, d.y_coffset = xb.buf.ptr, xb.cstride, xb.coffset
-                dw = self._grad_view(l.name, 0)
-                sel = {"cfg": -1}
-                cfgs = [-1] + (list(range(int(lib.fcn_conv2d_wgrad_num_configs()))) if self.autotune else [])
-                ws_floats = max([ws_floats] + [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), cf, None)) for cf in cfgs])
-                op = Op("wgrad", l.name, lambda st, d=d, dw=dw, sel=sel: L.check(lib.fcn_conv2d_wgrad_cfg_f32(
-                    C.byref(d), dw.ptr, None, self._ws.ptr, sel["cfg"], st)), 2.0 * n * c * h * w * co * k * k)
-                op.sel = sel
-                op.layers = [l.name]
-                ops.append(op)
-                wgrad_done.add(l.name)
-            if gbot is not None:
-                d = swapped()
-                d.w, d.bias, d.y = self.params_dev[l.name][0].ptr, None, gbot.buf.ptr
-                d.y_cstride, d.y_coffset = gbot.cstride, gbot.coffset
-                d.flags = L.CONV_ACCUM if state(gbot) == "full" else 0
-                rec = emit_dgrads(l.name, [(d, 2.0 * n * c * h * w * co * k * k)], [l.bottoms[0]])
-                mark(gbot, rec)
-
-        for l in reversed(spec.layers):
-            t = l.type
-            if t in DATA_TYPES or t in ("Concat", "Slice") or (t == "ReLU" and l.name in self._fused_relu_layers()):
-                if t == "Slice" and l.name in self.copy_slices and any(tp in G for tp in l.tops):
-                    raise NotImplementedError("backward through the copied Slice %s" % l.name)
-                continue
-            if t == "Accuracy":
-                continue                     # a metric: no gradient, no entry in loss_blobs
-            if t in ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss"):
-                g = G.get(l.bottoms[0])
-                if g is None:
-                    continue
-                if l.bottoms[1] in self.need_grad:
-                    raise NotImplementedError("loss layer %s: gradient w.r.t. the second bottom" % l.name)
-                if state(g) != "none":
-                    raise NotImplementedError("loss gradient would have to accumulate into %s" % l.bottoms[0])
-                mark(g)                      # written by the forward loss kernel (da)
-                continue
-            if t == "Sigmoid" and l.tops[0] in skip_sigmoid_of:
-                # fused into the conv epilogue in forward; backward is its own small kernel
-                yb, gtop, gbot = B[l.tops[0]], G.get(l.tops[0]), G.get(l.bottoms[0])
-                if gtop is None or gbot is None or state(gtop) == "none":
-                    continue
-                acc = 1 if state(gbot) == "full" else 0
-                count = yb.pixels * yb.cstride
-                if yb.coffset or gtop.coffset or gbot.coffset or yb.cstride != gbot.cstride:
-                    raise NotImplementedError("sigmoid backward on channel slices")
-                ops.append(Op("sigmoid_bwd", l.name, lambda st, y=yb, a=gtop, b=gbot, acc=acc, n=count: L.check(
-                    lib.fcn_sigmoid_bwd_f32(y.ptr, a.ptr, b.ptr, n, acc, st))))
-                mark(gbot)
-                continue
-            gtop = G.get(l.tops[0]) if l.tops else None
-            if gtop is None or state(gtop) == "none":
-                continue                     # no gradient reaches this layer
-            if t == "Convolution":
-                meta = self._conv_layer_meta[l.name]
-                xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-                p = l.sub("convolution_param")
-                k, s, pad = kernel_stride_pad(p)
-                n, cin, h, w = xb.shape
-                _, cout, oh, ow = yb.shape
-                if meta.get("relu") and l.tops[0] not in relu_done:
-                    whole = concat_relu.get(l.tops[0])
-                    if whole is not None and whole in G and state(G[whole]) == "full":
-                        # every member of this Concat is a convolution with an in-place ReLU and the gradient of the whole
-                        # concatenation is final: ONE contiguous launch masks all members (an inception module: 4 -> 1)
-                        gw, yw = G[whole], B[whole]
-                        relu_ops[whole] = Op("relu_bwd", whole, lambda st, g=gw, y=yw: L.check(lib.fcn_relu_bwd_f32(
-                            g.ptr, y.ptr, g.ptr, y.pixels, y.channels, y.cstride, st)), 0.0, 12.0 * yw.pixels * yw.channels)
-                        ops.append(relu_ops[whole])
-                        relu_done.update(concat_members[whole])
-                        # the members' data gradients only need this masked gradient and write four different buffers (the
-                        # module input and the outputs of the reduce / pool layers): one grouped launch at the top of the
-                        # module's backward instead of four scattered ones
-                        items, names, targets, tnames = [], [], [], []
-                        for m in concat_members[whole]:
-                            lm = [q for q in self.producers.get(m, []) if q.type == "Convolution"][0]
-                            gb = G.get(lm.bottoms[0])
-                            if gb is None or lm.name not in flip_layout or state(gb) != "none" or any(gb.buf.ptr == tb for tb in targets):
-                                continue
-                            items.append(dgrad_desc(lm, G[m], gb, False))
-                            names.append(lm.name)
-                            targets.append(gb.buf.ptr)
-                            tnames.append(lm.bottoms[0])
-                        if len(items) > 1:
-                            rec = emit_dgrads("+".join(names), items, tnames)
-                            for nm, tn in zip(names, tnames):
-                                dgrad_done.add(nm)
-                                mark(G[tn], rec)
-                        # ... and their weight gradients need nothing else either: one grouped launch
-                        mem_layers = [[q for q in self.producers.get(m, []) if q.type == "Convolution"][0] for m in concat_members[whole]]
-                        emit_wgrads(mem_layers, [G[m] for m in concat_members[whole]])
-                        # the layers feeding the members (3x3_reduce, 5x5_reduce) get their whole gradient from that dgrad
-                        # launch: they become ready together too
-                        sibs = []
-                        for lm in mem_layers:
-                            if lm.name not in dgrad_done:
-                                continue
-                            prods = [q for q in self.producers.get(lm.bottoms[0], []) if q.type == "Convolution"]
-                            cons = [q for q in self.consumers.get(lm.bottoms[0], []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)]
-                            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in self.alias and lm.bottoms[0] in G:
-                                sibs.append(prods[0])
-                        if len(sibs) > 1:
-                            for q in sibs:
-                                sibling_reduces[q.name] = sibs
-                    else:
-                        rop = Op("relu_bwd", l.name, lambda st, g=gtop, y=yb: L.check(lib.fcn_relu_bwd_f32(
-                            g.ptr, y.ptr, g.ptr, y.pixels, y.channels, y.cstride, st)), 0.0, 12.0 * yb.pixels * cout)
-                        ops.append(rop)
-                        if l.tops[0] not in self.alias:
-                            relu_ops[l.tops[0]] = rop
-                        relu_done.add(l.tops[0])
-                sibs = sibling_reduces.get(l.name)
-                if sibs and l.name not in wgrad_done and all(state(G[q.tops[0]]) == "full" for q in sibs):
-                    # first of the module's reduce layers to be visited: mask and take the weight gradients of all of them now
-                    for q in sibs:
-                        if q.tops[0] not in relu_done and self._conv_layer_meta[q.name].get("relu"):
-                            gq, yq = G[q.tops[0]], B[q.tops[0]]
-                            relu_ops[q.tops[0]] = Op("relu_bwd", q.name, lambda st, g=gq, y=yq: L.check(lib.fcn_relu_bwd_f32(
-                                g.ptr, y.ptr, g.ptr, y.pixels, y.channels, y.cstride, st)), 0.0, 12.0 * yq.pixels * yq.channels)
-                            ops.append(relu_ops[q.tops[0]])
-                            relu_done.add(q.tops[0])
-                    emit_wgrads(sibs, [G[q.tops[0]] for q in sibs])
-                emit_wgrads([l], [gtop])
-                gbot = G.get(l.bottoms[0])
-                if gbot is not None and l.name not in dgrad_done:
-                    if s != 1:
-                        rec = emit_tdgrad(l, gtop, gbot, state(gbot) == "full")
-                    else:
-                        rec = emit_dgrads(l.name, [dgrad_desc(l, gtop, gbot, state(gbot) == "full")], [l.bottoms[0]])
-                    mark(gbot, rec)
-                continue
-            if t == "Eltwise" and str(l.sub("eltwise_param").get("operation", "SUM")) == "SUM":
-                p = l.sub("eltwise_param")
-                # d(bottom_i) = dY for every bottom (train/fcn_bbox fuse_pool4 / fuse_pool3: skip connections)
-                if any(float(c) != 1.0 for c in p.getall("coeff")):
-                    raise NotImplementedError("Eltwise SUM backward with coefficients (%s)" % l.name)
-                for bn in l.bottoms:
-                    gb = G.get(bn)
-                    if gb is None:
-                        continue
-                    if state(gb) == "full":
-                        if gtop.coffset or gb.coffset or gb.cstride != gtop.cstride:
-                            raise NotImplementedError("Eltwise SUM backward accumulating into a channel slice")
-                        ops.append(Op("eltwise_bwd", l.name + ":" + bn, lambda st, a=gtop, b=gb: L.check(lib.fcn_eltwise_fwd_f32(
-                            a.ptr, b.ptr, b.ptr, a.pixels * a.cstride, L.ELT_SUM, 1.0, 1.0, st))))
-                    else:
-                        ops.append(Op("eltwise_bwd", l.name + ":" + bn, lambda st, a=gtop, b=gb: L.check(lib.fcn_copy_channels_f32(
-                            a.buf.ptr, b.buf.ptr, a.pixels, a.channels, a.cstride, a.coffset, b.cstride, b.coffset, st))))
-                    mark(gb)
-                continue
-            if t == "Deconvolution" and self._deconv_dense(l):
-                gbot = G.get(l.bottoms[0])
-                emit_dense_deconv_bwd(l, gtop, gbot)
-                continue
-            gbot = G.get(l.bottoms[0]) if l.bottoms else None
-            if gbot is None:
-                continue
-            acc = 1 if state(gbot) == "full" else 0
-            pool_writer = None
-            if t == "Pooling":
-                pp = l.sub("pooling_param")
-                if str(pp.get("pool", "MAX")) != "MAX":
-                    raise NotImplementedError("backward of AVE pooling (%s)" % l.name)
-                xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-                n, c, h, w = xb.shape
-                _, _, oh, ow = yb.shape
-                k, s, pad = kernel_stride_pad(pp)
-                idx = self.aux_dev[l.name]
-                prec = dict(pool=l.bottoms[0], mask=(None, 0, 0))      # finish_dgrads may fold a ReLU backward into this pass
-                ops.append(Op("maxpool_bwd", l.name, lambda st, a=gtop, b=gbot, idx=idx, g=(n, h, w, c), kk=(k, s, pad, oh, ow), acc=acc, r=prec:
-                              L.check(lib.fcn_maxpool_bwd_mask_f32(a.buf.ptr, idx.ptr, b.buf.ptr, g[0], g[1], g[2], g[3], b.cstride, b.coffset,
-                                                                   kk[0], kk[1], kk[2], kk[3], kk[4], a.cstride, a.coffset, acc, r["mask"][0],
-                                                                   r["mask"][1], r["mask"][2], st))))
-                pool_writer = prec
-            elif t == "LRN":
-                xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-                p = l.sub("lrn_param")
-                ls, al, be = int(p.get("local_size", 5)), float(p.get("alpha", 1.0)), float(p.get("beta", 0.75))
-                sc = self.aux_dev[l.name]
-                if gtop.coffset or gbot.coffset or xb.coffset or yb.coffset:
-                    raise NotImplementedError("LRN backward on channel slices")
-                ops.append(Op("lrn_bwd", l.name, lambda st, x=xb, y=yb, sc=sc, a=gtop, b=gbot, q=(ls, al, be), acc=acc: L.check(
-                    lib.fcn_lrn_bwd_f32(x.ptr, y.ptr, sc.ptr, a.ptr, b.ptr, x.pixels, x.channels, x.cstride, y.cstride, q[0], q[1], q[2], acc, st))))
-            elif t == "Dropout":
-                if acc:
-                    raise NotImplementedError("dropout backward into an already written gradient")
-                ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
-                n, c, h, w = B[l.bottoms[0]].shape
-                ops.append(Op("dropout_bwd", l.name, lambda st, a=gtop, b=gbot, g=(n, c, h, w), r=ratio: L.check(lib.fcn_dropout_f32(
-                    a.buf.ptr, b.buf.ptr, g[0], g[1], g[2], g[3], a.cstride, a.coffset, b.cstride, b.coffset, r, self.dropout_seed,
-                    self.dropout_index_offset, st))))
-            elif t == "Eltwise":
-                p = l.sub("eltwise_param")
-                opname = str(p.get("operation", "SUM"))
-                if opname != "PROD" or len(l.bottoms) != 2:
-                    raise NotImplementedError("backward of Eltwise %s" % l.name)
-                if l.bottoms[1] in self.need_grad:
-                    raise NotImplementedError("Eltwise PROD backward w.r.t. both bottoms (%s)" % l.name)
-                if acc:
-                    raise NotImplementedError("Eltwise backward into an already written gradient")
-                other = B[l.bottoms[1]]
-                count = gtop.pixels * gtop.cstride
-                if gtop.coffset or gbot.coffset or other.coffset or other.cstride != gtop.cstride:
-                    raise NotImplementedError("Eltwise backward on channel slices")
-                ops.append(Op("eltwise_bwd", l.name, lambda st, a=gtop, o=other, b=gbot, n=count: L.check(lib.fcn_eltwise_fwd_f32(
-                    a.ptr, o.ptr, b.ptr, n, L.ELT_PROD, 1.0, 1.0, st))))
-            elif t == "Deconvolution":
-                if any(m != 0.0 for m in l.lr_mult) or not l.lr_mult:
-                    raise NotImplementedError("learnable depthwise Deconvolution %s (group == channels): only group 1 learns; the reference "
-                                              "freezes its bilinear upsampling, lr_mult 0" % l.name)
-                p = l.sub("convolution_param")
-                k, s, pad = kernel_stride_pad(p)
-                xb, yb = B[l.bottoms[0]], B[l.tops[0]]
-                n, c, h, w = xb.shape
-                _, _, oh, ow = yb.shape
-                wdev = self.params_dev[l.name][0].ptr
-                ops.append(Op("deconv_bwd", l.name, lambda st, a=gtop, b=gbot, g=(n, h, w, c, k, s, pad, oh, ow), acc=acc, wdev=wdev: L.check(
-                    lib.fcn_deconv_depthwise_bwd_f32(a.buf.ptr, wdev, b.ptr, g[0], g[1], g[2], g[3], b.cstride, g[4], g[5], g[6], g[7], g[8],
-                                                     a.cstride, a.coffset, acc, st))))
-            elif t == "Sigmoid":
-                yb = B[l.tops[0]]
-                ops.append(Op("sigmoid_bwd", l.name, lambda st, y=yb, a=gtop, b=gbot, acc=acc: L.check(
-                    lib.fcn_sigmoid_bwd_f32(y.ptr, a.ptr, b.ptr, y.pixels * y.cstride, acc, st))))
-            elif t == "ReLU":
-                yb = B[l.tops[0]]
-                ops.append(Op("relu_bwd", l.name, lambda st, y=yb, a=gtop, b=gbot: L.check(lib.fcn_relu_bwd_f32(
-                    a.ptr, y.ptr, b.ptr, y.pixels, y.channels, y.cstride, st))))
-            elif t == "Power":
-                continue        # input transform: nothing upstream learns
-            else:
-                raise NotImplementedError("backward of layer type %s (%s)" % (t, l.name))
-            mark(gbot, pool_writer)
-        finish_dgrads()
-        self._ws = DeviceBuffer(ws_floats * 4, zero=False)
-        self.bwd_ops = ops
+        plan = BackwardPlanner(self)
+        plan.run()
+        self.bwd_ops, self._ws = plan.ops, plan.ws
+        self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
             self._tune_wgrads()
         self._plan_buckets()
@@ -1032,7 +554,7 @@ class TrainEngine(Engine):
         # happen inside a stream capture); graphs are captured from the second step on
         first = not getattr(self, "_warm", False)
         self._warm = True
-        use_graph = os.environ.get("FCN_TRAIN_GRAPH", "1") != "0" and os.environ.get("FCN_NO_GRAPH", "0") in ("", "0") and not first
+        use_graph = os.environ.get("FCN_TRAIN_GRAPH", "1") != "0" and graphs_enabled() and not first
         triggers: Dict[int, List[dict]] = {}
         for b in self.buckets:
             triggers.setdefault(b["after_op"], []).append(b)
