@@ -12,8 +12,8 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
-from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, tconv_desc
-from .netspec import DATA_TYPES, Layer
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, tconv_desc
+from .netspec import DATA_TYPES, Layer, crop_window
 
 
 @dataclass
@@ -63,6 +63,7 @@ class BackwardPlanner:
         # ... and the ones _one_bottom hands (layer, dY, dX, accumulate)
         self.one_bottom = {"Pooling": self._pooling, "LRN": self._lrn, "Dropout": self._dropout, "Eltwise": self._eltwise_prod,
                            "Deconvolution": self._depthwise_deconv, "Sigmoid": self._sigmoid_plain, "ReLU": self._relu_plain,
+                           "Crop": self._crop,
                            "Power": lambda l, gtop, gbot, acc: None}      # input transform: nothing upstream learns
 
     def run(self) -> None:
@@ -473,7 +474,9 @@ class BackwardPlanner:
         gbot = self.G.get(l.bottoms[0]) if gtop is not None and l.bottoms else None
         if gbot is None:
             return
-        acc = 1 if self.state(gbot) == "full" else 0
+        # an in-place layer (bottom == top: drop6 / drop7 of the published FCN nets, an unfused in-place Sigmoid, ReLU or LRN) rewrites dY
+        # as dX - there is nothing to accumulate into, whatever the layer type; `+=` into its own dY would be dY + f(dY)
+        acc = 1 if self.state(gbot) == "full" and gbot is not gtop else 0
         emit = self.one_bottom.get(l.type)
         if emit is None:
             raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
@@ -488,6 +491,20 @@ class BackwardPlanner:
             gtop.buf.ptr, idx.ptr, gbot.buf.ptr, g.n, g.h, g.w, g.cin, gbot.cstride, gbot.coffset, g.k, g.s, g.pad, g.oh, g.ow,
             gtop.cstride, gtop.coffset, acc, rec.mask[0], rec.mask[1], rec.mask[2], st))))
         self.mark(gbot, rec)
+
+    def _crop(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        """dX of bottom 0: dY inside the window and zeros outside in one launch, or += dY inside it when dX already holds a gradient.
+        Bottom 1 lent its shape: no gradient goes there."""
+        lib = self.lib
+        _, (_, oc, oy, ox) = crop_window(l, self.B[l.bottoms[0]].shape, self.B[l.bottoms[1]].shape)
+        if oc or gbot.channels != gtop.channels:
+            raise NotImplementedError("backward of Crop %s along the channel axis" % l.name)
+        n, c, h, w = gbot.shape
+        _, _, oh, ow = gtop.shape
+        self.ops.append(Op("crop_bwd", l.name, lambda st: L.check(lib.fcn_crop_bwd_f32(
+            gtop.buf.ptr, gbot.buf.ptr, n, h, w, c, gbot.cstride, gbot.coffset, oy, ox, oh, ow, gtop.cstride, gtop.coffset, acc, st)),
+            0.0, 4.0 * (gtop.pixels + gbot.pixels) * c))
+        self.mark(gbot)
 
     def _lrn(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
         xb, yb = self.B[l.bottoms[0]], self.B[l.tops[0]]
@@ -506,9 +523,10 @@ class BackwardPlanner:
         e, lib = self.e, self.lib
         ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
         n, c, h, w = self.B[l.bottoms[0]].shape
+        salt = dropout_layer_salt(self.spec, l)      # the mask the forward launch of this layer drew
         self.ops.append(Op("dropout_bwd", l.name, lambda st: L.check(lib.fcn_dropout_f32(
-            gtop.buf.ptr, gbot.buf.ptr, n, c, h, w, gtop.cstride, gtop.coffset, gbot.cstride, gbot.coffset, ratio, e.dropout_seed,
-            e.dropout_index_offset, st))))
+            gtop.buf.ptr, gbot.buf.ptr, n, c, h, w, gtop.cstride, gtop.coffset, gbot.cstride, gbot.coffset, ratio,
+            (e.dropout_seed + salt) & 0xFFFFFFFF, e.dropout_index_offset, st))))
         self.mark(gbot)
 
     def _eltwise_prod(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:

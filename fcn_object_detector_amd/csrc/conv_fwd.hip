@@ -1946,7 +1946,9 @@ int validate(const fcn_conv_desc& d) {
                 FCN_E_ARG, "conv: OH/OW (%d,%d) do not match floor((H+2p-k)/s)+1", d.OH, d.OW);
     FCN_REQUIRE(d.OH > 0 && d.OW > 0, FCN_E_ARG, "conv: empty output");
     FCN_REQUIRE(d.y_cstride >= d.y_coffset + d.Cout && d.y_coffset >= 0, FCN_E_ARG, "conv: output slice exceeds y_cstride");
-    FCN_REQUIRE(d.kh * d.kw < 4096, FCN_E_UNSUPPORTED, "conv: kernel window %dx%d too large", d.kh, d.kw);
+    // (4096 taps exactly is the data gradient of FCN-32s' k64 / s32 upsampling.  The per-lane loader's kt / kw by kw_magic =
+    //  ceil(65536 / kw) is exact there: a window of exactly 4096 taps has a power-of-two kw, which divides 65536.)
+    FCN_REQUIRE(d.kh * d.kw <= 4096, FCN_E_UNSUPPORTED, "conv: kernel window %dx%d too large", d.kh, d.kw);
     FCN_REQUIRE((long long)d.N * d.H * d.W * d.x_cstride < (1ll << 31) && (long long)d.Cout * d.kh * d.kw * d.Cin < (1ll << 31),
                 FCN_E_UNSUPPORTED, "conv: tensor too large for 32-bit element offsets");
     FCN_REQUIRE(d.in_shift == 0.f, FCN_E_UNSUPPORTED, "conv: in_shift is applied by the producer of the input (fcn_nchw_to_nhwc_f32 / fcn_preprocess_bgr8)");

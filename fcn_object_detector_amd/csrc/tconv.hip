@@ -220,7 +220,7 @@ int validate(const fcn_tconv_desc& d) {
                 "tconv: non-positive extent");
     FCN_REQUIRE(d.stride <= TC_MAX_STRIDE, FCN_E_UNSUPPORTED, "tconv: stride %d above %d", d.stride, TC_MAX_STRIDE);
     FCN_REQUIRE(d.pad < d.kh && d.pad < d.kw, FCN_E_UNSUPPORTED, "tconv: pad %d must stay below the kernel extent %dx%d", d.pad, d.kh, d.kw);
-    FCN_REQUIRE(d.kh * d.kw < 4096, FCN_E_UNSUPPORTED, "tconv: kernel window %dx%d too large", d.kh, d.kw);
+    FCN_REQUIRE(d.kh * d.kw <= 4096, FCN_E_UNSUPPORTED, "tconv: kernel window %dx%d too large", d.kh, d.kw);      // (64 x 64: the x32 upsampling of FCN-32s)
     const int ca4 = (d.Ca + 3) & ~3;
     FCN_REQUIRE(d.a_cstride % 4 == 0 && d.a_cstride >= ca4, FCN_E_ALIGN, "tconv: a_cstride (%d) must be a multiple of 4 holding Ca (%d) padded to 4",
                 d.a_cstride, d.Ca);

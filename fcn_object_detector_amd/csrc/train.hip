@@ -1245,7 +1245,8 @@ __device__ __forceinline__ unsigned dropout_hash(unsigned index, unsigned seed) 
     return x;
 }
 
-__global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int C, int H, int W,
+// (x and y may be the same view - an in-place Dropout layer, forward and backward: a lane reads and writes its own element only)
+__global__ __launch_bounds__(256) void dropout_kernel(const float* x, float* y, int N, int C, int H, int W,
                                                       int x_cstride, int x_coffset, int y_cstride, int y_coffset, unsigned thresh, float scale,
                                                       unsigned seed, unsigned index_offset) {
     const long long total = (long long)N * H * W * C;

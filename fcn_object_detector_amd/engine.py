@@ -27,7 +27,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as L
-from .netspec import Layer, NetSpec, kernel_stride_pad
+from .netspec import Layer, NetSpec, crop_window, kernel_stride_pad
 
 F32 = np.float32
 
@@ -46,6 +46,15 @@ def graphs_enabled() -> bool:
     """False under FCN_NO_GRAPH=1: plain launches instead of hipGraphs (e.g. under a profiler).  Reads the environment at every
     call - tests and tools set the variable after import."""
     return os.environ.get("FCN_NO_GRAPH", "0") in ("", "0")
+
+
+def dropout_layer_salt(spec: NetSpec, l: Layer) -> int:
+    """What the k-th Dropout layer of a net adds to the step's dropout seed: k * 2^28.  The mask is a function of (element index, seed)
+    alone, so two Dropout layers of one shape (drop6 / drop7 of the published FCN nets) would otherwise drop the same units in every
+    step.  0 for the first layer: nets with one Dropout layer draw what they always drew.  Seeds count iterations, so layer k at
+    iteration i draws what layer 0 draws at iteration i + k * 2^28 - beyond any run."""
+    k = [q.name for q in spec.layers if q.type == "Dropout"].index(l.name)
+    return (k << 28) & 0xFFFFFFFF
 
 
 class ConvGeom(namedtuple("ConvGeom", "n cin h w cout oh ow k s pad")):
@@ -630,7 +639,8 @@ class Engine:
             if t == "Power" and l.tops[0] in self.shift:
                 continue      # folded into the consumer convolutions' loaders
             ops = self._emit_simple(l)
-            tasks.append(dict(kind="op", layer=l, ops=ops, reads=[self._range(b) for b in l.bottoms],
+            read = l.bottoms[:1] if t == "Crop" else l.bottoms      # a Crop's second bottom is a shape, not data
+            tasks.append(dict(kind="op", layer=l, ops=ops, reads=[self._range(b) for b in read],
                               writes=[self._range(tp) for tp in l.tops], pool_desc=self._fusable_pool_desc(l)))
         return tasks
 
@@ -1285,13 +1295,13 @@ class Engine:
         """The launches of one layer that is not a convolution."""
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice"):
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
                 "Slice": self._fwd_slice, "Concat": self._fwd_concat, "Eltwise": self._fwd_eltwise,
-                "Deconvolution": self._fwd_deconvolution}.get(t)
+                "Deconvolution": self._fwd_deconvolution, "Crop": self._fwd_crop}.get(t)
         if emit is None:
             raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
         return emit(l, halves)
@@ -1304,6 +1314,19 @@ class Engine:
         fn = lib.fcn_copy_channels_f16 if sb.esize == 2 else lib.fcn_copy_channels_f32
         return Op("copy", name, lambda st: L.check(fn(sb.buf.ptr, db.buf.ptr, pixels, c, sb.cstride, so, db.cstride, do, st)),
                   0.0, 2.0 * sb.esize * pixels * c)
+
+    def _fwd_crop(self, l: Layer, halves: List[str]) -> List[Op]:
+        """Crop: the window of bottom 0 at crop_param's offsets, in the size of bottom 1 - which lends its shape and is never read."""
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.esize != yb.esize:
+            raise NotImplementedError("f16 engine: Crop %s copies between half and float32 blobs" % l.name)
+        _, (_, oc, oy, ox) = crop_window(l, xb.shape, self.blobs[l.bottoms[1]].shape)
+        n, _, h, w = xb.shape
+        _, c, oh, ow = yb.shape
+        fn = lib.fcn_crop_fwd_f16 if xb.esize == 2 else lib.fcn_crop_fwd_f32
+        return [Op("crop", l.name, lambda st: L.check(fn(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset + oc, oy, ox, oh, ow,
+                                                         yb.cstride, yb.coffset, st)), 0.0, 2.0 * xb.esize * yb.pixels * c)]
 
     def _fwd_pooling(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()
@@ -1377,8 +1400,9 @@ class Engine:
             return [self._copy_op(l.name, xb, xb.coffset, yb, yb.coffset, xb.pixels, xb.channels)]
         ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
         n, c, h, w = xb.shape
+        salt = dropout_layer_salt(self.spec, l)
         return [Op("dropout", l.name, lambda st: L.check(lib.fcn_dropout_f32(
-            xb.buf.ptr, yb.buf.ptr, n, c, h, w, xb.cstride, xb.coffset, yb.cstride, yb.coffset, ratio, self.dropout_seed,
+            xb.buf.ptr, yb.buf.ptr, n, c, h, w, xb.cstride, xb.coffset, yb.cstride, yb.coffset, ratio, (self.dropout_seed + salt) & 0xFFFFFFFF,
             self.dropout_index_offset, st)),
             0.0, 8.0 * xb.pixels * c)]
 

@@ -238,6 +238,9 @@ PROTOTYPES = {
     "fcn_tconv_bank_floats": (_sz, [_i, _i, _i, _i]),
     "fcn_tconv_bank_pack_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fcn_channel_sum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fcn_crop_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
+    "fcn_crop_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
+    "fcn_crop_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

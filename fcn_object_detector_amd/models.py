@@ -13,6 +13,11 @@ lr/decay multipliers) as
   * ``vgg16_fcn_bbox``              <->  reference train/fcn_bbox/train_val.prototxt (bbox branch + seg branch)
 
 tests/test_models.py checks that equivalence layer by layer whenever /root/reference is present.
+
+``voc_fcn32s`` / ``voc_fcn16s`` / ``voc_fcn8s`` are not reference nets: they emit the structure of the published FCN nets for
+PASCAL VOC (Long, Shelhamer, Darrell: "Fully Convolutional Networks for Semantic Segmentation") - VGG16 with ``pad: 100`` on
+conv1_1, convolutional fc6 / fc7, group-1 Deconvolution upsampling and ``Crop`` layers aligning the skip connections and the
+score map - as test and tool material.
 """
 from __future__ import annotations
 
@@ -342,3 +347,98 @@ def vgg16_bounding_box_deploy(batch: int = 10, height: int = 448, width: int = 4
     w.layer("coverage/sig", "Sigmoid", ["cvg/classifier"], ["coverage"])
     w.layer("bbox/regressor", "Convolution", ["dropout5"], ["bboxes"], _conv_body(4 * num_classes, 1, bias_value=0.0))
     return w.text()
+
+
+# ----------------------------------------------------------------------
+# the published FCN-32s / 16s / 8s nets (PASCAL VOC)
+# ----------------------------------------------------------------------
+
+def _voc_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, pad: int, fillers: bool, relu: Optional[str] = None) -> None:
+    fill = '    weight_filler { type: "xavier" }\n    bias_filler { type: "constant" value: 0.1 }\n' if fillers else ""
+    body = ("  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  convolution_param {\n    num_output: %d\n    pad: %d\n    kernel_size: %d\n    stride: 1\n%s  }") % (num_output, pad, k, fill)
+    w.layer(name, "Convolution", [bottom], [name], body)
+    if relu:
+        w.layer(relu, "ReLU", [name], [name])
+
+
+def _voc_upscore(w: _Writer, name: str, bottom: str, num_output: int, k: int, s: int, fillers: bool) -> None:
+    fill = '    weight_filler { type: "bilinear" }\n' if fillers else ""
+    body = ("  param { lr_mult: 0 }\n  convolution_param {\n    num_output: %d\n    bias_term: false\n    kernel_size: %d\n"
+            "    stride: %d\n%s  }") % (num_output, k, s, fill)
+    w.layer(name, "Deconvolution", [bottom], [name], body)
+
+
+def _voc_crop(w: _Writer, name: str, bottom: str, like: str, offset: int) -> None:
+    w.layer(name, "Crop", [bottom, like], [name], "  crop_param {\n    axis: 2\n    offset: %d\n  }" % offset)
+
+
+def _voc_fcn(variant: int, phase: str, num_classes: int, shape: Sequence[int], width_div: int, fc_div: Optional[int], fillers: bool) -> str:
+    if phase not in ("TRAIN", "TEST"):
+        raise ValueError("phase must be 'TRAIN' or 'TEST'")
+    n, c, h, wd = (int(v) for v in shape)
+    w = _Writer()
+    w.raw('name: "voc-fcn%ds"' % variant)
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: %d dim: %d dim: %d } }" % (n, c, h, wd))
+    if phase == "TRAIN":
+        w.layer("label", "Input", [], ["label"], "  input_param { shape { dim: %d dim: 1 dim: %d dim: %d } }" % (n, h, wd))
+    prev = "data"
+    for blk, convs, width_ in VGG16:
+        for i in range(1, convs + 1):
+            nm = "conv%d_%d" % (blk, i)
+            _voc_conv(w, nm, prev, max(width_ // width_div, 1), 3, 100 if (blk, i) == (1, 1) else 1, fillers, "relu%d_%d" % (blk, i))
+            prev = nm
+        w.layer("pool%d" % blk, "Pooling", [prev], ["pool%d" % blk], "  pooling_param {\n    pool: MAX\n    kernel_size: 2\n    stride: 2\n  }")
+        prev = "pool%d" % blk
+    fc = max(4096 // (fc_div or width_div), 1)
+    for nm, k, tag in (("fc6", 7, "6"), ("fc7", 1, "7")):
+        _voc_conv(w, nm, prev, fc, k, 0, fillers, "relu" + tag)
+        w.layer("drop" + tag, "Dropout", [nm], [nm], "  dropout_param {\n    dropout_ratio: 0.5\n  }")
+        prev = nm
+    nc = num_classes
+    _voc_conv(w, "score_fr", "fc7", nc, 1, 0, fillers)
+    if variant == 32:
+        _voc_upscore(w, "upscore", "score_fr", nc, 64, 32, fillers)
+        _voc_crop(w, "score", "upscore", "data", 19)
+    else:
+        _voc_upscore(w, "upscore2", "score_fr", nc, 4, 2, fillers)
+        _voc_conv(w, "score_pool4", "pool4", nc, 1, 0, fillers)
+        _voc_crop(w, "score_pool4c", "score_pool4", "upscore2", 5)
+        w.layer("fuse_pool4", "Eltwise", ["upscore2", "score_pool4c"], ["fuse_pool4"], "  eltwise_param {\n    operation: SUM\n  }")
+        if variant == 16:
+            _voc_upscore(w, "upscore16", "fuse_pool4", nc, 32, 16, fillers)
+            _voc_crop(w, "score", "upscore16", "data", 27)
+        else:
+            _voc_upscore(w, "upscore_pool4", "fuse_pool4", nc, 4, 2, fillers)
+            _voc_conv(w, "score_pool3", "pool3", nc, 1, 0, fillers)
+            _voc_crop(w, "score_pool3c", "score_pool3", "upscore_pool4", 9)
+            w.layer("fuse_pool3", "Eltwise", ["upscore_pool4", "score_pool3c"], ["fuse_pool3"], "  eltwise_param {\n    operation: SUM\n  }")
+            _voc_upscore(w, "upscore8", "fuse_pool3", nc, 16, 8, fillers)
+            _voc_crop(w, "score", "upscore8", "data", 31)
+    if phase == "TRAIN":
+        w.layer("loss", "SoftmaxWithLoss", ["score", "label"], ["loss"], "  loss_param {\n    ignore_label: 255\n    normalize: false\n  }")
+    return w.text()
+
+
+def voc_fcn32s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
+               fc_div: Optional[int] = None, fillers: bool = False) -> str:
+    """The published FCN-32s: VGG16 (conv1_1 with pad 100) to pool5, fc6 (k7) / fc7 (k1) as convolutions with ReLU and Dropout,
+    score_fr, a x32 Deconvolution (k64 s32, no bias, lr_mult 0) and score = Crop(upscore, data) at offset 19.  TRAIN adds the label
+    input and SoftmaxWithLoss (normalize: false, ignore_label: 255); TEST ends at `score`.  width_div / fc_div divide the VGG widths
+    and the 4096 of fc6 / fc7 (tests).  The published files carry no fillers (the nets are initialised by net surgery);
+    fillers=True writes xavier / constant 0.1 into the convolutions and the bilinear filler into the upsampling layers."""
+    return _voc_fcn(32, phase, num_classes, shape, width_div, fc_div, fillers)
+
+
+def voc_fcn16s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
+               fc_div: Optional[int] = None, fillers: bool = False) -> str:
+    """The published FCN-16s: as voc_fcn32s to score_fr, then upscore2 (k4 s2), score_pool4 on pool4 cropped to it at offset 5, their
+    sum, upscore16 (k32 s16) and score = Crop(upscore16, data) at offset 27."""
+    return _voc_fcn(16, phase, num_classes, shape, width_div, fc_div, fillers)
+
+
+def voc_fcn8s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
+              fc_div: Optional[int] = None, fillers: bool = False) -> str:
+    """The published FCN-8s: as voc_fcn16s to fuse_pool4, then upscore_pool4 (k4 s2), score_pool3 on pool3 cropped to it at offset 9,
+    their sum, upscore8 (k16 s8) and score = Crop(upscore8, data) at offset 31."""
+    return _voc_fcn(8, phase, num_classes, shape, width_div, fc_div, fillers)

@@ -76,6 +76,33 @@ def deconv_out(h: int, k: int, s: int, p: int) -> int:
     return s * (h - 1) + k - 2 * p
 
 
+def crop_window(l: "Layer", b0: Shape, b1: Shape) -> Tuple[Shape, Tuple[int, ...]]:
+    """Caffe's CropLayer: (shape of the top, offset into bottom 0 per axis).  Axes before crop_param.axis (default 2, negative counts
+    from the end) keep bottom 0's extent, axes from it on take bottom 1's; no offset means 0, one offset applies to every cropped
+    axis, otherwise exactly one per cropped axis.  Bottom 1 only lends its shape."""
+    cp = l.sub("crop_param")
+    if len(b0) != 4 or len(b1) != 4:
+        raise ValueError("layer %s: Crop takes two 4-d blobs, got %s and %s" % (l.name, b0, b1))
+    axis = int(cp.get("axis", 2))
+    if not -4 <= axis < 4:
+        raise ValueError("layer %s: crop axis %d is outside [-4, 4)" % (l.name, axis))
+    axis += 4 if axis < 0 else 0
+    if axis == 0:
+        raise NotImplementedError("layer %s: Crop along the batch axis (axis: 0)" % l.name)
+    offs = [int(o) for o in cp.getall("offset")]
+    if len(offs) > 1 and len(offs) != 4 - axis:
+        raise ValueError("layer %s: %d crop offsets for %d cropped axes (none, one, or one per axis)" % (l.name, len(offs), 4 - axis))
+    if b0[0] != b1[0]:
+        raise ValueError("layer %s: batch of %d cropped to the shape of a batch of %d" % (l.name, b0[0], b1[0]))
+    shape, offset = list(b0), [0, 0, 0, 0]
+    for i in range(axis, 4):
+        offset[i] = offs[0] if len(offs) == 1 else offs[i - axis] if offs else 0
+        shape[i] = b1[i]
+        if offset[i] < 0 or offset[i] + b1[i] > b0[i]:
+            raise ValueError("layer %s: crop of axis %d at offset %d + size %d leaves the extent %d" % (l.name, i, offset[i], b1[i], b0[i]))
+    return tuple(shape), tuple(offset)
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 
@@ -202,6 +229,10 @@ class NetSpec:
                     shapes[l.tops[1]] = (bots[0][1],)
             elif t in ("ReLU", "Sigmoid", "Power", "LRN", "Dropout", "Softmax", "TanH"):
                 shapes[l.tops[0]] = bots[0]
+            elif t == "Crop":
+                if len(bots) != 2 or len(l.tops) != 1:
+                    raise ValueError("layer %s: Crop takes two bottoms (the blob and the shape donor) and has one top" % l.name)
+                shapes[l.tops[0]] = crop_window(l, bots[0], bots[1])[0]
             elif t == "Eltwise":
                 for b in bots[1:]:
                     if b != bots[0]:

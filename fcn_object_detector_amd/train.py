@@ -180,7 +180,8 @@ class TrainEngine(Engine):
         for l in self.spec.layers:
             if l.type in DATA_TYPES:
                 continue
-            if self._learns(l) or any(b in need for b in l.bottoms):
+            through = l.bottoms[:1] if l.type == "Crop" else l.bottoms      # a Crop's second bottom only lends its shape
+            if self._learns(l) or any(b in need for b in through):
                 need.update(l.tops)
         return need
 

@@ -614,6 +614,27 @@ int    fcn_tconv_bank_pack_f32(const float* w, float* packed, int Ca, int Cb, in
  * sums ITS y, which after the role swap is the layer's input).  One workgroup per channel, fixed order: bit-reproducible. */
 int    fcn_channel_sum_f32(const float* dy, float* db, int pixels, int C, int cstride, int coffset, fcn_stream_t s);
 
+/* ---- Crop (Caffe CropLayer: the skip connections and the final score map of the published FCN-32s / 16s / 8s nets): a window copy
+ *      between two NHWC views with channel strides, and its adjoint.  x / dX is the N x H x W view, y / dY the N x OH x OW window at
+ *      (off_y, off_x); a crop along the channel axis is the caller adding its offset to x_coffset.
+ *      Contract, as for fcn_copy_channels_f16: pointers 16-byte aligned and channel strides multiples of 16 bytes (4 floats / 8 halves)
+ *      else FCN_E_ALIGN; null pointers, non-positive extents, a slice wider than its stride, a negative offset or off + O > extent on
+ *      either axis FCN_E_ARG; a view past 2^31 elements FCN_E_UNSUPPORTED; every check precedes the first HIP call.  Channel offsets
+ *      that are both multiples of the 16-byte group move 16 bytes per lane (the last C % group channels one by one), any other offset
+ *      one element per lane.  Exactly channels y_coffset .. y_coffset + C - 1 of every output pixel are written, nothing outside
+ *      channels x_coffset .. x_coffset + C - 1 of the window of x is read.  One pass, one writer per element, no atomics: results do
+ *      not depend on the run. ---- */
+/* y[n, oy, ox, y_coffset + c] = x[n, oy + off_y, ox + off_x, x_coffset + c], c < C */
+int  fcn_crop_fwd_f32(const float* x, float* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int off_y, int off_x,
+                      int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
+int  fcn_crop_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int off_y, int off_x,
+                      int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
+/* accumulate 0: ONE launch writes channels dx_coffset .. dx_coffset + C - 1 of every pixel of dX - dY inside the window, zeros outside
+ * (no memset in front).  accumulate 1: dX += dY inside the window and nothing outside it is touched (a blob with several consumers).
+ * There is no half-float twin: the half-float engine is inference only. */
+int  fcn_crop_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int off_y, int off_x,
+                      int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
