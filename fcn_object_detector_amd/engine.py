@@ -27,7 +27,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as L
-from .netspec import Layer, NetSpec, crop_window, kernel_stride_pad
+from .netspec import Layer, NetSpec, as_nchw, crop_window, kernel_stride_pad
 
 F32 = np.float32
 
@@ -93,6 +93,21 @@ def tconv_desc(a: "Blob", b: "Blob", g: ConvGeom, bank: int, bias: Optional[int]
     d.b_cstride, d.b_coffset = b.cstride, b.coffset
     d.flags = flags
     return d
+
+
+def ip_pack_bank(w: np.ndarray, c: int, h: int, wd: int, cstride: int, dtype=F32) -> np.ndarray:
+    """Caffe's (num_output, C*H*W) InnerProduct bank -> (num_output, H*W*cstride) in the memory order of a row of the NHWC bottom:
+    column p * cstride + ch holds Caffe's column ch * H*W + p, the pad channels' columns are zero."""
+    n = w.shape[0]
+    out = np.zeros((n, h * wd, cstride), dtype)
+    out[:, :, :c] = w.reshape(n, c, h * wd).transpose(0, 2, 1)
+    return out.reshape(n, h * wd * cstride)
+
+
+def ip_unpack_bank(packed: np.ndarray, c: int, h: int, wd: int, cstride: int) -> np.ndarray:
+    """The inverse of ip_pack_bank, as float32: what read_param and snapshots return."""
+    n = packed.shape[0]
+    return np.ascontiguousarray(packed.reshape(n, h * wd, cstride)[:, :, :c].transpose(0, 2, 1), dtype=F32).reshape(n, c * h * wd)
 
 
 class DeviceBuffer:
@@ -173,14 +188,25 @@ class Blob:
         self.pinned: Optional[PinnedArray] = None
         self.host_valid = False        # host copy reflects the device contents
         self.is_input = False
+        self.rows = False              # an (N,) label blob of a loss / Accuracy over N score rows: N pixels of one channel
+
+    @property
+    def nchw(self) -> Optional[Tuple[int, int, int, int]]:
+        """The blob as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
+        channels (H = W = 1); an (N,) label that pairs with such score rows (`rows`) as N pixels of one channel; None for anything else (scalars,
+        per-class vectors: dense floats outside that machinery).  netspec.as_nchw is the rule."""
+        if self.rows and len(self.shape) == 1:
+            return (self.shape[0], 1, 1, 1)
+        return as_nchw(self.shape)
 
     @property
     def channels(self) -> int:
-        return self.shape[1] if len(self.shape) == 4 else 1
+        return self.nchw[1] if self.nchw is not None else 1
 
     @property
     def pixels(self) -> int:
-        return self.shape[0] * self.shape[2] * self.shape[3] if len(self.shape) == 4 else 1
+        g = self.nchw
+        return g[0] * g[2] * g[3] if g is not None else 1
 
     @property
     def ptr(self) -> int:
@@ -305,15 +331,15 @@ class Engine:
             if name in half_image:
                 esize[name] = 2
                 continue
-            wide = (not self.f16 or len(shp) != 4 or name in self.outputs or name in data_tops      # inputs stay float32 (Power(-127) quirk)
+            wide = (not self.f16 or len(shp) not in (2, 4) or name in self.outputs or name in data_tops      # inputs stay float32 (Power(-127) quirk)
                     or any(q.type == "Power" and q.bottoms[0] in data_tops for q in producers.get(name, []))
                     or any(q.type == "Sigmoid" for q in consumers.get(name, [])) or any(q.type == "Sigmoid" for q in producers.get(name, [])))
             esize[name] = 4 if wide else 2
         if self.f16:
             for name in self.shapes:
-                if esize[name] == 4 and len(self.shapes[name]) == 4 and name not in data_tops:
+                if esize[name] == 4 and len(self.shapes[name]) in (2, 4) and name not in data_tops:
                     # (Softmax and Deconvolution read halves and store float32: the out_f32 forms of their half kernels)
-                    bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution")]
+                    bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct")]
                     if bad:
                         raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 
@@ -331,7 +357,7 @@ class Engine:
                     prods = [p for p in producers.get(b, []) if not (p.type in ("ReLU", "Dropout") and p.bottoms == p.tops)]
                     good = (self.fuse and b not in data_tops and b not in alias and c % (16 // esize[b]) == 0 and len(prods) == 1
                             and esize[b] == esize[l.tops[0]]
-                            and prods[0].type in ("Convolution", "Pooling")
+                            and prods[0].type in ("Convolution", "Pooling", "InnerProduct")
                             and [q.type for q in consumers.get(b, []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)] == ["Concat"])
                     ok = ok and good
                     plan.append((b, off))
@@ -353,7 +379,7 @@ class Engine:
                     alias[l.tops[0]] = (bot, 0)
                     shift[l.tops[0]] = float(p.get("shift", 0.0))
             elif l.type == "Slice":
-                n, c, h, w = self.shapes[l.bottoms[0]]
+                n, c, h, w = as_nchw(self.shapes[l.bottoms[0]])
                 # tops are views of the bottom when every consumer can read a channel slice at a 16-byte aligned offset;
                 # otherwise (models/train_val.prototxt slices a 17-channel label record at 1, 5, 9, 13 for Eltwise layers)
                 # the slices are materialised by copies
@@ -374,10 +400,15 @@ class Engine:
         for name, shp in self.shapes.items():
             self.blobs[name] = Blob(name, shp)
             self.blobs[name].esize = esize[name]
+        for l in spec.layers:      # Caffe's data layers emit (N,) labels: beside N score rows such a blob is N pixels of one channel
+            if l.type in ("SoftmaxWithLoss", "Accuracy") and len(l.bottoms) == 2:
+                score, lab = self.shapes[l.bottoms[0]], self.shapes[l.bottoms[1]]
+                if len(score) == 2 and tuple(lab) == (score[0],):
+                    self.blobs[l.bottoms[1]].rows = True
         for name, blob in self.blobs.items():
             if name in alias:
                 continue
-            if len(blob.shape) == 4:
+            if blob.nchw is not None:
                 blob.cstride = _ra(blob.channels, blob.esize)
                 blob.buf = DeviceBuffer(blob.pixels * blob.cstride * blob.esize)
             else:
@@ -483,6 +514,11 @@ class Engine:
                     out[..., 3] = hi
                     out[..., 4] = (term - hi.astype(np.float64)).astype(np.float16)
             return out
+        if l.type == "InnerProduct":
+            # [num_output][H*W*cstride]: the columns in the order of the elements of a row of the NHWC bottom, zero at its pad channels
+            xb = self._ip_bottom(l)
+            _n, c, h, wd = xb.nchw
+            return ip_pack_bank(w, c, h, wd, xb.cstride, np.float16 if xb.esize == 2 else F32)
         if l.type == "Deconvolution":
             c, cog, kh, kw = w.shape
             if self._deconv_dense(l):
@@ -493,6 +529,15 @@ class Engine:
                 return out
             return np.ascontiguousarray(w.reshape(c, kh, kw))
         raise NotImplementedError(l.type)
+
+    def _ip_bottom(self, l: Layer) -> Blob:
+        """The bottom of an InnerProduct layer, which must be a whole buffer: a row of it is then the layer's input vector as it lies
+        in memory.  A bottom that is a channel window of a wider buffer (a Concat member, a Slice top) is refused by name."""
+        xb = self.blobs[l.bottoms[0]]
+        if xb.nchw is None or xb.coffset or xb.cstride != _ra(xb.channels, xb.esize):
+            raise NotImplementedError("InnerProduct %s: the bottom %s is a channel window of a wider buffer (or no 4-d / 2-d blob)"
+                                      % (l.name, l.bottoms[0]))
+        return xb
 
     def _deconv_dense(self, l: Layer) -> bool:
         """True: a group-1 Deconvolution (the transposed-convolution kernel); False: group == channels == num_output (the depthwise
@@ -540,6 +585,12 @@ class Engine:
         if index == 0 and lay.type == "Convolution":
             co, ci, kh, kw = shp
             return np.ascontiguousarray(raw.reshape(co, kh, kw, -1)[..., :ci].transpose(0, 3, 1, 2))
+        if index == 0 and lay.type == "InnerProduct":
+            xb = self._ip_bottom(lay)
+            _n, c, h, w = xb.nchw
+            if xb.esize == 2:
+                raw = raw.view(np.float16).astype(F32)
+            return ip_unpack_bank(raw.reshape(shp[0], -1), c, h, w, xb.cstride)
         if index == 0 and lay.type == "Deconvolution" and self._deconv_dense(lay):
             ci, co, kh, kw = shp
             return np.ascontiguousarray(raw.reshape(ci, kh, kw, -1)[..., :co].transpose(0, 3, 1, 2))
@@ -557,7 +608,7 @@ class Engine:
     def _conv_desc(self, l: Layer, fused_relu: bool, sig_top: Optional[str]) -> L.ConvDesc:
         g = self._geom(l)
         if int(l.sub("convolution_param").get("group", 1)) != 1:
-            raise NotImplementedError("grouped Convolution (layer %s) is not used by the reference nets" % l.name)
+            raise NotImplementedError("grouped Convolution (layer %s, group %d): the grouped launch for it is not built yet" % (l.name, int(l.sub("convolution_param").get("group", 1))))
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
         eps = 16 // xb.esize
         if xb.coffset % eps or xb.cstride % eps:
@@ -588,19 +639,29 @@ class Engine:
         b = self.blobs[name]
         return (b.buf.ptr, b.coffset, b.coffset + max(b.channels, 1))
 
-    def _fused_after(self, li: int, l: Layer, skip: set) -> Tuple[bool, Optional[str]]:
-        """(an in-place ReLU directly after convolution l rides in its epilogue, the top of a Sigmoid that does) - the layers so
-        absorbed join `skip`."""
-        layers, top = self.spec.layers, l.tops[0]
+    def _relu_after(self, li: int, l: Layer, skip: set) -> bool:
+        """True when the first layer that touches l's top is an in-place ReLU without a negative slope: it rides in l's epilogue
+        (Convolution, InnerProduct) and joins `skip`."""
+        top = l.tops[0]
         if not self.fuse:
-            return False, None
-        for nxt in layers[li + 1:]:          # in-place ReLU directly after this conv
+            return False
+        for nxt in self.spec.layers[li + 1:]:
             if top in nxt.bottoms or top in nxt.tops:
                 if nxt.type == "ReLU" and nxt.bottoms == [top] and nxt.tops == [top] and \
                         float(nxt.sub("relu_param").get("negative_slope", 0.0)) == 0.0:
                     skip.add(nxt.name)
-                    return True, None
+                    return True
                 break
+        return False
+
+    def _fused_after(self, li: int, l: Layer, skip: set) -> Tuple[bool, Optional[str]]:
+        """(an in-place ReLU directly after convolution l rides in its epilogue, the top of a Sigmoid that does) - the layers so
+        absorbed join `skip`."""
+        top = l.tops[0]
+        if not self.fuse:
+            return False, None
+        if self._relu_after(li, l, skip):
+            return True, None
         cons = self.consumers.get(top, [])
         if len(cons) == 1 and cons[0].type == "Sigmoid" and cons[0].tops[0] != top and len(self.producers.get(top, [])) == 1:
             skip.add(cons[0].name)
@@ -629,6 +690,12 @@ class Engine:
                                   reads=[self._range(l.bottoms[0])],
                                   writes=[self._range(top)] + ([self._range(sig_top)] if sig_top else [])))
                 self._conv_layer_meta[l.name] = dict(relu=fused_relu, sigmoid_top=sig_top)
+                continue
+            if t == "InnerProduct":
+                relu = self._relu_after(li, l, skip)
+                self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
+                tasks.append(dict(kind="op", layer=l, ops=self._fwd_inner_product(l, relu), reads=[self._range(l.bottoms[0])],
+                                  writes=[self._range(l.tops[0])], pool_desc=None))
                 continue
             if t == "Concat" and l.name not in self.copy_concats:
                 continue      # producers already wrote their slices
@@ -753,8 +820,8 @@ class Engine:
             count = int(np.prod(b.shape)) if b.shape else 1
             acc = DeviceBuffer(max(4 * count, 16), zero=True)
             self.score_acc[nm] = acc
-            if len(b.shape) == 4:
-                n, c, h, w = b.shape
+            if b.nchw is not None:
+                n, c, h, w = b.nchw
                 args = (acc.ptr, b.buf.ptr, n, h * w, c, b.cstride, b.coffset)
             else:
                 args = (acc.ptr, b.ptr, 1, 1, count, count, 0)
@@ -1399,7 +1466,7 @@ class Engine:
         if self.spec.phase == "TEST":
             return [self._copy_op(l.name, xb, xb.coffset, yb, yb.coffset, xb.pixels, xb.channels)]
         ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
-        n, c, h, w = xb.shape
+        n, c, h, w = xb.nchw
         salt = dropout_layer_salt(self.spec, l)
         return [Op("dropout", l.name, lambda st: L.check(lib.fcn_dropout_f32(
             xb.buf.ptr, yb.buf.ptr, n, c, h, w, xb.cstride, xb.coffset, yb.cstride, yb.coffset, ratio, (self.dropout_seed + salt) & 0xFFFFFFFF,
@@ -1506,6 +1573,38 @@ class Engine:
             a = yb
         return out
 
+    def _fwd_inner_product(self, l: Layer, relu: bool) -> List[Op]:
+        """InnerProduct at up to FCN_IP_MAX_ROWS rows: the weight-streaming kernels (csrc/inner_product.hip).  The bottom's rows are
+        the input vectors as they lie in memory, the bank was packed in that order at upload; the top is N pixels of num_output
+        channels, written at its channel offset (a member of a Concat of (N, C) blobs in place: _plan_buffers aliases it)."""
+        lib = L.load()
+        xb, yb = self._ip_bottom(l), self.blobs[l.tops[0]]
+        m, c, h, w = xb.nchw
+        n_out = yb.channels
+        k = h * w * xb.cstride
+        if m > L.IP_MAX_ROWS:
+            raise NotImplementedError("InnerProduct %s: a batch of %d rows (the streaming kernels take at most %d)" % (l.name, m, L.IP_MAX_ROWS))
+        if xb.esize == 4 and yb.esize != 4:
+            raise NotImplementedError("f16 engine: InnerProduct %s reads float32 and writes halves" % l.name)
+        devs = self.params_dev[l.name]
+        bias = devs[1].ptr if len(devs) > 1 else None
+        nbytes = int(lib.fcn_inner_product_fwd_workspace_bytes(m, k, n_out, xb.esize))
+        ws = DeviceBuffer(nbytes, zero=False) if nbytes else None
+        if ws is not None:
+            self._keep.append(ws)
+        wsp = ws.ptr if ws is not None else None
+        # non-temporal weight loads: the bank is read once per forward; launched alone behind a 512 MiB memset that policy took
+        # 0.5 - 0.9 of the default's time, replayed back to back about the same (DESIGN.md 4.11; not measured inside a net)
+        flags = (L.CONV_RELU if relu else 0) | L.IP_WEIGHTS_NT
+        if xb.esize == 2:
+            fn, flags = lib.fcn_inner_product_fwd_f16, flags | (L.CONV_OUT_F32 if yb.esize == 4 else 0)
+        else:
+            fn = lib.fcn_inner_product_fwd_f32
+        wptr = devs[0].ptr
+        return [Op("inner_product", l.name, lambda st: L.check(fn(xb.buf.ptr, k, wptr, bias, yb.buf.ptr, yb.cstride, yb.coffset, m, k, n_out,
+                                                                  flags, wsp, st)),
+                   2.0 * m * c * h * w * n_out, float(xb.esize) * (n_out * k + m * k) + float(yb.esize) * m * n_out)]
+
     def _fwd_deconvolution(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()
         g = self._geom(l)
@@ -1563,15 +1662,15 @@ class Engine:
     def _upload_copy(self, name: str, stream: Optional[int]) -> None:
         b = self.blobs[name]
         host = self.host_array(name)
-        dst = b.ptr if len(b.shape) != 4 else self._stage(name).ptr
+        dst = b.ptr if b.nchw is None else self._stage(name).ptr
         L.check(L.load().fcn_memcpy_h2d_async(dst, host.ctypes.data, host.nbytes, stream))
 
     def _upload_convert(self, name: str, stream: Optional[int]) -> None:
         b = self.blobs[name]
-        if len(b.shape) != 4:
+        if b.nchw is None:
             return
         lib = L.load()
-        n, c, h, w = b.shape
+        n, c, h, w = b.nchw
         st = self._stage(name)
         if b.esize == 2:
             L.check(lib.fcn_nchw_f32_to_nhwc_f16(st.ptr, b.buf.ptr, n, c, h, w, b.cstride, b.coffset, b.upload_shift, stream))
@@ -1580,10 +1679,10 @@ class Engine:
 
     def _download_convert(self, name: str, stream: Optional[int]) -> None:
         b = self.blobs[name]
-        if len(b.shape) != 4:
+        if b.nchw is None:
             return
         lib = L.load()
-        n, c, h, w = b.shape
+        n, c, h, w = b.nchw
         st = self._stage(name)
         if b.esize == 2:
             L.check(lib.fcn_nhwc_f16_to_nchw_f32(b.buf.ptr, st.ptr, n, c, h, w, b.cstride, b.coffset, stream))
@@ -1593,13 +1692,13 @@ class Engine:
     def _download_convert_all(self, stream: Optional[int]) -> None:
         """The layout kernels of ALL output blobs: the float32 4-d ones share one launch (fcn_nhwc_to_nchw_multi_f32 - behind a batch-1
         forward two launches of a few microseconds each were launch floor, not work), the others take their own."""
-        multi = [nm for nm in self.outputs if len(self.blobs[nm].shape) == 4 and self.blobs[nm].esize == 4]
+        multi = [nm for nm in self.outputs if self.blobs[nm].nchw is not None and self.blobs[nm].esize == 4]
         if 2 <= len(multi) <= 8:
             if not hasattr(self, "_multi_descs"):
                 arr = (L.LayoutDesc * len(multi))()
                 for d, nm in zip(arr, multi):
                     b = self.blobs[nm]
-                    n, c, h, w = b.shape
+                    n, c, h, w = b.nchw
                     d.src, d.dst, d.N, d.C, d.H, d.W, d.src_cstride, d.src_coffset = b.buf.ptr, self._stage(nm).ptr, n, c, h, w, b.cstride, b.coffset
                 self._multi_descs = arr
             L.check(L.load().fcn_nhwc_to_nchw_multi_f32(self._multi_descs, len(multi), stream))
@@ -1612,7 +1711,7 @@ class Engine:
     def _download_copy(self, name: str, stream: Optional[int]) -> None:
         b = self.blobs[name]
         host = self.host_array(name)
-        src = b.ptr if len(b.shape) != 4 else self._stage(name).ptr
+        src = b.ptr if b.nchw is None else self._stage(name).ptr
         L.check(L.load().fcn_memcpy_d2h_async(host.ctypes.data, src, host.nbytes, stream))
 
     def _enqueue_upload(self, name: str, stream: Optional[int]) -> None:
@@ -1696,7 +1795,7 @@ class Engine:
             for nm in self.inputs:
                 if nm not in self.device_fed:
                     self.host_array(nm)
-                    if len(self.blobs[nm].shape) == 4:
+                    if self.blobs[nm].nchw is not None:
                         self._stage(nm)
             if graphs_enabled():
                 if io and self.graph_io is None:
@@ -1750,7 +1849,7 @@ class Engine:
         if with_io:                      # nothing may allocate while the stream is capturing
             for nm in list(self.inputs) + list(self.outputs):
                 self.host_array(nm)
-                if len(self.blobs[nm].shape) == 4:
+                if self.blobs[nm].nchw is not None:
                     self._stage(nm)
         if not getattr(self, "_warm", False):
             # code objects load lazily on a kernel's first launch, which must not happen inside a stream capture

@@ -103,6 +103,8 @@ class DetectParams(C.Structure):
 
 
 CONV_RELU, CONV_SIGMOID2, CONV_ACCUM, CONV_OUT_F32, CONV_F16, CONV_OUT_F16, CONV_MASK = 1, 2, 4, 8, 16, 32, 64
+IP_MAX_ROWS = 32               # FCN_IP_MAX_ROWS: rows the InnerProduct streaming kernels take
+IP_WEIGHTS_NT = 256            # FCN_IP_WEIGHTS_NT
 CONV_IMAGE_ONES = 128      # half image whose channels 3 and 4 are the constant 1 (the folded Power shift): see include/fcnhip.h
 ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
 SOLVER_KINDS = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADADELTA": 4, "ADAM": 5}      # FCN_SOLVER_*
@@ -241,6 +243,12 @@ PROTOTYPES = {
     "fcn_crop_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_inner_product_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fcn_inner_product_fwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fcn_inner_product_fwd_f32": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "fcn_inner_product_fwd_f16": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "fcn_inner_product_bwd_data_f32": (_i, [_vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
+    "fcn_inner_product_bwd_weights_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 4 + [_vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

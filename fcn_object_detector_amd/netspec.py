@@ -103,6 +103,29 @@ def crop_window(l: "Layer", b0: Shape, b1: Shape) -> Tuple[Shape, Tuple[int, ...
     return tuple(shape), tuple(offset)
 
 
+def as_nchw(shape: Shape) -> Optional[Tuple[int, int, int, int]]:
+    """A blob's shape as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
+    channels (H = W = 1); None for anything else.  Engine.Blob.nchw and the channel-axis layers (Concat, Slice) share this rule."""
+    if len(shape) == 4:
+        return tuple(shape)
+    if len(shape) == 2:
+        return (shape[0], shape[1], 1, 1)
+    return None
+
+
+def _channel_axis_bottoms(l: "Layer", bots: Sequence[Shape]) -> List[Tuple[int, int, int, int]]:
+    """The bottoms of a Concat / Slice as NCHW: all 4-d or all 2-d, refused by layer name otherwise."""
+    g = [as_nchw(b) for b in bots]
+    if not bots or any(x is None for x in g) or len({len(b) for b in bots}) != 1:
+        raise ValueError("layer %s: %s takes 4-d blobs or 2-d blobs (not a mix), got %s" % (l.name, l.type, list(bots)))
+    return g
+
+
+def _like(nchw: Tuple[int, int, int, int], model: Shape) -> Shape:
+    """An NCHW result in the dimensionality of the layer's bottoms."""
+    return tuple(nchw) if len(model) == 4 else (nchw[0], nchw[1])
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 
@@ -181,6 +204,19 @@ class NetSpec:
                 n, c, h, w = bots[0]
                 self.param_shapes[l.name] = [(c, co // g, k, k)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
                 shapes[l.tops[0]] = (n, co, deconv_out(h, k, s, pad), deconv_out(w, k, s, pad))
+            elif t == "InnerProduct":
+                # Caffe's InnerProductLayer: everything behind the batch axis is one vector of K = C*H*W elements in (c, h, w) order
+                p = l.sub("inner_product_param")
+                if int(p.get("axis", 1)) != 1:
+                    raise NotImplementedError("layer %s: InnerProduct over axis %d (only axis 1)" % (l.name, int(p.get("axis", 1))))
+                if bool(p.get("transpose", False)):
+                    raise NotImplementedError("layer %s: InnerProduct with transpose: true" % l.name)
+                if len(bots) != 1 or len(bots[0]) not in (2, 4):
+                    raise ValueError("layer %s: InnerProduct takes one 4-d or 2-d bottom, got %s" % (l.name, bots))
+                co = int(p.get("num_output"))
+                kk = int(np.prod(bots[0][1:]))
+                self.param_shapes[l.name] = [(co, kk)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
+                shapes[l.tops[0]] = (bots[0][0], co)
             elif t == "Pooling":
                 p = l.sub("pooling_param")
                 n, c, h, w = bots[0]
@@ -193,17 +229,18 @@ class NetSpec:
                 axis = int(l.sub("concat_param").get("axis", l.sub("concat_param").get("concat_dim", 1)))
                 if axis != 1:
                     raise NotImplementedError("Concat along axis %d" % axis)
-                n, _, h, w = bots[0]
-                for b in bots[1:]:
+                g4 = _channel_axis_bottoms(l, bots)
+                n, _, h, w = g4[0]
+                for b in g4[1:]:
                     if (b[0], b[2], b[3]) != (n, h, w):
                         raise ValueError("layer %s: concat inputs disagree: %s" % (l.name, bots))
-                shapes[l.tops[0]] = (n, sum(b[1] for b in bots), h, w)
+                shapes[l.tops[0]] = _like((n, sum(b[1] for b in g4), h, w), bots[0])
             elif t == "Slice":
                 sp = l.sub("slice_param")
                 axis = int(sp.get("axis", sp.get("slice_dim", 1)))
                 if axis != 1:
                     raise NotImplementedError("Slice along axis %d" % axis)
-                n, c, h, w = bots[0]
+                n, c, h, w = _channel_axis_bottoms(l, bots[:1])[0]
                 pts = [int(x) for x in sp.getall("slice_point")]
                 if not pts:
                     step = c // len(l.tops)
@@ -212,7 +249,7 @@ class NetSpec:
                 if len(edges) != len(l.tops) + 1 or any(b <= a for a, b in zip(edges[:-1], edges[1:])):
                     raise ValueError("layer %s: bad slice points %s for %d channels" % (l.name, pts, c))
                 for tp, a, b in zip(l.tops, edges[:-1], edges[1:]):
-                    shapes[tp] = (n, b - a, h, w)
+                    shapes[tp] = _like((n, b - a, h, w), bots[0])
             elif t in LOSS_TYPES:
                 shapes[l.tops[0]] = ()
             elif t == "Accuracy":
@@ -220,8 +257,8 @@ class NetSpec:
                 ap = l.sub("accuracy_param")
                 if int(ap.get("axis", 1)) != 1:
                     raise NotImplementedError("Accuracy over axis %d (layer %s): only the channel axis" % (int(ap.get("axis", 1)), l.name))
-                if len(bots) != 2 or len(bots[0]) != 4 or not 1 <= len(l.tops) <= 2:
-                    raise ValueError("layer %s: Accuracy takes a 4-d score blob and a label blob, and has one or two tops" % l.name)
+                if len(bots) != 2 or len(bots[0]) not in (2, 4) or not 1 <= len(l.tops) <= 2:
+                    raise ValueError("layer %s: Accuracy takes a 4-d or 2-d score blob and a label blob, and has one or two tops" % l.name)
                 if int(ap.get("top_k", 1)) < 1 or int(ap.get("top_k", 1)) > bots[0][1]:
                     raise ValueError("layer %s: top_k %d is outside [1, %d]" % (l.name, int(ap.get("top_k", 1)), bots[0][1]))
                 shapes[l.tops[0]] = ()
@@ -298,7 +335,7 @@ def fill_params(spec: NetSpec, seed: int = 0) -> Dict[str, List[np.ndarray]]:
     rng = np.random.default_rng(seed)
     out: Dict[str, List[np.ndarray]] = {}
     for l in spec.param_layers():
-        p = l.sub("convolution_param")
+        p = l.sub("inner_product_param" if l.type == "InnerProduct" else "convolution_param")
         shapes = spec.param_shapes[l.name]
         blobs = [fill_blob(shapes[0], p.get("weight_filler"), rng)]
         if len(shapes) > 1:

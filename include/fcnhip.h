@@ -635,6 +635,41 @@ int  fcn_crop_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_
 int  fcn_crop_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int off_y, int off_x,
                       int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
 
+/* ---- InnerProduct (Caffe InnerProductLayer) at M <= FCN_IP_MAX_ROWS input rows: y[m][n] = sum_k x[m][k] * w[n][k] + bias[n].
+ *      x: M rows of K elements, x_rstride elements apart (a row of an NHWC blob of H*W*cstride elements IS such a row); w: the bank
+ *      [N][K], K contiguous, in the order of the elements of a row of x (zero columns where x holds pad channels); y / dY: M pixels of
+ *      y_cstride channels, the layer's N outputs at channel y_coffset (a member of a Concat over (N, C) blobs is written in place); bias may be NULL.
+ *      At these row counts the layer is a stream over the bank: every byte of w (and of dW) crosses the memory bus once per call for
+ *      every M, in 16-byte accesses; sums over lanes, over K slices (forward) and over slices of the rows of w (bwd_data) are combined
+ *      in a fixed order, without atomics: the same call gives the same bits.  Shapes that are split leave partial sums in d_workspace
+ *      (fcn_inner_product_workspace_bytes(M, K, N) bytes, valid for all four entry points and both element types; 0: none is needed and
+ *      d_workspace may be NULL) and run a second small launch; all launches are capturable.
+ *      Contract: null pointers (x, w, y, dy, dx, dw; the workspace where one is needed), non-positive extents, a row stride below K, a
+ *      slice outside its pixel, unknown flags FCN_E_ARG; pointers off 16 bytes, K or a stride that is not a multiple of 16 bytes (4 floats
+ *      / 8 halves) FCN_E_ALIGN; M > FCN_IP_MAX_ROWS (run the layer as a 1x1 convolution over M pixels: the bank is its OHWI bank), N * K
+ *      or a view past 2^31 elements FCN_E_UNSUPPORTED.  Every check precedes the first HIP call. ---- */
+#define FCN_IP_MAX_ROWS 32
+#define FCN_IP_WEIGHTS_NT 256   /* forward flag: the loads of w carry the non-temporal hint (a bank read once, from cold caches) */
+size_t fcn_inner_product_workspace_bytes(int M, int K, int N);
+/* what the forward of one element type alone needs (esize 4: float32, 2: half floats; anything else 0): an inference engine holds
+ * this per layer instead of the slabs of bwd_data, which are tens of megabytes for a large bank */
+size_t fcn_inner_product_fwd_workspace_bytes(int M, int K, int N, int esize);
+/* flags: FCN_CONV_RELU | FCN_IP_WEIGHTS_NT */
+int  fcn_inner_product_fwd_f32(const float* x, int x_rstride, const float* w, const float* bias, float* y, int y_cstride, int y_coffset,
+                               int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* x, w and y hold half floats, float32 accumulation and bias; flags: FCN_CONV_RELU | FCN_CONV_OUT_F32 (y is float32) | FCN_IP_WEIGHTS_NT */
+int  fcn_inner_product_fwd_f16(const void* x, int x_rstride, const void* w, const float* bias, void* y, int y_cstride, int y_coffset,
+                               int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* The two backward entry points are complete and guard-tested, but NO ENGINE CALLS THEM YET: the training planner has no
+ * InnerProduct entry (a training net with such a layer is refused by layer name).  Their signatures may still change with that
+ * emitter - it applies the layer's own ReLU mask to dY before these calls and may need a channel offset on dX.
+ * dX[m][k] (+)= sum_n dY[m][n] * w[n][k];  flags: FCN_CONV_ACCUM adds into dX (gradient fan-in) */
+int  fcn_inner_product_bwd_data_f32(const float* dy, int dy_cstride, int dy_coffset, const float* w, float* dx, int dx_rstride,
+                                    int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* dW[n][k] (+)= sum_m dY[m][n] * x[m][k];  db[n] (+)= sum_m dY[m][n] (db may be NULL);  accumulate 1 adds (iter_size) */
+int  fcn_inner_product_bwd_weights_f32(const float* x, int x_rstride, const float* dy, int dy_cstride, int dy_coffset,
+                                       float* dw, float* db, int M, int K, int N, int accumulate, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
