@@ -223,7 +223,7 @@ class BackwardPlanner:
             n_ = len(rec.descs)
             arr = (L.ConvDesc * n_)(*rec.descs)
             gws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(n_)), zero=False)
-            cfg = e._tuned_cfg("dgrad:" + rec.name, arr, n_, gws) if e.autotune else -1
+            cfg = e.tuner.conv_cfg("dgrad:" + rec.name, arr, n_, gws) if e.autotune else -1
             L.call("fcn_conv2d_group_prepare", arr, n_, gws.ptr, cfg, C.byref(rec.launch))
             e._keep.extend([arr, gws, rec.launch])
             e._group_workspaces.append(gws)
@@ -252,7 +252,7 @@ class BackwardPlanner:
     def wgrad_op(self, name: str, d: L.ConvDesc, dw: DevView, db: Optional[DevView], flops: float) -> None:
         """The weight (and bias) gradient of one problem: d.x the layer's input, d.y its dY."""
         e, lib = self.e, self.lib
-        sel = {"cfg": -1}      # -1: the library's heuristic; _tune_wgrads() replaces it once the workspace exists
+        sel = {"cfg": -1}      # -1: the library's heuristic; Tuner.wgrad_cfgs() replaces it once the workspace exists
         op = Op("wgrad", name, lambda st: L.check(lib.fcn_conv2d_wgrad_cfg_f32(
             C.byref(d), dw.ptr, db.ptr if db else None, e._ws.ptr, sel["cfg"], st)), flops)
         self._book_wgrad(op, sel, [name], [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), c, None)) for c in self._wgrad_cfgs()])

@@ -22,11 +22,13 @@ import ctypes as C
 import os
 import threading
 from collections import namedtuple
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import lib as L
+from . import tune as T
 from .netspec import Layer, NetSpec, as_nchw, crop_window, kernel_stride_pad
 
 F32 = np.float32
@@ -229,13 +231,64 @@ class Op:
         self.bytes = bytes_
 
 
+Range = Tuple[int, int, int]      # (buffer address, first channel, one past the last channel) of a blob view
+
+
+@dataclass(eq=False)
+class ConvTask:
+    """A convolution of the forward plan: a descriptor for the grouped launch of its level."""
+    layer: Layer
+    desc: L.ConvDesc
+    flops: float
+    bytes: float
+    reads: List[Range]
+    writes: List[Range]
+
+
+@dataclass(eq=False)
+class OpTask:
+    """Any other layer (or fused run of layers) that launches something: its ops; pool_desc if it is a MAX pooling that can
+    ride in a convolution launch."""
+    layer: Layer
+    ops: List[Op]
+    reads: List[Range]
+    writes: List[Range]
+    pool_desc: Optional[L.PoolDesc] = None
+
+
+Task = Union[ConvTask, OpTask]
+
+
+def ranges_hit(a: Sequence[Range], b: Sequence[Range]) -> bool:
+    return any(x[0] == y[0] and x[1] < y[2] and y[1] < x[2] for x in a for y in b)
+
+
+def task_waits(later: Task, earlier: Task) -> bool:
+    """`later` reads what `earlier` writes, or overwrites what it writes or reads."""
+    return ranges_hit(later.reads, earlier.writes) or ranges_hit(later.writes, earlier.writes) or ranges_hit(later.writes, earlier.reads)
+
+
+def task_levels(tasks: Sequence[Task], group_convs: bool = True) -> List[int]:
+    """Dependency level of every task (layer order in, so a task waits only for earlier ones): tasks on one level are mutually
+    independent.  group_convs False: strict layer order, one level per task."""
+    levels: List[int] = []
+    for i, ti in enumerate(tasks):
+        levels.append(max([levels[j] + 1 for j in range(i) if task_waits(ti, tasks[j])], default=0) if group_convs else i)
+    return levels
+
+
+def task_floats(tasks: Sequence[Task], levels: Sequence[int], i: int) -> bool:
+    """Nothing of the next level waits for task i: it may run on that level as well."""
+    return not any(levels[j] == levels[i] + 1 and task_waits(tj, tasks[i]) for j, tj in enumerate(tasks) if j != i)
+
+
 class Engine:
     """Executes a NetSpec on one GPU through libfcnhip.so."""
 
     def __init__(self, spec: NetSpec, data_shapes: Optional[Dict[str, Tuple[int, ...]]] = None,
                  params: Optional[Dict[str, List[np.ndarray]]] = None, device: int = 0,
                  fuse: bool = True, group_convs: bool = True, autotune: bool = True, dtype: str = "f32",
-                 tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None, tune_streams: Optional[int] = None,
+                 tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None,
                  share_params: Optional["Engine"] = None, score_outputs: bool = False):
         """share_params: Net::ShareTrainedLayersWith - every parameter layer whose name the given engine also has reads that
         engine's flat parameter buffer in place (no copy; a solver step is visible to the next forward of this engine).
@@ -258,12 +311,6 @@ class Engine:
         self.fuse = fuse
         self.group_convs = group_convs
         self.autotune = autotune
-        self._chosen_cfgs: Dict[str, int] = {}          # grouped launch -> tile configuration the autotuner picked
-        self._tune_from = tune_from                     # a replica of the same net: reuse its plan instead of timing again
-        # autotuner: only tile configurations whose workgroup holds at most this much LDS (engines that share the GPU with
-        # other streams: small footprints let workgroups of concurrent launches fit on a CU side by side)
-        self._tune_max_lds = int(tune_max_lds_kb if tune_max_lds_kb is not None else os.environ.get("FCN_TUNE_MAX_LDS_KB", "160")) * 1024
-        self._tune_streams = int(tune_streams if tune_streams is not None else os.environ.get("FCN_TUNE_STREAMS", "1"))      # > 1: throughput timing
         L.call("fcn_init", device)
         sp = C.c_void_p()
         L.call("fcn_stream_create", C.byref(sp))
@@ -288,10 +335,21 @@ class Engine:
         self.dropout_index_offset = 0           # data-parallel rank r: r * (elements of the dropout blob)
         self.inputs = spec.data_tops()
         self.outputs = [b for b in spec.output_blobs() if b in self.shapes]
+        # autotuner: only tile configurations whose workgroup holds at most this much LDS (engines that share the GPU with
+        # other streams: small footprints let workgroups of concurrent launches fit on a CU side by side)
+        max_lds = int(tune_max_lds_kb if tune_max_lds_kb is not None else os.environ.get("FCN_TUNE_MAX_LDS_KB", "160")) * 1024
+        # tune_from: a replica of the same net, whose plan is reused instead of timing again
+        self.tuner = T.Tuner(self.stream, T.key_suffix(self.shapes.get(self.inputs[0], ()) if self.inputs else None, self.f16, max_lds),
+                             spec.phase == "TEST", max_lds, tune_from._chosen_cfgs if tune_from is not None else None)
         self._plan_buffers()
         self._alloc_params(params)
         self._build_ops()
-        self._release_tuning_resources()
+        self.tuner.release()      # (a TrainEngine tunes its backward plan after this, and releases again)
+
+    @property
+    def _chosen_cfgs(self) -> Dict[str, object]:
+        """What the autotuner decided: cache key -> tile configuration, or the code of a cut / a move."""
+        return self.tuner.chosen
 
     # ------------------------------------------------------------------ buffers
     def _plan_buffers(self) -> None:
@@ -668,12 +726,12 @@ class Engine:
             return False, cons[0].tops[0]
         return False, None
 
-    def _collect_tasks(self) -> List[dict]:
+    def _collect_tasks(self) -> List[Task]:
         """Layer list -> tasks with read/write sets: one per convolution (a descriptor for the grouped launches) and one per
         other layer that launches anything (its ops)."""
         spec = self.spec
         skip: set = set()
-        tasks: List[dict] = []
+        tasks: List[Task] = []
         for li, l in enumerate(spec.layers):
             if l.name in skip:
                 continue
@@ -684,18 +742,16 @@ class Engine:
                 top = l.tops[0]
                 fused_relu, sig_top = self._fused_after(li, l, skip)
                 g = self._geom(l)
-                tasks.append(dict(kind="conv", layer=l, desc=self._conv_desc(l, fused_relu, sig_top),
-                                  flops=g.flops,
-                                  bytes=4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout),
-                                  reads=[self._range(l.bottoms[0])],
-                                  writes=[self._range(top)] + ([self._range(sig_top)] if sig_top else [])))
+                tasks.append(ConvTask(l, self._conv_desc(l, fused_relu, sig_top), g.flops,
+                                      4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout),
+                                      reads=[self._range(l.bottoms[0])],
+                                      writes=[self._range(top)] + ([self._range(sig_top)] if sig_top else [])))
                 self._conv_layer_meta[l.name] = dict(relu=fused_relu, sigmoid_top=sig_top)
                 continue
             if t == "InnerProduct":
                 relu = self._relu_after(li, l, skip)
                 self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
-                tasks.append(dict(kind="op", layer=l, ops=self._fwd_inner_product(l, relu), reads=[self._range(l.bottoms[0])],
-                                  writes=[self._range(l.tops[0])], pool_desc=None))
+                tasks.append(OpTask(l, self._fwd_inner_product(l, relu), reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])]))
                 continue
             if t == "Concat" and l.name not in self.copy_concats:
                 continue      # producers already wrote their slices
@@ -707,8 +763,8 @@ class Engine:
                 continue      # folded into the consumer convolutions' loaders
             ops = self._emit_simple(l)
             read = l.bottoms[:1] if t == "Crop" else l.bottoms      # a Crop's second bottom is a shape, not data
-            tasks.append(dict(kind="op", layer=l, ops=ops, reads=[self._range(b) for b in read],
-                              writes=[self._range(tp) for tp in l.tops], pool_desc=self._fusable_pool_desc(l)))
+            tasks.append(OpTask(l, ops, reads=[self._range(b) for b in read], writes=[self._range(tp) for tp in l.tops],
+                                pool_desc=self._fusable_pool_desc(l)))
         return tasks
 
     def _build_ops(self) -> None:
@@ -719,26 +775,13 @@ class Engine:
         tasks = self._collect_tasks()
         if self.fuse and self.spec.phase == "TEST" and os.environ.get("FCN_FUSE_POOL_LRN", "1") != "0":
             tasks = self._fuse_pool_lrn(tasks)
-
-        def hit(a, b) -> bool:
-            return any(x[0] == y[0] and x[1] < y[2] and y[1] < x[2] for x in a for y in b)
-
-        levels: List[int] = []
-        for i, ti in enumerate(tasks):
-            lv = 0
-            if self.group_convs:
-                for j in range(i):
-                    tj = tasks[j]
-                    if hit(ti["reads"], tj["writes"]) or hit(ti["writes"], tj["writes"]) or hit(ti["writes"], tj["reads"]):
-                        lv = max(lv, levels[j] + 1)
-            else:
-                lv = i            # strict layer order, one launch per layer
-            levels.append(lv)
-        self._move_floaters(tasks, levels, hit)
-        tail = self._plan_tail(tasks, levels, hit)
-        order = sorted(range(len(tasks)), key=lambda i: (levels[i], 0 if tasks[i]["kind"] == "op" else 1, i))
-        pending: List[dict] = []
-        pending_pools: List[dict] = []
+        levels = task_levels(tasks, self.group_convs)
+        if self.autotune and self.group_convs and self.fuse and not self.f16 and self.spec.phase == "TEST" and os.environ.get("FCN_LEVEL_MOVE", "1") != "0":
+            self.tuner.move_floaters(tasks, levels)
+        tail = self._plan_tail(tasks, levels)
+        order = sorted(range(len(tasks)), key=lambda i: (levels[i], 1 if isinstance(tasks[i], ConvTask) else 0, i))
+        pending: List[ConvTask] = []
+        pending_pools: List[OpTask] = []
         cur = None
         for i in order:
             if levels[i] != cur:
@@ -746,28 +789,28 @@ class Engine:
                 pending, cur = [], levels[i]
             if tail is not None and any(tasks[i] is ht for ht in tail["heads"]):
                 continue      # evaluated by the launches that produce its input
-            if tasks[i]["kind"] == "conv":
+            if isinstance(tasks[i], ConvTask):
                 pending.append(tasks[i])
-            elif tasks[i].get("pool_desc") is not None and self.fuse and self.group_convs:
+            elif tasks[i].pool_desc is not None and self.fuse and self.group_convs:
                 pending_pools.append(tasks[i])
             else:
-                self.ops.extend(tasks[i]["ops"])
+                self.ops.extend(tasks[i].ops)
         self._emit_convs(pending, pending_pools, tail)
         self.levels = max(levels) + 1 if levels else 0
         if self.score_outputs:
             self._emit_score_ops()
 
-    def _emit_group(self, chunk: List[dict], fused: List[dict], tail: Optional[dict]) -> None:
+    def _emit_group(self, chunk: List[ConvTask], fused: List[OpTask], tail: Optional[dict]) -> None:
         """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""
         lib = L.load()
-        name = "+".join(it["layer"].name for it in chunk)
-        flops = sum(it["flops"] for it in chunk)
-        byts = sum(it["bytes"] for it in chunk)
-        arr = (L.ConvDesc * len(chunk))(*[it["desc"] for it in chunk])
+        name = "+".join(it.layer.name for it in chunk)
+        flops = sum(it.flops for it in chunk)
+        byts = sum(it.bytes for it in chunk)
+        arr = (L.ConvDesc * len(chunk))(*[it.desc for it in chunk])
         ws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(len(chunk))), zero=False)
         self._group_workspaces.append(ws)
         grp = L.ConvGroup()
-        parr = (L.PoolDesc * max(len(fused), 1))(*[pt["pool_desc"] for pt in fused])
+        parr = (L.PoolDesc * max(len(fused), 1))(*[pt.pool_desc for pt in fused])
         tune_key = name + ("{+%d pool}" % len(fused) if fused else "")
         tailed = tail is not None and any(id(it) in tail["producers"] for it in chunk)
         if tailed:      # this launch writes (part of) the blob the narrow heads read: it carries them as its tail
@@ -776,21 +819,21 @@ class Engine:
             L.call("fcn_conv2d_group_attach_tail", ws.ptr, C.byref(tail["desc"]))
             tune_key += "{+tail%d}" % fin
             if fin:
-                flops += sum(ht["flops"] for ht in tail["heads"])
-                byts += sum(4.0 * ht["desc"].Cout * (ht["desc"].N * ht["desc"].OH * ht["desc"].OW + ht["desc"].Cin) for ht in tail["heads"])
-        cfg = self._tuned_cfg(tune_key, arr, len(chunk), ws, parr, len(fused)) if self.autotune else -1
+                flops += sum(ht.flops for ht in tail["heads"])
+                byts += sum(4.0 * ht.desc.Cout * (ht.desc.N * ht.desc.OH * ht.desc.OW + ht.desc.Cin) for ht in tail["heads"])
+        cfg = self.tuner.conv_cfg(tune_key, arr, len(chunk), ws, parr, len(fused)) if self.autotune else -1
         L.call("fcn_conv2d_group_prepare_fused", arr, len(chunk), parr, len(fused), ws.ptr, cfg, C.byref(grp))
         self._keep.extend([arr, parr, ws, grp])
         kind = "conv_group" if len(chunk) > 1 else "conv"
         label = "%s [cfg%d %dwg]" % (name, grp.cfg, grp.total_tiles)
         if fused:
-            label = "%s {+%s}" % (label, "+".join(pt["layer"].name for pt in fused))
-            byts += sum(pt["ops"][0].bytes for pt in fused)
+            label = "%s {+%s}" % (label, "+".join(pt.layer.name for pt in fused))
+            byts += sum(pt.ops[0].bytes for pt in fused)
         if tailed:
-            label = "%s {%s %s}" % (label, "tail:" if tail["desc"].finalize else "partial sums of", "+".join(ht["layer"].name for ht in tail["heads"]))
+            label = "%s {%s %s}" % (label, "tail:" if tail["desc"].finalize else "partial sums of", "+".join(ht.layer.name for ht in tail["heads"]))
         self.ops.append(Op(kind, label, lambda st, g=grp: L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(g), st)), flops, byts))
 
-    def _emit_convs(self, items: List[dict], pools: List[dict], tail: Optional[dict]) -> None:
+    def _emit_convs(self, items: List[ConvTask], pools: List[OpTask], tail: Optional[dict]) -> None:
         """One grouped launch per 16 convolutions of a level; the level's fusable MAX poolings ride in the first one.  Half-float
         engines may cut a level in two launches - its 3x3 / 5x5 convolutions and its 1x1 convolutions - when the autotuner
         finds the pair faster (the streaming kernel's configurations are shaped for one kind or the other)."""
@@ -799,14 +842,14 @@ class Engine:
             fused = pools[:2] if base == 0 and len(chunk) <= 8 else []
             parts = [chunk]
             if self.f16 and self.autotune and not fused and len(chunk) > 1:
-                parts = self._split_level(chunk)
+                parts = self.tuner.split_level(chunk)
             for part in parts:
                 self._emit_group(part, fused, tail)
                 fused = []
             if base == 0 and len(chunk) <= 8:
                 del pools[:2]
         for pt in pools:            # no convolution launch at this level to ride in
-            self.ops.extend(pt["ops"])
+            self.ops.extend(pt.ops)
         pools.clear()
 
     def _emit_score_ops(self) -> None:
@@ -827,7 +870,7 @@ class Engine:
                 args = (acc.ptr, b.ptr, 1, 1, count, count, 0)
             self.ops.append(Op("score", "score:" + nm, lambda st, a=args: L.check(lib.fcn_score_accumulate_f32(*a, st)), 0.0, 12.0 * count))
 
-    def _plan_tail(self, tasks: List[dict], levels: List[int], hit) -> Optional[dict]:
+    def _plan_tail(self, tasks: List[Task], levels: List[int]) -> Optional[dict]:
         """The detection heads (cvg/classifier + bbox/regressor of models/deploy.prototxt: 4 + 16 outputs over inception_5b/output) as the
         TAIL of the launches that produce their input (fcn_conv2d_group_attach_tail, csrc/conv_common.h): as a launch of their own they are
         0.03 GFLOP behind a whole launch's fixed cost (6 us of a 266 us frame).  Taken when the net's LAST convolution level holds only
@@ -835,32 +878,34 @@ class Engine:
         before, in whole 32-channel groups.  Returns None (heads launched as before) or the plan emit_group() works from."""
         if self.f16 or self.spec.phase != "TEST" or not (self.fuse and self.group_convs) or os.environ.get("FCN_CONV_TAIL", "0") != "1":
             return None
-        conv_idx = [i for i, t in enumerate(tasks) if t["kind"] == "conv"]
+        conv_idx = [i for i, t in enumerate(tasks) if isinstance(t, ConvTask)]
         if not conv_idx:
             return None
         lh = max(levels[i] for i in conv_idx)
         heads = [i for i in conv_idx if levels[i] == lh]
-        if any(levels[i] >= lh for i, t in enumerate(tasks) if t["kind"] != "conv") or not 1 <= len(heads) <= 4:
+        if any(levels[i] >= lh for i, t in enumerate(tasks) if not isinstance(t, ConvTask)) or not 1 <= len(heads) <= 4:
             return None
-        d0 = tasks[heads[0]]["desc"]
+        d0 = tasks[heads[0]].desc
         m = d0.N * d0.OH * d0.OW
         rows = 0
         for i in heads:
-            d = tasks[i]["desc"]
+            d = tasks[i].desc
             if (d.kh, d.kw, d.stride, d.pad) != (1, 1, 1, 0) or d.x != d0.x or d.x_cstride != d0.x_cstride or d.Cin != d0.Cin or d.Cin % 32 or d.Cin > 1024 or d.Cout % 4 \
                     or (d.flags & ~(L.CONV_RELU | L.CONV_SIGMOID2)) or d.y_cstride % 4 or d.y_coffset % 4 or (d.y2 and (d.y2_cstride % 4 or d.y2_coffset % 4)):
                 return None
             rows += d.Cout
         if rows > 24 or m > 4096:      # (scratch: K / 32 x M x rows floats)
             return None
-        xr = tasks[heads[0]]["reads"]
+        xr = tasks[heads[0]].reads
         producers: Dict[int, int] = {}
         covered = 0
         for i, t in enumerate(tasks):
-            if i in heads or not hit(t["writes"], xr):
+            if i in heads or not ranges_hit(t.writes, xr):
                 continue
-            d = t.get("desc")
-            if t["kind"] != "conv" or levels[i] not in (lh - 1, lh - 2) or d.y != d0.x or d.y_cstride != d0.x_cstride or d.N * d.OH * d.OW != m \
+            if not isinstance(t, ConvTask):
+                return None
+            d = t.desc
+            if levels[i] not in (lh - 1, lh - 2) or d.y != d0.x or d.y_cstride != d0.x_cstride or d.N * d.OH * d.OW != m \
                     or d.Cout % 32 or d.y_coffset % 32 or d.y_coffset + d.Cout > d0.Cin or (d.flags & ~L.CONV_RELU) or d.y_cstride % 4:
                 return None
             producers[id(t)] = levels[i]
@@ -875,7 +920,7 @@ class Engine:
         desc = L.ConvTail()
         desc.n = len(heads)
         for j, i in enumerate(heads):
-            desc.heads[j] = tasks[i]["desc"]
+            desc.heads[j] = tasks[i].desc
         sb, ab = int(lib.fcn_conv2d_tail_scratch_bytes(C.byref(desc))), int(lib.fcn_conv2d_tail_arrive_bytes(C.byref(desc)))
         if sb <= 0 or ab <= 0:
             return None
@@ -884,45 +929,45 @@ class Engine:
         self._keep.extend([scratch, arrive, desc])
         return dict(desc=desc, heads=[tasks[i] for i in heads], producers=producers, final_level=max(producers.values()))
 
-    def _fuse_pool_lrn(self, tasks: List[dict]) -> List[dict]:
+    def _fuse_pool_lrn(self, tasks: List[Task]) -> List[Task]:
         """MAX pooling directly followed by LRN (pool1 -> norm1) or LRN directly followed by MAX pooling (norm2 -> pool2)
         become ONE launch that never writes the blob between them (inference engines; fcn_maxpool_lrn5_fwd_f32).  The
         blob in the middle stays readable: read_blob() runs the first layer on its own when somebody asks for it."""
         B, lib = self.blobs, L.load()
-        out: List[dict] = []
+        out: List[Task] = []
         i = 0
         while i < len(tasks):
             a = tasks[i]
             b = tasks[i + 1] if i + 1 < len(tasks) else None
             op = None
-            if b is not None and a["kind"] == "op" and b["kind"] == "op":
-                la, lb = a["layer"], b["layer"]
+            if isinstance(a, OpTask) and isinstance(b, OpTask):
+                la, lb = a.layer, b.layer
                 if {la.type, lb.type} == {"Pooling", "LRN"} and len(la.tops) == 1 and lb.bottoms == [la.tops[0]] and la.tops[0] != la.bottoms[0]:
                     op = self._pool_lrn_op(la, lb)
             if op is None:
                 out.append(a)
                 i += 1
                 continue
-            self._lazy_blob_ops[a["layer"].tops[0]] = list(a["ops"])
+            self._lazy_blob_ops[a.layer.tops[0]] = list(a.ops)
             c = tasks[i + 2] if i + 2 < len(tasks) else None
-            op3 = self._pool_lrn_conv_op(a["layer"], b["layer"], c) if c is not None and c["kind"] == "conv" else None
+            op3 = self._pool_lrn_conv_op(a.layer, b.layer, c) if isinstance(c, ConvTask) else None
             if op3 is not None:      # ... -> 1x1 convolution in the same launch: the normalised blob is not written either
-                self._lazy_blob_ops[b["layer"].tops[0]] = [op]
-                out.append(dict(kind="op", layer=c["layer"], ops=[op3], reads=a["reads"], writes=c["writes"], pool_desc=None))
+                self._lazy_blob_ops[b.layer.tops[0]] = [op]
+                out.append(OpTask(c.layer, [op3], reads=a.reads, writes=c.writes))
                 i += 3
                 continue
-            out.append(dict(kind="op", layer=b["layer"], ops=[op], reads=a["reads"], writes=b["writes"], pool_desc=None))
+            out.append(OpTask(b.layer, [op], reads=a.reads, writes=b.writes))
             i += 2
         return out
 
-    def _pool_lrn_conv_op(self, la: Layer, lb: Layer, ct: dict) -> Optional[Op]:
+    def _pool_lrn_conv_op(self, la: Layer, lb: Layer, ct: ConvTask) -> Optional[Op]:
         """MAX pooling -> LRN -> 1x1 convolution (+ in-place ReLU) as one launch (fcn_maxpool_lrn5_conv1x1_fwd_f32: deploy.prototxt's
         pool1/3x3_s2 -> pool1/norm1 -> conv2/3x3_reduce): as a launch of its own that convolution is two chunks of K behind a whole
         launch's fixed cost.  The FLOPs of the convolution are booked on this op (kind "pool_lrn_conv")."""
         if os.environ.get("FCN_FUSE_POOL_LRN_CONV", "1") == "0" or la.type != "Pooling":
             return None
         B, lib = self.blobs, L.load()
-        lc, d = ct["layer"], ct["desc"]
+        lc, d = ct.layer, ct.desc
         mid = lb.tops[0]
         if lc.bottoms != [mid] or [q.name for q in self.consumers.get(mid, [])] != [lc.name] or len(self.producers.get(mid, [])) != 1 \
                 or mid in self.outputs or mid in self.alias:
@@ -947,7 +992,7 @@ class Engine:
         fn = lib.fcn_maxpool_lrn5_conv1x1_fwd_f16 if esz == 2 else lib.fcn_maxpool_lrn5_conv1x1_fwd_f32
         return Op("pool_lrn_conv", "%s+%s+%s" % (la.name, lb.name, lc.name), lambda st: L.check(fn(
             xb.ptr, n, h, w, c, xb.cstride, k, s, pad, oh, ow, al, be, kk, d.w, d.bias, d.Cout, relu, d.y, d.y_cstride, d.y_coffset, st)),
-            ct["flops"], float(esz) * (xb.pixels * c + n * oh * ow * d.Cout))
+            ct.flops, float(esz) * (xb.pixels * c + n * oh * ow * d.Cout))
 
     def _pool_lrn_op(self, la: Layer, lb: Layer) -> Optional[Op]:
         B, lib = self.blobs, L.load()
@@ -1018,341 +1063,6 @@ class Engine:
         d.OH, d.OW, d.y_cstride, d.y_coffset = oh, ow, yb.cstride, yb.coffset
         d.f16 = 1 if xb.esize == 2 else 0
         return d
-
-    def _load_tune_cache(self) -> Optional[dict]:
-        import json
-        path = os.environ.get("FCN_TUNE_CACHE")
-        if path and not hasattr(self, "_tune_cache"):
-            try:
-                with open(path) as f:
-                    self._tune_cache = json.load(f)
-            except (OSError, ValueError):
-                self._tune_cache = {}
-        return getattr(self, "_tune_cache", None)
-
-    def _save_tune_cache(self) -> None:
-        import json
-        path = os.environ.get("FCN_TUNE_CACHE")
-        if path and getattr(self, "_tune_cache", None) is not None:
-            try:
-                with open(path, "w") as f:
-                    json.dump(self._tune_cache, f, indent=0, sort_keys=True)
-            except OSError:
-                pass
-
-    def _tune_key(self, name: str) -> str:
-        key = "%s|%s" % (name, "x".join(str(d) for d in self.shapes.get(self.inputs[0], ())) if self.inputs else "")
-        if self.f16:
-            key += "|f16"
-        if self._tune_max_lds < 160 * 1024:
-            key += "|lds%d" % (self._tune_max_lds // 1024)
-        if self._tune_streams > 1:
-            key += "|x%d" % self._tune_streams
-        return key
-
-    def _tuned_cfg(self, name: str, arr, n: int, ws: DeviceBuffer, parr=None, npool: int = 0) -> int:
-        """Autotuned tile configuration of one grouped launch, remembered in $FCN_TUNE_CACHE (JSON) when that is set so
-        that a profiled run replays the plan of an earlier run without the tuning launches."""
-        cache = self._load_tune_cache()
-        key = self._tune_key(name)
-        ncfg = int(L.load().fcn_conv2d_num_configs())
-        if self._tune_from is not None and key in self._tune_from._chosen_cfgs:
-            self._chosen_cfgs[key] = self._tune_from._chosen_cfgs[key]
-            return self._chosen_cfgs[key]
-        if cache is not None and key in cache and 0 <= int(cache[key]) < ncfg:
-            self._chosen_cfgs[key] = int(cache[key])
-            return int(cache[key])
-        cfg = self._pick_conv_cfg(arr, n, ws, parr, npool)
-        self._chosen_cfgs[key] = cfg
-        if cache is not None:
-            cache[key] = cfg
-            self._save_tune_cache()
-        return cfg
-
-    def _pick_conv_cfg(self, arr, n: int, ws: DeviceBuffer, parr=None, npool: int = 0) -> int:
-        """Plan-time autotune of one grouped launch: time every tile configuration on the device, keep the fastest."""
-        return self._time_conv_cfgs(arr, n, ws, parr, npool)[0]
-
-    def _time_conv_cfgs(self, arr, n: int, ws: DeviceBuffer, parr=None, npool: int = 0) -> Tuple[int, float]:
-        """(fastest configuration, its milliseconds per launch) of one grouped launch."""
-        lib = L.load()
-        if not hasattr(self, "_tune_events"):
-            e0, e1 = C.c_void_p(), C.c_void_p()
-            L.call("fcn_event_create", C.byref(e0))
-            L.call("fcn_event_create", C.byref(e1))
-            self._tune_events = (e0, e1)
-        e0, e1 = self._tune_events
-        best, best_ms = -1, 1e30
-        timed: List[Tuple[float, int]] = []
-        grp = L.ConvGroup()
-        first_layer = int(lib.fcn_conv2d_first_layer_config())
-        # Cold timing (round 4, $FCN_TUNE_COLD=0 for the old way): inside a forward pass a launch finds its filters in HBM / the Infinity
-        # Cache, not in L2 - 24 MB of filters and ~250 MB of activations pass through the 4 MB L2s between two frames - but six
-        # repetitions of ONE launch back to back are warm from the second on, which favours the configurations that tolerate memory
-        # latency worst (rocprofv3's durations of whole forwards were 4-5 % longer than the back-to-back ones).  So every timed launch is
-        # preceded by a pass over a 64 MB scratch buffer that evicts the L2s; the event pair's own cost is the same for every
-        # configuration and leaves the ranking alone.
-        cold = self.spec.phase == "TEST" and os.environ.get("FCN_TUNE_COLD", "1") != "0"
-        # (tried, round 4: the plan's previous launch between the eviction and the timed launch, so that the inputs sit where a forward leaves
-        #  them - the chosen plans ran the frame in the same 0.2736 - 0.2743 ms)
-        if cold and not hasattr(self, "_tune_flush"):
-            self._tune_flush = DeviceBuffer(64 << 20, zero=False)
-        for cfg in range(int(lib.fcn_conv2d_num_configs())):
-            # (the LDS cap keeps the tiles of several frames in flight resident on one CU; the first-layer kernel puts one
-            #  workgroup per CU and frame and is exempt)
-            if int(lib.fcn_conv2d_config_lds_bytes(cfg)) > self._tune_max_lds and cfg != first_layer:
-                continue
-            if cfg == first_layer and os.environ.get("FCN_CONV_FIRST7", "1") == "0":
-                continue
-            if lib.fcn_conv2d_group_prepare_fused(arr, n, parr, npool, ws.ptr, cfg, C.byref(grp)) != 0:
-                continue      # a configuration that does not take this group (the first-layer kernel is shape-specific)
-            ms = C.c_float()
-            if self._tune_streams > 1:
-                # Throughput timing (engines that share the GPU with other frames, ForwardPipeline): the launch is issued on K streams
-                # at once, several times over - what is timed is how fast the chip gets through K concurrent copies, i.e. the
-                # configuration's cost in a saturated machine (its instructions per FLOP), not its latency on an empty one.  The
-                # copies write the same values into the same outputs.
-                if not hasattr(self, "_tune_side"):
-                    self._tune_side = []
-                    for _ in range(self._tune_streams - 1):
-                        sp = C.c_void_p()
-                        L.call("fcn_stream_create", C.byref(sp))
-                        self._tune_side.append(int(sp.value))
-                import time as _time
-                streams = [self.stream] + self._tune_side
-                for st in streams:
-                    L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), st))
-                L.call("fcn_device_sync")
-                t0 = _time.perf_counter()
-                for _ in range(8):
-                    for st in streams:
-                        L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), st))
-                L.call("fcn_device_sync")
-                t = (_time.perf_counter() - t0) * 1e3 * 6.0 / (8 * len(streams))
-            elif cold:
-                L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))      # (code object, kernel arguments)
-                samples = []
-                for _ in range(7):
-                    L.call("fcn_memset_async", self._tune_flush.ptr, 0, self._tune_flush.nbytes, self.stream)
-                    L.call("fcn_event_record", e0, self.stream)
-                    L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))
-                    L.call("fcn_event_record", e1, self.stream)
-                    L.call("fcn_event_sync", e1)
-                    L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                    samples.append(ms.value)
-                t = 6.0 * float(np.percentile(samples, 25))      # (disturbances only ever lengthen a launch: the lower quartile, not the median)
-            else:
-                for _ in range(2):
-                    L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))
-                L.call("fcn_event_record", e0, self.stream)
-                for _ in range(6):
-                    L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))
-                L.call("fcn_event_record", e1, self.stream)
-                L.call("fcn_event_sync", e1)
-                L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                t = ms.value
-            if t < best_ms:
-                best, best_ms = cfg, t
-            timed.append((t, cfg))
-        if not cold and self._tune_streams <= 1 and len(timed) > 1 and os.environ.get("FCN_TUNE_SECOND_LOOK", "1") != "0":
-            # (training engines and float16 plans - back-to-back timing: the same second look, five more rounds of six launches, the minimum)
-            finals = []
-            for t1, cfg in sorted(timed)[:3]:
-                if t1 > 1.04 * best_ms:
-                    break
-                if lib.fcn_conv2d_group_prepare_fused(arr, n, parr, npool, ws.ptr, cfg, C.byref(grp)) != 0:
-                    continue
-                ms = C.c_float()
-                rounds = [t1]
-                for _ in range(5):
-                    L.call("fcn_event_record", e0, self.stream)
-                    for _ in range(6):
-                        L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))
-                    L.call("fcn_event_record", e1, self.stream)
-                    L.call("fcn_event_sync", e1)
-                    L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                    rounds.append(ms.value)
-                finals.append((min(rounds), cfg))
-            if finals:
-                best_ms, best = min(finals)
-        if cold and len(timed) > 1:
-            # Second look at the closest contenders (round 4): the first pass's median of five separates configurations that differ by 2 % or
-            # more; two that differ by less are a coin toss there, and the plan of a 20-launch net then moves by half a per cent from run to run.
-            # The four fastest within 5 % are timed again, 31 cold launches each, and the smallest lower quartile wins.
-            finals = []
-            for t1, cfg in sorted(timed)[:4]:
-                if t1 > 1.05 * best_ms:
-                    break
-                if lib.fcn_conv2d_group_prepare_fused(arr, n, parr, npool, ws.ptr, cfg, C.byref(grp)) != 0:
-                    continue
-                samples = []
-                ms = C.c_float()
-                for _ in range(31):
-                    L.call("fcn_memset_async", self._tune_flush.ptr, 0, self._tune_flush.nbytes, self.stream)
-                    L.call("fcn_event_record", e0, self.stream)
-                    L.check(lib.fcn_conv2d_fwd_group_f32(C.byref(grp), self.stream))
-                    L.call("fcn_event_record", e1, self.stream)
-                    L.call("fcn_event_sync", e1)
-                    L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                    samples.append(ms.value)
-                finals.append((6.0 * float(np.percentile(samples, 25)), cfg))
-            if finals:
-                best_ms, best = min(finals)
-        return best, best_ms / 6.0
-
-    def _move_floaters(self, tasks: List[dict], levels: List[int], hit) -> None:
-        """Float engines: which LEVEL carries a convolution that nobody waits for?  An inception module is two levels -
-        {1x1, 3x3_reduce, 5x5_reduce} (+ the module's pooling) and {3x3, 5x5, pool_proj} - but the plain 1x1 branch is read by
-        nothing before the NEXT module: it may ride in either launch.  In the first it makes a latency-bound launch wider (at
-        28 x 28 the reduce level is one 32 x 32 tile per CU whichever way); in the second its short tiles fill the CUs beside the
-        long 3x3 tiles.  Every placement of a level's floaters is priced - both launches with their fastest configurations, timed
-        once - and the cheapest kept (round 4; the decision rides in the tune cache as a string of 0 / 1 per floater)."""
-        if not (self.autotune and self.group_convs and self.fuse) or self.f16 or self.spec.phase != "TEST" or os.environ.get("FCN_LEVEL_MOVE", "1") == "0":
-            return
-        lib = L.load()
-        nlev = max(levels) + 1 if levels else 0
-        for lv in range(nlev - 1):
-            a_idx = [i for i in range(len(tasks)) if levels[i] == lv and tasks[i]["kind"] == "conv"]
-            b_idx = [i for i in range(len(tasks)) if levels[i] == lv + 1 and tasks[i]["kind"] == "conv"]
-            if len(a_idx) < 2 or not b_idx or len(a_idx) > 8:
-                continue
-
-            def floats(i: int) -> bool:      # nothing of the next level reads or overwrites its output, or overwrites its input
-                ti = tasks[i]
-                return not any(levels[j] == lv + 1 and (hit(tj["reads"], ti["writes"]) or hit(tj["writes"], ti["writes"]) or hit(ti["reads"], tj["writes"]))
-                               for j, tj in enumerate(tasks) if j != i)
-
-            fl = [i for i in a_idx if floats(i)]
-            if not fl or len(fl) > 3 or len(b_idx) + len(fl) > 8:
-                continue
-            key = "move|" + self._tune_key("+".join(tasks[i]["layer"].name for i in a_idx) + ">" + "+".join(tasks[i]["layer"].name for i in b_idx))
-
-            def valid(code) -> bool:
-                return isinstance(code, str) and len(code) == len(fl) and set(code) <= {"0", "1"} and (len(fl) < len(a_idx) or "0" in code)
-
-            choice = None
-            if self._tune_from is not None and valid(self._tune_from._chosen_cfgs.get(key)):
-                choice = self._tune_from._chosen_cfgs[key]
-            else:
-                cache = self._load_tune_cache()
-                if cache is not None and valid(cache.get(key)):
-                    choice = cache[key]
-            if choice is None:
-                pools = {l2: [t["pool_desc"] for j, t in enumerate(tasks) if levels[j] == l2 and t["kind"] == "op" and t.get("pool_desc") is not None][:2]
-                         for l2 in (lv, lv + 1)}
-                memo: Dict[Tuple[int, Tuple[int, ...]], float] = {}
-
-                def cost(l2: int, sub: Tuple[int, ...]) -> float:
-                    if (l2, sub) not in memo:
-                        arr = (L.ConvDesc * len(sub))(*[tasks[i]["desc"] for i in sub])
-                        pl = pools[l2]
-                        parr = (L.PoolDesc * max(len(pl), 1))(*pl)
-                        ws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(len(sub))), zero=False)
-                        memo[(l2, sub)] = min(self._time_conv_cfgs(arr, len(sub), ws, parr, len(pl))[1] for _ in range(2))
-                        L.call("fcn_conv2d_group_release", ws.ptr)
-                        ws.free()
-                    return memo[(l2, sub)]
-
-                best, best_ms, base_ms = "0" * len(fl), None, None
-                for code in range(1 << len(fl)):
-                    moved = [fl[b] for b in range(len(fl)) if code >> b & 1]
-                    stay = tuple(i for i in a_idx if i not in moved)
-                    if not stay:
-                        continue
-                    ms = cost(lv, stay) + cost(lv + 1, tuple(b_idx + moved))
-                    if code == 0:
-                        base_ms = ms
-                    if best_ms is None or ms < best_ms:
-                        best, best_ms = "".join("1" if code >> b & 1 else "0" for b in range(len(fl))), ms
-                if base_ms is not None and best_ms > float(os.environ.get("FCN_MOVE_MARGIN", "0.99")) * base_ms:      # (timing noise: a move must be worth 1 % of the pair - 3 % until the tuner took a second look at close contenders)
-                    best = "0" * len(fl)
-                choice = best
-                cache = self._load_tune_cache()
-                if cache is not None:
-                    cache[key] = choice
-                    self._save_tune_cache()
-            self._chosen_cfgs[key] = choice
-            for b, i in enumerate(fl):
-                if choice[b] == "1":
-                    levels[i] = lv + 1
-
-    def _release_tuning_resources(self) -> None:
-        """Streams and scratch the autotuner made: an idle stream still holds a hardware queue (streams are dealt to the queues in creation
-        order), so they must be gone before the replicas of a pipeline create theirs."""
-        lib = L.load()
-        for st in getattr(self, "_tune_side", []):
-            lib.fcn_stream_sync(st)
-            lib.fcn_stream_destroy(st)
-        self._tune_side = []
-        if hasattr(self, "_tune_side"):
-            del self._tune_side
-        fl = getattr(self, "_tune_flush", None)
-        if fl is not None:
-            fl.free()
-            del self._tune_flush
-
-    def _split_level(self, chunk: List[dict]) -> List[List[dict]]:
-        """Half-float engines: which launches carry a level's convolutions?  The streaming kernel's configurations are shaped for one
-        kind of problem or another (filter sizes, channel counts), so for the two to four convolutions of an inception level every way
-        of cutting the level into launches is priced - each subset's fastest configuration is timed once - and the cheapest cut is
-        kept (round 3; rounds 2-3a knew two cuts: one launch, or 3x3 / 5x5 beside 1x1).  The decision rides in the tune cache beside the
-        configurations, as a string of group labels ("001": the third convolution has a launch of its own)."""
-        n = len(chunk)
-        if n < 2 or n > 4:
-            return [chunk]
-        lib = L.load()
-        key = "cut|" + self._tune_key("+".join(it["layer"].name for it in chunk))
-
-        def valid(code) -> bool:
-            return isinstance(code, str) and len(code) == n and all(ch.isdigit() and int(ch) < n for ch in code)
-
-        choice = None
-        if self._tune_from is not None and valid(self._tune_from._chosen_cfgs.get(key)):
-            choice = self._tune_from._chosen_cfgs[key]
-        else:
-            cache = self._load_tune_cache()
-            if cache is not None and valid(cache.get(key)):
-                choice = cache[key]
-        if choice is None:
-            memo: Dict[Tuple[int, ...], float] = {}
-
-            def cost(sub: Tuple[int, ...]) -> float:
-                if sub not in memo:
-                    part = [chunk[i] for i in sub]
-                    arr = (L.ConvDesc * len(part))(*[it["desc"] for it in part])
-                    ws = DeviceBuffer(int(lib.fcn_conv2d_group_workspace_bytes(len(part))), zero=False)
-                    memo[sub] = self._time_conv_cfgs(arr, len(part), ws)[1]
-                    L.call("fcn_conv2d_group_release", ws.ptr)
-                    ws.free()
-                return memo[sub]
-
-            def partitions(items: List[int]):      # set partitions as restricted-growth strings
-                def rec(i: int, labels: List[int], groups: int):
-                    if i == len(items):
-                        yield list(labels)
-                        return
-                    for g in range(groups + 1):
-                        labels.append(g)
-                        yield from rec(i + 1, labels, max(groups, g + 1))
-                        labels.pop()
-                yield from rec(0, [], 0)
-
-            best, best_ms = None, 1e30
-            for labels in partitions(list(range(n))):
-                groups = sorted(set(labels))
-                ms = sum(cost(tuple(i for i in range(n) if labels[i] == g)) for g in groups)
-                if ms < best_ms - 1e-7:
-                    best, best_ms = labels, ms
-            choice = "".join(str(g) for g in best)
-            cache = self._load_tune_cache()
-            if cache is not None:
-                cache[key] = choice
-                self._save_tune_cache()
-        self._chosen_cfgs[key] = choice
-        groups: Dict[str, List[dict]] = {}
-        for it, g in zip(chunk, choice):
-            groups.setdefault(g, []).append(it)
-        return [groups[g] for g in sorted(groups)]
 
     def _loss_grad_ptr(self, blob: str) -> Optional[int]:
         """Device address the loss kernel writes d(loss)/d(blob) to; None in an inference engine."""
@@ -2082,6 +1792,7 @@ class Engine:
                     ws.free()
             self._group_workspaces = []
             self.ops = []
+            self.tuner.release()
 
     def __del__(self):
         try:

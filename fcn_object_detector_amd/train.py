@@ -248,76 +248,9 @@ class TrainEngine(Engine):
         self.bwd_ops, self._ws = plan.ops, plan.ws
         self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
-            self._tune_wgrads()
+            self.tuner.wgrad_cfgs(self.bwd_ops)
+        self.tuner.release()
         self._plan_buckets()
-
-    def _tune_wgrads(self) -> None:
-        """Plan-time choice of every weight-gradient launch's configuration (the 64-wide tile shapes and the role-split kernel of
-        csrc/train.hip): each is timed on the buffers the step will use, the fastest is kept - and remembered in $FCN_TUNE_CACHE
-        beside the forward plan.  Gradient buffers hold garbage until the first real backward pass, which overwrites them."""
-        lib = L.load()
-        ncfg = int(lib.fcn_conv2d_wgrad_num_configs())
-        cache = self._load_tune_cache()
-        e0, e1 = C.c_void_p(), C.c_void_p()
-        L.call("fcn_event_create", C.byref(e0))
-        L.call("fcn_event_create", C.byref(e1))
-        dirty = False
-        for op in self.bwd_ops:
-            if op.kind != "wgrad":
-                continue
-            key = self._tune_key("wgrad:" + "+".join(op.layers))
-            if self._tune_from is not None and key in self._tune_from._chosen_cfgs:
-                op.sel["cfg"] = self._chosen_cfgs[key] = self._tune_from._chosen_cfgs[key]
-                continue
-            if cache is not None and key in cache and 0 <= int(cache[key]) < ncfg:
-                op.sel["cfg"] = self._chosen_cfgs[key] = int(cache[key])
-                continue
-            best, best_ms = -1, 1e30
-            timed = []
-            for cfg in range(ncfg):
-                op.sel["cfg"] = cfg
-                for _ in range(2):
-                    op.run(self.stream)
-                L.call("fcn_event_record", e0, self.stream)
-                for _ in range(5):
-                    op.run(self.stream)
-                L.call("fcn_event_record", e1, self.stream)
-                L.call("fcn_event_sync", e1)
-                ms = C.c_float()
-                L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                if ms.value < best_ms:
-                    best, best_ms = cfg, ms.value
-                timed.append((ms.value, cfg))
-            # a second look at the contenders within 4 % (as Engine._time_conv_cfgs): four more rounds of five launches each, the minimum counts
-            finals = []
-            for t1, cfg in sorted(timed)[:3]:
-                if t1 > 1.04 * best_ms or len(timed) < 2:
-                    break
-                op.sel["cfg"] = cfg
-                rounds = [t1]
-                for _ in range(4):
-                    L.call("fcn_event_record", e0, self.stream)
-                    for _ in range(5):
-                        op.run(self.stream)
-                    L.call("fcn_event_record", e1, self.stream)
-                    L.call("fcn_event_sync", e1)
-                    ms = C.c_float()
-                    L.call("fcn_event_elapsed_ms", e0, e1, C.byref(ms))
-                    rounds.append(ms.value)
-                finals.append((min(rounds), cfg))
-            if finals:
-                best = min(finals)[1]
-            op.sel["cfg"] = self._chosen_cfgs[key] = best
-            if cache is not None:
-                cache[key] = best
-                dirty = True
-        if dirty:
-            self._save_tune_cache()
-        for op in self.bwd_ops:
-            if op.kind == "wgrad":
-                op.name += " [cfg%d]" % op.sel["cfg"]
-        L.call("fcn_event_destroy", e0)
-        L.call("fcn_event_destroy", e1)
 
     def _plan_buckets(self, bucket_floats: int = 1536 * 1024) -> None:
         """Gradient buckets for the overlapped all-reduce: contiguous ranges of the flat gradient buffer (forward layer
