@@ -12,6 +12,7 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
+from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, tconv_desc
 from .netspec import DATA_TYPES, Layer, crop_window
 
@@ -436,7 +437,7 @@ class BackwardPlanner:
             self.mark(gb)
 
     def _deconvolution(self, l: Layer) -> None:
-        if not self.e._deconv_dense(l):
+        if self.e.param_segs[(l.name, 0)].kind != S.DECONV:
             return self._one_bottom(l)
         gtop = self._arrived(l)
         if gtop is not None:

@@ -295,7 +295,7 @@ class FCNObjectDetector:
         whose channels 3 and 4 are the constant 1): the kernel then writes whole pixels in one store."""
         if data.esize != 2:
             return 0
-        return 3 if data.name in getattr(self.engine, "_half_inputs", {}) and data.cstride == 8 and data.coffset == 0 else 1
+        return 3 if data.name in self.engine._half_inputs and data.cstride == 8 and data.coffset == 0 else 1
 
     def run_detector_batch(self, frames: Sequence[np.ndarray]) -> List[Tuple[np.ndarray, np.ndarray]]:
         """BASELINE configs[4] minus the fp16 arithmetic: `batch` frames through pre-processing, ONE forward and ONE fused

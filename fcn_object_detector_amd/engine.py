@@ -28,20 +28,12 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import lib as L
+from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, as_nchw, crop_window, kernel_stride_pad
+from .netspec import Layer, NetSpec, crop_window, kernel_stride_pad
+from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
-
-
-def _r4(c: int) -> int:
-    return (c + 3) // 4 * 4
-
-
-def _ra(c: int, esize: int) -> int:
-    """Channel count rounded up to whole 16-byte segments of `esize`-byte elements (4 floats / 8 halves)."""
-    eps = 16 // esize
-    return (c + eps - 1) // eps * eps
 
 
 def graphs_enabled() -> bool:
@@ -95,21 +87,6 @@ def tconv_desc(a: "Blob", b: "Blob", g: ConvGeom, bank: int, bias: Optional[int]
     d.b_cstride, d.b_coffset = b.cstride, b.coffset
     d.flags = flags
     return d
-
-
-def ip_pack_bank(w: np.ndarray, c: int, h: int, wd: int, cstride: int, dtype=F32) -> np.ndarray:
-    """Caffe's (num_output, C*H*W) InnerProduct bank -> (num_output, H*W*cstride) in the memory order of a row of the NHWC bottom:
-    column p * cstride + ch holds Caffe's column ch * H*W + p, the pad channels' columns are zero."""
-    n = w.shape[0]
-    out = np.zeros((n, h * wd, cstride), dtype)
-    out[:, :, :c] = w.reshape(n, c, h * wd).transpose(0, 2, 1)
-    return out.reshape(n, h * wd * cstride)
-
-
-def ip_unpack_bank(packed: np.ndarray, c: int, h: int, wd: int, cstride: int) -> np.ndarray:
-    """The inverse of ip_pack_bank, as float32: what read_param and snapshots return."""
-    n = packed.shape[0]
-    return np.ascontiguousarray(packed.reshape(n, h * wd, cstride)[:, :, :c].transpose(0, 2, 1), dtype=F32).reshape(n, c * h * wd)
 
 
 class DeviceBuffer:
@@ -194,12 +171,8 @@ class Blob:
 
     @property
     def nchw(self) -> Optional[Tuple[int, int, int, int]]:
-        """The blob as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
-        channels (H = W = 1); an (N,) label that pairs with such score rows (`rows`) as N pixels of one channel; None for anything else (scalars,
-        per-class vectors: dense floats outside that machinery).  netspec.as_nchw is the rule."""
-        if self.rows and len(self.shape) == 1:
-            return (self.shape[0], 1, 1, 1)
-        return as_nchw(self.shape)
+        """The blob as the NHWC machinery sees it (storage.blob_nchw): N x C x H x W, or None for dense floats outside it."""
+        return S.blob_nchw(self.shape, self.rows)
 
     @property
     def channels(self) -> int:
@@ -353,148 +326,17 @@ class Engine:
 
     # ------------------------------------------------------------------ buffers
     def _plan_buffers(self) -> None:
-        spec = self.spec
-        producers: Dict[str, List[Layer]] = {}
-        consumers: Dict[str, List[Layer]] = {}
-        for l in spec.layers:
-            for t in l.tops:
-                producers.setdefault(t, []).append(l)
-            for b in l.bottoms:
-                consumers.setdefault(b, []).append(l)
-        self.producers, self.consumers = producers, consumers
-        data_tops = set(self.inputs)
-        # f16 mode: everything is stored as halves except what leaves the net towards the f32 decode kernel - the output
-        # blobs and the input / output of a Sigmoid head (written by the convolution epilogue in f32)
-        # f16 mode, the image itself: the nets shift a [0,1] image by -127 (Power layer), which leaves 16 half-float levels
-        # for the whole input range - but a convolution is linear, conv(x + s) = conv(x) + s * conv(indicator), and the
-        # indicator of "inside the image" is what zero padding makes of a constant-1 channel.  The half image therefore
-        # holds the UN-shifted pixels in channels 0..2 and the constant 1 in channels 3 and 4 of its 8-channel segment
-        # (written once), and the first convolution's filters carry s * sum_c(w_c) per tap in those two channels, split
-        # into a half and its rounding remainder (_packed_weight): exact to 2^-22 of the shift term.
-        self._half_inputs: Dict[str, Tuple[str, float]] = {}      # data top -> (Power top, shift)
-        if self.f16 and self.fuse and os.environ.get("FCN_F16_IMAGE", "1") != "0":
-            for d in data_tops:
-                cons = consumers.get(d, [])
-                if len(self.shapes[d]) != 4 or self.shapes[d][1] > 3 or len(cons) != 1 or cons[0].type != "Power":
-                    continue
-                pw = cons[0].sub("power_param")
-                t = cons[0].tops[0]
-                if (float(pw.get("power", 1.0)) != 1.0 or float(pw.get("scale", 1.0)) != 1.0 or t == d or t in self.outputs
-                        or [q.type for q in consumers.get(t, [])] != ["Convolution"]):
-                    continue
-                self._half_inputs[d] = (t, float(pw.get("shift", 0.0)))
-        half_image = set(self._half_inputs) | {t for t, _s in self._half_inputs.values()}
-        esize: Dict[str, int] = {}
-        for name, shp in self.shapes.items():
-            if name in half_image:
-                esize[name] = 2
-                continue
-            wide = (not self.f16 or len(shp) not in (2, 4) or name in self.outputs or name in data_tops      # inputs stay float32 (Power(-127) quirk)
-                    or any(q.type == "Power" and q.bottoms[0] in data_tops for q in producers.get(name, []))
-                    or any(q.type == "Sigmoid" for q in consumers.get(name, [])) or any(q.type == "Sigmoid" for q in producers.get(name, [])))
-            esize[name] = 4 if wide else 2
-        if self.f16:
-            for name in self.shapes:
-                if esize[name] == 4 and len(self.shapes[name]) in (2, 4) and name not in data_tops:
-                    # (Softmax and Deconvolution read halves and store float32: the out_f32 forms of their half kernels)
-                    bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct")]
-                    if bad:
-                        raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
-
-        alias: Dict[str, Tuple[str, int]] = {}   # child blob -> (parent blob, channel offset in parent)
-        shift: Dict[str, float] = {}
-        self.copy_concats = set()
-        self.copy_slices = set()
-        for l in spec.layers:
-            if l.type == "Concat":
-                off = 0
-                ok = True
-                plan = []
-                for b in l.bottoms:
-                    c = self.shapes[b][1]
-                    prods = [p for p in producers.get(b, []) if not (p.type in ("ReLU", "Dropout") and p.bottoms == p.tops)]
-                    good = (self.fuse and b not in data_tops and b not in alias and c % (16 // esize[b]) == 0 and len(prods) == 1
-                            and esize[b] == esize[l.tops[0]]
-                            and prods[0].type in ("Convolution", "Pooling", "InnerProduct")
-                            and [q.type for q in consumers.get(b, []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)] == ["Concat"])
-                    ok = ok and good
-                    plan.append((b, off))
-                    off += c
-                if ok:
-                    for b, o in plan:
-                        alias[b] = (l.tops[0], o)
-                else:
-                    self.copy_concats.add(l.name)
-            elif l.type == "Dropout" and spec.phase == "TEST" and l.tops[0] != l.bottoms[0]:
-                alias[l.tops[0]] = (l.bottoms[0], 0)       # identity at test time: share the view
-            elif l.type == "Power" and self.fuse and l.tops[0] != l.bottoms[0]:
-                # Power(shift) directly on a net input that nothing else reads: the upload adds the shift, the
-                # device buffer holds the transformed blob and both names share it
-                p = l.sub("power_param")
-                bot = l.bottoms[0]
-                if (float(p.get("power", 1.0)) == 1.0 and float(p.get("scale", 1.0)) == 1.0 and bot in data_tops
-                        and bot not in alias and len(consumers.get(bot, [])) == 1 and len(self.shapes[bot]) == 4):
-                    alias[l.tops[0]] = (bot, 0)
-                    shift[l.tops[0]] = float(p.get("shift", 0.0))
-            elif l.type == "Slice":
-                n, c, h, w = as_nchw(self.shapes[l.bottoms[0]])
-                # tops are views of the bottom when every consumer can read a channel slice at a 16-byte aligned offset;
-                # otherwise (models/train_val.prototxt slices a 17-channel label record at 1, 5, 9, 13 for Eltwise layers)
-                # the slices are materialised by copies
-                offs, off = [], 0
-                for t in l.tops:
-                    offs.append(off)
-                    off += self.shapes[t][1]
-                viewable = all(o % (16 // esize[l.bottoms[0]]) == 0 for o in offs) and all(
-                    q.type in ("Convolution", "Pooling", "Concat") for t in l.tops for q in consumers.get(t, []))
-                if viewable:
-                    for t, o in zip(l.tops, offs):
-                        alias[t] = (l.bottoms[0], o)
-                else:
-                    self.copy_slices.add(l.name)
-        self.alias, self.shift = alias, shift
-
-        # allocate roots, then resolve views
-        for name, shp in self.shapes.items():
-            self.blobs[name] = Blob(name, shp)
-            self.blobs[name].esize = esize[name]
-        for l in spec.layers:      # Caffe's data layers emit (N,) labels: beside N score rows such a blob is N pixels of one channel
-            if l.type in ("SoftmaxWithLoss", "Accuracy") and len(l.bottoms) == 2:
-                score, lab = self.shapes[l.bottoms[0]], self.shapes[l.bottoms[1]]
-                if len(score) == 2 and tuple(lab) == (score[0],):
-                    self.blobs[l.bottoms[1]].rows = True
-        for name, blob in self.blobs.items():
-            if name in alias:
-                continue
-            if blob.nchw is not None:
-                blob.cstride = _ra(blob.channels, blob.esize)
-                blob.buf = DeviceBuffer(blob.pixels * blob.cstride * blob.esize)
-            else:
-                blob.cstride = 1
-                blob.buf = DeviceBuffer(max(16, 4 * int(np.prod(blob.shape)) if blob.shape else 16))
-        for name in alias:
-            root, off = name, 0
-            total_shift = 0.0
-            seen = 0
-            while root in alias:
-                total_shift += shift.get(root, 0.0)
-                root, o = alias[root]
-                off += o
-                seen += 1
-                if seen > 64:
-                    raise RuntimeError("alias cycle at blob %s" % name)
-            b, r = self.blobs[name], self.blobs[root]
-            if b.esize != r.esize:
-                raise NotImplementedError("f16 engine: blob %s (%d-byte elements) is a view of %s (%d-byte)" % (name, b.esize, root, r.esize))
-            b.buf, b.coffset, b.cstride = r.buf, r.coffset + off, r.cstride
-            if total_shift and root in self._half_inputs:
-                b.lazy_shift = total_shift        # the device keeps the un-shifted half image: reading the Power top adds the shift
-            elif total_shift:
-                r.upload_shift = total_shift      # device copy of the input = host value + shift
-                r.lazy_shift = -total_shift       # reading the input back undoes it
-        for nm in self.inputs:
-            if nm in self.blobs:
-                self.blobs[nm].is_input = True
+        """One DeviceBuffer per blob that owns its storage, every other blob a channel window of one: storage.plan_blobs decides."""
+        plan = S.plan_blobs(self.spec, self.shapes, self.inputs, self.outputs, self.f16, self.fuse, os.environ.get("FCN_F16_IMAGE", "1") != "0")
+        self.producers, self.consumers = plan.producers, plan.consumers
+        self.alias, self.shift, self.copy_concats, self.copy_slices = plan.alias, plan.shift, plan.copy_concats, plan.copy_slices
+        self._half_inputs = plan.half_inputs      # data top -> (Power top, shift)
+        bufs = {root: DeviceBuffer(nbytes) for root, nbytes in plan.root_bytes.items()}
+        for name, v in plan.views.items():
+            b = self.blobs[name] = Blob(name, v.shape)
+            b.esize, b.rows, b.is_input = v.esize, v.rows, name in self.inputs
+            b.buf, b.coffset, b.cstride = bufs[v.root], v.coffset, v.cstride
+            b.upload_shift, b.lazy_shift = v.upload_shift, v.lazy_shift
         for d in self._half_inputs:                 # the two constant-1 channels, once: every writer of the image touches channels 0..2 only
             b = self.blobs[d]
             ones = np.zeros((b.pixels, b.cstride), np.float16)
@@ -508,8 +350,7 @@ class Engine:
         from .netspec import fill_params
         if params is None:
             params = fill_params(self.spec, seed=0)
-        self.param_layout: List[dict] = []
-        off = 0
+        self.param_segs: Dict[Tuple[str, int], S.ParamSeg] = {}      # (layer, blob index) -> its segment, shared layers' included
         src = self._share_from
         if src is not None:
             # shared layers: views INTO the source's flat buffer (the packed bytes of a float32 layer do not depend on the phase:
@@ -525,6 +366,9 @@ class Engine:
                 self.shared_layers.add(l.name)
                 self.params_host[l.name] = src.params_host[l.name]
                 self.params_dev[l.name] = [DevView(v.ptr, v.nbytes) for v in src.params_dev[l.name]]
+                self.param_segs.update({(l.name, i): src.param_segs[(l.name, i)] for i in range(len(mine))})
+        # the device layout of every blob this engine owns (storage.py): kernels' layout, offsets in 4-byte words
+        self.param_layout, self.param_count = S.param_layout(self.spec, self.blobs, self.f16, self.shared_layers)
         for l in self.spec.param_layers():
             if l.name in self.shared_layers:
                 continue
@@ -541,85 +385,24 @@ class Engine:
                     a = a.reshape(shp)
                 host.append(a.copy())
             self.params_host[l.name] = host
-            packed = [self._packed_weight(l)] + host[1:]
-            for i, arr in enumerate(packed):
-                lm = l.lr_mult[i] if i < len(l.lr_mult) else 1.0
-                dm = l.decay_mult[i] if i < len(l.decay_mult) else 1.0
-                # offsets count 4-byte words (= floats in the f32 engine, where the solver and RCCL index this buffer)
-                self.param_layout.append(dict(layer=l.name, index=i, offset=off, count=int(arr.size), shape=tuple(arr.shape),
-                                              lr_mult=float(lm), decay_mult=float(dm), nbytes=int(arr.nbytes)))
-                off += _r4((int(arr.nbytes) + 3) // 4)
-        self.param_count = off
-        self.param_flat = DeviceBuffer(max(off, 4) * 4, zero=True)
-        for e in self.param_layout:
-            self.params_dev.setdefault(e["layer"], []).append(DevView(self.param_flat.ptr + 4 * e["offset"], e["nbytes"]))
+        self.param_flat = DeviceBuffer(max(self.param_count, 4) * 4, zero=True)
+        for seg in self.param_layout:
+            self.param_segs[(seg.layer, seg.index)] = seg
+            self.params_dev.setdefault(seg.layer, []).append(DevView(self.param_flat.ptr + 4 * seg.offset, seg.nbytes))
         for l in self.spec.param_layers():
             if l.name not in self.shared_layers:
                 self._upload_params(l)
 
-    def _packed_weight(self, l: Layer) -> np.ndarray:
-        w = self.params_host[l.name][0]
-        if l.type == "Convolution":
-            co, ci, kh, kw = w.shape
-            xs = self.blobs[l.bottoms[0]].esize              # element type of the layer's input: 16-byte segments of it
-            out = np.zeros((co, kh, kw, _ra(ci, xs)), np.float16 if xs == 2 else F32)   # OHWI, Cin padded to whole segments
-            out[..., :ci] = w.transpose(0, 2, 3, 1)
-            for _d, (t, sh) in getattr(self, "_half_inputs", {}).items():
-                if l.bottoms[0] == t and sh:
-                    # the folded Power shift: channels 3 and 4 see the constant 1 (zero in the padding, like the shifted image)
-                    term = np.float64(sh) * out[..., :ci].astype(np.float64).sum(-1)      # of the ROUNDED filters: what the device multiplies
-                    hi = term.astype(np.float16)
-                    out[..., 3] = hi
-                    out[..., 4] = (term - hi.astype(np.float64)).astype(np.float16)
-            return out
-        if l.type == "InnerProduct":
-            # [num_output][H*W*cstride]: the columns in the order of the elements of a row of the NHWC bottom, zero at its pad channels
-            xb = self._ip_bottom(l)
-            _n, c, h, wd = xb.nchw
-            return ip_pack_bank(w, c, h, wd, xb.cstride, np.float16 if xb.esize == 2 else F32)
-        if l.type == "Deconvolution":
-            c, cog, kh, kw = w.shape
-            if self._deconv_dense(l):
-                # group 1: [Cin][kh][kw][Cout padded to 4] - an OHWI bank of Cin outputs over Cout inputs, which is what the layer's data
-                # gradient (a forward convolution of dY) and its weight gradient (roles swapped) read as it stands
-                out = np.zeros((c, kh, kw, _r4(cog)), F32)
-                out[..., :cog] = w.transpose(0, 2, 3, 1)
-                return out
-            return np.ascontiguousarray(w.reshape(c, kh, kw))
-        raise NotImplementedError(l.type)
-
-    def _ip_bottom(self, l: Layer) -> Blob:
-        """The bottom of an InnerProduct layer, which must be a whole buffer: a row of it is then the layer's input vector as it lies
-        in memory.  A bottom that is a channel window of a wider buffer (a Concat member, a Slice top) is refused by name."""
-        xb = self.blobs[l.bottoms[0]]
-        if xb.nchw is None or xb.coffset or xb.cstride != _ra(xb.channels, xb.esize):
-            raise NotImplementedError("InnerProduct %s: the bottom %s is a channel window of a wider buffer (or no 4-d / 2-d blob)"
-                                      % (l.name, l.bottoms[0]))
-        return xb
-
-    def _deconv_dense(self, l: Layer) -> bool:
-        """True: a group-1 Deconvolution (the transposed-convolution kernel); False: group == channels == num_output (the depthwise
-        kernels).  Every other grouping is refused, by name."""
-        p = l.sub("convolution_param")
-        g, co = int(p.get("group", 1)), int(p.get("num_output"))
-        c = self.spec.param_shapes[l.name][0][0]
-        if g == c and co == c:
-            return False
-        if g == 1:
-            if self.f16:
-                raise NotImplementedError("f16 engine: layer type Deconvolution with group 1 (%s) has no half-float kernel" % l.name)
-            return True
-        raise NotImplementedError("Deconvolution %s: group %d with %d -> %d channels (only group 1 and group == channels == num_output)"
-                                  % (l.name, g, c, co))
+    def _folded_shift(self, l: Layer) -> float:
+        """The Power shift that convolution l carries in channels 3 and 4 of its filters: its bottom is the Power top of a half image."""
+        return next((sh for t, sh in self._half_inputs.values() if t == l.bottoms[0]), 0.0) if l.type == "Convolution" else 0.0
 
     def _upload_params(self, l: Layer) -> None:
         if l.name in self.shared_layers:
             raise RuntimeError("layer %s reads the parameters of another engine (share_params): set them there" % l.name)
-        host = self.params_host[l.name]
-        packed = [self._packed_weight(l)] + [np.ascontiguousarray(h) for h in host[1:]]
-        devs = self.params_dev[l.name]
-        for i, arr in enumerate(packed):
-            L.call("fcn_memcpy_h2d_async", devs[i].ptr, arr.ctypes.data, arr.nbytes, None)
+        packed = [S.pack(self.param_segs[(l.name, i)], h, self._folded_shift(l) if i == 0 else 0.0) for i, h in enumerate(self.params_host[l.name])]
+        for arr, dev in zip(packed, self.params_dev[l.name]):
+            L.call("fcn_memcpy_h2d_async", dev.ptr, arr.ctypes.data, arr.nbytes, None)
         L.call("fcn_device_sync")
 
     def set_params(self, layer: str, blobs: Sequence[np.ndarray]) -> None:
@@ -635,24 +418,11 @@ class Engine:
         """Caffe-layout host copy (conv: OIHW, bias) of one parameter blob as the device holds it now - for a shared layer, the
         source engine's current weights."""
         with self.lock:
-            v, shp = self.params_dev[layer][index], self.params_host[layer][index].shape
-            raw = np.empty(v.nbytes // 4, F32)
+            v = self.params_dev[layer][index]
+            raw = np.empty(v.nbytes, np.uint8)
             L.call("fcn_memcpy_d2h_async", raw.ctypes.data, v.ptr, raw.nbytes, self.stream)
             L.call("fcn_stream_sync", self.stream)
-        lay = next(l for l in self.spec.layers if l.name == layer)
-        if index == 0 and lay.type == "Convolution":
-            co, ci, kh, kw = shp
-            return np.ascontiguousarray(raw.reshape(co, kh, kw, -1)[..., :ci].transpose(0, 3, 1, 2))
-        if index == 0 and lay.type == "InnerProduct":
-            xb = self._ip_bottom(lay)
-            _n, c, h, w = xb.nchw
-            if xb.esize == 2:
-                raw = raw.view(np.float16).astype(F32)
-            return ip_unpack_bank(raw.reshape(shp[0], -1), c, h, w, xb.cstride)
-        if index == 0 and lay.type == "Deconvolution" and self._deconv_dense(lay):
-            ci, co, kh, kw = shp
-            return np.ascontiguousarray(raw.reshape(ci, kh, kw, -1)[..., :co].transpose(0, 3, 1, 2))
-        return raw.reshape(shp).copy()
+        return S.unpack(self.param_segs[(layer, index)], raw)
 
     # ------------------------------------------------------------------ plan
     def _geom(self, l: Layer, ksp: Optional[Tuple[int, int, int]] = None) -> ConvGeom:
@@ -675,8 +445,8 @@ class Engine:
         if xb.esize == 2:
             flags |= L.CONV_F16 | (L.CONV_OUT_F32 if yb.esize == 4 else 0)
             # the half image of _half_inputs: channels 3 and 4 are the constant 1 (written once, _plan_buffers), 5..7 stay zero and
-            # _packed_weight puts the folded shift into the filters' channels 3 and 4 - the first-layer kernel may take them as constants
-            if any(l.bottoms[0] == t and sh for t, sh in getattr(self, "_half_inputs", {}).values()) and _ra(g.cin, 2) == 8 and xb.cstride == 8:
+            # storage.pack puts the folded shift into the filters' channels 3 and 4 - the first-layer kernel may take them as constants
+            if self._folded_shift(l) and _ra(g.cin, 2) == 8 and xb.cstride == 8:
                 flags |= L.CONV_IMAGE_ONES
         elif yb.esize != 4:
             flags |= L.CONV_OUT_F16      # first layer of an f16 net: float32 image in, halves out
@@ -1288,7 +1058,7 @@ class Engine:
         the input vectors as they lie in memory, the bank was packed in that order at upload; the top is N pixels of num_output
         channels, written at its channel offset (a member of a Concat of (N, C) blobs in place: _plan_buffers aliases it)."""
         lib = L.load()
-        xb, yb = self._ip_bottom(l), self.blobs[l.tops[0]]
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]      # (a whole buffer: storage.param_layout refuses any other bottom)
         m, c, h, w = xb.nchw
         n_out = yb.channels
         k = h * w * xb.cstride
@@ -1322,7 +1092,7 @@ class Engine:
         c, co, k = g.cin, g.cout, g.k
         wdev = self.params_dev[l.name][0].ptr
         bdev = self.params_dev[l.name][1].ptr if len(self.params_dev[l.name]) > 1 else None
-        if self._deconv_dense(l):
+        if self.param_segs[(l.name, 0)].kind == S.DECONV:
             # group 1: the transposed convolution on the matrix cores.  Its bank is re-packed from the blob in front of every
             # launch (one small launch): the blob may have been stepped by a solver, set through net.params or belong to
             # another engine (share_params) since the last forward.

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import lib as L
 from . import proto
+from . import storage as S
 from .backward import BackwardPlanner
 from .engine import Blob, DevView, DeviceBuffer, Engine, Op, PinnedArray, _r4, graphs_enabled
 from .netspec import DATA_TYPES, Layer, NetSpec
@@ -225,7 +226,7 @@ class TrainEngine(Engine):
             self.clip_dev = DeviceBuffer(16, zero=True)      # word 0: the factor, word 1: the sum of squares (for read_clip())
             self.clip_ws = DeviceBuffer(int(L.load().fcn_grad_clip_workspace_bytes()), zero=False)
         segs = (L.SolverSeg * len(self.param_layout))(*[
-            L.SolverSeg(e["offset"], e["count"], e["lr_mult"], e["decay_mult"]) for e in self.param_layout])
+            L.SolverSeg(e.offset, e.count, e.lr_mult, e.decay_mult) for e in self.param_layout])
         self._segs_host = segs
         self.segs_dev = DeviceBuffer(max(C.sizeof(segs), 16), zero=False)
         L.call("fcn_memcpy_h2d_async", self.segs_dev.ptr, C.addressof(segs), C.sizeof(segs), None)
@@ -236,10 +237,8 @@ class TrainEngine(Engine):
         self.loss_host = {name: p.array for name, p in self._loss_pinned.items()}
 
     def _grad_view(self, layer: str, index: int) -> DevView:
-        for e in self.param_layout:
-            if e["layer"] == layer and e["index"] == index:
-                return DevView(self.grad_flat.ptr + 4 * e["offset"], 4 * e["count"])
-        raise KeyError((layer, index))
+        seg = self.param_segs[(layer, index)]
+        return DevView(self.grad_flat.ptr + 4 * seg.offset, 4 * seg.count)
 
     # ------------------------------------------------------------------ backward plan
     def _build_backward(self) -> None:
@@ -262,12 +261,12 @@ class TrainEngine(Engine):
             return
         cur = None
         for e in self.param_layout:
-            if cur is None or (e["index"] == 0 and cur["count"] >= bucket_floats):
-                cur = dict(offset=e["offset"], count=0, layers=[])
+            if cur is None or (e.index == 0 and cur["count"] >= bucket_floats):
+                cur = dict(offset=e.offset, count=0, layers=[])
                 self.buckets.append(cur)
-            cur["count"] = e["offset"] + _r4(e["count"]) - cur["offset"]
-            if e["layer"] not in cur["layers"]:
-                cur["layers"].append(e["layer"])
+            cur["count"] = e.offset + _r4(e.count) - cur["offset"]
+            if e.layer not in cur["layers"]:
+                cur["layers"].append(e.layer)
         wg_index = {}
         for i, op in enumerate(self.bwd_ops):
             if op.kind == "wgrad":
@@ -611,38 +610,15 @@ class TrainEngine(Engine):
 
     def _unpack(self, flat: np.ndarray) -> Dict[str, List[np.ndarray]]:
         out: Dict[str, List[np.ndarray]] = {}
-        types = {l.name: l.type for l in self.spec.layers}
         for e in self.param_layout:
-            a = flat[e["offset"]:e["offset"] + e["count"]].reshape(e["shape"])
-            if e["index"] == 0 and types[e["layer"]] == "Convolution":
-                host_shape = self.params_host[e["layer"]][0].shape
-                a = a[..., :host_shape[1]].transpose(0, 3, 1, 2)
-            elif e["index"] == 0 and types[e["layer"]] == "Deconvolution":
-                host_shape = self.params_host[e["layer"]][0].shape
-                if a.ndim == 4:      # group 1: [Cin][kh][kw][Cout padded to 4] on the device
-                    a = a[..., :host_shape[1]].transpose(0, 3, 1, 2)
-                else:
-                    a = a.reshape(host_shape)
-            out.setdefault(e["layer"], []).append(np.ascontiguousarray(a))
+            out.setdefault(e.layer, []).append(S.unpack(e, flat[e.offset:e.offset + e.count]))
         return out
 
     def _pack(self, per_layer: Dict[str, List[np.ndarray]]) -> np.ndarray:
         """Inverse of _unpack: Caffe-layout blobs -> the flat device layout (padded input channels stay zero)."""
         flat = np.zeros(max(self.param_count, 4), F32)
-        types = {l.name: l.type for l in self.spec.layers}
         for e in self.param_layout:
-            a = np.asarray(per_layer[e["layer"]][e["index"]], F32)
-            if e["index"] == 0 and types[e["layer"]] == "Convolution":
-                co, ci, kh, kw = self.params_host[e["layer"]][0].shape
-                d = np.zeros(e["shape"], F32)
-                d[..., :ci] = a.reshape(co, ci, kh, kw).transpose(0, 2, 3, 1)
-                a = d
-            elif e["index"] == 0 and types[e["layer"]] == "Deconvolution" and len(e["shape"]) == 4:
-                ci, co, kh, kw = self.params_host[e["layer"]][0].shape
-                d = np.zeros(e["shape"], F32)
-                d[..., :co] = a.reshape(ci, co, kh, kw).transpose(0, 2, 3, 1)
-                a = d
-            flat[e["offset"]:e["offset"] + e["count"]] = a.reshape(-1)
+            flat[e.offset:e.offset + e.count] = S.pack(e, per_layer[e.layer][e.index]).reshape(-1)
         return flat
 
     def download_history(self) -> List[np.ndarray]:

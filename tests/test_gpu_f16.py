@@ -371,6 +371,33 @@ def test_f16_engine_forward_of_the_detectnet_deploy_net(gpu):
     eng.close()
 
 
+@pytest.mark.parametrize("half_image", [True, False])
+def test_f16_engine_read_param_returns_the_filters_the_device_holds(gpu, monkeypatch, half_image):
+    """read_param on the half-float engine of the same net: every convolution bank comes back in Caffe's layout as the host blob
+    rounded to the element type of the layer's bottom - the first layer included, whose bank carries the folded Power shift in two
+    of its pad channels (half image) or stays float32 (FCN_F16_IMAGE=0) - and every bias exactly."""
+    from fcn_object_detector_amd import models, proto
+    from fcn_object_detector_amd.engine import Engine
+    from fcn_object_detector_amd.netspec import NetSpec, fill_params
+    monkeypatch.setenv("FCN_F16_IMAGE", "1" if half_image else "0")
+    msg = proto.parse_text(models.googlenet_detectnet_deploy(2, 96, 128, 3))
+    spec = NetSpec(msg, "TEST")
+    spec.infer()
+    eng = Engine(NetSpec(msg, "TEST"), params=fill_params(spec, seed=21), device=0, autotune=False, dtype="f16")
+    try:
+        assert eng.blobs["transformed_data"].esize == (2 if half_image else 4) and eng.blobs["conv1/7x7_s2"].esize == 2
+        layers = [l for l in eng.spec.param_layers() if l.type == "Convolution"]
+        assert len(layers) == 59 and layers[0].name == "conv1/7x7_s2"
+        for l in layers:
+            w, b = eng.params_host[l.name]
+            want = w.astype(np.float16).astype(np.float32) if eng.blobs[l.bottoms[0]].esize == 2 else w
+            got = eng.read_param(l.name, 0)
+            assert got.shape == w.shape and got.dtype == np.float32 and np.array_equal(got, want), l.name
+            assert np.array_equal(eng.read_param(l.name, 1), b), l.name
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("n,h,w,cout,relu", [(2, 448, 448, 64, 1), (5, 100, 130, 48, 0), (1, 64, 64, 64, 1), (11, 40, 200, 40, 1)])
 def test_f16_first_layer_kernel_matches_oracle(gpu, monkeypatch, n, h, w, cout, relu):
     """conv_first7_f16_kernel (configuration 30 on half-float problems: 7x7 / stride 2 / pad 3 on 8-half pixels), chosen by the

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 import ref_ip64 as R
-from fcn_object_detector_amd.engine import ip_pack_bank, ip_unpack_bank
+from fcn_object_detector_amd.storage import ip_pack_bank, ip_unpack_bank
 
 
 @pytest.mark.parametrize("shape,n", [((3, 20), 7), ((2, 5, 3, 4), 6), ((1, 16, 1, 1), 4)])
