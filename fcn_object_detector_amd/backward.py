@@ -42,6 +42,7 @@ class BackwardPlanner:
         self.e, self.spec, self.B, self.G, self.lib = eng, eng.spec, eng.blobs, eng.grad_blobs, L.load()
         self.ops: List[Op] = []
         self.ws_floats = 1                                   # workspace of the weight-gradient launches: the largest any of them needs
+        self.ip_ws_bytes = 0                                 # ... and of the InnerProduct data gradients, which run beside them (_inner_product)
         self.written: Dict[int, List[Tuple[int, int]]] = {}  # gradient buffer -> channel ranges already holding a gradient
         self.writers: Dict[str, List[object]] = {}           # gradient blob -> what wrote it, in order (a dgrad / pooling record or None)
         self.concat_members: Dict[str, List[str]] = {}       # Concat output -> its member blobs
@@ -56,7 +57,7 @@ class BackwardPlanner:
         self.skip_sigmoid_of = {m["sigmoid_top"]: name for name, m in eng._conv_layer_meta.items() if m.get("sigmoid_top")}
         nothing = lambda l: None
         # layer types that look at the plan state themselves ...
-        self.emitters = {"Convolution": self._convolution, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
+        self.emitters = {"Convolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
                          "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": nothing,
                          "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
                          "Accuracy": nothing,      # a metric: no gradient, no entry in loss_blobs
@@ -74,6 +75,7 @@ class BackwardPlanner:
             (self.emitters.get(l.type) or self._one_bottom)(l)
         self._finish_dgrads()
         self.ws = DeviceBuffer(self.ws_floats * 4, zero=False)
+        self.ip_ws = DeviceBuffer(self.ip_ws_bytes, zero=False) if self.ip_ws_bytes else None
 
     # ------------------------------------------------------------------ write state of the gradient views
     def state(self, g: Blob) -> str:
@@ -132,17 +134,19 @@ class BackwardPlanner:
         for l in self.spec.layers:
             if l.type != "Convolution" or self.G.get(l.bottoms[0]) is None or self.G.get(l.tops[0]) is None:
                 continue
-            g = e._geom(l)
-            cin, cout, k = g.cin, g.cout, g.k
-            wdev = e.params_dev[l.name][0].ptr
+            g, ng = e._geom(l), e._conv_groups(l)
+            cin, cout, k = g.cin // ng, g.cout // ng, g.k      # of one group: its bank is rows i*cout .. of the layer's (storage.conv_groups)
             if g.s == 1:
                 self.flip_layout[l.name] = flip_floats
-                flip_segs.append(L.FlipSeg((wdev - e.param_flat.ptr) // 4, flip_floats, cout, k, k, cin, _r4(cin), _r4(cout)))
-                flip_floats += _r4(cin * k * k * _r4(cout))
-            else:
-                bank = self.tbank[l.name] = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(cout, cin, k, k)), 4) * 4, zero=True)
-                packs.append(Op("tconv_pack", l.name, lambda st, wdev=wdev, bank=bank, cout=cout, cin=cin, k=k: L.check(
-                    lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, cout, cin, _r4(cin), k, k, st))))
+            for i in range(ng):
+                wdev = e.params_dev[l.name][0].ptr + 4 * i * cout * k * k * _r4(cin)
+                if g.s == 1:
+                    flip_segs.append(L.FlipSeg((wdev - e.param_flat.ptr) // 4, flip_floats, cout, k, k, cin, _r4(cin), _r4(cout)))
+                    flip_floats += self._flip_floats(cin, cout, k)
+                else:
+                    bank = self.tbank[self._tbank_key(l, i)] = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(cout, cin, k, k)), 4) * 4, zero=True)
+                    packs.append(Op("tconv_pack", self._tbank_key(l, i), lambda st, wdev=wdev, bank=bank, cout=cout, cin=cin, k=k: L.check(
+                        lib.fcn_tconv_bank_pack_f32(wdev, bank.ptr, cout, cin, _r4(cin), k, k, st))))
         self.flip_flat = DeviceBuffer(max(flip_floats, 4) * 4, zero=True)
         if flip_segs:
             seg_arr = (L.FlipSeg * len(flip_segs))(*flip_segs)
@@ -153,37 +157,54 @@ class BackwardPlanner:
                 e.param_flat.ptr, e._flip_flat.ptr, e._flip_segs_dev.ptr, n, st))))
         self.ops.extend(packs)
 
+    @staticmethod
+    def _flip_floats(cin: int, cout: int, k: int) -> int:
+        """Floats of one flipped bank [cin][k][k][r4(cout)] in flip_flat."""
+        return _r4(cin * k * k * _r4(cout))
+
+    @staticmethod
+    def _tbank_key(l: Layer, group: int) -> str:
+        return l.name if group == 0 else "%s#%d" % (l.name, group)
+
     # ------------------------------------------------------------------ data gradients
-    def emit_tdgrad(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Dgrad:
+    def emit_tdgrad(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool, group: int = 0) -> Dgrad:
         """Data gradient of the strided convolution l: the transposed convolution of dY, written at the size of the layer's input
         (rows / columns of it that lay under no window get zeros).  Prepared in _finish_dgrads like the grouped launches, because
         the ReLU mask of the layer below may still be folded into its epilogue."""
-        g, lib = self.e._geom(l), self.lib
+        g, lib, ng = self.e._geom(l), self.lib, self.e._conv_groups(l)
         if gtop.coffset % 4 or gtop.cstride - gtop.coffset < _r4(g.cout):
             raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % l.tops[0])
         if g.pad >= g.k:
             raise NotImplementedError("data gradient of the strided convolution %s with pad %d >= kernel %d" % (l.name, g.pad, g.k))
-        d = tconv_desc(gtop, gbot, g.swapped(), self.tbank[l.name].ptr, flags=L.CONV_ACCUM if accumulate else 0)
-        rec = Dgrad(l.name, [d], [l.bottoms[0]], L.TConvPlan())
-        rec.op = Op("tconv_dgrad", l.name, lambda st, pl=rec.launch: L.check(lib.fcn_tconv2d_f32(C.byref(pl), st)), g.flops)
+        cin_g, cout_g = g.cin // ng, g.cout // ng
+        d = tconv_desc(gtop, gbot, g.swapped()._replace(cin=cout_g, cout=cin_g), self.tbank[self._tbank_key(l, group)].ptr,
+                       flags=L.CONV_ACCUM if accumulate else 0)
+        d.a += 4 * group * cout_g           # the group's channels of dY ...
+        d.b_coffset += group * cin_g        # ... make its channels of dX
+        rec = Dgrad(self._tbank_key(l, group), [d], [l.bottoms[0]], L.TConvPlan())
+        rec.op = Op("tconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_tconv2d_f32(C.byref(pl), st)), g.flops / (ng * ng))
         self.ops.append(rec.op)
         self.dgrad_records.append(rec)
         self.e._keep.append(d)
         return rec
 
-    def dgrad_desc(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool) -> Tuple[L.ConvDesc, float]:
-        """Data gradient of convolution l = the forward kernel on dY with the flipped / transposed bank."""
-        g = self.e._geom(l)
+    def dgrad_desc(self, l: Layer, gtop: Blob, gbot: Blob, accumulate: bool, group: int = 0) -> Tuple[L.ConvDesc, float]:
+        """Data gradient of convolution l (of its group `group`) = the forward kernel on dY with the flipped / transposed bank: a group
+        reads its Cout/g channels of dY and writes its Cin/g channels of dX."""
+        g, ng = self.e._geom(l), self.e._conv_groups(l)
         if g.s != 1:
             raise RuntimeError("dgrad_desc is the stride-1 path; strided layers go through emit_tdgrad (%s)" % l.name)
-        cin_dg = _r4(g.cout)      # the flipped bank reads Cout4 input channels: the gradient view must expose them contiguously
-        if gtop.cstride - gtop.coffset < cin_dg:
+        cin_g, cout_g = g.cin // ng, g.cout // ng
+        cin_dg = _r4(cout_g)      # the flipped bank reads Cout4 input channels: the gradient view must expose them contiguously
+        if gtop.cstride - gtop.coffset - group * cout_g < cin_dg:
             raise NotImplementedError("gradient view of %s too narrow for the data-gradient pass" % l.tops[0])
-        wt = DevView(self.flip_flat.ptr + 4 * self.flip_layout[l.name], g.cin * g.k * g.k * cin_dg * 4)
-        dd = conv_desc(gtop, gbot, g.swapped()._replace(cin=cin_dg, s=1, pad=g.k - 1 - g.pad), wt.ptr,
+        wt = DevView(self.flip_flat.ptr + 4 * (self.flip_layout[l.name] + group * self._flip_floats(cin_g, cout_g, g.k)), cin_g * g.k * g.k * cin_dg * 4)
+        dd = conv_desc(gtop, gbot, g.swapped()._replace(cin=cin_dg, cout=cin_g, s=1, pad=g.k - 1 - g.pad), wt.ptr,
                        flags=L.CONV_ACCUM if accumulate else 0)
+        dd.x += 4 * group * cout_g
+        dd.y_coffset += group * cin_g
         self.e._keep.append(dd)
-        return dd, g.flops
+        return dd, g.flops / (ng * ng)
 
     def emit_dgrads(self, name: str, items: List[Tuple[L.ConvDesc, float]], targets: List[str]) -> Dgrad:
         """One grouped launch for data-gradient passes that write different buffers.  The group is prepared (and
@@ -208,10 +229,14 @@ class BackwardPlanner:
                     rec.mask = (B[x].buf.ptr, B[x].cstride, B[x].coffset)
                     self.ops.remove(rop)
                 continue
-            d = rec.descs[rec.targets.index(x)]
             act = B[x]
-            d.y2, d.y2_cstride, d.y2_coffset = act.buf.ptr, act.cstride, act.coffset
-            d.flags |= L.CONV_MASK
+            if x not in rec.targets:
+                raise RuntimeError("the last writer of the gradient of %s does not name it among its targets" % x)
+            for d, t in zip(rec.descs, rec.targets):      # (the groups of a grouped convolution each write their own channels of dX)
+                if t == x:
+                    first = d.b_coffset if isinstance(d, L.TConvDesc) else d.y_coffset
+                    d.y2, d.y2_cstride, d.y2_coffset = act.buf.ptr, act.cstride, act.coffset + first - self.G[x].coffset
+                    d.flags |= L.CONV_MASK
             self.ops.remove(rop)
         for rec in self.dgrad_records:
             if isinstance(rec.launch, L.TConvPlan):
@@ -240,7 +265,9 @@ class BackwardPlanner:
         self.ops.append(op)
         return op
 
-    def _book_wgrad(self, op: Op, sel: dict, names: List[str], ws_floats: List[int]) -> None:
+    def _book_wgrad(self, op: Op, sel: Optional[dict], names: List[str], ws_floats: List[int]) -> None:
+        """A weight-gradient launch: kind "wgrad" puts it on the step's second stream, op.layers tells the data-parallel exchange which
+        buckets wait for it, op.sel (None: one form only) is what Tuner.wgrad_cfgs() chooses."""
         self.ws_floats = max([self.ws_floats] + ws_floats)
         op.sel = sel
         op.layers = names
@@ -258,25 +285,35 @@ class BackwardPlanner:
             C.byref(d), dw.ptr, db.ptr if db else None, e._ws.ptr, sel["cfg"], st)), flops)
         self._book_wgrad(op, sel, [name], [int(lib.fcn_conv2d_wgrad_workspace_floats_cfg(C.byref(d), c, None)) for c in self._wgrad_cfgs()])
 
-    def wgrad_item(self, l: Layer, gtop: Blob) -> Tuple[L.ConvDesc, DevView, Optional[DevView], float]:
-        """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns."""
-        e, g, xb = self.e, self.e._geom(l), self.B[l.bottoms[0]]
+    def wgrad_items(self, l: Layer, gtop: Blob) -> List[Tuple[L.ConvDesc, DevView, Optional[DevView], float]]:
+        """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns: one per group, dW and db at
+        the group's rows."""
+        e, g, xb, ng = self.e, self.e._geom(l), self.B[l.bottoms[0]], self.e._conv_groups(l)
         if gtop.coffset % 4 or gtop.cstride % 4:
             raise NotImplementedError("gradient view of %s is not 16-byte aligned" % l.tops[0])
-        d = conv_desc(xb, gtop, g._replace(cin=_r4(g.cin)))
-        e._keep.append(d)
+        cin_g, cout_g = g.cin // ng, g.cout // ng
         dw = e._grad_view(l.name, 0)
         db = e._grad_view(l.name, 1) if len(e.params_dev[l.name]) > 1 else None
-        return d, dw, db, g.flops
+        out = []
+        for i in range(ng):
+            d = conv_desc(xb, gtop, g._replace(cin=_r4(cin_g), cout=cout_g))
+            d.x += 4 * i * cin_g
+            d.y_coffset += i * cout_g
+            e._keep.append(d)
+            rows = cout_g * g.k * g.k * _r4(cin_g)
+            out.append((d, DevView(dw.ptr + 4 * i * rows, 4 * rows), DevView(db.ptr + 4 * i * cout_g, 4 * cout_g) if db is not None else None,
+                        g.flops / (ng * ng)))
+        return out
 
     def emit_wgrads(self, layers_: List[Layer], gtops: List[Blob]) -> None:
         """Weight (and bias) gradients of layers that are ready together: one launch + one reduction for up to four."""
         e, lib = self.e, self.lib
-        todo = [(l_, g_) for l_, g_ in zip(layers_, gtops) if e._learns(l_) and l_.name not in self.wgrad_done]
+        todo = [(l_.name, it) for l_, g_ in zip(layers_, gtops) if e._learns(l_) and l_.name not in self.wgrad_done
+                for it in self.wgrad_items(l_, g_)]
         for base in range(0, len(todo), 4):
             chunk = todo[base:base + 4]
-            its = [self.wgrad_item(l_, g_) for l_, g_ in chunk]
-            names = [l_.name for l_, _ in chunk]
+            its = [it for _, it in chunk]
+            names = list(dict.fromkeys(nm for nm, _ in chunk))      # (the groups of a grouped layer are items of one name)
             if len(its) == 1:
                 self.wgrad_op(names[0], *its[0])
                 continue
@@ -310,10 +347,12 @@ class BackwardPlanner:
         self.emit_wgrads([l], [gtop])
         gbot = G.get(l.bottoms[0])
         if gbot is not None and l.name not in self.dgrad_done:
+            acc, ng = self.state(gbot) == "full", e._conv_groups(l)
             if e._geom(l).s != 1:
-                rec = self.emit_tdgrad(l, gtop, gbot, self.state(gbot) == "full")
+                recs = [self.emit_tdgrad(l, gtop, gbot, acc, i) for i in range(ng)]
+                rec = recs[0] if ng == 1 else None      # (no single launch writes all of dX: the ReLU mask below stays a launch of its own)
             else:
-                rec = self.emit_dgrads(l.name, [self.dgrad_desc(l, gtop, gbot, self.state(gbot) == "full")], [l.bottoms[0]])
+                rec = self.emit_dgrads(l.name, [self.dgrad_desc(l, gtop, gbot, acc, i) for i in range(ng)], [l.bottoms[0]] * ng)
             self.mark(gbot, rec)
 
     def _concat_module(self, whole: str) -> None:
@@ -338,7 +377,8 @@ class BackwardPlanner:
         for m in members:
             lm = self._conv_of(m)
             gb = G.get(lm.bottoms[0])
-            if gb is None or lm.name not in self.flip_layout or self.state(gb) != "none" or any(gb.buf.ptr == tb for tb in targets):
+            if gb is None or lm.name not in self.flip_layout or self.state(gb) != "none" or any(gb.buf.ptr == tb for tb in targets) \
+                    or self.e._conv_groups(lm) != 1:
                 continue
             items.append(self.dgrad_desc(lm, G[m], gb, False))
             names.append(lm.name)
@@ -377,6 +417,46 @@ class BackwardPlanner:
                 self.relu_ops[q.tops[0]] = self.relu_bwd_op(q.name, self.B[q.tops[0]], G[q.tops[0]])
                 self.relu_done.add(q.tops[0])
         self.emit_wgrads(sibs, [G[q.tops[0]] for q in sibs])
+
+    # ------------------------------------------------------------------ InnerProduct
+    def _inner_product(self, l: Layer) -> None:
+        """The weight-streaming kernels of csrc/inner_product.hip at M <= FCN_IP_MAX_ROWS rows: dW / db from the layer's input rows and
+        dY, dX = dY x bank.  Rows of the bottom and of its gradient are H*W*cstride floats apart and the bank holds zeros in the columns
+        of the pad channels, so pad channels of dX and pad columns of dW come out zero: the solver, weight decay and clipping run over
+        the packed buffer as it is."""
+        gtop = self._arrived(l)
+        if gtop is None:
+            return
+        e, lib, top = self.e, self.lib, l.tops[0]
+        xb = self.B[l.bottoms[0]]
+        m, c, h, w = xb.nchw
+        k, n_out = h * w * xb.cstride, gtop.channels
+        if m > L.IP_MAX_ROWS:
+            raise NotImplementedError("InnerProduct %s: a batch of %d rows (the streaming kernels take at most %d)" % (l.name, m, L.IP_MAX_ROWS))
+        if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
+            self.relu_bwd_op(l.name, self.B[top], gtop)      # the layer's own in-place ReLU, on dY first
+            self.relu_done.add(top)
+        if e._learns(l) and l.name not in self.wgrad_done:
+            dw = e._grad_view(l.name, 0)
+            db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
+            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_inner_product_bwd_weights_f32(
+                xb.buf.ptr, k, gtop.buf.ptr, gtop.cstride, gtop.coffset, dw.ptr, db, m, k, n_out, 0, st)),
+                2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out))
+            self._book_wgrad(op, None, [l.name], [])
+        gbot = self.G.get(l.bottoms[0])
+        if gbot is None:
+            return
+        if gbot.coffset or gbot.cstride != xb.cstride or gbot.cstride != _r4(c):      # (storage.param_layout refused the forward's already)
+            raise NotImplementedError("InnerProduct %s: the gradient of the bottom %s is a channel window of a wider buffer" % (l.name, l.bottoms[0]))
+        # the slabs of bwd_data are NOT the weight gradients' workspace: those launches run on the second stream at the same time
+        self.ip_ws_bytes = max(self.ip_ws_bytes, int(lib.fcn_inner_product_workspace_bytes(m, k, n_out)))
+        flags = L.CONV_ACCUM if self.state(gbot) == "full" else 0
+        wptr = e.params_dev[l.name][0].ptr
+        self.ops.append(Op("inner_product_bwd", l.name, lambda st: L.check(lib.fcn_inner_product_bwd_data_f32(
+            gtop.buf.ptr, gtop.cstride, gtop.coffset, wptr, gbot.buf.ptr, k, m, k, n_out, flags,
+            e._ip_ws.ptr if e._ip_ws is not None else None, st)),
+            2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out)))
+        self.mark(gbot)
 
     # ------------------------------------------------------------------ the other layers that look at the plan state themselves
     def _slice(self, l: Layer) -> None:
@@ -484,14 +564,27 @@ class BackwardPlanner:
         emit(l, gtop, gbot, acc)
 
     def _pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
-        if str(l.sub("pooling_param").get("pool", "MAX")) != "MAX":
-            raise NotImplementedError("backward of AVE pooling (%s)" % l.name)
+        pp = l.sub("pooling_param")
+        if str(pp.get("pool", "MAX")) == "AVE":
+            return self._ave_pooling(l, gtop, gbot, acc, bool(pp.get("global_pooling", False)))
+        if str(pp.get("pool", "MAX")) != "MAX":
+            raise NotImplementedError("backward of %s pooling (%s)" % (pp.get("pool"), l.name))
         g, lib, idx = self.e._geom(l), self.lib, self.e.aux_dev[l.name]
         rec = PoolBwd(l.bottoms[0])      # _finish_dgrads may fold a ReLU backward into this pass
         self.ops.append(Op("maxpool_bwd", l.name, lambda st: L.check(lib.fcn_maxpool_bwd_mask_f32(
             gtop.buf.ptr, idx.ptr, gbot.buf.ptr, g.n, g.h, g.w, g.cin, gbot.cstride, gbot.coffset, g.k, g.s, g.pad, g.oh, g.ow,
             gtop.cstride, gtop.coffset, acc, rec.mask[0], rec.mask[1], rec.mask[2], st))))
         self.mark(gbot, rec)
+
+    def _ave_pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int, global_pooling: bool) -> None:
+        """fcn_avepool_bwd_f32: a gather, one lane per 16-byte channel group of a dX pixel (global pooling: the forward's k = H, stride 1)."""
+        g, lib = self.e._geom(l, (gbot.shape[2], 1, 0) if global_pooling else None), self.lib
+        if gtop.coffset % 4 or gtop.cstride % 4 or gbot.coffset % 4 or gbot.cstride % 4:
+            raise NotImplementedError("backward of AVE pooling %s: a gradient view that is not 16-byte aligned" % l.name)
+        self.ops.append(Op("avepool_bwd", l.name, lambda st: L.check(lib.fcn_avepool_bwd_f32(
+            gtop.buf.ptr, gbot.buf.ptr, g.n, g.h, g.w, g.cin, gbot.cstride, gbot.coffset, g.k, g.s, g.pad, g.oh, g.ow,
+            gtop.cstride, gtop.coffset, acc, st)), 0.0, 4.0 * (gtop.pixels + gbot.pixels * (1 + acc)) * g.cin))
+        self.mark(gbot)
 
     def _crop(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
         """dX of bottom 0: dY inside the window and zeros outside in one launch, or += dY inside it when dX already holds a gradient.
@@ -523,7 +616,7 @@ class BackwardPlanner:
             raise NotImplementedError("dropout backward into an already written gradient")
         e, lib = self.e, self.lib
         ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
-        n, c, h, w = self.B[l.bottoms[0]].shape
+        n, c, h, w = self.B[l.bottoms[0]].nchw
         salt = dropout_layer_salt(self.spec, l)      # the mask the forward launch of this layer drew
         self.ops.append(Op("dropout_bwd", l.name, lambda st: L.check(lib.fcn_dropout_f32(
             gtop.buf.ptr, gbot.buf.ptr, n, c, h, w, gtop.cstride, gtop.coffset, gbot.cstride, gbot.coffset, ratio,

@@ -1075,6 +1075,50 @@ __global__ __launch_bounds__(512) void maxpool_bwd_patch_kernel(const float* __r
     *dst = g;
 }
 
+// AVE pool backward in gather form: a lane owns one 16-byte channel group of one dX pixel and adds dY[oy][ox] / divisor(oy, ox) over
+// the windows that contain the pixel, in ascending (oy, ox) order - one writer per element, no atomics, the same bits every call.
+// divisor: Caffe's pool_size, the window clipped to the PADDED extent (what avepool_kernel divides by).  Lanes run over
+// (pixel, channel group) with the group fastest: a wave reads and writes consecutive 16-byte pieces.  The last group of a C that is
+// no multiple of 4 loads its 16 bytes whole (they lie inside the pixel: strides and offsets are multiples of 4) and stores C % 4 floats.
+__global__ __launch_bounds__(256) void avepool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int N, int H, int W, int C,
+                                                          int dx_cstride, int dx_coffset, int k, int stride, int pad, int OH, int OW,
+                                                          int dy_cstride, int dy_coffset, int accumulate) {
+    const unsigned C4 = ((unsigned)C + 3u) >> 2;
+    const unsigned total = (unsigned)N * H * W * C4;
+    for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
+        const unsigned pix = t / C4;
+        const int c = (int)(t - pix * C4) * 4;
+        const unsigned row = pix / (unsigned)W;
+        const int ix = (int)(pix - row * (unsigned)W);
+        const int n = (int)(row / (unsigned)H);
+        const int iy = (int)(row - (unsigned)n * (unsigned)H);
+        // outputs whose window covers (iy, ix): oy*stride - pad <= iy < oy*stride - pad + k (none when stride > k skips the pixel)
+        const int oy_lo = max(0, (iy + pad - k + stride) / stride), oy_hi = min(OH - 1, (iy + pad) / stride);
+        const int ox_lo = max(0, (ix + pad - k + stride) / stride), ox_hi = min(OW - 1, (ix + pad) / stride);
+        v4f g = {0.f, 0.f, 0.f, 0.f};
+        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+            const int hs = oy * stride - pad;
+            const int hh = min(hs + k, H + pad) - hs;
+            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                const int ws = ox * stride - pad;
+                const float area = (float)(hh * (min(ws + k, W + pad) - ws));
+                const v4f d = *reinterpret_cast<const v4f*>(dy + ((size_t)(n * OH + oy) * OW + ox) * dy_cstride + dy_coffset + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e] += d[e] / area;
+            }
+        }
+        float* dst = dx + (size_t)pix * dx_cstride + dx_coffset + c;
+        if (c + 4 <= C) {
+            if (accumulate) g += *reinterpret_cast<const v4f*>(dst);
+            *reinterpret_cast<v4f*>(dst) = g;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 3; ++e)
+                if (e < C - c) dst[e] = accumulate ? g[e] + dst[e] : g[e];
+        }
+    }
+}
+
 // LRN backward: dX = dY*scale^-beta - (2 alpha beta / n) * X * sum_{window} (dY * Y / scale)
 __global__ __launch_bounds__(256) void lrn_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ scale,
                                                       const float* __restrict__ dy, float* __restrict__ dx, long long pixels, int C,
@@ -1976,6 +2020,28 @@ int fcn_maxpool_bwd_f32(const float* dy, const int32_t* idx, float* dx, int N, i
                         int stride, int pad, int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s) {
     return fcn_maxpool_bwd_mask_f32(dy, idx, dx, N, H, W, C, dx_cstride, dx_coffset, k, stride, pad, OH, OW, dy_cstride, dy_coffset, accumulate,
                                     nullptr, 0, 0, s);
+}
+
+int fcn_avepool_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int k, int stride, int pad,
+                        int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s) {
+    FCN_REQUIRE(dy && dx, FCN_E_ARG, "avepool_bwd: null pointer");
+    FCN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && OH > 0 && OW > 0, FCN_E_ARG,
+                "avepool_bwd: non-positive extent");
+    FCN_REQUIRE((long long)(OH - 1) * stride - pad < H && (long long)(OW - 1) * stride - pad < W, FCN_E_ARG,
+                "avepool_bwd: last window starts outside the image (OH/OW too large)");
+    FCN_REQUIRE(dx_coffset >= 0 && dy_coffset >= 0 && dx_cstride >= dx_coffset + C && dy_cstride >= dy_coffset + C, FCN_E_ARG,
+                "avepool_bwd: channel slice out of range");
+    FCN_REQUIRE(dx_cstride % 4 == 0 && dx_coffset % 4 == 0 && dy_cstride % 4 == 0 && dy_coffset % 4 == 0, FCN_E_ALIGN,
+                "avepool_bwd: channel strides and offsets must be multiples of 4 floats");
+    FCN_REQUIRE((((uintptr_t)dy | (uintptr_t)dx) & 15) == 0, FCN_E_ALIGN, "avepool_bwd: dy and dx must be 16-byte aligned");
+    const long long work = (long long)N * H * W * ((C + 3) / 4);
+    FCN_REQUIRE(work < (1ll << 31) && (long long)N * OH * OW * dy_cstride < (1ll << 31) && (long long)N * H * W * dx_cstride < (1ll << 31) &&
+                    (long long)k * k < (1ll << 24) && (long long)(OH - 1) * stride + k < (1ll << 30) && (long long)(OW - 1) * stride + k < (1ll << 30),
+                FCN_E_UNSUPPORTED, "avepool_bwd: a view past 2^31 elements or a window past 2^24 pixels");
+    hipLaunchKernelGGL(avepool_bwd_kernel, dim3(stream_grid(work, 256)), dim3(256), 0, as_stream(s), dy, dx, N, H, W, C, dx_cstride, dx_coffset,
+                       k, stride, pad, OH, OW, dy_cstride, dy_coffset, accumulate);
+    FCN_LAUNCH_CHECK("avepool_bwd");
+    return 0;
 }
 
 int fcn_deconv_depthwise_bwd_f32(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int dx_cstride, int k, int stride,

@@ -433,10 +433,14 @@ class Engine:
         k, s, pad = ksp or kernel_stride_pad(l.sub("pooling_param" if l.type == "Pooling" else "convolution_param"))
         return ConvGeom(n, cin, h, w, cout, oh, ow, k, s, pad)
 
-    def _conv_desc(self, l: Layer, fused_relu: bool, sig_top: Optional[str]) -> L.ConvDesc:
-        g = self._geom(l)
-        if int(l.sub("convolution_param").get("group", 1)) != 1:
-            raise NotImplementedError("grouped Convolution (layer %s, group %d): the grouped launch for it is not built yet" % (l.name, int(l.sub("convolution_param").get("group", 1))))
+    def _conv_groups(self, l: Layer) -> int:
+        """`group` of a Convolution (storage.conv_groups decided, and refused, when the parameters were laid out)."""
+        return int(l.sub("convolution_param").get("group", 1)) if l.type == "Convolution" else 1
+
+    def _conv_desc(self, l: Layer, fused_relu: bool, sig_top: Optional[str], group: int = 0) -> L.ConvDesc:
+        """The descriptor of convolution l, or of its group `group`: a group is an ordinary problem of Cin/g inputs and Cout/g outputs
+        whose x, bank, bias and y_coffset are advanced to the group's channels and rows (storage.conv_groups)."""
+        g, ng = self._geom(l), self._conv_groups(l)
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
         eps = 16 // xb.esize
         if xb.coffset % eps or xb.cstride % eps:
@@ -455,7 +459,17 @@ class Engine:
         if sig_top:
             flags |= L.CONV_SIGMOID2
         pd = self.params_dev[l.name]
-        d = conv_desc(xb, yb, g._replace(cin=_ra(g.cin, xb.esize)), pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, flags)
+        cin_g, cout_g = g.cin // ng, g.cout // ng
+        d = conv_desc(xb, yb, g._replace(cin=_ra(cin_g, xb.esize), cout=cout_g), pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, flags)
+        if ng > 1:
+            if sig_top or self._folded_shift(l) or cout_g % (16 // yb.esize):
+                raise NotImplementedError("grouped Convolution %s: a fused Sigmoid, a folded input shift or output groups of %d channels "
+                                          "that split a 16-byte segment of the top" % (l.name, cout_g))
+            d.x += xb.esize * group * cin_g
+            d.w += xb.esize * group * cout_g * g.k * g.k * cin_g
+            if d.bias:
+                d.bias += 4 * group * cout_g
+            d.y_coffset += group * cout_g
         if sig_top:
             sb = self.blobs[sig_top]
             if sb.esize != 4:
@@ -511,11 +525,16 @@ class Engine:
             if t == "Convolution":
                 top = l.tops[0]
                 fused_relu, sig_top = self._fused_after(li, l, skip)
-                g = self._geom(l)
-                tasks.append(ConvTask(l, self._conv_desc(l, fused_relu, sig_top), g.flops,
-                                      4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout),
-                                      reads=[self._range(l.bottoms[0])],
-                                      writes=[self._range(top)] + ([self._range(sig_top)] if sig_top else [])))
+                g, ng = self._geom(l), self._conv_groups(l)
+                # a grouped layer is `group` ordinary problems of one level: each reads and writes its own channels, and together they
+                # carry 1/group of the dense layer's FLOPs and weight bytes
+                cin_g, cout_g = g.cin // ng, g.cout // ng
+                (xp, xlo, _), (yp, ylo, _) = self._range(l.bottoms[0]), self._range(top)
+                for i in range(ng):
+                    tasks.append(ConvTask(l, self._conv_desc(l, fused_relu, sig_top, i), g.flops / (ng * ng),
+                                          4.0 * (g.n * cin_g * g.h * g.w + g.n * cout_g * g.oh * g.ow + cout_g * cin_g * g.k * g.k + cout_g),
+                                          reads=[(xp, xlo + i * cin_g, xlo + (i + 1) * cin_g)],
+                                          writes=[(yp, ylo + i * cout_g, ylo + (i + 1) * cout_g)] + ([self._range(sig_top)] if sig_top else [])))
                 self._conv_layer_meta[l.name] = dict(relu=fused_relu, sigmoid_top=sig_top)
                 continue
             if t == "InnerProduct":

@@ -14,6 +14,11 @@ lr/decay multipliers) as
 
 tests/test_models.py checks that equivalence layer by layer whenever /root/reference is present.
 
+``caffenet`` / ``goturn_tracker`` / ``bvlc_googlenet`` are not files of the reference either: they emit the structure of the published
+BVLC reference CaffeNet, of the GOTURN tracker (Held, Thrun, Savarese: "Learning to Track at 100 FPS with Deep Regression Networks")
+and of BVLC GoogLeNet with its auxiliary heads - the nets the reference's curation scripts run through pycaffe and the net its
+detector body is fine-tuned from.
+
 ``voc_fcn32s`` / ``voc_fcn16s`` / ``voc_fcn8s`` are not reference nets: they emit the structure of the published FCN nets for
 PASCAL VOC (Long, Shelhamer, Darrell: "Fully Convolutional Networks for Semantic Segmentation") - VGG16 with ``pad: 100`` on
 conv1_1, convolutional fc6 / fc7, group-1 Deconvolution upsampling and ``Crop`` layers aligning the skip connections and the
@@ -92,29 +97,43 @@ def _lrn(w: _Writer, name: str, bottom: str) -> None:
     w.layer(name, "LRN", [bottom], [name], "  lrn_param { local_size: 5 alpha: 0.0001 beta: 0.75 }")
 
 
-def _googlenet_body(w: _Writer, data_blob: str) -> str:
-    w.layer("deploy_transform", "Power", [data_blob], ["transformed_data"], "  power_param { shift: -127.0 }")
-    _conv_relu(w, "conv1/7x7_s2", "conv1/relu_7x7", "transformed_data", 64, 7, 3, 2)
+def _googlenet_body(w: _Writer, data_blob: str, bvlc_div: int = 0):
+    """GoogLeNet v1 to the last inception module.  bvlc_div 0: the DetectNet body (input shift, no pool4, Dropout behind inception_5b),
+    returns its last blob.  bvlc_div d > 0: the body of BVLC GoogLeNet at widths / d - no input shift, pool4/3x3_s2 behind
+    inception_4e, no Dropout - returns (last blob, the taps of the auxiliary heads behind inception_4a and inception_4d)."""
+    wd = (lambda c: max(c // bvlc_div, 1)) if bvlc_div else (lambda c: c)
+    taps: List[str] = []
+    if not bvlc_div:
+        w.layer("deploy_transform", "Power", [data_blob], ["transformed_data"], "  power_param { shift: -127.0 }")
+        data_blob = "transformed_data"
+    _conv_relu(w, "conv1/7x7_s2", "conv1/relu_7x7", data_blob, wd(64), 7, 3, 2)
     _pool(w, "pool1/3x3_s2", "conv1/7x7_s2", 3, 2)
     _lrn(w, "pool1/norm1", "pool1/3x3_s2")
-    _conv_relu(w, "conv2/3x3_reduce", "conv2/relu_3x3_reduce", "pool1/norm1", 64, 1)
-    _conv_relu(w, "conv2/3x3", "conv2/relu_3x3", "conv2/3x3_reduce", 192, 3, 1)
+    _conv_relu(w, "conv2/3x3_reduce", "conv2/relu_3x3_reduce", "pool1/norm1", wd(64), 1)
+    _conv_relu(w, "conv2/3x3", "conv2/relu_3x3", "conv2/3x3_reduce", wd(192), 3, 1)
     _lrn(w, "conv2/norm2", "conv2/3x3")
     _pool(w, "pool2/3x3_s2", "conv2/norm2", 3, 2)
     prev = "pool2/3x3_s2"
     for mod, c1, c3r, c3, c5r, c5, cp in INCEPTION:
-        _conv_relu(w, mod + "/1x1", mod + "/relu_1x1", prev, c1, 1)
-        _conv_relu(w, mod + "/3x3_reduce", mod + "/relu_3x3_reduce", prev, c3r, 1)
-        _conv_relu(w, mod + "/3x3", mod + "/relu_3x3", mod + "/3x3_reduce", c3, 3, 1)
-        _conv_relu(w, mod + "/5x5_reduce", mod + "/relu_5x5_reduce", prev, c5r, 1)
-        _conv_relu(w, mod + "/5x5", mod + "/relu_5x5", mod + "/5x5_reduce", c5, 5, 2)
+        _conv_relu(w, mod + "/1x1", mod + "/relu_1x1", prev, wd(c1), 1)
+        _conv_relu(w, mod + "/3x3_reduce", mod + "/relu_3x3_reduce", prev, wd(c3r), 1)
+        _conv_relu(w, mod + "/3x3", mod + "/relu_3x3", mod + "/3x3_reduce", wd(c3), 3, 1)
+        _conv_relu(w, mod + "/5x5_reduce", mod + "/relu_5x5_reduce", prev, wd(c5r), 1)
+        _conv_relu(w, mod + "/5x5", mod + "/relu_5x5", mod + "/5x5_reduce", wd(c5), 5, 2)
         _pool(w, mod + "/pool", prev, 3, 1, 1)
-        _conv_relu(w, mod + "/pool_proj", mod + "/relu_pool_proj", mod + "/pool", cp, 1)
+        _conv_relu(w, mod + "/pool_proj", mod + "/relu_pool_proj", mod + "/pool", wd(cp), 1)
         w.layer(mod + "/output", "Concat", [mod + "/1x1", mod + "/3x3", mod + "/5x5", mod + "/pool_proj"], [mod + "/output"])
         prev = mod + "/output"
         if mod == "inception_3b":
             _pool(w, "pool3/3x3_s2", prev, 3, 2)
             prev = "pool3/3x3_s2"
+        if bvlc_div and mod in ("inception_4a", "inception_4d"):
+            taps.append(prev)
+        if bvlc_div and mod == "inception_4e":
+            _pool(w, "pool4/3x3_s2", prev, 3, 2)
+            prev = "pool4/3x3_s2"
+    if bvlc_div:
+        return prev, taps
     w.layer("pool5/drop_s1", "Dropout", [prev], ["pool5/drop_s1"], "  dropout_param { dropout_ratio: 0.4 }")
     return "pool5/drop_s1"
 
@@ -442,3 +461,149 @@ def voc_fcn8s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] =
     """The published FCN-8s: as voc_fcn16s to fuse_pool4, then upscore_pool4 (k4 s2), score_pool3 on pool3 cropped to it at offset 9,
     their sum, upscore8 (k16 s8) and score = Crop(upscore8, data) at offset 31."""
     return _voc_fcn(8, phase, num_classes, shape, width_div, fc_div, fillers)
+
+
+# ----------------------------------------------------------------------
+# BVLC reference CaffeNet, the GOTURN tracker, BVLC GoogLeNet
+# ----------------------------------------------------------------------
+
+def _strip_fillers(text: str) -> str:
+    return "\n".join(ln for ln in text.split("\n") if "_filler" not in ln) + ("\n" if text.endswith("\n") else "")
+
+
+def _inputs(w: _Writer, phase: str, batch: int, images: Sequence[str], size: int, label: Optional[Tuple[str, Sequence[int]]]) -> None:
+    for nm in images:
+        w.layer(nm, "Input", [], [nm], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, size, size))
+    if label is not None and phase != "DEPLOY":
+        w.layer(label[0], "Input", [], [label[0]], "  input_param { shape { %s } }" % " ".join("dim: %d" % d for d in label[1]))
+
+
+def _cn_conv(w: _Writer, name: str, relu: str, bottom: str, num_output: int, k: int, pad: int, stride: int, group: int, bias: float,
+             frozen: bool) -> None:
+    mult = ("  param { lr_mult: 0 decay_mult: 0 }\n  param { lr_mult: 0 decay_mult: 0 }" if frozen
+            else "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }")
+    geo = ["    num_output: %d" % num_output] + (["    pad: %d" % pad] if pad else []) + ["    kernel_size: %d" % k] + \
+          (["    group: %d" % group] if group != 1 else []) + (["    stride: %d" % stride] if stride != 1 else [])
+    body = "%s\n  convolution_param {\n%s\n    weight_filler { type: \"gaussian\" std: 0.01 }\n    bias_filler { type: \"constant\" value: %g }\n  }" % (
+        mult, "\n".join(geo), bias)
+    w.layer(name, "Convolution", [bottom], [name], body)
+    w.layer(relu, "ReLU", [name], [name])
+
+
+def _cn_fc(w: _Writer, name: str, bottom: str, num_output: int, std: float, bias: float, relu: Optional[str] = None, drop: Optional[str] = None,
+           ratio: float = 0.5, filler: str = "gaussian") -> None:
+    fill = '    weight_filler { type: "xavier" }' if filler == "xavier" else '    weight_filler { type: "gaussian" std: %g }' % std
+    w.layer(name, "InnerProduct", [bottom], [name], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  inner_product_param {\n    num_output: %d\n%s\n    bias_filler { type: \"constant\" value: %g }\n  }" % (num_output, fill, bias))
+    if relu:
+        w.layer(relu, "ReLU", [name], [name])
+    if drop:
+        w.layer(drop, "Dropout", [name], [name], "  dropout_param { dropout_ratio: %g }" % ratio)
+
+
+def _caffenet_tower(w: _Writer, data_blob: str, suffix: str, width_div: int, frozen: bool) -> str:
+    """conv1 .. pool5 of CaffeNet (pooling before normalisation, conv2 / conv4 / conv5 in two groups); layer and blob names + suffix."""
+    wd = lambda c: max(c // width_div, 1)
+    n = lambda nm: nm + suffix
+    lrn = "  lrn_param { local_size: 5 alpha: 0.0001 beta: 0.75 }"
+    pool = "  pooling_param { pool: MAX kernel_size: 3 stride: 2 }"
+    _cn_conv(w, n("conv1"), n("relu1"), data_blob, wd(96), 11, 0, 4, 1, 0.0, frozen)
+    w.layer(n("pool1"), "Pooling", [n("conv1")], [n("pool1")], pool)
+    w.layer(n("norm1"), "LRN", [n("pool1")], [n("norm1")], lrn)
+    _cn_conv(w, n("conv2"), n("relu2"), n("norm1"), wd(256), 5, 2, 1, 2, 1.0, frozen)
+    w.layer(n("pool2"), "Pooling", [n("conv2")], [n("pool2")], pool)
+    w.layer(n("norm2"), "LRN", [n("pool2")], [n("norm2")], lrn)
+    _cn_conv(w, n("conv3"), n("relu3"), n("norm2"), wd(384), 3, 1, 1, 1, 0.0, frozen)
+    _cn_conv(w, n("conv4"), n("relu4"), n("conv3"), wd(384), 3, 1, 1, 2, 1.0, frozen)
+    _cn_conv(w, n("conv5"), n("relu5"), n("conv4"), wd(256), 3, 1, 1, 2, 1.0, frozen)
+    w.layer(n("pool5"), "Pooling", [n("conv5")], [n("pool5")], pool)
+    return n("pool5")
+
+
+def _check_phase(phase: str) -> None:
+    if phase not in ("TRAIN", "TEST", "DEPLOY"):
+        raise ValueError("phase must be 'TRAIN', 'TEST' or 'DEPLOY'")
+
+
+def caffenet(phase: str = "DEPLOY", batch: int = 10, num_classes: int = 1000, width_div: int = 1, fc_div: Optional[int] = None,
+             size: int = 227, fillers: bool = True) -> str:
+    """BVLC reference CaffeNet: conv1 11x11 / s4, pool1, norm1, conv2 (group 2), pool2, norm2, conv3, conv4 (group 2), conv5 (group 2), pool5,
+    fc6, fc7 (ReLU, Dropout 0.5), fc8.  TRAIN ends in SoftmaxWithLoss over an (N,) `label`, TEST adds Accuracy, DEPLOY takes `data`
+    alone and ends in Softmax `prob`.  width_div / fc_div divide the convolution widths and the 4096 of fc6 / fc7, size is the image
+    edge (tests); fillers=False leaves the fillers out."""
+    _check_phase(phase)
+    w = _Writer()
+    w.raw('name: "CaffeNet"')
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch,)))
+    feat = _caffenet_tower(w, "data", "", width_div, False)
+    fc = max(4096 // (fc_div or width_div), 1)
+    _cn_fc(w, "fc6", feat, fc, 0.005, 1.0, "relu6", "drop6")
+    _cn_fc(w, "fc7", "fc6", fc, 0.005, 1.0, "relu7", "drop7")
+    _cn_fc(w, "fc8", "fc7", num_classes, 0.01, 0.0)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["fc8"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["fc8", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["fc8", "label"], ["loss"])
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def goturn_tracker(phase: str = "DEPLOY", batch: int = 1, width_div: int = 1, fc_div: Optional[int] = None, size: int = 227,
+                   fillers: bool = True) -> str:
+    """The GOTURN tracker: two frozen CaffeNet towers, conv1 .. pool5 on `image` (the search region) and conv1_p .. pool5_p on `target`,
+    their Concat, fc6-new, fc7-new, fc7-newb (ReLU, Dropout 0.5) and fc8-shapes: the 4 corner coordinates.  TRAIN and TEST add the
+    (N, 4) `bbox` input and L1Loss against it."""
+    _check_phase(phase)
+    w = _Writer()
+    w.raw('name: "GOTURN"')
+    _inputs(w, phase, batch, ["image", "target"], size, ("bbox", (batch, 4)))
+    a = _caffenet_tower(w, "image", "", width_div, True)
+    b = _caffenet_tower(w, "target", "_p", width_div, True)
+    w.layer("concat", "Concat", [a, b], ["pool5_concat"], "  concat_param { axis: 1 }")
+    fc = max(4096 // (fc_div or width_div), 1)
+    _cn_fc(w, "fc6-new", "pool5_concat", fc, 0.005, 1.0, "relu6", "drop6")
+    _cn_fc(w, "fc7-new", "fc6-new", fc, 0.005, 1.0, "relu7", "drop7")
+    _cn_fc(w, "fc7-newb", "fc7-new", fc, 0.005, 1.0, "relu7b", "drop7b")
+    _cn_fc(w, "fc8-shapes", "fc7-newb", 4, 0.01, 0.0)
+    if phase != "DEPLOY":
+        w.layer("loss", "L1Loss", ["fc8-shapes", "bbox"], ["loss"])
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def _googlenet_aux_head(w: _Writer, tag: str, tap: str, num_classes: int, div: int, fc_div: int) -> None:
+    """loss1/* / loss2/*: AVE 5x5 / s3, 1x1 convolution to 128, fc 1024 (ReLU, Dropout 0.7), classifier, SoftmaxWithLoss at weight 0.3."""
+    n = lambda nm: "%s/%s" % (tag, nm)
+    w.layer(n("ave_pool"), "Pooling", [tap], [n("ave_pool")], "  pooling_param { pool: AVE kernel_size: 5 stride: 3 }")
+    _conv_relu(w, n("conv"), n("relu_conv"), n("ave_pool"), max(128 // div, 1), 1)
+    _cn_fc(w, n("fc"), n("conv"), max(1024 // fc_div, 1), 0.0, 0.2, n("relu_fc"), n("drop_fc"), 0.7, filler="xavier")
+    _cn_fc(w, n("classifier"), n("fc"), num_classes, 0.0, 0.0, filler="xavier")
+    w.layer(n("loss"), "SoftmaxWithLoss", [n("classifier"), "label"], [n(tag)], extra="  loss_weight: 0.3")
+
+
+def bvlc_googlenet(phase: str = "DEPLOY", batch: int = 10, num_classes: int = 1000, aux: bool = True, width_div: int = 1,
+                   fc_div: Optional[int] = None, size: int = 224, fillers: bool = True) -> str:
+    """BVLC GoogLeNet, the net the detector body (googlenet_detectnet_*) is fine-tuned from: the same inception stack with pool4/3x3_s2
+    behind inception_4e, then pool5/7x7_s1 (AVE), Dropout 0.4 and loss3/classifier.  TRAIN adds (aux=True) the auxiliary heads
+    loss1/* behind inception_4a and loss2/* behind inception_4d, each a SoftmaxWithLoss at loss_weight 0.3, and loss3/loss3; TEST adds
+    loss3/top-1 and loss3/top-5 Accuracy; DEPLOY takes `data` alone and ends in Softmax `prob`.  width_div divides every convolution
+    width, fc_div (default: width_div) the 1024 of the auxiliary fc layers."""
+    _check_phase(phase)
+    w = _Writer()
+    w.raw('name: "GoogleNet"')
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch,)))
+    feat, taps = _googlenet_body(w, "data", bvlc_div=width_div)
+    if phase == "TRAIN" and aux:
+        _googlenet_aux_head(w, "loss1", taps[0], num_classes, width_div, fc_div or width_div)
+        _googlenet_aux_head(w, "loss2", taps[1], num_classes, width_div, fc_div or width_div)
+    w.layer("pool5/7x7_s1", "Pooling", [feat], ["pool5/7x7_s1"], "  pooling_param { pool: AVE kernel_size: 7 stride: 1 }")
+    w.layer("pool5/drop_7x7_s1", "Dropout", ["pool5/7x7_s1"], ["pool5/7x7_s1"], "  dropout_param { dropout_ratio: 0.4 }")
+    _cn_fc(w, "loss3/classifier", "pool5/7x7_s1", num_classes, 0.0, 0.0, filler="xavier")
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["loss3/classifier"], ["prob"])
+    else:
+        w.layer("loss3/loss3", "SoftmaxWithLoss", ["loss3/classifier", "label"], ["loss3/loss3"], extra="  loss_weight: 1")
+        if phase == "TEST":
+            w.layer("loss3/top-1", "Accuracy", ["loss3/classifier", "label"], ["loss3/top-1"])
+            w.layer("loss3/top-5", "Accuracy", ["loss3/classifier", "label"], ["loss3/top-5"], "  accuracy_param { top_k: 5 }")
+    return w.text() if fillers else _strip_fillers(w.text())

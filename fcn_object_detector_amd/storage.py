@@ -252,6 +252,7 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
             if i == 0 and l.type == "Convolution":
                 esize = views[l.bottoms[0]].esize          # element type of the layer's input: 16-byte segments of it
                 co, ci, kh, kw = host_shape
+                conv_groups(l, co, ci, esize)
                 kind, shape = CONV, (co, kh, kw, _ra(ci, esize))
             elif i == 0 and l.type == "InnerProduct":
                 # the bottom must be a whole buffer: a row of it is then the layer's input vector as it lies in memory
@@ -283,6 +284,24 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
                                  float(l.decay_mult[i] if i < len(l.decay_mult) else 1.0), count * esize, esize, bottom))
             off += _r4((count * esize + 3) // 4)
     return segs, off
+
+
+def conv_groups(l: Layer, cout: int, cin_g: int, esize: int) -> int:
+    """`group` of a Convolution whose blob is (cout, cin_g, k, k).  A (Cout, Cin/g, k, k) blob lies as [Cout][kh][kw][ra(Cin/g)]: group i's
+    bank is the contiguous run of rows i*Cout/g .. (i+1)*Cout/g, an ordinary OHWI bank, PROVIDED the group's channels start on a
+    16-byte segment of the bottom and of the top - Cin/g and Cout/g whole numbers of segments (4 floats / 8 halves).  Anything else
+    is refused here, by layer name (depthwise convolution among them)."""
+    g = int(l.sub("convolution_param").get("group", 1))
+    if g == 1:
+        return 1
+    eps = 16 // esize
+    if g < 1 or cout % g:
+        raise ValueError("Convolution %s: group %d does not divide num_output %d" % (l.name, g, cout))
+    if cin_g % eps or (cout // g) % eps:
+        raise NotImplementedError("grouped Convolution %s: group %d leaves %d input and %d output channels per group, not whole 16-byte "
+                                  "segments (%d %s)%s" % (l.name, g, cin_g, cout // g, eps, "floats" if esize == 4 else "halves",
+                                                          ": depthwise convolution has no kernel here" if cin_g == 1 else ""))
+    return g
 
 
 def ip_pack_bank(w: np.ndarray, c: int, h: int, wd: int, cstride: int, dtype=F32) -> np.ndarray:

@@ -192,13 +192,14 @@ class TrainEngine(Engine):
         self.need_grad = need
         roots: Dict[int, DeviceBuffer] = {}      # activation buffer address -> gradient buffer
         for name, b in self.blobs.items():
-            if name not in need or len(b.shape) != 4:
+            if name not in need or b.nchw is None:
                 continue
             gb = roots.get(b.buf.ptr)
             if gb is None:
                 gb = DeviceBuffer(b.buf.nbytes, zero=True)
                 roots[b.buf.ptr] = gb
             g = Blob(name, b.shape)
+            g.rows = b.rows
             g.buf, g.coffset, g.cstride = gb, b.coffset, b.cstride
             self.grad_blobs[name] = g
 
@@ -244,7 +245,7 @@ class TrainEngine(Engine):
     def _build_backward(self) -> None:
         plan = BackwardPlanner(self)
         plan.run()
-        self.bwd_ops, self._ws = plan.ops, plan.ws
+        self.bwd_ops, self._ws, self._ip_ws = plan.ops, plan.ws, plan.ip_ws
         self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
             self.tuner.wgrad_cfgs(self.bwd_ops)
@@ -289,7 +290,7 @@ class TrainEngine(Engine):
             out = set()
             layers = self.spec.layers
             for li, l in enumerate(layers):
-                if l.type == "Convolution" and self._conv_layer_meta.get(l.name, {}).get("relu"):
+                if l.type in ("Convolution", "InnerProduct") and self._conv_layer_meta.get(l.name, {}).get("relu"):
                     top = l.tops[0]
                     for nxt in layers[li + 1:]:
                         if top in nxt.bottoms or top in nxt.tops:
@@ -660,11 +661,11 @@ class TrainEngine(Engine):
     def read_grad(self, name: str) -> np.ndarray:
         """NCHW host copy of a blob's gradient (debug / tests)."""
         g = self.grad_blobs[name]
-        n, c, h, w = g.shape
+        n, c, h, w = g.nchw
         raw = np.empty((n, h, w, g.cstride), F32)
         L.call("fcn_memcpy_d2h_async", raw.ctypes.data, g.buf.ptr, raw.nbytes, self.stream)
         L.call("fcn_stream_sync", self.stream)
-        return np.ascontiguousarray(raw[..., g.coffset:g.coffset + c].transpose(0, 3, 1, 2))
+        return np.ascontiguousarray(raw[..., g.coffset:g.coffset + c].transpose(0, 3, 1, 2)).reshape(g.shape)
 
     def save(self, path: str) -> None:
         params = self.download_params()

@@ -228,7 +228,7 @@ class Tuner:
         the first real backward pass, which overwrites them."""
         ncfg = int(L.load().fcn_conv2d_wgrad_num_configs())
         for op in ops:
-            if op.kind != "wgrad":
+            if op.kind != "wgrad" or op.sel is None:      # (an InnerProduct weight gradient has one form: nothing to choose)
                 continue
 
             def select(cfg: int) -> bool:

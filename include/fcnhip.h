@@ -479,6 +479,16 @@ int  fcn_maxpool_bwd_f32(const float* dy, const int32_t* idx, float* dx, int N, 
 int  fcn_maxpool_bwd_mask_f32(const float* dy, const int32_t* idx, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset,
                               int k, int stride, int pad, int OH, int OW, int dy_cstride, int dy_coffset, int accumulate,
                               const float* relu_y, int relu_y_cstride, int relu_y_coffset, fcn_stream_t s);
+/* AVE pool backward (Caffe PoolingLayer, pool: AVE), the argument list of fcn_maxpool_bwd_f32 without idx:
+ * dX[n][iy][ix][c] (+)= sum over the windows (oy, ox) that contain (iy, ix), in ascending (oy, ox) order, of dY[n][oy][ox][c] / divisor(oy, ox),
+ * divisor = the window clipped to the padded extent, what fcn_avepool_fwd_f32 divides by.  A gather with one writer per element and no
+ * atomics: the same call gives the same bits.  Pixels under no window (stride > k) get zero, or stay as they are with accumulate; only
+ * channels dx_coffset .. dx_coffset + C - 1 are written (C need not be a multiple of 4).
+ * Contract: null pointers, non-positive extents, negative pad, a last window that starts outside the image, a negative offset or a
+ * slice wider than its stride FCN_E_ARG; dx_cstride, dx_coffset, dy_cstride or dy_coffset not a multiple of 4 floats, dy or dx off
+ * 16 bytes FCN_E_ALIGN; a view past 2^31 elements FCN_E_UNSUPPORTED.  Every check precedes the first HIP call. */
+int  fcn_avepool_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset,
+                         int k, int stride, int pad, int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
 int  fcn_lrn_bwd_f32(const float* x, const float* y, const float* scale, const float* dy, float* dx, int pixels, int C,
                      int x_cstride, int y_cstride, int local_size, float alpha, float beta, int accumulate, fcn_stream_t s);
 /* Dropout (TRAIN): y = x * mask / (1 - ratio); mask of element (n,c,h,w) = hash(NCHW index, seed) >= ratio * 2^32.
@@ -660,9 +670,7 @@ int  fcn_inner_product_fwd_f32(const float* x, int x_rstride, const float* w, co
 /* x, w and y hold half floats, float32 accumulation and bias; flags: FCN_CONV_RELU | FCN_CONV_OUT_F32 (y is float32) | FCN_IP_WEIGHTS_NT */
 int  fcn_inner_product_fwd_f16(const void* x, int x_rstride, const void* w, const float* bias, void* y, int y_cstride, int y_coffset,
                                int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
-/* The two backward entry points are complete and guard-tested, but NO ENGINE CALLS THEM YET: the training planner has no
- * InnerProduct entry (a training net with such a layer is refused by layer name).  Their signatures may still change with that
- * emitter - it applies the layer's own ReLU mask to dY before these calls and may need a channel offset on dX.
+/* The two backward entry points (the training planner applies the layer's own ReLU mask to dY before these calls).
  * dX[m][k] (+)= sum_n dY[m][n] * w[n][k];  flags: FCN_CONV_ACCUM adds into dX (gradient fan-in) */
 int  fcn_inner_product_bwd_data_f32(const float* dy, int dy_cstride, int dy_coffset, const float* w, float* dx, int dx_rstride,
                                     int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);

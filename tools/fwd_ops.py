@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""GPU: per-launch HIP-event times of one forward of the deploy net.  usage: python tools/fwd_ops.py batch f32|f16"""
+"""GPU: per-launch HIP-event times of one forward of a deploy net.  usage: python tools/fwd_ops.py batch f32|f16 [builder]
+builder: googlenet_detectnet_deploy (default), caffenet, goturn_tracker or bvlc_googlenet (their DEPLOY form)."""
 import os
 import sys
 
@@ -14,11 +15,15 @@ from fcn_object_detector_amd.netspec import NetSpec, fill_params  # noqa: E402
 
 def main():
     n, dtype = int(sys.argv[1]), sys.argv[2]
-    msg = proto.parse_text(models.googlenet_detectnet_deploy(batch=n))
+    builder = sys.argv[3] if len(sys.argv) > 3 else "googlenet_detectnet_deploy"
+    fn = getattr(models, builder)
+    msg = proto.parse_text(fn(batch=n) if builder == "googlenet_detectnet_deploy" else fn("DEPLOY", batch=n))
     spec = NetSpec(msg, "TEST")
     spec.infer()
     eng = Engine(NetSpec(msg, "TEST"), params=fill_params(spec, seed=1234), device=0, dtype=dtype)
-    eng.host_array("data")[...] = np.random.default_rng(0).random((n, 3, 448, 448), dtype=np.float32)
+    rng = np.random.default_rng(0)
+    for nm in eng.inputs:
+        eng.host_array(nm)[...] = rng.random(eng.shapes[nm], dtype=np.float32)
     eng.upload_inputs()
     eng.forward_resident(2, use_graph=False)
     rows = eng.time_ops(reps=10)
@@ -28,6 +33,8 @@ def main():
         print("%-10s %-64s %8.1f us %7.1f TF/s %7.1f GB/s" % (kind, name[:64], ms * 1e3, fl / ms / 1e9 if ms else 0, by / ms / 1e6 if ms else 0))
         by_kind[kind] = by_kind.get(kind, 0.0) + ms
     print("total %.3f ms  " % tot + "  ".join("%s %.3f" % kv for kv in sorted(by_kind.items(), key=lambda kv: -kv[1])))
+    if "inner_product" in by_kind:
+        print("inner_product share of the forward: %.1f %%" % (100.0 * by_kind["inner_product"] / tot))
     eng.close()
 
 
