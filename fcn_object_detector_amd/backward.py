@@ -59,6 +59,7 @@ class BackwardPlanner:
         # layer types that look at the plan state themselves ...
         self.emitters = {"Convolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
                          "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": nothing,
+                         "BatchNorm": self._batchnorm, "Scale": self._batchnorm,
                          "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
                          "Accuracy": nothing,      # a metric: no gradient, no entry in loss_blobs
                          **{t: nothing for t in DATA_TYPES}}
@@ -548,6 +549,75 @@ class BackwardPlanner:
             d = conv_desc(gtop, gbot, gs, e.params_dev[l.name][0].ptr, flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
             e._keep.append(d)
             self.mark(gbot, self.emit_dgrads(l.name, [(d, flops)], [l.bottoms[0]]))
+
+    # ------------------------------------------------------------------ BatchNorm / Scale / ReLU chains
+    def _batchnorm(self, l: Layer) -> None:
+        """Backward of the chain that starts at l (engine._bn_chain_after; a Scale or ReLU absorbed into a chain has no entry and emits
+        nothing): one reduce launch - sum dy' and sum dy' x-hat per channel, dy' = dY under the chain's ReLU mask - and one apply launch
+        dX (+)= gamma invstd (dy' - sum dy' / m - x-hat sum dy' x-hat / m).  With a Scale the two sums ARE d(beta) and d(gamma) and go
+        straight to its gradient views; the launch is on the main stream (it shares the forward's workspace) and names its layer, so
+        the data-parallel exchange of that bucket waits for it.  With global statistics (a frozen BatchNorm) and for Scale alone the
+        apply launch degenerates to dX (+)= gamma invstd dy', and the reduce launch runs only for a Scale that learns."""
+        e, lib, B, G = self.e, self.lib, self.B, self.G
+        ch = e._bn_chains.get(l.name)
+        if ch is None:
+            return
+        gtop = G.get(ch.y)
+        if gtop is None or self.state(gtop) == "none":
+            return
+        gbot = G.get(ch.x)
+        xb, yb = B[ch.x], B[ch.y]
+        pix, c = xb.pixels, xb.channels
+        for g in (gtop, gbot):
+            if g is not None and (g.coffset % 4 or g.cstride % 4):
+                raise NotImplementedError("backward of %s %s: a gradient view that is not 16-byte aligned" % (l.type, l.name))
+        aux = e.aux_dev.get(l.name)
+        if aux is not None:
+            hat = (aux.ptr, _r4(c), 0)
+        elif ch.bn is None:
+            hat = (xb.buf.ptr, xb.cstride, xb.coffset)      # Scale alone, not in place: its input is still there
+        else:
+            raise RuntimeError("BatchNorm %s kept no x-hat for its backward pass" % l.name)
+        mask = (yb.buf.ptr, yb.cstride, yb.coffset) if ch.relu is not None else (None, 0, 0)
+        learns = ch.scale is not None and e._learns(ch.scale) and ch.scale.name not in self.wgrad_done
+        centred = ch.bn is not None and not ch.global_stats
+        sums = (None, None)
+        booked = None      # the launch the exchange of the Scale's bucket waits for: the LAST one that touches its gradient views
+        if learns or (centred and gbot is not None):
+            if ch.save is None:      # (Scale alone: nothing was saved in the forward pass)
+                ch.save = DeviceBuffer(4 * _r4(c) * 4, zero=True)
+                e._keep.append(ch.save)
+            dbeta, dgamma = ch.save.ptr + 8 * _r4(c), ch.save.ptr + 12 * _r4(c)
+            if learns:
+                dgamma = e._grad_view(ch.scale.name, 0).ptr
+                if len(e.params_dev[ch.scale.name]) > 1:      # (without a bias blob the sum of dy' has no gradient view to go to)
+                    dbeta = e._grad_view(ch.scale.name, 1).ptr
+                self.wgrad_done.add(ch.scale.name)
+            booked = Op("bn_bwd_reduce", l.name, lambda st: L.check(lib.fcn_batchnorm_bwd_reduce_f32(
+                gtop.buf.ptr, hat[0], mask[0], pix, c, gtop.cstride, gtop.coffset, hat[1], hat[2], mask[1], mask[2], dbeta, dgamma,
+                e._bn_ws.ptr, st)), 3.0 * pix * c, (8.0 + (4.0 if mask[0] else 0.0)) * pix * c)
+            self.ops.append(booked)
+            if centred:
+                sums = (dbeta, dgamma)
+        if gbot is None:
+            if learns:
+                booked.layers = [ch.scale.name]
+            return
+        acc = 1 if self.state(gbot) == "full" and gbot is not gtop else 0
+        save = ch.save.ptr if centred else None
+        bvar, bfac, eps = None, None, 0.0
+        if ch.bn is not None:
+            eps = float(ch.bn.sub("batch_norm_param").get("eps", 1e-5))
+            if not centred:
+                bvar, bfac = e.params_dev[ch.bn.name][1].ptr, e.params_dev[ch.bn.name][2].ptr
+        gamma = e.params_dev[ch.scale.name][0].ptr if ch.scale is not None else None
+        self.ops.append(Op("bn_bwd_apply", l.name, lambda st: L.check(lib.fcn_batchnorm_bwd_apply_f32(
+            gtop.buf.ptr, hat[0] if centred else None, mask[0], gbot.buf.ptr, pix, c, gtop.cstride, gtop.coffset, hat[1], hat[2], mask[1], mask[2],
+            gbot.cstride, gbot.coffset, save, bvar, bfac, eps, gamma, sums[0], sums[1], acc, st)),
+            4.0 * pix * c, (8.0 + (4.0 if centred else 0.0) + (4.0 if mask[0] else 0.0) + 4.0 * acc) * pix * c))
+        if learns:      # (the apply launch reads the two sums where the reduce launch left them: the exchange must not sum them before)
+            self.ops[-1].layers = [ch.scale.name]
+        self.mark(gbot)
 
     # ------------------------------------------------------------------ one bottom, one top, one launch dY -> dX
     def _one_bottom(self, l: Layer) -> None:

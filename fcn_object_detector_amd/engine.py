@@ -22,7 +22,7 @@ import ctypes as C
 import os
 import threading
 from collections import namedtuple
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -30,7 +30,7 @@ import numpy as np
 from . import lib as L
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, crop_window, kernel_stride_pad
+from .netspec import Layer, NetSpec, bn_global_stats, crop_window, kernel_stride_pad
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -232,6 +232,21 @@ class OpTask:
 Task = Union[ConvTask, OpTask]
 
 
+@dataclass(eq=False)
+class BnChain:
+    """A fused run BatchNorm -> Scale -> ReLU (any part may be missing, BatchNorm or Scale comes first): x the blob it reads, y the
+    one it writes, mids the tops in between that the fused launch never writes.  save: mean, invstd and the two backward sums of a
+    BatchNorm, 4 x r4(C) floats."""
+    x: str
+    y: str
+    bn: Optional[Layer] = None
+    scale: Optional[Layer] = None
+    relu: Optional[Layer] = None
+    mids: List[str] = field(default_factory=list)
+    save: Optional["DeviceBuffer"] = None
+    global_stats: bool = False
+
+
 def ranges_hit(a: Sequence[Range], b: Sequence[Range]) -> bool:
     return any(x[0] == y[0] and x[1] < y[2] and y[1] < x[2] for x in a for y in b)
 
@@ -300,7 +315,10 @@ class Engine:
         self._keep: List[object] = []
         self._conv_layer_meta: Dict[str, dict] = {}
         self._group_workspaces: List[DeviceBuffer] = []      # workspaces of prepared launch groups (released on close)
-        self.aux_dev: Dict[str, DeviceBuffer] = {}      # TRAIN: pooling argmax / LRN scale kept for backward
+        self.aux_dev: Dict[str, DeviceBuffer] = {}      # TRAIN: pooling argmax / LRN scale / BatchNorm x-hat kept for backward
+        self._bn_chains: Dict[str, BnChain] = {}        # first layer of a BatchNorm / Scale / ReLU chain -> the chain
+        self._bn_ws_bytes = 0                           # the largest fcn_batchnorm_workspace_bytes over the net's layers
+        self._bn_ws: Optional[DeviceBuffer] = None
         self._lazy_blob_ops: Dict[str, List[Op]] = {}   # blobs that fused launches do not write -> the launches that do
         self.loss_blobs: Dict[str, float] = {}          # loss top -> loss_weight
         self.device_fed: set = set()             # input blobs a producer writes straight into HBM (device scene renderer): never uploaded
@@ -510,6 +528,98 @@ class Engine:
             return False, cons[0].tops[0]
         return False, None
 
+    def _bn_chain_after(self, li: int, l: Layer, skip: set) -> "BnChain":
+        """The chain BatchNorm -> Scale -> ReLU (negative_slope 0) that starts at layer l (a BatchNorm or a Scale): a link joins while it
+        is the first layer after its predecessor that touches the predecessor's top, and - when it writes a top of its own - the only
+        consumer of that blob, which is no output of the net (the fused launch never writes it).  In place (the ResNet prototxts) and
+        with separate tops (the reference's commented-out pairs).  Absorbed layers join `skip`, like _relu_after's."""
+        ch = BnChain(l.bottoms[0], l.tops[0])
+        setattr(ch, "bn" if l.type == "BatchNorm" else "scale", l)
+        last = l
+        want = ["Scale", "ReLU"] if l.type == "BatchNorm" else ["ReLU"]
+        while self.fuse and want:
+            top = last.tops[0]
+            nxt = next((q for q in self.spec.layers[self.spec.layers.index(last) + 1:] if top in q.bottoms or top in q.tops), None)
+            if nxt is None or nxt.type not in want or nxt.bottoms != [top] or len(nxt.tops) != 1:
+                break
+            if nxt.type == "ReLU" and float(nxt.sub("relu_param").get("negative_slope", 0.0)) != 0.0:
+                break
+            if nxt.tops[0] != top and ([q.name for q in self.consumers.get(top, [])] != [nxt.name] or top in self.outputs
+                                       or len(self.producers.get(top, [])) != 1 or top in self.alias or nxt.tops[0] in self.alias):
+                break
+            if nxt.tops[0] != top:
+                ch.mids.append(top)
+            setattr(ch, "scale" if nxt.type == "Scale" else "relu", nxt)
+            skip.add(nxt.name)
+            ch.y = nxt.tops[0]
+            last = nxt
+            want = want[want.index(nxt.type) + 1:]
+        return ch
+
+    def _bn_apply_op(self, name: str, xb: Blob, yb: Blob, ch: "BnChain", scale: bool, relu: bool, xhat: Optional[DeviceBuffer]) -> Op:
+        """One launch y = relu?(gamma * (x - mean) * invstd + beta) of the chain ch (csrc/batchnorm.hip), any of its parts left out."""
+        lib = L.load()
+        pix, c = xb.pixels, xb.channels
+        bn = self.params_dev[ch.bn.name] if ch.bn is not None else None
+        sc = self.params_dev[ch.scale.name] if scale and ch.scale is not None else None
+        eps = float(ch.bn.sub("batch_norm_param").get("eps", 1e-5)) if ch.bn is not None else 0.0
+        save = ch.save.ptr if ch.save is not None and not ch.global_stats else None
+        blobs = [v.ptr for v in bn] if bn is not None and save is None else [None, None, None]
+        gamma, beta = (sc[0].ptr if sc else None), (sc[1].ptr if sc and len(sc) > 1 else None)
+        if xb.esize == 2:
+            return Op("bn_apply", name, lambda st: L.check(lib.fcn_batchnorm_apply_f16(
+                xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, *blobs, eps, gamma, beta, int(relu), st)),
+                4.0 * pix * c, 4.0 * pix * c)
+        hp = xhat.ptr if xhat is not None else None
+        return Op("bn_apply", name, lambda st: L.check(lib.fcn_batchnorm_apply_f32(
+            xb.buf.ptr, yb.buf.ptr, hp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), save, *blobs, eps, gamma, beta,
+            int(relu), st)), 4.0 * pix * c, (8.0 + (4.0 if hp else 0.0)) * pix * c)
+
+    def _fwd_batchnorm(self, ch: "BnChain") -> List[Op]:
+        """Forward of a BatchNorm / Scale / ReLU chain: in TRAIN with batch statistics the statistics launch (which also moves the three
+        blobs: part of every TRAIN forward, inside the step graph) and ONE apply launch; otherwise the apply launch alone, which takes
+        mean and invstd from the blobs in its prologue - a TEST engine that shares a training net's blobs sees the current averages.
+        TRAIN keeps x-hat (for Scale alone in place: its input) in aux_dev, as pooling keeps its argmax."""
+        lib, B = L.load(), self.blobs
+        first = ch.bn or ch.scale
+        xb, yb = B[ch.x], B[ch.y]
+        if xb.nchw is None or xb.shape != yb.shape:
+            raise NotImplementedError("%s %s on a blob that is neither 4-d nor 2-d" % (first.type, first.name))
+        if xb.esize != yb.esize or any(B[m].esize != xb.esize for m in ch.mids):
+            raise NotImplementedError("f16 engine: %s %s between half and float32 blobs" % (first.type, first.name))
+        eps_g = 16 // xb.esize
+        if xb.coffset % eps_g or yb.coffset % eps_g or xb.cstride % eps_g or yb.cstride % eps_g:
+            raise NotImplementedError("%s %s: a channel window that is not 16-byte aligned" % (first.type, first.name))
+        pix, c = xb.pixels, xb.channels
+        ch.global_stats = ch.bn is not None and bn_global_stats(ch.bn, self.spec.phase)
+        if xb.esize == 2 and ch.bn is not None and not ch.global_stats:
+            raise NotImplementedError("f16 engine: BatchNorm %s with batch statistics (half floats are inference only)" % ch.bn.name)
+        train = self.spec.phase == "TRAIN"
+        ops: List[Op] = []
+        name = "+".join(q.name for q in (ch.bn, ch.scale, ch.relu) if q is not None)
+        if ch.bn is not None and (train or not ch.global_stats):
+            # mean, invstd, then (backward, BatchNorm without a learning Scale) sum dy', sum dy' x-hat: four runs of C floats
+            ch.save = DeviceBuffer(4 * _r4(c) * 4, zero=True)
+            self._keep.append(ch.save)
+        if train or (ch.bn is not None and not ch.global_stats):      # one workspace for every reducing launch of the net, forward and backward
+            self._bn_ws_bytes = max(self._bn_ws_bytes, int(lib.fcn_batchnorm_workspace_bytes(pix, c)))
+        if ch.bn is not None and not ch.global_stats:
+            f = float(ch.bn.sub("batch_norm_param").get("moving_average_fraction", 0.999))
+            eps = float(ch.bn.sub("batch_norm_param").get("eps", 1e-5))
+            bm, bv, bf = (v.ptr for v in self.params_dev[ch.bn.name])
+            ops.append(Op("bn_stats", ch.bn.name, lambda st: L.check(lib.fcn_batchnorm_stats_f32(
+                xb.buf.ptr, pix, c, xb.cstride, xb.coffset, bm, bv, bf, f, eps, ch.save.ptr, self._bn_ws.ptr, st)), 6.0 * pix * c, 8.0 * pix * c))
+        xhat = None
+        need = getattr(self, "need_grad", None)
+        if train and (need is None or ch.y in need) and (ch.bn is not None or ch.x == ch.y):
+            xhat = self.aux_dev[first.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
+        ops.append(self._bn_apply_op(name, xb, yb, ch, True, ch.relu is not None, xhat))
+        # the tops in the middle of a chain with separate tops own a buffer that the fused launch leaves alone: read_blob() fills it on demand
+        for m in ch.mids:
+            self._lazy_blob_ops[m] = [self._bn_apply_op(m, xb, B[m], ch, ch.scale is not None and m in ch.scale.tops, False, None)]
+        self._bn_chains[first.name] = ch
+        return ops
+
     def _collect_tasks(self) -> List[Task]:
         """Layer list -> tasks with read/write sets: one per convolution (a descriptor for the grouped launches) and one per
         other layer that launches anything (its ops)."""
@@ -542,6 +652,10 @@ class Engine:
                 self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
                 tasks.append(OpTask(l, self._fwd_inner_product(l, relu), reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])]))
                 continue
+            if t in ("BatchNorm", "Scale"):
+                ch = self._bn_chain_after(li, l, skip)
+                tasks.append(OpTask(l, self._fwd_batchnorm(ch), reads=[self._range(ch.x)], writes=[self._range(ch.y)]))
+                continue
             if t == "Concat" and l.name not in self.copy_concats:
                 continue      # producers already wrote their slices
             if t == "Slice" and l.name not in self.copy_slices:
@@ -562,6 +676,8 @@ class Engine:
         Tasks on one level are mutually independent; all convolutions of a level share ONE grouped launch
         (an inception module becomes {1x1, 3x3_reduce, 5x5_reduce} then {3x3, 5x5, pool_proj})."""
         tasks = self._collect_tasks()
+        if self._bn_ws_bytes:
+            self._bn_ws = DeviceBuffer(self._bn_ws_bytes, zero=False)
         if self.fuse and self.spec.phase == "TEST" and os.environ.get("FCN_FUSE_POOL_LRN", "1") != "0":
             tasks = self._fuse_pool_lrn(tasks)
         levels = task_levels(tasks, self.group_convs)
@@ -861,7 +977,7 @@ class Engine:
         """The launches of one layer that is not a convolution."""
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop"):
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
@@ -945,6 +1061,16 @@ class Engine:
         """ReLU, Sigmoid and Power as layers of their own."""
         lib, t = L.load(), l.type
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if halves:
+            # a ReLU of its own over halves (on the Eltwise tops of a ResNet): the BatchNorm / Scale apply launch with every operand
+            # NULL is y = relu(x), exactly
+            if float(l.sub("relu_param").get("negative_slope", 0.0)) != 0.0 or xb.esize != 2 or yb.esize != 2 or xb.nchw is None \
+                    or xb.coffset % 8 or yb.coffset % 8:
+                raise NotImplementedError("f16 engine: ReLU %s with a negative slope, between half and float32 blobs or on an unaligned window" % l.name)
+            pix, c = xb.pixels, xb.channels
+            return [Op("relu", l.name, lambda st: L.check(lib.fcn_batchnorm_apply_f16(
+                xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, None, None, None, 0.0, None, None, 1, st)),
+                0.0, 4.0 * pix * c)]
         if xb.coffset or yb.coffset or xb.cstride != yb.cstride:
             raise NotImplementedError("%s on a channel slice (layer %s)" % (t, l.name))
         count = xb.pixels * xb.cstride

@@ -250,6 +250,12 @@ PROTOTYPES = {
     "fcn_inner_product_fwd_f16": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
     "fcn_inner_product_bwd_data_f32": (_i, [_vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "fcn_inner_product_bwd_weights_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 4 + [_vp]),
+    "fcn_batchnorm_workspace_bytes": (_sz, [_i, _i]),
+    "fcn_batchnorm_stats_f32": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "fcn_batchnorm_apply_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
+    "fcn_batchnorm_apply_f16": (_i, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
+    "fcn_batchnorm_bwd_reduce_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _vp]),
+    "fcn_batchnorm_bwd_apply_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

@@ -607,3 +607,91 @@ def bvlc_googlenet(phase: str = "DEPLOY", batch: int = 10, num_classes: int = 10
             w.layer("loss3/top-1", "Accuracy", ["loss3/classifier", "label"], ["loss3/top-1"])
             w.layer("loss3/top-5", "Accuracy", ["loss3/classifier", "label"], ["loss3/top-5"], "  accuracy_param { top_k: 5 }")
     return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# ResNet-50 / 101 / 152 (He et al., "Deep Residual Learning for Image Recognition"; the published Caffe prototxts' names)
+# ----------------------------------------------------------------------
+
+RESNET_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+
+
+def _resnet_block_names(count: int, numbered: bool) -> List[str]:
+    """Block letters of one stage as published: a, b, c ..., or a, b1, b2 ... in stages 3 and 4 of ResNet-101 / 152."""
+    if not numbered:
+        return [chr(ord("a") + i) for i in range(count)]
+    return ["a"] + ["b%d" % i for i in range(1, count)]
+
+
+def _rn_conv_bn(w: _Writer, tag: str, bottom: str, num_output: int, k: int, pad: int, stride: int, phase: str, relu: bool,
+                conv_name: Optional[str] = None, bias: bool = False) -> str:
+    """Convolution `res<tag>` (bias_term: false but for conv1) with BatchNorm `bn<tag>`, Scale `scale<tag>` (bias_term: true) and ReLU
+    `res<tag>_relu` in place on its top; returns the top."""
+    name = conv_name or "res" + tag
+    sfx = tag if conv_name is None else "_" + conv_name
+    geo = "    num_output: %d\n    kernel_size: %d\n    pad: %d\n    stride: %d\n" % (num_output, k, pad, stride)
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / (k * k * num_output)) ** 0.5
+    if bias:
+        fill += "    bias_filler { type: \"constant\" value: 0 }\n"
+    else:
+        geo += "    bias_term: false\n"
+    w.layer(name, "Convolution", [bottom], [name], "  convolution_param {\n%s%s  }" % (geo, fill))
+    stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+    w.layer("bn" + sfx, "BatchNorm", [name], [name], stats)
+    w.layer("scale" + sfx, "Scale", [name], [name], "  scale_param { bias_term: true }")
+    if relu:
+        w.layer(name + "_relu" if conv_name is None else conv_name + "_relu", "ReLU", [name], [name])
+    return name
+
+
+def resnet(phase: str = "DEPLOY", depth: int = 50, batch: int = 1, num_classes: int = 1000, width_div: int = 1, size: int = 224,
+           fillers: bool = True) -> str:
+    """ResNet-50 / 101 / 152 with the published layer and blob names (a downloaded ResNet-50-model.caffemodel maps by name): conv1 7x7 / 2
+    with bias, bn_conv1, scale_conv1, conv1_relu, pool1 MAX 3x3 / 2, the bottleneck stages res2a .. res5c (branch1 on the first block of
+    a stage, branch2a / b / c, bias_term: false, BatchNorm and Scale in place, stride 2 on the first 1x1 convolutions of stages 3 - 5),
+    pool5 AVE 7 (global pooling at other sizes), fc1000 and prob.  use_global_stats: true only in DEPLOY, as published; TRAIN ends in
+    SoftmaxWithLoss over an (N,) `label`, TEST adds Accuracy.  width_div divides every convolution width, size is the image edge (tests)."""
+    _check_phase(phase)
+    if depth not in RESNET_BLOCKS:
+        raise ValueError("depth must be one of %s" % sorted(RESNET_BLOCKS))
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "ResNet-%d"' % depth)
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch,)))
+    _rn_conv_bn(w, "", "data", wd(64), 7, 3, 2, phase, True, conv_name="conv1", bias=True)
+    w.layer("pool1", "Pooling", ["conv1"], ["pool1"], "  pooling_param { pool: MAX kernel_size: 3 stride: 2 }")
+    feat = "pool1"
+    for stage, count in zip((2, 3, 4, 5), RESNET_BLOCKS[depth]):
+        mid, out = wd(64 << (stage - 2)), wd(256 << (stage - 2))
+        for bi, letter in enumerate(_resnet_block_names(count, depth > 50 and stage in (3, 4))):
+            tag = "%d%s" % (stage, letter)
+            stride = 2 if bi == 0 and stage > 2 else 1
+            short = feat if bi else _rn_conv_bn(w, tag + "_branch1", feat, out, 1, 0, stride, phase, False)
+            x = _rn_conv_bn(w, tag + "_branch2a", feat, mid, 1, 0, stride, phase, True)
+            x = _rn_conv_bn(w, tag + "_branch2b", x, mid, 3, 1, 1, phase, True)
+            x = _rn_conv_bn(w, tag + "_branch2c", x, out, 1, 0, 1, phase, False)
+            feat = "res" + tag
+            w.layer(feat, "Eltwise", [short, x], [feat])
+            w.layer(feat + "_relu", "ReLU", [feat], [feat])
+    pool = "kernel_size: 7 stride: 1" if size == 224 else "global_pooling: true"
+    w.layer("pool5", "Pooling", [feat], ["pool5"], "  pooling_param { pool: AVE %s }" % pool)
+    _cn_fc(w, "fc1000", "pool5", num_classes, 0.01, 0.0)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["fc1000"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["fc1000", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["fc1000", "label"], ["loss"])
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def resnet50(phase: str = "DEPLOY", **kw) -> str:
+    return resnet(phase, depth=50, **kw)
+
+
+def resnet101(phase: str = "DEPLOY", **kw) -> str:
+    return resnet(phase, depth=101, **kw)
+
+
+def resnet152(phase: str = "DEPLOY", **kw) -> str:
+    return resnet(phase, depth=152, **kw)

@@ -126,6 +126,12 @@ def _like(nchw: Tuple[int, int, int, int], model: Shape) -> Shape:
     return tuple(nchw) if len(model) == 4 else (nchw[0], nchw[1])
 
 
+def bn_global_stats(l: "Layer", phase: str) -> bool:
+    """BatchNormLayer's use_global_stats: the moving averages normalise (default: in the TEST phase), not the batch's statistics."""
+    v = l.sub("batch_norm_param").get("use_global_stats")
+    return phase == "TEST" if v is None else bool(v)
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 
@@ -266,6 +272,29 @@ class NetSpec:
                     shapes[l.tops[1]] = (bots[0][1],)
             elif t in ("ReLU", "Sigmoid", "Power", "LRN", "Dropout", "Softmax", "TanH"):
                 shapes[l.tops[0]] = bots[0]
+            elif t == "BatchNorm":
+                # Caffe's BatchNormLayer over the channel axis: blobs (C,) mean sum, (C,) variance sum, (1,) scale factor - statistics,
+                # not parameters: the layer insists on lr_mult 0 for each ("Cannot configure batch normalization statistics as layer parameters")
+                if len(bots) != 1 or len(bots[0]) not in (2, 4) or len(l.tops) != 1:
+                    raise ValueError("layer %s: BatchNorm takes one 4-d or 2-d bottom and has one top, got %s" % (l.name, bots))
+                if any(m != 0.0 for m in l.lr_mult):
+                    raise ValueError("layer %s: BatchNorm blobs are statistics, their lr_mult must be 0 (got %s)" % (l.name, l.lr_mult))
+                c = bots[0][1]
+                self.param_shapes[l.name] = [(c,), (c,), (1,)]
+                shapes[l.tops[0]] = bots[0]
+            elif t == "Scale":
+                # Caffe's ScaleLayer with the multiplier as a learned blob over the channel axis: (C,) gamma and, with bias_term, (C,) beta
+                sp = l.sub("scale_param")
+                if len(bots) == 2:
+                    raise NotImplementedError("layer %s: Scale with two bottoms (the multiplier as a blob of the net)" % l.name)
+                if len(bots) != 1 or len(bots[0]) not in (2, 4) or len(l.tops) != 1:
+                    raise ValueError("layer %s: Scale takes one 4-d or 2-d bottom and has one top, got %s" % (l.name, bots))
+                if int(sp.get("axis", 1)) != 1 or int(sp.get("num_axes", 1)) != 1:
+                    raise NotImplementedError("layer %s: Scale over axis %d, num_axes %d (only the channel axis: axis 1, num_axes 1)"
+                                              % (l.name, int(sp.get("axis", 1)), int(sp.get("num_axes", 1))))
+                c = bots[0][1]
+                self.param_shapes[l.name] = [(c,)] + ([(c,)] if bool(sp.get("bias_term", False)) else [])
+                shapes[l.tops[0]] = bots[0]
             elif t == "Crop":
                 if len(bots) != 2 or len(l.tops) != 1:
                     raise ValueError("layer %s: Crop takes two bottoms (the blob and the shape donor) and has one top" % l.name)
@@ -334,9 +363,20 @@ def fill_params(spec: NetSpec, seed: int = 0) -> Dict[str, List[np.ndarray]]:
     """Seeded filler initialisation of every learnable blob, in layer order."""
     rng = np.random.default_rng(seed)
     out: Dict[str, List[np.ndarray]] = {}
+    one = proto.parse_text("type: \"constant\" value: 1")
     for l in spec.param_layers():
-        p = l.sub("inner_product_param" if l.type == "InnerProduct" else "convolution_param")
         shapes = spec.param_shapes[l.name]
+        if l.type == "BatchNorm":      # Caffe sets the three blobs to zero, whatever the prototxt says
+            out[l.name] = [np.zeros(s, np.float32) for s in shapes]
+            continue
+        if l.type == "Scale":          # ScaleLayer: filler defaults to constant 1, bias_filler (BiasLayer's) to constant 0
+            p = l.sub("scale_param")
+            blobs = [fill_blob(shapes[0], p.get("filler") if p.get("filler") is not None else one, rng)]
+            if len(shapes) > 1:
+                blobs.append(fill_blob(shapes[1], p.get("bias_filler"), rng))
+            out[l.name] = blobs
+            continue
+        p = l.sub("inner_product_param" if l.type == "InnerProduct" else "convolution_param")
         blobs = [fill_blob(shapes[0], p.get("weight_filler"), rng)]
         if len(shapes) > 1:
             blobs.append(fill_blob(shapes[1], p.get("bias_filler"), rng))

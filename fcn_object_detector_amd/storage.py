@@ -277,11 +277,13 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
                     raise NotImplementedError("f16 engine: layer type Deconvolution with group 1 (%s) has no half-float kernel" % l.name)
                 else:
                     kind, shape = DECONV, (c, kh, kw, _r4(cog))
-            elif i == 0:
+            elif i == 0 and l.type not in ("BatchNorm", "Scale"):      # (their blobs are per-channel vectors as they are: PLAIN)
                 raise NotImplementedError(l.type)
             count = int(np.prod(shape))
-            segs.append(ParamSeg(l.name, i, kind, off, count, shape, host_shape, float(l.lr_mult[i] if i < len(l.lr_mult) else 1.0),
-                                 float(l.decay_mult[i] if i < len(l.decay_mult) else 1.0), count * esize, esize, bottom))
+            lr, decay = float(l.lr_mult[i] if i < len(l.lr_mult) else 1.0), float(l.decay_mult[i] if i < len(l.decay_mult) else 1.0)
+            if l.type == "BatchNorm":
+                lr = decay = 0.0      # statistics, written by the forward pass alone: the solver never moves them, whatever the prototxt says
+            segs.append(ParamSeg(l.name, i, kind, off, count, shape, host_shape, lr, decay, count * esize, esize, bottom))
             off += _r4((count * esize + 3) // 4)
     return segs, off
 

@@ -168,7 +168,7 @@ class TrainEngine(Engine):
     # ------------------------------------------------------------------ gradient buffers
     def _learns(self, l: Layer) -> bool:
         """True if the solver will move any blob of this layer: Caffe's param_propagate_down (lr_mult != 0)."""
-        if l.name not in self.spec.param_shapes:
+        if l.name not in self.spec.param_shapes or l.type == "BatchNorm":      # (BatchNorm's blobs are statistics: lr_mult 0, forced)
             return False
         n = len(self.spec.param_shapes[l.name])
         return any((l.lr_mult[i] if i < len(l.lr_mult) else 1.0) != 0.0 for i in range(n))
@@ -270,7 +270,7 @@ class TrainEngine(Engine):
                 cur["layers"].append(e.layer)
         wg_index = {}
         for i, op in enumerate(self.bwd_ops):
-            if op.kind == "wgrad":
+            if op.kind == "wgrad" or hasattr(op, "layers"):      # (a main-stream launch that writes parameter gradients names its layers too)
                 for nm in getattr(op, "layers", [op.name]):
                     wg_index[nm] = i
         lib = L.load()
@@ -297,6 +297,7 @@ class TrainEngine(Engine):
                             if nxt.type == "ReLU":
                                 out.add(nxt.name)
                             break
+            out.update(ch.relu.name for ch in self._bn_chains.values() if ch.relu is not None)      # ... or into a BatchNorm / Scale chain
             self._fused_relu_cache = out
         return self._fused_relu_cache
 

@@ -678,6 +678,45 @@ int  fcn_inner_product_bwd_data_f32(const float* dy, int dy_cstride, int dy_coff
 int  fcn_inner_product_bwd_weights_f32(const float* x, int x_rstride, const float* dy, int dy_cstride, int dy_coffset,
                                        float* dw, float* db, int M, int K, int N, int accumulate, fcn_stream_t s);
 
+/* ---- BatchNorm / Scale (Caffe BatchNormLayer, ScaleLayer over the channel axis) on NHWC views (csrc/batchnorm.hip).
+ *      Views are the usual (pixels, C, cstride, coffset); a lane owns one 16-byte channel group of a pixel (4 floats / 8 halves).  Only
+ *      channels coffset .. coffset + C - 1 of a view are ever written (C need not be a multiple of the group: the last group is stored
+ *      in part, as fcn_avepool_bwd_f32 does); whole groups are LOADED, so strides and offsets are multiples of the group.
+ *      Reductions use no atomics: slabs of pixels are folded by one workgroup each, their partial results lie in d_workspace
+ *      (fcn_batchnorm_workspace_bytes(pixels, C) bytes, for both reducing entry points) and a second launch folds them per channel in a
+ *      fixed order (lane l of a wave folds slabs l, l + 64, .. ascending, then the lanes fold by halves).  The same call gives the same bits.
+ *      Contract of all five: null pointers, non-positive extents, a slice outside its pixel, operands that must come together and do not
+ *      FCN_E_ARG; a stride or offset that is no multiple of the group, x / y / dy / dx / xhat / workspace off 16 bytes FCN_E_ALIGN.  Every
+ *      check precedes the first HIP call; all launches are capturable. ---- */
+size_t fcn_batchnorm_workspace_bytes(int pixels, int C);
+/* Batch statistics of a view: save[c] = mean, save[C + c] = 1 / sqrt(var + eps), var = E[(x - mean)^2] (biased), centred per slab and
+ * combined by Chan's formula - never E[x^2] - E[x]^2.  The three blobs (all or none) get Caffe's moving-average step in the same launch:
+ * factor = factor * f + 1, mean_sum = mean_sum * f + mean, var_sum = var_sum * f + var * (m / (m - 1) if m > 1 else 1), m = pixels. */
+int  fcn_batchnorm_stats_f32(const float* x, int pixels, int C, int x_cstride, int x_coffset, float* blob_mean, float* blob_var,
+                             float* blob_factor, float moving_average_fraction, float eps, float* save, void* d_workspace, fcn_stream_t s);
+/* y = relu?(gamma[c] * xhat + beta[c]), xhat = (x - mean[c]) * invstd[c].  mean / invstd: `save` (as fcn_batchnorm_stats_f32 left it), or
+ * computed per channel from the three blobs in the kernel's prologue (global statistics: s = factor == 0 ? 0 : 1 / factor, mean = s *
+ * mean_sum, invstd = 1 / sqrt(s * var_sum + eps)), or (0, 1) when both are NULL (Scale alone).  gamma, beta NULL: 1, 0.  xhat (may be
+ * NULL): a buffer of its own, xhat_cstride floats per pixel, the view's channels at 0.  y may be x. */
+int  fcn_batchnorm_apply_f32(const float* x, float* y, float* xhat, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                             int xhat_cstride, const float* save, const float* blob_mean, const float* blob_var, const float* blob_factor, float eps,
+                             const float* gamma, const float* beta, int relu, fcn_stream_t s);
+/* inference twin: x and y hold halves (groups of 8), the blobs, gamma and beta stay float32, arithmetic in float32 */
+int  fcn_batchnorm_apply_f16(const void* x, void* y, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                             const float* blob_mean, const float* blob_var, const float* blob_factor, float eps, const float* gamma,
+                             const float* beta, int relu, fcn_stream_t s);
+/* sum_dy[c] = sum dy', sum_dyx[c] = sum dy' * xhat over the pixels; dy' = dy where relu_y > 0 and 0 elsewhere (relu_y NULL: dy' = dy).
+ * With a Scale in the chain these are d(beta) and d(gamma); for Scale alone xhat is the layer's input.  Both are overwritten. */
+int  fcn_batchnorm_bwd_reduce_f32(const float* dy, const float* xhat, const float* relu_y, int pixels, int C, int dy_cstride, int dy_coffset,
+                                  int xhat_cstride, int xhat_coffset, int y_cstride, int y_coffset, float* sum_dy, float* sum_dyx,
+                                  void* d_workspace, fcn_stream_t s);
+/* dx (+)= gamma * invstd * (dy' - sum_dy / m - xhat * sum_dyx / m), m = pixels; with the sums NULL (global statistics, Scale alone)
+ * dx (+)= gamma * invstd * dy' and xhat may be NULL.  invstd: save[C + c], or from blob_var / blob_factor / eps, or 1.  dx may be dy. */
+int  fcn_batchnorm_bwd_apply_f32(const float* dy, const float* xhat, const float* relu_y, float* dx, int pixels, int C, int dy_cstride,
+                                 int dy_coffset, int xhat_cstride, int xhat_coffset, int y_cstride, int y_coffset, int dx_cstride, int dx_coffset,
+                                 const float* save, const float* blob_var, const float* blob_factor, float eps, const float* gamma,
+                                 const float* sum_dy, const float* sum_dyx, int accumulate, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */

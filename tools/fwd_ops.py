@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """GPU: per-launch HIP-event times of one forward of a deploy net.  usage: python tools/fwd_ops.py batch f32|f16 [builder]
-builder: googlenet_detectnet_deploy (default), caffenet, goturn_tracker or bvlc_googlenet (their DEPLOY form)."""
+builder: googlenet_detectnet_deploy (default), caffenet, goturn_tracker, bvlc_googlenet or resnet50 / resnet101 / resnet152 (their DEPLOY form)."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """GPU: per-launch timing of one training step (forward ops, backward ops, update) of the DetectNet GoogLeNet net, or of a
-classifier net with Input layers.  usage: python tools/train_profile.py [batch] [caffenet|goturn_tracker|bvlc_googlenet]"""
+classifier net with Input layers.  usage: python tools/train_profile.py [batch] [caffenet|goturn_tracker|bvlc_googlenet|resnet50|resnet101|resnet152]"""
 import os
 import sys
 
@@ -50,7 +50,7 @@ def main():
 
 
 def report(eng):
-    tot, ip = {}, 0.0
+    tot, ip, bn = {}, 0.0, 0.0
     for label, ops in (("fwd", eng.ops), ("bwd", eng.bwd_ops)):
         rows = eng.time_ops(reps=5, ops=ops)
         t = sum(r[2] for r in rows)
@@ -66,9 +66,12 @@ def report(eng):
         for kind, name, ms, fl, by in sorted(rows, key=lambda r: -r[2])[:25]:
             print("      %-12s %-110s %8.1f us %6.1f TF/s" % (kind, name[:110], ms * 1e3, fl / ms / 1e9 if ms else 0))
         tot[label] = t
+        bn += sum(ms for kind, name, ms, fl, by in rows if kind.startswith("bn_"))
         ip += sum(ms for kind, name, ms, fl, by in rows if kind in ("inner_product", "inner_product_bwd") or
                   (kind == "wgrad" and any(l.name == name.split(" ")[0] and l.type == "InnerProduct" for l in eng.spec.layers)))
     print(tot)
+    if bn:
+        print("BatchNorm / Scale launches: %.3f ms, %.1f %% of forward + backward" % (bn, 100.0 * bn / sum(tot.values())))
     if ip:
         print("InnerProduct launches: %.3f ms, %.1f %% of forward + backward" % (ip, 100.0 * ip / sum(tot.values())))
 
