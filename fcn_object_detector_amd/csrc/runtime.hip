@@ -190,4 +190,30 @@ int fcn_graph_destroy(fcn_graph_t g) {
     return 0;
 }
 
+int fcn_stream_create_replica(fcn_stream_t* s, int index) {
+    FCN_REQUIRE(s, FCN_E_ARG, "fcn_stream_create_replica: null");
+    if (index >= 0 && index < FCN_REPLICA_STREAMS) {
+        // numerically LOWER is higher priority; least == greatest on a device without stream priorities
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least) {
+            hipStream_t st = nullptr;
+            if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest) == hipSuccess) {
+                *s = st;
+                return 0;
+            }
+        }
+        (void)hipGetLastError();      // the refusal is answered by the plain stream below, not left behind as a sticky error
+    }
+    return fcn_stream_create(s);
+}
+
+int fcn_stream_is_prioritized(fcn_stream_t s, int* h_yes) {
+    FCN_REQUIRE(s && h_yes, FCN_E_ARG, "fcn_stream_is_prioritized: null");
+    int least = 0, greatest = 0, prio = 0;
+    FCN_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    FCN_HIP(hipStreamGetPriority(as_stream(s), &prio));
+    *h_yes = (greatest < least && prio == greatest) ? 1 : 0;
+    return 0;
+}
+
 }  // extern "C"

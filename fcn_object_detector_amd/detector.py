@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as L
-from .engine import DeviceBuffer, Engine, PinnedArray
+from .engine import DeviceBuffer, Engine, PinnedArray, replica_streams
 
 F32 = np.float32
 
@@ -498,10 +498,11 @@ class DetectorPipeline:
     def __init__(self, make_engine, depth: int = 3, **detector_kw):
         self.detectors: List[FCNObjectDetector] = []
         first = None
-        for _ in range(max(int(depth), 1)):
-            eng = make_engine(first)            # make_engine(tune_from) -> Engine (batch 1)
-            first = first or eng
-            self.detectors.append(FCNObjectDetector(eng, **detector_kw))
+        with replica_streams():                 # the factory's engines take replica streams: a hardware queue each (engine.py)
+            for _ in range(max(int(depth), 1)):
+                eng = make_engine(first)            # make_engine(tune_from) -> Engine (batch 1)
+                first = first or eng
+                self.detectors.append(FCNObjectDetector(eng, **detector_kw))
         self._queue: List[FCNObjectDetector] = []
         self._next = 0
 

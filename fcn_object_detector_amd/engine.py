@@ -42,6 +42,31 @@ def graphs_enabled() -> bool:
     return os.environ.get("FCN_NO_GRAPH", "0") in ("", "0")
 
 
+_replica_ctx = threading.local()
+
+
+class replica_streams:
+    """Context under which every Engine built (by this thread) is a replica of a frame pipeline and takes a replica stream
+    (fcn_stream_create_replica: a hardware queue that the null stream and the process's plain streams do not share), numbered
+    in the order of construction.  For pipelines whose engines come from a caller's factory (DetectorPipeline); lone engines and
+    the training engine's streams stay plain."""
+
+    def __enter__(self) -> "replica_streams":
+        self._outer = getattr(_replica_ctx, "next", None)
+        _replica_ctx.next = 0
+        return self
+
+    def __exit__(self, *exc) -> None:
+        _replica_ctx.next = self._outer
+
+
+def _take_replica_index() -> Optional[int]:
+    i = getattr(_replica_ctx, "next", None)
+    if i is not None:
+        _replica_ctx.next = i + 1
+    return i
+
+
 def dropout_layer_salt(spec: NetSpec, l: Layer) -> int:
     """What the k-th Dropout layer of a net adds to the step's dropout seed: k * 2^28.  The mask is a function of (element index, seed)
     alone, so two Dropout layers of one shape (drop6 / drop7 of the published FCN nets) would otherwise drop the same units in every
@@ -277,8 +302,10 @@ class Engine:
                  params: Optional[Dict[str, List[np.ndarray]]] = None, device: int = 0,
                  fuse: bool = True, group_convs: bool = True, autotune: bool = True, dtype: str = "f32",
                  tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None,
-                 share_params: Optional["Engine"] = None, score_outputs: bool = False):
-        """share_params: Net::ShareTrainedLayersWith - every parameter layer whose name the given engine also has reads that
+                 share_params: Optional["Engine"] = None, score_outputs: bool = False, replica: Optional[int] = None):
+        """replica: this engine is replica number `replica` of a frame pipeline and takes a replica stream (default: the next
+        number of an enclosing `replica_streams()` context, else a plain stream).
+        share_params: Net::ShareTrainedLayersWith - every parameter layer whose name the given engine also has reads that
         engine's flat parameter buffer in place (no copy; a solver step is visible to the next forward of this engine).
         score_outputs: the engine is built for scoring (Solver::Test, `caffe test`): every forward also adds each output blob
         to a device accumulator (score_begin() / forward_score() / score_read())."""
@@ -301,8 +328,15 @@ class Engine:
         self.autotune = autotune
         L.call("fcn_init", device)
         sp = C.c_void_p()
-        L.call("fcn_stream_create", C.byref(sp))
+        self.replica = replica if replica is not None else _take_replica_index()
+        if self.replica is None:
+            L.call("fcn_stream_create", C.byref(sp))
+        else:
+            L.call("fcn_stream_create_replica", C.byref(sp), int(self.replica))
         self.stream = int(sp.value)
+        yes = C.c_int(0)
+        L.call("fcn_stream_is_prioritized", self.stream, C.byref(yes))
+        self.stream_prioritized = bool(yes.value)      # False on a replica: the runtime refused, its queue is shared again
         self.lock = threading.RLock()
         self.shapes = spec.infer(data_shapes)
         self.blobs: Dict[str, Blob] = {}
@@ -1725,8 +1759,10 @@ class ForwardPipeline:
     hands consecutive frames to them round-robin, so the hardware queues interleave the launches of different frames
     How many workgroups of DIFFERENT launches fit on a CU is bounded by LDS, so the replicas' autotuner is restricted to tile
     configurations of at most `max_lds_kb` per workgroup: this costs nothing on a lone stream (2530 frames/s either way) and
-    is worth +20 % once frames overlap.  Measured (enough hardware queues, see lib.load): 2530 frames/s one frame at a time,
-    4000-4130 with three in flight, 4300-4480 with four, 3400 with five.  Per-frame results are those of a lone engine
+    is worth +20 % once frames overlap.  Each replica takes a replica stream (fcn_stream_create_replica): a hardware queue of its
+    own also under the runtime's default limit of four queues.  Measured, kernels only: about 3600 frames/s one frame at a time,
+    4840-4900 with three in flight, 5400-5440 with four at either queue limit (round 3, plain streams and 16 queues: 2530 /
+    4000-4130 / 4300-4480, and 3400 with five - a fifth replica takes a plain stream and has not been measured since).  Per-frame results are those of a lone engine
     with the same tile plan, bit for bit: the replicas run the same kernels on private buffers."""
 
     def __init__(self, make_spec: Callable[[], NetSpec], params: Optional[Dict[str, List[np.ndarray]]] = None, device: int = 0, depth: int = 4,
@@ -1739,7 +1775,8 @@ class ForwardPipeline:
         if max_lds_kb is not None:
             engine_kw.setdefault("tune_max_lds_kb", max_lds_kb)
         for i in range(depth):
-            self.engines.append(Engine(make_spec(), params=params, device=device, tune_from=self.engines[0] if i else None, **engine_kw))
+            self.engines.append(Engine(make_spec(), params=params, device=device, tune_from=self.engines[0] if i else None, replica=i,
+                                       **engine_kw))
         self._pending: List[Engine] = []
         self._next = 0
 

@@ -86,6 +86,7 @@ class ColorParams(C.Structure):
 
 
 GAUSS_MAX_RADIUS = 15
+REPLICA_STREAMS = 4            # FCN_REPLICA_STREAMS
 
 
 class FlipSeg(C.Structure):
@@ -141,6 +142,8 @@ PROTOTYPES = {
     "fcn_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "fcn_graph_launch": (_i, [_vp, _vp]),
     "fcn_graph_destroy": (_i, [_vp]),
+    "fcn_stream_create_replica": (_i, [C.POINTER(_vp), _i]),
+    "fcn_stream_is_prioritized": (_i, [_vp, C.POINTER(_i)]),
     "fcn_nchw_to_nhwc_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "fcn_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fcn_nhwc_to_nchw_multi_f32": (_i, [C.POINTER(LayoutDesc), _i, _vp]),
@@ -280,7 +283,9 @@ def load() -> C.CDLL:
         # not overlap: with 4 queues a fourth replica stream of a frame pipeline aliases another one and throughput DROPS
         # (3460 vs 4300 frames/s), the two-stream training step runs 6.60 vs 6.37 ms; with 8 the node pipeline lost a third
         # of its rate as soon as another pipeline's four idle streams existed (2590 vs 3600 frames/s).  16 covers the
-        # engines a process of this package keeps alive at once; no measured cost against 8.
+        # engines a process of this package keeps alive at once; no measured cost against 8.  (The frame pipelines' replicas no
+        # longer depend on this: fcn_stream_create_replica takes their queues from the pool of another stream priority, which the
+        # default limit of 4 covers.  Plain streams - the training step's two, lone engines - are what the 16 still serves.)
         # An embedding process should export GPU_MAX_HW_QUEUES itself; the variable is only filled in
         # here when nobody has set it and $FCN_SET_HW_QUEUES is not 0 - and that is said once, not done silently.
         global HW_QUEUES
@@ -314,6 +319,15 @@ def load() -> C.CDLL:
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def substitute(obj):
+    """Put `obj` in the loaded library's place (what load() returns) and return what was there: tools that time or count the
+    library's calls wrap the real object and hand it back when they are done (tools/frame_path.py)."""
+    global _lib
+    load()
+    prev, _lib = _lib, obj
+    return prev
 
 
 def check(rc: int) -> None:

@@ -76,6 +76,18 @@ int  fcn_graph_begin(fcn_stream_t s);
 int  fcn_graph_end(fcn_stream_t s, fcn_graph_t* g);
 int  fcn_graph_launch(fcn_graph_t g, fcn_stream_t s);
 int  fcn_graph_destroy(fcn_graph_t g);
+/* The stream of replica `index` of a frame pipeline (several engines of one net, one frame each in flight): non-blocking like
+ * fcn_stream_create's, created at the HIGHEST stream priority the device reports.  The HIP runtime hands out hardware queues from one
+ * pool per priority, each pool as large as the process's queue limit (4 by default): the replicas' streams then share no hardware queue
+ * with the null stream or with the process's plain streams.  All replicas take the same priority, so none outranks another - but they do
+ * outrank the process's plain streams (and work of other processes at normal priority) wherever the hardware arbitrates between queues.
+ * A pool holds as many queues as the limit: replicas 0 .. FCN_REPLICA_STREAMS - 1 (the default limit) take priority streams; a higher or
+ * negative index would only alias a queue inside that pool and takes a plain stream instead, as does every index on a device without
+ * stream priorities or under a runtime that refuses the request.  fcn_stream_is_prioritized reports which kind a stream is (*h_yes = 1:
+ * created at the device's highest priority, and the device has more than one; else 0).  Destroyed with fcn_stream_destroy. */
+#define FCN_REPLICA_STREAMS 4
+int  fcn_stream_create_replica(fcn_stream_t* s, int index);
+int  fcn_stream_is_prioritized(fcn_stream_t s, int* h_yes);
 
 /* ---- blob layout at the pycaffe boundary (blob.data is NCHW) ---- */
 /* dst[n,h,w,dst_coffset + c] = src[n,c,h,w] + shift; dst channel stride dst_cstride.  `shift` lets the
