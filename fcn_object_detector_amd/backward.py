@@ -13,14 +13,15 @@ from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
 from . import storage as S
-from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, tconv_desc
+from .netspec import DATA_TYPES, Layer, crop_window, layer_dilation
 
 
 @dataclass
 class Dgrad:
     """One data-gradient launch, prepared once the whole plan is known: a group of stride-1 passes that write different buffers
-    (ConvDesc, launch: L.ConvGroup) or the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan).
+    (ConvDesc, launch: L.ConvGroup), the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan) or the
+    dilated convolution of dY with the flipped bank of one dilated layer (DConvDesc, launch: L.DConvPlan).
     targets[i]: the blob descs[i] writes."""
     name: str
     descs: list
@@ -110,6 +111,11 @@ class BackwardPlanner:
     def _conv_of(self, blob: str) -> Layer:
         return [q for q in self.e.producers.get(blob, []) if q.type == "Convolution"][0]
 
+    @staticmethod
+    def _dilated(l: Layer) -> bool:
+        """A Convolution that csrc/dconv.hip runs (engine._dconv_task): it stays out of the grouped dense launches."""
+        return l.type == "Convolution" and layer_dilation(l) > 1
+
     def _find_concat_relu(self) -> None:
         """Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch."""
         e, B = self.e, self.B
@@ -118,7 +124,7 @@ class BackwardPlanner:
                 self.concat_members.setdefault(parent, []).append(child)
         for parent, members in self.concat_members.items():
             prods = [[q for q in e.producers.get(m, []) if q.type == "Convolution"] for m in members]
-            if all(len(pr) == 1 and e._conv_layer_meta.get(pr[0].name, {}).get("relu") for pr in prods) and \
+            if all(len(pr) == 1 and e._conv_layer_meta.get(pr[0].name, {}).get("relu") and not self._dilated(pr[0]) for pr in prods) and \
                     sum(B[m].channels for m in members) == B[parent].channels and B[parent].coffset == 0:
                 for m in members:
                     self.concat_relu[m] = parent
@@ -136,6 +142,14 @@ class BackwardPlanner:
             if l.type != "Convolution" or self.G.get(l.bottoms[0]) is None or self.G.get(l.tops[0]) is None:
                 continue
             g, ng = e._geom(l), e._conv_groups(l)
+            if self._dilated(l):      # the data gradient is the same dilated kernel on the flipped bank: stride 1, pad' = dil (k-1) - pad >= 0
+                dil = layer_dilation(l)
+                if g.s != 1:
+                    raise NotImplementedError("dilated Convolution %s: the data gradient of a dilated layer with stride %d (its bottom %s "
+                                              "needs a gradient)" % (l.name, g.s, l.bottoms[0]))
+                if g.pad > dil * (g.k - 1):
+                    raise NotImplementedError("dilated Convolution %s: the data gradient with pad %d above dilation * (kernel - 1) = %d (its "
+                                              "bottom %s needs a gradient)" % (l.name, g.pad, dil * (g.k - 1), l.bottoms[0]))
             cin, cout, k = g.cin // ng, g.cout // ng, g.k      # of one group: its bank is rows i*cout .. of the layer's (storage.conv_groups)
             if g.s == 1:
                 self.flip_layout[l.name] = flip_floats
@@ -240,6 +254,13 @@ class BackwardPlanner:
                     d.flags |= L.CONV_MASK
             self.ops.remove(rop)
         for rec in self.dgrad_records:
+            if isinstance(rec.launch, L.DConvPlan):
+                d = rec.descs[0]
+                dws = DeviceBuffer(int(lib.fcn_dconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+                L.call("fcn_dconv2d_prepare", C.byref(d), 1, dws.ptr, -1, C.byref(rec.launch))
+                e._keep.extend([dws, rec.launch])
+                rec.op.name = "%s [d%d %dwg]" % (rec.name, d.dilation, rec.launch.total_tiles)
+                continue
             if isinstance(rec.launch, L.TConvPlan):
                 d = rec.descs[0]
                 tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
@@ -290,6 +311,8 @@ class BackwardPlanner:
         """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns: one per group, dW and db at
         the group's rows."""
         e, g, xb, ng = self.e, self.e._geom(l), self.B[l.bottoms[0]], self.e._conv_groups(l)
+        if self._dilated(l):
+            raise RuntimeError("wgrad_items is the dense path; dilated layers go through _dilated_convolution (%s)" % l.name)
         if gtop.coffset % 4 or gtop.cstride % 4:
             raise NotImplementedError("gradient view of %s is not 16-byte aligned" % l.tops[0])
         cin_g, cout_g = g.cin // ng, g.cout // ng
@@ -330,10 +353,48 @@ class BackwardPlanner:
             self._book_wgrad(op, sel, names, [int(lib.fcn_conv2d_wgrad_group_workspace_floats_cfg(arr, m, c)) for c in self._wgrad_cfgs()])
 
     # ------------------------------------------------------------------ Convolution
+    def _dilated_convolution(self, l: Layer, gtop: Blob) -> None:
+        """Backward of a Convolution with dilation > 1 (csrc/dconv.hip): the layer's own ReLU mask on dY, the weight gradient on the
+        second stream (one form only: op.sel is None), and dX = the dilated convolution of dY with the flipped bank, stride 1,
+        pad' = dil (k-1) - pad, accumulating where dX already holds a gradient; _finish_dgrads may fold the ReLU mask of the layer
+        below into it, as for a dense pass."""
+        e, G, lib, top = self.e, self.G, self.lib, l.tops[0]
+        g, dil, xb = e._geom(l), layer_dilation(l), self.B[l.bottoms[0]]
+        if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
+            rop = self.relu_bwd_op(l.name, self.B[top], gtop)
+            if top not in e.alias:
+                self.relu_ops[top] = rop
+            self.relu_done.add(top)
+        if e._learns(l) and l.name not in self.wgrad_done:
+            d = dconv_desc(xb, gtop, g, dil)
+            dw = e._grad_view(l.name, 0)
+            db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
+            e._keep.append(d)
+            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_dconv2d_wgrad_f32(C.byref(d), dw.ptr, db, e._ws.ptr, st)), g.flops,
+                    4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout))
+            # (the launch runs on the second stream behind the other weight gradients, never beside them: it shares their workspace)
+            self._book_wgrad(op, None, [l.name], [int(lib.fcn_dconv2d_wgrad_workspace_floats(C.byref(d)))])
+        gbot = G.get(l.bottoms[0])
+        if gbot is None or l.name in self.dgrad_done:
+            return
+        if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(g.cout):
+            raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % top)
+        wt = self.flip_flat.ptr + 4 * self.flip_layout[l.name]
+        dd = dconv_desc(gtop, gbot, g.swapped()._replace(s=1, pad=dil * (g.k - 1) - g.pad), dil, wt,
+                        flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
+        rec = Dgrad(l.name, [dd], [l.bottoms[0]], L.DConvPlan())
+        rec.op = Op("dconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_dconv2d_f32(C.byref(pl), st)), g.flops)
+        self.ops.append(rec.op)
+        self.dgrad_records.append(rec)
+        e._keep.append(dd)
+        self.mark(gbot, rec)
+
     def _convolution(self, l: Layer) -> None:
         gtop = self._arrived(l)
         if gtop is None:
             return
+        if self._dilated(l):
+            return self._dilated_convolution(l, gtop)
         e, G, top = self.e, self.G, l.tops[0]
         if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
             whole = self.concat_relu.get(top)
@@ -401,7 +462,7 @@ class BackwardPlanner:
                 continue
             prods = [q for q in e.producers.get(lm.bottoms[0], []) if q.type == "Convolution"]
             cons = [q for q in e.consumers.get(lm.bottoms[0], []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)]
-            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in e.alias and lm.bottoms[0] in self.G:
+            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in e.alias and lm.bottoms[0] in self.G and not self._dilated(prods[0]):
                 sibs.append(prods[0])
         if len(sibs) > 1:
             for q in sibs:

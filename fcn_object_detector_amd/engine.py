@@ -30,7 +30,7 @@ import numpy as np
 from . import lib as L
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, bn_global_stats, crop_window, kernel_stride_pad
+from .netspec import Layer, NetSpec, bn_global_stats, crop_window, kernel_stride_pad, layer_dilation
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -111,6 +111,19 @@ def tconv_desc(a: "Blob", b: "Blob", g: ConvGeom, bank: int, bias: Optional[int]
     d.Cb, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
     d.b_cstride, d.b_coffset = b.cstride, b.coffset
     d.flags = flags
+    return d
+
+
+def dconv_desc(x: "Blob", y: "Blob", g: ConvGeom, dilation: int, w: Optional[int] = None, bias: Optional[int] = None,
+               flags: int = 0) -> L.DConvDesc:
+    """fcn_dconv_desc: the dilated convolution `g` reading the view x through the OHWI bank w and writing the view y - activations
+    (forward) or gradients (the data-gradient pass on the flipped bank, the weight gradient with y = dY)."""
+    d = L.DConvDesc()
+    d.x, d.w, d.bias, d.y = x.ptr, w, bias, y.buf.ptr
+    d.N, d.H, d.W, d.Cin, d.x_cstride = g.n, g.h, g.w, g.cin, x.cstride
+    d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
+    d.y_cstride, d.y_coffset = y.cstride, y.coffset
+    d.flags, d.dilation = flags, dilation
     return d
 
 
@@ -246,12 +259,14 @@ class ConvTask:
 @dataclass(eq=False)
 class OpTask:
     """Any other layer (or fused run of layers) that launches something: its ops; pool_desc if it is a MAX pooling that can
-    ride in a convolution launch."""
+    ride in a convolution launch; dconv if it is a dilated Convolution (its ops are made when its level is emitted: the dilated
+    convolutions of one level that read one bottom share a launch)."""
     layer: Layer
     ops: List[Op]
     reads: List[Range]
     writes: List[Range]
     pool_desc: Optional[L.PoolDesc] = None
+    dconv: Optional[L.DConvDesc] = None
 
 
 Task = Union[ConvTask, OpTask]
@@ -666,6 +681,9 @@ class Engine:
             t = l.type
             if t in ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data"):
                 continue
+            if t == "Convolution" and layer_dilation(l) > 1:
+                tasks.append(self._dconv_task(li, l, skip))
+                continue
             if t == "Convolution":
                 top = l.tops[0]
                 fused_relu, sig_top = self._fused_after(li, l, skip)
@@ -721,23 +739,67 @@ class Engine:
         order = sorted(range(len(tasks)), key=lambda i: (levels[i], 1 if isinstance(tasks[i], ConvTask) else 0, i))
         pending: List[ConvTask] = []
         pending_pools: List[OpTask] = []
+        pending_dconvs: List[OpTask] = []
         cur = None
         for i in order:
             if levels[i] != cur:
+                self._emit_dconvs(pending_dconvs)
                 self._emit_convs(pending, pending_pools, tail)
-                pending, cur = [], levels[i]
+                pending, pending_dconvs, cur = [], [], levels[i]
             if tail is not None and any(tasks[i] is ht for ht in tail["heads"]):
                 continue      # evaluated by the launches that produce its input
             if isinstance(tasks[i], ConvTask):
                 pending.append(tasks[i])
             elif tasks[i].pool_desc is not None and self.fuse and self.group_convs:
                 pending_pools.append(tasks[i])
+            elif tasks[i].dconv is not None:
+                pending_dconvs.append(tasks[i])
             else:
                 self.ops.extend(tasks[i].ops)
+        self._emit_dconvs(pending_dconvs)
         self._emit_convs(pending, pending_pools, tail)
         self.levels = max(levels) + 1 if levels else 0
         if self.score_outputs:
             self._emit_score_ops()
+
+    def _dconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
+        """A Convolution with dilation > 1: a problem of csrc/dconv.hip, not of the tiled family.  The bank is the layer's parameter
+        blob where it lies; an in-place ReLU behind the layer rides in the epilogue."""
+        dil = layer_dilation(l)
+        if self.f16:
+            raise NotImplementedError("f16 engine: Convolution %s with dilation %d has no half-float kernel" % (l.name, dil))
+        if self._conv_groups(l) > 1:
+            raise NotImplementedError("Convolution %s: group %d together with dilation %d" % (l.name, self._conv_groups(l), dil))
+        g = self._geom(l)
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.coffset % 4 or xb.cstride % 4:
+            raise NotImplementedError("dilated Convolution %s: input view is not 16-byte aligned" % l.name)
+        relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_dconv_desc has no second output for a Sigmoid)
+        self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
+        pd = self.params_dev[l.name]
+        d = dconv_desc(xb, yb, g, dil, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, L.CONV_RELU if relu else 0)
+        return OpTask(l, [], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], dconv=d)
+
+    def _emit_dconvs(self, items: List[OpTask]) -> None:
+        """The dilated convolutions of one level: those that read the same bottom (the four branches of an ASPP head) share ONE
+        fcn_dconv2d_prepare plan and launch.  FLOPs and bytes are booked as a ConvTask's."""
+        lib = L.load()
+        by_bottom: Dict[Range, List[OpTask]] = {}
+        for it in items:
+            by_bottom.setdefault(it.reads[0], []).append(it)
+        for chunk in by_bottom.values():
+            arr = (L.DConvDesc * len(chunk))(*[it.dconv for it in chunk])
+            ws = DeviceBuffer(int(lib.fcn_dconv2d_workspace_bytes(arr, len(chunk))), zero=False)
+            plan = L.DConvPlan()
+            L.call("fcn_dconv2d_prepare", arr, len(chunk), ws.ptr, -1, C.byref(plan))
+            self._keep.extend([arr, ws, plan])
+            flops = byts = 0.0
+            for it in chunk:
+                g = self._geom(it.layer)
+                flops += g.flops
+                byts += 4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout)
+            label = "%s [d%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join(str(it.dconv.dilation) for it in chunk), plan.total_tiles)
+            self.ops.append(Op("dconv", label, lambda st, p=plan: L.check(lib.fcn_dconv2d_f32(C.byref(p), st)), flops, byts))
 
     def _emit_group(self, chunk: List[ConvTask], fused: List[OpTask], tail: Optional[dict]) -> None:
         """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""

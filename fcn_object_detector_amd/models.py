@@ -23,6 +23,10 @@ detector body is fine-tuned from.
 PASCAL VOC (Long, Shelhamer, Darrell: "Fully Convolutional Networks for Semantic Segmentation") - VGG16 with ``pad: 100`` on
 conv1_1, convolutional fc6 / fc7, group-1 Deconvolution upsampling and ``Crop`` layers aligning the skip connections and the
 score map - as test and tool material.
+
+``deeplab_largefov`` / ``deeplab_aspp`` emit the structure of DeepLab-LargeFOV and of the DeepLab-v2 ASPP head on VGG16 (Chen et al.):
+the stride-8 VGG16 body with dilated conv5_* and a dilated 3x3 fc6 (one per rate in the ASPP head), without the published Interp /
+ImageSegData layers.
 """
 from __future__ import annotations
 
@@ -695,3 +699,96 @@ def resnet101(phase: str = "DEPLOY", **kw) -> str:
 
 def resnet152(phase: str = "DEPLOY", **kw) -> str:
     return resnet(phase, depth=152, **kw)
+
+
+# ----------------------------------------------------------------------
+# DeepLab-LargeFOV and the DeepLab-v2 ASPP head on VGG16 (Chen, Papandreou, Kokkinos, Murphy, Yuille: "Semantic Image Segmentation with
+# Deep Convolutional Nets and Fully Connected CRFs" / "DeepLab: ... Atrous Convolution, and Fully Connected CRFs"; the published names)
+# ----------------------------------------------------------------------
+
+def _dl_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, pad: int = 0, dilation: int = 1, relu: Optional[str] = None,
+             drop: Optional[str] = None, lr: Tuple[float, float] = (1.0, 2.0), std: Optional[float] = None) -> str:
+    geo = ["    num_output: %d" % num_output] + (["    pad: %d" % pad] if pad else []) + ["    kernel_size: %d" % k] + \
+          (["    dilation: %d" % dilation] if dilation != 1 else [])
+    fill = '    weight_filler { type: "xavier" }' if std is None else '    weight_filler { type: "gaussian" std: %g }' % std
+    w.layer(name, "Convolution", [bottom], [name], "  param { lr_mult: %g decay_mult: 1 }\n  param { lr_mult: %g decay_mult: 0 }\n"
+            "  convolution_param {\n%s\n%s\n    bias_filler { type: \"constant\" value: 0 }\n  }" % (lr[0], lr[1], "\n".join(geo), fill))
+    if relu:
+        w.layer(relu, "ReLU", [name], [name])
+    if drop:
+        w.layer(drop, "Dropout", [name], [name], "  dropout_param { dropout_ratio: 0.5 }")
+    return name
+
+
+def _dl_pool(w: _Writer, name: str, bottom: str, stride: int, pool: str = "MAX") -> str:
+    w.layer(name, "Pooling", [bottom], [name], "  pooling_param { pool: %s kernel_size: 3 stride: %d pad: 1 }" % (pool, stride))
+    return name
+
+
+def deeplab_score_size(size: int) -> int:
+    """Edge of the score map of the DeepLab nets below for an input edge `size`: three 3x3 / s2 / pad 1 poolings in Caffe's ceil mode
+    (321 -> 41); every other layer keeps the extent."""
+    for _ in range(3):
+        size = -(-(size + 2 - 3) // 2) + 1
+    return size
+
+
+def _deeplab_vgg(w: _Writer, phase: str, batch: int, size: int, width_div: int) -> str:
+    """conv1_1 .. pool5 of the DeepLab VGG16: pool1 - pool3 3x3 / s2 / pad 1, pool4 and pool5 3x3 / s1 / pad 1, conv5_* with dilation 2
+    (pad 2): the stride-8 body.  The label input has the score map's size (the published nets shrink the label in their data layer)."""
+    sm = deeplab_score_size(size)
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, sm, sm)))
+    prev = "data"
+    for blk, convs, width_ in VGG16:
+        for i in range(1, convs + 1):
+            d = 2 if blk == 5 else 1
+            prev = _dl_conv(w, "conv%d_%d" % (blk, i), prev, max(width_ // width_div, 1), 3, d, d, relu="relu%d_%d" % (blk, i))
+        prev = _dl_pool(w, "pool%d" % blk, prev, 2 if blk <= 3 else 1)
+    return prev
+
+
+def _deeplab_tail(w: _Writer, phase: str, score: str) -> None:
+    if phase == "DEPLOY":
+        return
+    if phase == "TEST":
+        w.layer("accuracy", "Accuracy", [score, "label"], ["accuracy"], "  accuracy_param { ignore_label: 255 }")
+    w.layer("loss", "SoftmaxWithLoss", [score, "label"], ["loss"], "  loss_param { ignore_label: 255 }")
+
+
+def deeplab_largefov(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
+                     fc6_dilation: int = 12) -> str:
+    """DeepLab-LargeFOV on VGG16 with the published names: the stride-8 body (_deeplab_vgg), pool5a (AVE 3x3 / s1 / pad 1), fc6 3x3 with
+    1024 outputs at dilation 12 (pad 12), fc7 1x1 (ReLU, Dropout 0.5 behind both) and fc8_voc12 (lr_mult 10 / 20).  TRAIN and TEST end
+    in SoftmaxWithLoss with ignore_label 255 (TEST adds Accuracy) on a `label` input of the score map's size; DEPLOY ends at
+    fc8_voc12.  The published Interp / ImageSegData layers are not emitted.  width_div / fc_div divide the VGG widths and the 1024."""
+    _check_phase(phase)
+    w = _Writer()
+    w.raw('name: "DeepLab-LargeFOV"')
+    feat = _deeplab_vgg(w, phase, batch, size, width_div)
+    feat = _dl_pool(w, "pool5a", feat, 1, "AVE")
+    fc = max(1024 // fc_div, 1)
+    _dl_conv(w, "fc6", feat, fc, 3, fc6_dilation, fc6_dilation, relu="relu6", drop="drop6")
+    _dl_conv(w, "fc7", "fc6", fc, 1, relu="relu7", drop="drop7")
+    _dl_conv(w, "fc8_voc12", "fc7", num_classes, 1, lr=(10.0, 20.0), std=0.01)
+    _deeplab_tail(w, phase, "fc8_voc12")
+    return w.text()
+
+
+def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
+                 rates: Sequence[int] = (6, 12, 18, 24)) -> str:
+    """The DeepLab-v2 VGG16 head (atrous spatial pyramid pooling): behind pool5 one branch per rate r, fc6_i 3x3 with 1024 outputs at
+    dilation r (pad r), fc7_i 1x1 (ReLU, Dropout 0.5 behind both), fc8_voc12_i; the branches' scores are summed by the Eltwise
+    fc8_voc12.  Phases, label and width_div / fc_div as deeplab_largefov."""
+    _check_phase(phase)
+    w = _Writer()
+    w.raw('name: "DeepLab-v2-ASPP"')
+    feat = _deeplab_vgg(w, phase, batch, size, width_div)
+    fc = max(1024 // fc_div, 1)
+    scores = []
+    for i, r in enumerate(rates, 1):
+        _dl_conv(w, "fc6_%d" % i, feat, fc, 3, int(r), int(r), relu="relu6_%d" % i, drop="drop6_%d" % i)
+        _dl_conv(w, "fc7_%d" % i, "fc6_%d" % i, fc, 1, relu="relu7_%d" % i, drop="drop7_%d" % i)
+        scores.append(_dl_conv(w, "fc8_voc12_%d" % i, "fc7_%d" % i, num_classes, 1, lr=(10.0, 20.0), std=0.01))
+    w.layer("fc8_voc12", "Eltwise", scores, ["fc8_voc12"], "  eltwise_param { operation: SUM }")
+    _deeplab_tail(w, phase, "fc8_voc12")
+    return w.text()

@@ -61,8 +61,22 @@ def kernel_stride_pad(p: proto.Msg) -> Tuple[int, int, int]:
     return int(k), int(p.get("stride", 1)), int(p.get("pad", 0))
 
 
-def conv_out(h: int, k: int, s: int, p: int) -> int:
-    return (h + 2 * p - k) // s + 1
+def layer_dilation(l: "Layer") -> int:
+    """convolution_param.dilation of a Convolution / Deconvolution: absent = 1, one value, or two equal ones (both spatial axes);
+    anything else is refused by layer name, and so is a dilated Deconvolution."""
+    vals = [int(v) for v in l.sub("convolution_param").getall("dilation")]
+    if len(vals) > 2 or len(set(vals)) > 1:
+        raise NotImplementedError("layer %s: dilation %s (one value, or the same value for both spatial axes)" % (l.name, vals))
+    d = vals[0] if vals else 1
+    if d < 1:
+        raise ValueError("layer %s: dilation %d is below 1" % (l.name, d))
+    if d > 1 and l.type == "Deconvolution":
+        raise NotImplementedError("layer %s: Deconvolution with dilation %d (dilation is supported for Convolution only)" % (l.name, d))
+    return d
+
+
+def conv_out(h: int, k: int, s: int, p: int, d: int = 1) -> int:
+    return (h + 2 * p - (d * (k - 1) + 1)) // s + 1
 
 
 def pool_out(h: int, k: int, s: int, p: int) -> int:
@@ -200,14 +214,18 @@ class NetSpec:
                 g = int(p.get("group", 1))
                 co = int(p.get("num_output"))
                 n, c, h, w = bots[0]
+                d = layer_dilation(l)
+                if d > 1 and (conv_out(h, k, s, pad, d) < 1 or conv_out(w, k, s, pad, d) < 1):
+                    raise ValueError("layer %s: the %dx%d window with dilation %d exceeds the padded %dx%d bottom" % (l.name, k, k, d, h + 2 * pad, w + 2 * pad))
                 self.param_shapes[l.name] = [(co, c // g, k, k)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
-                shapes[l.tops[0]] = (n, co, conv_out(h, k, s, pad), conv_out(w, k, s, pad))
+                shapes[l.tops[0]] = (n, co, conv_out(h, k, s, pad, d), conv_out(w, k, s, pad, d))
             elif t == "Deconvolution":
                 p = l.sub("convolution_param")
                 k, s, pad = kernel_stride_pad(p)
                 g = int(p.get("group", 1))
                 co = int(p.get("num_output"))
                 n, c, h, w = bots[0]
+                layer_dilation(l)      # (refuses a dilated Deconvolution by name)
                 self.param_shapes[l.name] = [(c, co // g, k, k)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
                 shapes[l.tops[0]] = (n, co, deconv_out(h, k, s, pad), deconv_out(w, k, s, pad))
             elif t == "InnerProduct":
