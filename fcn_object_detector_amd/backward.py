@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Tuple
 from . import lib as L
 from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window, layer_dilation
+from .netspec import DATA_TYPES, Layer, crop_window, interp_size, layer_dilation
 
 
 @dataclass
@@ -59,7 +59,7 @@ class BackwardPlanner:
         nothing = lambda l: None
         # layer types that look at the plan state themselves ...
         self.emitters = {"Convolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
-                         "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": nothing,
+                         "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": self._concat,
                          "BatchNorm": self._batchnorm, "Scale": self._batchnorm,
                          "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
                          "Accuracy": nothing,      # a metric: no gradient, no entry in loss_blobs
@@ -67,7 +67,7 @@ class BackwardPlanner:
         # ... and the ones _one_bottom hands (layer, dY, dX, accumulate)
         self.one_bottom = {"Pooling": self._pooling, "LRN": self._lrn, "Dropout": self._dropout, "Eltwise": self._eltwise_prod,
                            "Deconvolution": self._depthwise_deconv, "Sigmoid": self._sigmoid_plain, "ReLU": self._relu_plain,
-                           "Crop": self._crop,
+                           "Crop": self._crop, "Interp": self._interp,
                            "Power": lambda l, gtop, gbot, acc: None}      # input transform: nothing upstream learns
 
     def run(self) -> None:
@@ -525,6 +525,27 @@ class BackwardPlanner:
         if l.name in self.e.copy_slices and any(tp in self.G for tp in l.tops):
             raise NotImplementedError("backward through the copied Slice %s" % l.name)
 
+    def _concat(self, l: Layer) -> None:
+        """A Concat whose members are views of its top has nothing to do: their gradients are views of its gradient.  One that copies
+        (a member with other consumers, or written by a layer that cannot write a channel window) hands every member its channels of dY:
+        the Crop adjoint over the whole extent, adding where the member's gradient already holds one."""
+        if l.name not in self.e.copy_concats:
+            return
+        gtop = self._arrived(l)
+        if gtop is None:
+            return
+        lib, off = self.lib, 0
+        for b in l.bottoms:
+            gbot, c = self.G.get(b), self.B[b].channels
+            if gbot is not None:
+                acc = 1 if self.state(gbot) == "full" else 0
+                n, _, h, w = gbot.nchw
+                self.ops.append(Op("concat_bwd", "%s:%s" % (l.name, b), lambda st, gbot=gbot, c=c, off=off, acc=acc, n=n, h=h, w=w: L.check(lib.fcn_crop_bwd_f32(
+                    gtop.buf.ptr, gbot.buf.ptr, n, h, w, c, gbot.cstride, gbot.coffset, 0, 0, h, w, gtop.cstride, gtop.coffset + off, acc, st)),
+                    0.0, 4.0 * gbot.pixels * c * (2 + acc)))
+                self.mark(gbot)
+            off += c
+
     def _loss(self, l: Layer) -> None:
         g = self.G.get(l.bottoms[0])
         if g is None:
@@ -729,6 +750,17 @@ class BackwardPlanner:
         self.ops.append(Op("crop_bwd", l.name, lambda st: L.check(lib.fcn_crop_bwd_f32(
             gtop.buf.ptr, gbot.buf.ptr, n, h, w, c, gbot.cstride, gbot.coffset, oy, ox, oh, ow, gtop.cstride, gtop.coffset, acc, st)),
             0.0, 4.0 * (gtop.pixels + gbot.pixels) * c))
+        self.mark(gbot)
+
+    def _interp(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        """fcn_interp_bwd_f32: a gather, one lane per 16-byte channel group of a dX pixel; one launch writes all of dX (zeros where the
+        pads crop or a shrink never reads), or adds into it when dX already holds a gradient."""
+        lib = self.lib
+        n, c, h, w = gbot.shape
+        oh, ow, pad_beg, pad_end = interp_size(l, h, w)
+        self.ops.append(Op("interp_bwd", l.name, lambda st: L.check(lib.fcn_interp_bwd_f32(
+            gtop.buf.ptr, gbot.buf.ptr, n, h, w, c, gbot.cstride, gbot.coffset, pad_beg, pad_end, oh, ow, gtop.cstride, gtop.coffset, acc, st)),
+            0.0, 4.0 * (gtop.pixels + gbot.pixels * (1 + acc)) * c))
         self.mark(gbot)
 
     def _lrn(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:

@@ -30,7 +30,7 @@ import numpy as np
 from . import lib as L
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, bn_global_stats, crop_window, kernel_stride_pad, layer_dilation
+from .netspec import Layer, NetSpec, bn_global_stats, crop_window, interp_size, kernel_stride_pad, layer_dilation
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -1073,13 +1073,13 @@ class Engine:
         """The launches of one layer that is not a convolution."""
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU"):
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
                 "Slice": self._fwd_slice, "Concat": self._fwd_concat, "Eltwise": self._fwd_eltwise,
-                "Deconvolution": self._fwd_deconvolution, "Crop": self._fwd_crop}.get(t)
+                "Deconvolution": self._fwd_deconvolution, "Crop": self._fwd_crop, "Interp": self._fwd_interp}.get(t)
         if emit is None:
             raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
         return emit(l, halves)
@@ -1105,6 +1105,25 @@ class Engine:
         fn = lib.fcn_crop_fwd_f16 if xb.esize == 2 else lib.fcn_crop_fwd_f32
         return [Op("crop", l.name, lambda st: L.check(fn(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset + oc, oy, ox, oh, ow,
                                                          yb.cstride, yb.coffset, st)), 0.0, 2.0 * xb.esize * yb.pixels * c)]
+
+    def _fwd_interp(self, l: Layer, halves: List[str]) -> List[Op]:
+        """Interp: bilinear resampling of the bottom's effective window (interp_param's pads crop) to the top's size.  Halves are read
+        as halves and stored as halves or - a net's output - as float32."""
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.esize == 4 and yb.esize == 2:
+            raise NotImplementedError("f16 engine: Interp %s reads the float32 blob %s and writes halves" % (l.name, l.bottoms[0]))
+        n, c, h, w = xb.shape
+        oh, ow, pad_beg, pad_end = interp_size(l, h, w)
+        byts = float(xb.esize) * n * (h + pad_beg + pad_end) * (w + pad_beg + pad_end) * c + float(yb.esize) * yb.pixels * c
+        if xb.esize == 2:
+            out_f32 = 1 if yb.esize == 4 else 0
+            run = lambda st: L.check(lib.fcn_interp_fwd_f16(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset, pad_beg, pad_end, oh, ow,
+                                                            yb.cstride, yb.coffset, out_f32, st))
+        else:
+            run = lambda st: L.check(lib.fcn_interp_fwd_f32(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset, pad_beg, pad_end, oh, ow,
+                                                            yb.cstride, yb.coffset, st))
+        return [Op("interp", l.name, run, 0.0, byts)]
 
     def _fwd_pooling(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()

@@ -25,8 +25,8 @@ conv1_1, convolutional fc6 / fc7, group-1 Deconvolution upsampling and ``Crop`` 
 score map - as test and tool material.
 
 ``deeplab_largefov`` / ``deeplab_aspp`` emit the structure of DeepLab-LargeFOV and of the DeepLab-v2 ASPP head on VGG16 (Chen et al.):
-the stride-8 VGG16 body with dilated conv5_* and a dilated 3x3 fc6 (one per rate in the ASPP head), without the published Interp /
-ImageSegData layers.
+the stride-8 VGG16 body with dilated conv5_* and a dilated 3x3 fc6 (one per rate in the ASPP head); ``interp=True`` adds the
+published ``Interp`` layers (fc8_interp, label_shrink).  The published ImageSegData layer is not emitted.
 """
 from __future__ import annotations
 
@@ -733,10 +733,15 @@ def deeplab_score_size(size: int) -> int:
     return size
 
 
-def _deeplab_vgg(w: _Writer, phase: str, batch: int, size: int, width_div: int) -> str:
+def _deeplab_vgg(w: _Writer, phase: str, batch: int, size: int, width_div: int, interp: bool = False) -> str:
     """conv1_1 .. pool5 of the DeepLab VGG16: pool1 - pool3 3x3 / s2 / pad 1, pool4 and pool5 3x3 / s1 / pad 1, conv5_* with dilation 2
-    (pad 2): the stride-8 body.  The label input has the score map's size (the published nets shrink the label in their data layer)."""
-    sm = deeplab_score_size(size)
+    (pad 2): the stride-8 body.  The label input has the score map's size (the published nets shrink the label in their data layer) -
+    or, with `interp`, the image's: the published label_shrink layer (_deeplab_tail) shrinks it, which needs size = 1 modulo 8."""
+    if interp and size % 8 != 1:
+        raise ValueError("DeepLab with interp=True: size %d is not 1 modulo 8 (zoom_factor 8 of the %d x %d score map gives %d, and "
+                         "shrink_factor 8 of the label must give the score map)" % (size, deeplab_score_size(size), deeplab_score_size(size),
+                                                                                    8 * (deeplab_score_size(size) - 1) + 1))
+    sm = size if interp else deeplab_score_size(size)
     _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, sm, sm)))
     prev = "data"
     for blk, convs, width_ in VGG16:
@@ -747,42 +752,53 @@ def _deeplab_vgg(w: _Writer, phase: str, batch: int, size: int, width_div: int) 
     return prev
 
 
-def _deeplab_tail(w: _Writer, phase: str, score: str) -> None:
+def _deeplab_tail(w: _Writer, phase: str, score: str, interp: bool = False) -> None:
+    """Loss (and, in TEST, Accuracy) on the score map.  interp, under the published names: DEPLOY ends in fc8_interp, the score map at
+    the image's size (Interp, zoom_factor 8); TRAIN / TEST read label_shrink, every 8th pixel of the image-sized label (Interp,
+    shrink_factor 8: positions that fall on label pixels, so the class ids and the 255s arrive as they are)."""
     if phase == "DEPLOY":
+        if interp:
+            w.layer("fc8_interp", "Interp", [score], ["fc8_interp"], "  interp_param {\n    zoom_factor: 8\n  }")
         return
+    label = "label"
+    if interp:
+        label = "label_shrink"
+        w.layer(label, "Interp", ["label"], [label], "  interp_param {\n    shrink_factor: 8\n    pad_beg: 0\n    pad_end: 0\n  }")
     if phase == "TEST":
-        w.layer("accuracy", "Accuracy", [score, "label"], ["accuracy"], "  accuracy_param { ignore_label: 255 }")
-    w.layer("loss", "SoftmaxWithLoss", [score, "label"], ["loss"], "  loss_param { ignore_label: 255 }")
+        w.layer("accuracy", "Accuracy", [score, label], ["accuracy"], "  accuracy_param { ignore_label: 255 }")
+    w.layer("loss", "SoftmaxWithLoss", [score, label], ["loss"], "  loss_param { ignore_label: 255 }")
 
 
 def deeplab_largefov(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
-                     fc6_dilation: int = 12) -> str:
+                     fc6_dilation: int = 12, interp: bool = False) -> str:
     """DeepLab-LargeFOV on VGG16 with the published names: the stride-8 body (_deeplab_vgg), pool5a (AVE 3x3 / s1 / pad 1), fc6 3x3 with
     1024 outputs at dilation 12 (pad 12), fc7 1x1 (ReLU, Dropout 0.5 behind both) and fc8_voc12 (lr_mult 10 / 20).  TRAIN and TEST end
     in SoftmaxWithLoss with ignore_label 255 (TEST adds Accuracy) on a `label` input of the score map's size; DEPLOY ends at
-    fc8_voc12.  The published Interp / ImageSegData layers are not emitted.  width_div / fc_div divide the VGG widths and the 1024."""
+    fc8_voc12.  interp=True adds the published Interp layers (_deeplab_tail): DEPLOY ends in fc8_interp at the image's size, and the
+    `label` input of TRAIN / TEST has the image's size and is shrunk by label_shrink; size must then be 1 modulo 8.  The published
+    ImageSegData layer is not emitted.  width_div / fc_div divide the VGG widths and the 1024."""
     _check_phase(phase)
     w = _Writer()
     w.raw('name: "DeepLab-LargeFOV"')
-    feat = _deeplab_vgg(w, phase, batch, size, width_div)
+    feat = _deeplab_vgg(w, phase, batch, size, width_div, interp)
     feat = _dl_pool(w, "pool5a", feat, 1, "AVE")
     fc = max(1024 // fc_div, 1)
     _dl_conv(w, "fc6", feat, fc, 3, fc6_dilation, fc6_dilation, relu="relu6", drop="drop6")
     _dl_conv(w, "fc7", "fc6", fc, 1, relu="relu7", drop="drop7")
     _dl_conv(w, "fc8_voc12", "fc7", num_classes, 1, lr=(10.0, 20.0), std=0.01)
-    _deeplab_tail(w, phase, "fc8_voc12")
+    _deeplab_tail(w, phase, "fc8_voc12", interp)
     return w.text()
 
 
 def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
-                 rates: Sequence[int] = (6, 12, 18, 24)) -> str:
+                 rates: Sequence[int] = (6, 12, 18, 24), interp: bool = False) -> str:
     """The DeepLab-v2 VGG16 head (atrous spatial pyramid pooling): behind pool5 one branch per rate r, fc6_i 3x3 with 1024 outputs at
     dilation r (pad r), fc7_i 1x1 (ReLU, Dropout 0.5 behind both), fc8_voc12_i; the branches' scores are summed by the Eltwise
-    fc8_voc12.  Phases, label and width_div / fc_div as deeplab_largefov."""
+    fc8_voc12.  Phases, label, interp and width_div / fc_div as deeplab_largefov."""
     _check_phase(phase)
     w = _Writer()
     w.raw('name: "DeepLab-v2-ASPP"')
-    feat = _deeplab_vgg(w, phase, batch, size, width_div)
+    feat = _deeplab_vgg(w, phase, batch, size, width_div, interp)
     fc = max(1024 // fc_div, 1)
     scores = []
     for i, r in enumerate(rates, 1):
@@ -790,5 +806,5 @@ def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, w
         _dl_conv(w, "fc7_%d" % i, "fc6_%d" % i, fc, 1, relu="relu7_%d" % i, drop="drop7_%d" % i)
         scores.append(_dl_conv(w, "fc8_voc12_%d" % i, "fc7_%d" % i, num_classes, 1, lr=(10.0, 20.0), std=0.01))
     w.layer("fc8_voc12", "Eltwise", scores, ["fc8_voc12"], "  eltwise_param { operation: SUM }")
-    _deeplab_tail(w, phase, "fc8_voc12")
+    _deeplab_tail(w, phase, "fc8_voc12", interp)
     return w.text()

@@ -117,6 +117,37 @@ def crop_window(l: "Layer", b0: Shape, b1: Shape) -> Tuple[Shape, Tuple[int, ...
     return tuple(shape), tuple(offset)
 
 
+def interp_size(l: "Layer", h: int, w: int) -> Tuple[int, int, int, int]:
+    """DeepLab-Caffe's InterpLayer: (height of the top, width of the top, pad_beg, pad_end) for an h x w bottom.  pad_beg / pad_end are
+    <= 0 and crop: the effective input is rows and columns -pad_beg .. h + pad_end - 1.  Per axis the output extent is (He - 1) //
+    shrink_factor + 1, He + (He - 1) (zoom_factor - 1), both (shrink first), or interp_param's height / width; as in Caffe a field counts
+    as given when the prototxt writes it, a factor of 1 included.  Everything else is refused by layer name."""
+    p = l.sub("interp_param")
+    pad_beg, pad_end = int(p.get("pad_beg", 0)), int(p.get("pad_end", 0))
+    if pad_beg > 0 or pad_end > 0:
+        raise ValueError("layer %s: Interp with pad_beg %d / pad_end %d: only pads <= 0 (they crop)" % (l.name, pad_beg, pad_end))
+    he, we = h + pad_beg + pad_end, w + pad_beg + pad_end
+    if he < 1 or we < 1:
+        raise ValueError("layer %s: pad_beg %d / pad_end %d leave nothing of the %d x %d bottom" % (l.name, pad_beg, pad_end, h, w))
+    given = {k: int(p.get(k)) for k in ("height", "width", "zoom_factor", "shrink_factor") if p.get(k) is not None}
+    shrink, zoom = given.get("shrink_factor"), given.get("zoom_factor")
+    if any(f is not None and f < 1 for f in (shrink, zoom)):
+        raise ValueError("layer %s: Interp factors must be at least 1 (zoom_factor %s, shrink_factor %s)" % (l.name, zoom, shrink))
+    if shrink is not None or zoom is not None:
+        oh, ow = he, we
+        if shrink is not None:
+            oh, ow = (oh - 1) // shrink + 1, (ow - 1) // shrink + 1
+        if zoom is not None:
+            oh, ow = oh + (oh - 1) * (zoom - 1), ow + (ow - 1) * (zoom - 1)
+    elif "height" in given and "width" in given:
+        oh, ow = given["height"], given["width"]
+    else:
+        raise ValueError("layer %s: Interp needs zoom_factor, shrink_factor or both height and width" % l.name)
+    if oh < 1 or ow < 1:
+        raise ValueError("layer %s: Interp to %d x %d: the output extents must be at least 1" % (l.name, oh, ow))
+    return oh, ow, pad_beg, pad_end
+
+
 def as_nchw(shape: Shape) -> Optional[Tuple[int, int, int, int]]:
     """A blob's shape as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
     channels (H = W = 1); None for anything else.  Engine.Blob.nchw and the channel-axis layers (Concat, Slice) share this rule."""
@@ -317,6 +348,15 @@ class NetSpec:
                 if len(bots) != 2 or len(l.tops) != 1:
                     raise ValueError("layer %s: Crop takes two bottoms (the blob and the shape donor) and has one top" % l.name)
                 shapes[l.tops[0]] = crop_window(l, bots[0], bots[1])[0]
+            elif t == "Interp":
+                if len(bots) == 2:
+                    raise NotImplementedError("layer %s: Interp with two bottoms (the second one lending its size)" % l.name)
+                if len(bots) != 1 or len(bots[0]) != 4 or len(l.tops) != 1:
+                    raise ValueError("layer %s: Interp takes one 4-d bottom and has one top, got %s" % (l.name, bots))
+                if l.tops[0] == l.bottoms[0]:
+                    raise ValueError("layer %s: Interp cannot run in place" % l.name)
+                oh, ow, _, _ = interp_size(l, bots[0][2], bots[0][3])
+                shapes[l.tops[0]] = (bots[0][0], bots[0][1], oh, ow)
             elif t == "Eltwise":
                 for b in bots[1:]:
                     if b != bots[0]:

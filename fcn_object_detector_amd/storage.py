@@ -111,8 +111,9 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     if f16:
         for name in shapes:
             if esize[name] == 4 and len(shapes[name]) in (2, 4) and name not in data_tops:
-                # (Softmax and Deconvolution read halves and store float32: the out_f32 forms of their half kernels)
-                bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct")]
+                # (Softmax, Deconvolution and Interp read halves and store float32: the out_f32 forms of their half kernels)
+                bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct",
+                                                                                 "Interp")]
                 if bad:
                     raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 

@@ -714,6 +714,34 @@ int  fcn_crop_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_
 int  fcn_crop_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int off_y, int off_x,
                       int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
 
+/* ---- Interp (DeepLab-Caffe's InterpLayer: fc8_interp and label_shrink of the published DeepLab nets, the resizing of a pyramid-pooling
+ *      head): bilinear resampling with aligned corners between two NHWC views with channel strides, and its adjoint.  x / dX is the
+ *      N x H x W bottom, of which rows and columns -pad_beg .. H + pad_end - 1 (W alike) are the effective input of He x We; y / dY is
+ *      N x OH x OW.  Output index o of n2 lies at position o (n1 - 1) / (n2 - 1) of the effective input's n1, kept in integers: cell
+ *      i0 = num / (n2 - 1), neighbour i1 = min(i0 + 1, n1 - 1) with weight lam = float(num % (n2 - 1)) / float(n2 - 1), num = o (n1 - 1);
+ *      position 0 when n1 or n2 is 1.  y = (1-ly) ((1-lx) p00 + lx p01) + ly ((1-lx) p10 + lx p11) in float32 without contraction; a
+ *      weight of zero selects the pixel itself, so equal extents - and every output that falls on an input pixel - copy bit for bit.
+ *      Contract: null pointers, non-positive extents, a positive pad, an effective extent below 1 or a slice wider than its stride
+ *      FCN_E_ARG; a row or an axis past 2^31 lanes (OH * He, OW * We, W * x_cstride, OW * y_cstride, N * H, N * OH) or an output
+ *      extent past 2^24 FCN_E_UNSUPPORTED; element offsets are 64-bit, so the views themselves may pass 2^31 bytes; every check precedes
+ *      the first HIP call.  float32: strides and channel offsets that are all multiples of 4 floats under 16-byte aligned pointers move
+ *      16 bytes per lane (the last C % 4 channels one by one), anything else one element per lane.  Exactly channels y_coffset ..
+ *      y_coffset + C - 1 of every output pixel are written, nothing outside channels x_coffset .. x_coffset + C - 1 of the effective
+ *      input is read.  No atomics anywhere: results do not depend on the run. ---- */
+int  fcn_interp_fwd_f32(const float* x, float* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int pad_beg, int pad_end,
+                        int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
+/* halves in; halves (out_f32 0) or float32 (out_f32 1: a net's output behind the layer) out, rounded once from the float32 blend.  The
+ * pointers must be 16-byte aligned, x_cstride and x_coffset multiples of 8 halves, y_cstride and y_coffset of 8 halves or 4 floats, else
+ * FCN_E_ALIGN; C is free (the last C % 8 channels move one by one). */
+int  fcn_interp_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int pad_beg, int pad_end,
+                        int OH, int OW, int y_cstride, int y_coffset, int out_f32, fcn_stream_t s);
+/* The adjoint as a gather: a pixel of dX sums, in ascending output row and ascending output column inside a row, the pixels of dY it fed
+ * with a weight that is not zero.  accumulate 0: ONE launch writes channels dx_coffset .. dx_coffset + C - 1 of every pixel of dX - zero
+ * where nothing feeds it: cropped away by the pads, or never read by a shrink (no memset in front).  accumulate 1: dX += the sum at the
+ * pixels something feeds, and nothing else is touched (a blob with several consumers).  There is no half-float twin. */
+int  fcn_interp_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int pad_beg, int pad_end,
+                        int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
+
 /* ---- InnerProduct (Caffe InnerProductLayer) at M <= FCN_IP_MAX_ROWS input rows: y[m][n] = sum_k x[m][k] * w[n][k] + bias[n].
  *      x: M rows of K elements, x_rstride elements apart (a row of an NHWC blob of H*W*cstride elements IS such a row); w: the bank
  *      [N][K], K contiguous, in the order of the elements of a row of x (zero columns where x holds pad channels); y / dY: M pixels of
