@@ -13,15 +13,16 @@ from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
 from . import storage as S
-from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window, interp_size, layer_dilation
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, rconv_desc, tconv_desc
+from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, layer_dilation
 
 
 @dataclass
 class Dgrad:
     """One data-gradient launch, prepared once the whole plan is known: a group of stride-1 passes that write different buffers
     (ConvDesc, launch: L.ConvGroup), the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan) or the
-    dilated convolution of dY with the flipped bank of one dilated layer (DConvDesc, launch: L.DConvPlan).
+    dilated / rectangular convolution of dY with the flipped bank of one dilated / rectangular layer (DConvDesc, launch: L.DConvPlan;
+    RConvDesc, launch: L.RConvPlan).
     targets[i]: the blob descs[i] writes."""
     name: str
     descs: list
@@ -112,9 +113,15 @@ class BackwardPlanner:
         return [q for q in self.e.producers.get(blob, []) if q.type == "Convolution"][0]
 
     @staticmethod
+    def _rect(l: Layer) -> bool:
+        """A Convolution that csrc/rconv.hip runs (engine._rconv_task), whatever its dilation."""
+        return l.type == "Convolution" and is_rectangular(l)
+
+    @staticmethod
     def _dilated(l: Layer) -> bool:
-        """A Convolution that csrc/dconv.hip runs (engine._dconv_task): it stays out of the grouped dense launches."""
-        return l.type == "Convolution" and layer_dilation(l) > 1
+        """A Convolution that csrc/dconv.hip or csrc/rconv.hip runs (engine._dconv_task, engine._rconv_task): it stays out of the
+        grouped dense launches."""
+        return l.type == "Convolution" and (layer_dilation(l) > 1 or is_rectangular(l))
 
     def _find_concat_relu(self) -> None:
         """Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch."""
@@ -140,6 +147,20 @@ class BackwardPlanner:
         packs: List[Op] = []
         for l in self.spec.layers:
             if l.type != "Convolution" or self.G.get(l.bottoms[0]) is None or self.G.get(l.tops[0]) is None:
+                continue
+            if self._rect(l):      # the data gradient is the same rectangular kernel on the flipped bank: strides 1, pad' = d (k-1) - pad >= 0 per axis
+                r = e._rgeom(l)
+                if r.sh != 1 or r.sw != 1:
+                    raise NotImplementedError("rectangular Convolution %s: the data gradient of a rectangular layer with stride %dx%d (its "
+                                              "bottom %s needs a gradient)" % (l.name, r.sh, r.sw, l.bottoms[0]))
+                for axis, pad, k in (("h", r.ph, r.kh), ("w", r.pw, r.kw)):
+                    if pad > r.d * (k - 1):
+                        raise NotImplementedError("rectangular Convolution %s: the data gradient with pad_%s %d above dilation * (kernel_%s - 1) = "
+                                                  "%d (its bottom %s needs a gradient)" % (l.name, axis, pad, axis, r.d * (k - 1), l.bottoms[0]))
+                self.flip_layout[l.name] = flip_floats
+                wdev = e.params_dev[l.name][0].ptr
+                flip_segs.append(L.FlipSeg((wdev - e.param_flat.ptr) // 4, flip_floats, r.cout, r.kh, r.kw, r.cin, _r4(r.cin), _r4(r.cout)))
+                flip_floats += _r4(r.cin * r.kh * r.kw * _r4(r.cout))
                 continue
             g, ng = e._geom(l), e._conv_groups(l)
             if self._dilated(l):      # the data gradient is the same dilated kernel on the flipped bank: stride 1, pad' = dil (k-1) - pad >= 0
@@ -261,6 +282,13 @@ class BackwardPlanner:
                 e._keep.extend([dws, rec.launch])
                 rec.op.name = "%s [d%d %dwg]" % (rec.name, d.dilation, rec.launch.total_tiles)
                 continue
+            if isinstance(rec.launch, L.RConvPlan):
+                d = rec.descs[0]
+                rws = DeviceBuffer(int(lib.fcn_rconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+                L.call("fcn_rconv2d_prepare", C.byref(d), 1, rws.ptr, -1, C.byref(rec.launch))
+                e._keep.extend([rws, rec.launch])
+                rec.op.name = "%s [%dx%d %dwg]" % (rec.name, d.kh, d.kw, rec.launch.total_tiles)
+                continue
             if isinstance(rec.launch, L.TConvPlan):
                 d = rec.descs[0]
                 tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
@@ -310,9 +338,9 @@ class BackwardPlanner:
     def wgrad_items(self, l: Layer, gtop: Blob) -> List[Tuple[L.ConvDesc, DevView, Optional[DevView], float]]:
         """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns: one per group, dW and db at
         the group's rows."""
-        e, g, xb, ng = self.e, self.e._geom(l), self.B[l.bottoms[0]], self.e._conv_groups(l)
         if self._dilated(l):
-            raise RuntimeError("wgrad_items is the dense path; dilated layers go through _dilated_convolution (%s)" % l.name)
+            raise RuntimeError("wgrad_items is the dense path; dilated and rectangular layers have emitters of their own (%s)" % l.name)
+        e, g, xb, ng = self.e, self.e._geom(l), self.B[l.bottoms[0]], self.e._conv_groups(l)
         if gtop.coffset % 4 or gtop.cstride % 4:
             raise NotImplementedError("gradient view of %s is not 16-byte aligned" % l.tops[0])
         cin_g, cout_g = g.cin // ng, g.cout // ng
@@ -389,10 +417,47 @@ class BackwardPlanner:
         e._keep.append(dd)
         self.mark(gbot, rec)
 
+    def _rect_convolution(self, l: Layer, gtop: Blob) -> None:
+        """Backward of a rectangular Convolution (csrc/rconv.hip), the shape of _dilated_convolution: the layer's own ReLU mask on dY,
+        the weight gradient on the second stream (one form only: op.sel is None), and dX = the rectangular convolution of dY with
+        the flipped bank, strides 1, pad_h' = d (kh-1) - pad_h, pad_w' = d (kw-1) - pad_w, accumulating where dX already holds a
+        gradient; _finish_dgrads may fold the ReLU mask of the layer below into it, as for a dense pass."""
+        e, G, lib, top = self.e, self.G, self.lib, l.tops[0]
+        g, xb = e._rgeom(l), self.B[l.bottoms[0]]
+        if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
+            rop = self.relu_bwd_op(l.name, self.B[top], gtop)
+            if top not in e.alias:
+                self.relu_ops[top] = rop
+            self.relu_done.add(top)
+        if e._learns(l) and l.name not in self.wgrad_done:
+            d = rconv_desc(xb, gtop, g)
+            dw = e._grad_view(l.name, 0)
+            db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
+            e._keep.append(d)
+            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_rconv2d_wgrad_f32(C.byref(d), dw.ptr, db, e._ws.ptr, st)), g.flops, g.bytes)
+            # (the launch runs on the second stream behind the other weight gradients, never beside them: it shares their workspace)
+            self._book_wgrad(op, None, [l.name], [int(lib.fcn_rconv2d_wgrad_workspace_floats(C.byref(d)))])
+        gbot = G.get(l.bottoms[0])
+        if gbot is None or l.name in self.dgrad_done:
+            return
+        if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(g.cout):
+            raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % top)
+        wt = self.flip_flat.ptr + 4 * self.flip_layout[l.name]
+        dd = rconv_desc(gtop, gbot, g.swapped()._replace(sh=1, sw=1, ph=g.d * (g.kh - 1) - g.ph, pw=g.d * (g.kw - 1) - g.pw), wt,
+                        flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
+        rec = Dgrad(l.name, [dd], [l.bottoms[0]], L.RConvPlan())
+        rec.op = Op("rconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_rconv2d_f32(C.byref(pl), st)), g.flops)
+        self.ops.append(rec.op)
+        self.dgrad_records.append(rec)
+        e._keep.append(dd)
+        self.mark(gbot, rec)
+
     def _convolution(self, l: Layer) -> None:
         gtop = self._arrived(l)
         if gtop is None:
             return
+        if self._rect(l):
+            return self._rect_convolution(l, gtop)
         if self._dilated(l):
             return self._dilated_convolution(l, gtop)
         e, G, top = self.e, self.G, l.tops[0]

@@ -30,7 +30,7 @@ import numpy as np
 from . import lib as L
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, bn_global_stats, crop_window, interp_size, kernel_stride_pad, layer_dilation
+from .netspec import Layer, NetSpec, bn_global_stats, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation, layer_geometry
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -124,6 +124,36 @@ def dconv_desc(x: "Blob", y: "Blob", g: ConvGeom, dilation: int, w: Optional[int
     d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
     d.y_cstride, d.y_coffset = y.cstride, y.coffset
     d.flags, d.dilation = flags, dilation
+    return d
+
+
+class RectGeom(namedtuple("RectGeom", "n cin h w cout oh ow kh kw sh sw ph pw d")):
+    """The geometry of a rectangular Convolution (csrc/rconv.hip): input n x cin x h x w, output n x cout x oh x ow, kernel kh x kw at
+    strides (sh, sw) with pads (ph, pw) and one dilation d for both axes."""
+    __slots__ = ()
+
+    @property
+    def flops(self) -> float:
+        return 2.0 * self.n * self.oh * self.ow * self.cin * self.cout * self.kh * self.kw
+
+    @property
+    def bytes(self) -> float:
+        return 4.0 * (self.n * self.cin * self.h * self.w + self.n * self.cout * self.oh * self.ow + self.cout * self.cin * self.kh * self.kw + self.cout)
+
+    def swapped(self) -> "RectGeom":
+        """The same layer seen from its output: input and output trade places (the data-gradient pass)."""
+        return self._replace(cin=self.cout, h=self.oh, w=self.ow, cout=self.cin, oh=self.h, ow=self.w)
+
+
+def rconv_desc(x: "Blob", y: "Blob", g: RectGeom, w: Optional[int] = None, bias: Optional[int] = None, flags: int = 0) -> L.RConvDesc:
+    """fcn_rconv_desc: the rectangular convolution `g` reading the view x through the OHWI bank w and writing the view y - activations
+    (forward) or gradients (the data-gradient pass on the flipped bank, the weight gradient with y = dY)."""
+    d = L.RConvDesc()
+    d.x, d.w, d.bias, d.y = x.ptr, w, bias, y.buf.ptr
+    d.N, d.H, d.W, d.Cin, d.x_cstride = g.n, g.h, g.w, g.cin, x.cstride
+    d.Cout, d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w, d.OH, d.OW = g.cout, g.kh, g.kw, g.ph, g.pw, g.sh, g.sw, g.oh, g.ow
+    d.y_cstride, d.y_coffset = y.cstride, y.coffset
+    d.flags, d.dilation = flags, g.d
     return d
 
 
@@ -267,6 +297,7 @@ class OpTask:
     writes: List[Range]
     pool_desc: Optional[L.PoolDesc] = None
     dconv: Optional[L.DConvDesc] = None
+    rconv: Optional[L.RConvDesc] = None      # a rectangular Convolution: as dconv, through csrc/rconv.hip
 
 
 Task = Union[ConvTask, OpTask]
@@ -500,6 +531,12 @@ class Engine:
         k, s, pad = ksp or kernel_stride_pad(l.sub("pooling_param" if l.type == "Pooling" else "convolution_param"))
         return ConvGeom(n, cin, h, w, cout, oh, ow, k, s, pad)
 
+    def _rgeom(self, l: Layer) -> RectGeom:
+        """Per-axis geometry of a rectangular Convolution (netspec.is_rectangular) from its blobs and netspec.layer_geometry."""
+        n, cin, h, w = self.blobs[l.bottoms[0]].shape
+        _, cout, oh, ow = self.blobs[l.tops[0]].shape
+        return RectGeom(n, cin, h, w, cout, oh, ow, *layer_geometry(l), layer_dilation(l))
+
     def _conv_groups(self, l: Layer) -> int:
         """`group` of a Convolution (storage.conv_groups decided, and refused, when the parameters were laid out)."""
         return int(l.sub("convolution_param").get("group", 1)) if l.type == "Convolution" else 1
@@ -681,6 +718,9 @@ class Engine:
             t = l.type
             if t in ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data"):
                 continue
+            if t == "Convolution" and is_rectangular(l):
+                tasks.append(self._rconv_task(li, l, skip))
+                continue
             if t == "Convolution" and layer_dilation(l) > 1:
                 tasks.append(self._dconv_task(li, l, skip))
                 continue
@@ -740,12 +780,14 @@ class Engine:
         pending: List[ConvTask] = []
         pending_pools: List[OpTask] = []
         pending_dconvs: List[OpTask] = []
+        pending_rconvs: List[OpTask] = []
         cur = None
         for i in order:
             if levels[i] != cur:
                 self._emit_dconvs(pending_dconvs)
+                self._emit_rconvs(pending_rconvs)
                 self._emit_convs(pending, pending_pools, tail)
-                pending, pending_dconvs, cur = [], [], levels[i]
+                pending, pending_dconvs, pending_rconvs, cur = [], [], [], levels[i]
             if tail is not None and any(tasks[i] is ht for ht in tail["heads"]):
                 continue      # evaluated by the launches that produce its input
             if isinstance(tasks[i], ConvTask):
@@ -754,9 +796,12 @@ class Engine:
                 pending_pools.append(tasks[i])
             elif tasks[i].dconv is not None:
                 pending_dconvs.append(tasks[i])
+            elif tasks[i].rconv is not None:
+                pending_rconvs.append(tasks[i])
             else:
                 self.ops.extend(tasks[i].ops)
         self._emit_dconvs(pending_dconvs)
+        self._emit_rconvs(pending_rconvs)
         self._emit_convs(pending, pending_pools, tail)
         self.levels = max(levels) + 1 if levels else 0
         if self.score_outputs:
@@ -800,6 +845,44 @@ class Engine:
                 byts += 4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout)
             label = "%s [d%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join(str(it.dconv.dilation) for it in chunk), plan.total_tiles)
             self.ops.append(Op("dconv", label, lambda st, p=plan: L.check(lib.fcn_dconv2d_f32(C.byref(p), st)), flops, byts))
+
+    def _rconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
+        """A Convolution whose axes differ in kernel, pad or stride (dilated or not): a problem of csrc/rconv.hip, never of the tiled
+        family or the tuner.  The bank is the layer's parameter blob where it lies; an in-place ReLU behind the layer rides in the
+        epilogue."""
+        kh, kw, sh, sw, ph, pw = layer_geometry(l)
+        what = "%dx%d stride %dx%d pad %dx%d" % (kh, kw, sh, sw, ph, pw)
+        if self.f16:
+            raise NotImplementedError("f16 engine: rectangular Convolution %s (%s) has no half-float kernel" % (l.name, what))
+        if self._conv_groups(l) > 1:
+            raise NotImplementedError("rectangular Convolution %s (%s): group %d" % (l.name, what, self._conv_groups(l)))
+        g = self._rgeom(l)
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.coffset % 4 or xb.cstride % 4:
+            raise NotImplementedError("rectangular Convolution %s: input view is not 16-byte aligned" % l.name)
+        relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_rconv_desc has no second output for a Sigmoid)
+        self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
+        pd = self.params_dev[l.name]
+        d = rconv_desc(xb, yb, g, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, L.CONV_RELU if relu else 0)
+        return OpTask(l, [], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], rconv=d)
+
+    def _emit_rconvs(self, items: List[OpTask]) -> None:
+        """The rectangular convolutions of one level: those that read the same bottom (the 1x3 / 3x1 pair of an 8-grid Inception
+        module) share ONE fcn_rconv2d_prepare plan and launch.  FLOPs are booked as 2 N OH OW Cin Cout kh kw."""
+        lib = L.load()
+        by_bottom: Dict[Range, List[OpTask]] = {}
+        for it in items:
+            by_bottom.setdefault(it.reads[0], []).append(it)
+        for chunk in by_bottom.values():
+            arr = (L.RConvDesc * len(chunk))(*[it.rconv for it in chunk])
+            ws = DeviceBuffer(int(lib.fcn_rconv2d_workspace_bytes(arr, len(chunk))), zero=False)
+            plan = L.RConvPlan()
+            L.call("fcn_rconv2d_prepare", arr, len(chunk), ws.ptr, -1, C.byref(plan))
+            self._keep.extend([arr, ws, plan])
+            geoms = [self._rgeom(it.layer) for it in chunk]
+            label = "%s [%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join("%dx%d" % (g.kh, g.kw) for g in geoms), plan.total_tiles)
+            self.ops.append(Op("rconv", label, lambda st, p=plan: L.check(lib.fcn_rconv2d_f32(C.byref(p), st)),
+                               sum(g.flops for g in geoms), sum(g.bytes for g in geoms)))
 
     def _emit_group(self, chunk: List[ConvTask], fused: List[OpTask], tail: Optional[dict]) -> None:
         """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""

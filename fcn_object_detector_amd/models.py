@@ -808,3 +808,138 @@ def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, w
     w.layer("fc8_voc12", "Eltwise", scores, ["fc8_voc12"], "  eltwise_param { operation: SUM }")
     _deeplab_tail(w, phase, "fc8_voc12", interp)
     return w.text()
+
+
+# ----------------------------------------------------------------------
+# Inception-v3 (Szegedy, Vanhoucke, Ioffe, Shlens, Wojna: "Rethinking the Inception Architecture for Computer Vision"): the structure of
+# the paper - factorised 1x7 / 7x1 and 1x3 / 3x1 convolutions - under a naming scheme of this project's own
+# ----------------------------------------------------------------------
+
+def _iv3_conv(w: _Writer, name: str, bottom: str, num_output: int, kernel, phase: str, pad=0, stride: int = 1) -> str:
+    """Convolution `<name>` (bias_term: false; kernel and pad an int or an (h, w) pair, written as kernel_h / kernel_w / pad_h / pad_w
+    where the axes differ) with BatchNorm `<name>/bn`, Scale `<name>/scale` (bias_term: true) and ReLU `<name>/relu` in place on its
+    top; returns the top."""
+    kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
+    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    if (kh, ph) == (kw, pw):
+        geo = "    num_output: %d\n    kernel_size: %d\n    pad: %d\n    stride: %d\n" % (num_output, kh, ph, stride)
+    else:
+        geo = "    num_output: %d\n    kernel_h: %d\n    kernel_w: %d\n    pad_h: %d\n    pad_w: %d\n    stride: %d\n" % (num_output, kh, kw, ph, pw, stride)
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / (kh * kw * num_output)) ** 0.5
+    w.layer(name, "Convolution", [bottom], [name], "  convolution_param {\n%s    bias_term: false\n%s  }" % (geo, fill))
+    stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+    w.layer(name + "/bn", "BatchNorm", [name], [name], stats)
+    w.layer(name + "/scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
+    w.layer(name + "/relu", "ReLU", [name], [name])
+    return name
+
+
+def _iv3_pool(w: _Writer, name: str, bottom: str, pool: str, stride: int) -> str:
+    w.layer(name, "Pooling", [bottom], [name], "  pooling_param { pool: %s kernel_size: 3 stride: %d%s }" % (pool, stride, " pad: 1" if stride == 1 else ""))
+    return name
+
+
+def inception_v3_grids(size) -> List[Tuple[int, int]]:
+    """The (h, w) grids of Inception-v3 on a `size` input (an edge or an (h, w) pair): behind the stem (35 at 299), behind the first
+    reduction (17) and behind the second (8).  A reduction concatenates a 3x3 / 2 convolution, whose extent Caffe floors, with a
+    3x3 / 2 pooling, whose extent Caffe ceils: a size at which the two disagree is a ValueError."""
+    from .netspec import conv_out, pool_out
+    hw = (size, size) if isinstance(size, int) else tuple(int(v) for v in size)
+    if len(hw) != 2 or min(hw) < 1:
+        raise ValueError("size must be an edge or an (h, w) pair, got %r" % (size,))
+
+    def stem(v: int) -> int:
+        v = conv_out(conv_out(conv_out(v, 3, 2, 0), 3, 1, 0), 3, 1, 1)          # conv1 3x3 / 2, conv2 3x3, conv3 3x3 pad 1
+        v = conv_out(pool_out(v, 3, 2, 0), 3, 1, 0) if v >= 3 else 0             # pool1, conv4 1x1, conv5 3x3
+        return pool_out(v, 3, 2, 0) if v >= 3 else 0                            # pool2
+    grids = [tuple(stem(v) for v in hw)]
+    for which in ("reduction_a", "reduction_b"):
+        if min(grids[-1]) < 3:
+            raise ValueError("inception_v3: a %s input leaves a %dx%d grid in front of %s (at least 3x3)" % (hw, grids[-1][0], grids[-1][1], which))
+        c, p = tuple(conv_out(v, 3, 2, 0) for v in grids[-1]), tuple(pool_out(v, 3, 2, 0) for v in grids[-1])
+        if c != p:
+            raise ValueError("inception_v3: on a %s input %s's 3x3 / 2 convolution gives a %dx%d grid and its 3x3 / 2 pooling %dx%d: they cannot "
+                             "be concatenated (299, or 171 x 139, agree)" % (hw, which, c[0], c[1], p[0], p[1]))
+        grids.append(c)
+    return grids
+
+
+def inception_v3(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size=299, fillers: bool = True) -> str:
+    """Inception-v3: the structure of the paper (no published prototxt was at hand: the names below are this project's, and a
+    caffemodel from elsewhere maps only if it uses them).  The stem (conv1 3x3 / 2, conv2 3x3, conv3 3x3 pad 1, pool1 MAX 3x3 / 2,
+    conv4 1x1, conv5 3x3, pool2 MAX 3x3 / 2), three 35-grid modules mixed_35a / b / c, the grid reduction reduction_a, four 17-grid
+    modules mixed_17a .. d with 1x7 / 7x1 chains, reduction_b with its 1x7, 7x1, 3x3 / 2 branch, two 8-grid modules mixed_8a / b with
+    the split 1x3 / 3x1 pairs, pool3 (global AVE), drop (ratio 0.2), the InnerProduct `classifier`, and `prob` (DEPLOY), `loss`
+    (SoftmaxWithLoss over an (N,) `label`; TRAIN and TEST) and `accuracy` (TEST).  No auxiliary head.
+
+    Names: a convolution is `<module>/<branch>_<kh>x<kw>` (`<branch>` = 1x1, 5x5, 3x3dbl, 7x7, 7x7dbl, 3x3, 7x7x3, pool; a letter
+    a, b, c ... where a branch has several of one shape), its top has the same name, and BatchNorm `<name>/bn`, Scale `<name>/scale`
+    and ReLU `<name>/relu` follow in place; a module's pooling is `<module>/pool`, its Concat and output blob `<module>`.  A
+    rectangular layer is written with kernel_h / kernel_w / pad_h / pad_w.  width_div divides every convolution width, size is the
+    image edge or an (h, w) pair; inception_v3_grids refuses a size at which a reduction's convolution and pooling grids differ."""
+    _check_phase(phase)
+    inception_v3_grids(size)
+    hw = (size, size) if isinstance(size, int) else tuple(int(v) for v in size)
+    wd = lambda c: max(c // width_div, 1)
+    cv = lambda name, bottom, c, k, pad=0, stride=1: _iv3_conv(w, name, bottom, wd(c), k, phase, pad, stride)
+    w = _Writer()
+    w.raw('name: "Inception-v3"')
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, hw[0], hw[1]))
+    if phase != "DEPLOY":
+        w.layer("label", "Input", [], ["label"], "  input_param { shape { dim: %d } }" % batch)
+    x = cv("conv1_3x3", "data", 32, 3, 0, 2)
+    x = cv("conv2_3x3", x, 32, 3)
+    x = cv("conv3_3x3", x, 64, 3, 1)
+    x = _iv3_pool(w, "pool1", x, "MAX", 2)
+    x = cv("conv4_1x1", x, 80, 1)
+    x = cv("conv5_3x3", x, 192, 3)
+    x = _iv3_pool(w, "pool2", x, "MAX", 2)
+    for m, pf in (("mixed_35a", 32), ("mixed_35b", 64), ("mixed_35c", 64)):
+        b1 = cv(m + "/1x1_1x1", x, 64, 1)
+        b2 = cv(m + "/5x5_5x5", cv(m + "/5x5_1x1", x, 48, 1), 64, 5, 2)
+        b3 = cv(m + "/3x3dbl_1x1", x, 64, 1)
+        b3 = cv(m + "/3x3dbl_b_3x3", cv(m + "/3x3dbl_a_3x3", b3, 96, 3, 1), 96, 3, 1)
+        b4 = cv(m + "/pool_1x1", _iv3_pool(w, m + "/pool", x, "AVE", 1), pf, 1)
+        w.layer(m, "Concat", [b1, b2, b3, b4], [m])
+        x = m
+    m = "reduction_a"
+    b1 = cv(m + "/3x3_3x3", x, 384, 3, 0, 2)
+    b2 = cv(m + "/3x3dbl_a_3x3", cv(m + "/3x3dbl_1x1", x, 64, 1), 96, 3, 1)
+    b2 = cv(m + "/3x3dbl_b_3x3", b2, 96, 3, 0, 2)
+    w.layer(m, "Concat", [b1, b2, _iv3_pool(w, m + "/pool", x, "MAX", 2)], [m])
+    x = m
+    for m, c7 in (("mixed_17a", 128), ("mixed_17b", 160), ("mixed_17c", 160), ("mixed_17d", 192)):
+        b1 = cv(m + "/1x1_1x1", x, 192, 1)
+        b2 = cv(m + "/7x7_1x7", cv(m + "/7x7_1x1", x, c7, 1), c7, (1, 7), (0, 3))
+        b2 = cv(m + "/7x7_7x1", b2, 192, (7, 1), (3, 0))
+        b3 = cv(m + "/7x7dbl_a_7x1", cv(m + "/7x7dbl_1x1", x, c7, 1), c7, (7, 1), (3, 0))
+        b3 = cv(m + "/7x7dbl_b_7x1", cv(m + "/7x7dbl_a_1x7", b3, c7, (1, 7), (0, 3)), c7, (7, 1), (3, 0))
+        b3 = cv(m + "/7x7dbl_b_1x7", b3, 192, (1, 7), (0, 3))
+        b4 = cv(m + "/pool_1x1", _iv3_pool(w, m + "/pool", x, "AVE", 1), 192, 1)
+        w.layer(m, "Concat", [b1, b2, b3, b4], [m])
+        x = m
+    m = "reduction_b"
+    b1 = cv(m + "/3x3_3x3", cv(m + "/3x3_1x1", x, 192, 1), 320, 3, 0, 2)
+    b2 = cv(m + "/7x7x3_1x7", cv(m + "/7x7x3_1x1", x, 192, 1), 192, (1, 7), (0, 3))
+    b2 = cv(m + "/7x7x3_3x3", cv(m + "/7x7x3_7x1", b2, 192, (7, 1), (3, 0)), 192, 3, 0, 2)
+    w.layer(m, "Concat", [b1, b2, _iv3_pool(w, m + "/pool", x, "MAX", 2)], [m])
+    x = m
+    for m in ("mixed_8a", "mixed_8b"):
+        b1 = cv(m + "/1x1_1x1", x, 320, 1)
+        b2 = cv(m + "/3x3_1x1", x, 384, 1)
+        b2a, b2b = cv(m + "/3x3_1x3", b2, 384, (1, 3), (0, 1)), cv(m + "/3x3_3x1", b2, 384, (3, 1), (1, 0))
+        b3 = cv(m + "/3x3dbl_3x3", cv(m + "/3x3dbl_1x1", x, 448, 1), 384, 3, 1)
+        b3a, b3b = cv(m + "/3x3dbl_1x3", b3, 384, (1, 3), (0, 1)), cv(m + "/3x3dbl_3x1", b3, 384, (3, 1), (1, 0))
+        b4 = cv(m + "/pool_1x1", _iv3_pool(w, m + "/pool", x, "AVE", 1), 192, 1)
+        w.layer(m, "Concat", [b1, b2a, b2b, b3a, b3b, b4], [m])
+        x = m
+    w.layer("pool3", "Pooling", [x], ["pool3"], "  pooling_param { pool: AVE global_pooling: true }")
+    w.layer("drop", "Dropout", ["pool3"], ["pool3"], "  dropout_param { dropout_ratio: 0.2 }")
+    _cn_fc(w, "classifier", "pool3", classes, 0.01, 0.0)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["classifier"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["classifier", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["classifier", "label"], ["loss"])
+    return w.text() if fillers else _strip_fillers(w.text())

@@ -50,15 +50,59 @@ def _phase_included(msg: proto.Msg, phase: str) -> bool:
     return True
 
 
+def _axis_pair(p: proto.Msg, what: str, both: str, h: str, w: str, default: Optional[int], least: int) -> Tuple[int, int]:
+    """One of Caffe's either/or geometry fields as (h, w): `both` once (both axes) or twice ((h, w), the way Caffe repeats it), or `h`
+    AND `w`; `default` when nothing is written (None: the field is required)."""
+    vals, vh, vw = p.getall(both), p.getall(h), p.getall(w)
+    if vals and (vh or vw):
+        raise ValueError("%s: both %s and %s / %s are given (one form or the other)" % (what, both, h, w))
+    if bool(vh) != bool(vw):
+        raise ValueError("%s: %s without %s (both or neither)" % ((what, h, w) if vh else (what, w, h)))
+    if len(vals) > 2 or len(vh) > 1 or len(vw) > 1:
+        raise ValueError("%s: %s given %d times (once, or twice as (h, w))" % (what, both if vals else h if len(vh) > 1 else w,
+                                                                              max(len(vals), len(vh), len(vw))))
+    if vh:
+        out = (int(vh[0]), int(vw[0]))
+    elif vals:
+        out = (int(vals[0]), int(vals[-1]))
+    elif default is None:
+        raise ValueError("%s without %s" % (what, both))
+    else:
+        out = (default, default)
+    if min(out) < least:
+        raise ValueError("%s: %s %s is below %d" % (what, both, "x".join(str(v) for v in out), least))
+    return out
+
+
+def _geometry(p: proto.Msg, what: str) -> Tuple[int, int, int, int, int, int]:
+    kh, kw = _axis_pair(p, what, "kernel_size", "kernel_h", "kernel_w", None, 1)
+    sh, sw = _axis_pair(p, what, "stride", "stride_h", "stride_w", 1, 1)
+    ph, pw = _axis_pair(p, what, "pad", "pad_h", "pad_w", 0, 0)
+    return kh, kw, sh, sw, ph, pw
+
+
+def layer_geometry(l: "Layer") -> Tuple[int, int, int, int, int, int]:
+    """(kh, kw, sh, sw, ph, pw) of a Convolution / Deconvolution / Pooling layer by Caffe's rules: the kernel is kernel_size or
+    kernel_h AND kernel_w, the stride is stride or stride_h / stride_w (default 1), the pad is pad or pad_h / pad_w (default 0);
+    kernel_size / stride / pad written twice mean (h, w).  Both forms of one field, one of an _h / _w pair alone, any other count,
+    a kernel or stride below 1 and a pad below 0 are ValueErrors that name the layer."""
+    return _geometry(l.sub("pooling_param" if l.type == "Pooling" else "convolution_param"), "layer %s" % l.name)
+
+
+def is_rectangular(l: "Layer") -> bool:
+    """The two spatial axes of the layer differ in kernel extent, stride or pad."""
+    kh, kw, sh, sw, ph, pw = layer_geometry(l)
+    return (kh, sh, ph) != (kw, sw, pw)
+
+
 def kernel_stride_pad(p: proto.Msg) -> Tuple[int, int, int]:
-    k = p.get("kernel_size")
-    if k is None:
-        k = p.get("kernel_h")
-    if k is None:
-        raise ValueError("layer without kernel_size")
-    if p.get("kernel_w") is not None and int(p.get("kernel_w")) != int(k):
-        raise NotImplementedError("non-square kernels are not used by the reference nets")
-    return int(k), int(p.get("stride", 1)), int(p.get("pad", 0))
+    """(kernel, stride, pad) of a layer whose two spatial axes agree, however it is written; a layer whose axes differ has no such
+    answer (layer_geometry gives the per-axis values)."""
+    kh, kw, sh, sw, ph, pw = _geometry(p, "layer")
+    if (kh, sh, ph) != (kw, sw, pw):
+        raise NotImplementedError("kernel %dx%d stride %dx%d pad %dx%d: the axes differ (netspec.layer_geometry has the per-axis values)"
+                                  % (kh, kw, sh, sw, ph, pw))
+    return kh, sh, ph
 
 
 def layer_dilation(l: "Layer") -> int:
@@ -73,6 +117,16 @@ def layer_dilation(l: "Layer") -> int:
     if d > 1 and l.type == "Deconvolution":
         raise NotImplementedError("layer %s: Deconvolution with dilation %d (dilation is supported for Convolution only)" % (l.name, d))
     return d
+
+
+def _square(l: "Layer") -> Tuple[int, int, int]:
+    """(kernel, stride, pad) of a Pooling / Deconvolution layer; one whose axes differ is refused by layer name (rectangular
+    windows are supported for Convolution only)."""
+    kh, kw, sh, sw, ph, pw = layer_geometry(l)
+    if (kh, sh, ph) != (kw, sw, pw):
+        raise NotImplementedError("layer %s: %s with kernel %dx%d stride %dx%d pad %dx%d (axes that differ are supported for Convolution only)"
+                                  % (l.name, l.type, kh, kw, sh, sw, ph, pw))
+    return kh, sh, ph
 
 
 def conv_out(h: int, k: int, s: int, p: int, d: int = 1) -> int:
@@ -241,18 +295,19 @@ class NetSpec:
                 raise KeyError("layer %s: unknown bottom blob %s" % (l.name, e)) from None
             if t == "Convolution":
                 p = l.sub("convolution_param")
-                k, s, pad = kernel_stride_pad(p)
+                kh, kw, sh, sw, ph, pw = layer_geometry(l)
                 g = int(p.get("group", 1))
                 co = int(p.get("num_output"))
                 n, c, h, w = bots[0]
                 d = layer_dilation(l)
-                if d > 1 and (conv_out(h, k, s, pad, d) < 1 or conv_out(w, k, s, pad, d) < 1):
-                    raise ValueError("layer %s: the %dx%d window with dilation %d exceeds the padded %dx%d bottom" % (l.name, k, k, d, h + 2 * pad, w + 2 * pad))
-                self.param_shapes[l.name] = [(co, c // g, k, k)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
-                shapes[l.tops[0]] = (n, co, conv_out(h, k, s, pad, d), conv_out(w, k, s, pad, d))
+                rect = (kh, sh, ph) != (kw, sw, pw)
+                if (d > 1 or rect) and (conv_out(h, kh, sh, ph, d) < 1 or conv_out(w, kw, sw, pw, d) < 1):
+                    raise ValueError("layer %s: the %dx%d window with dilation %d exceeds the padded %dx%d bottom" % (l.name, kh, kw, d, h + 2 * ph, w + 2 * pw))
+                self.param_shapes[l.name] = [(co, c // g, kh, kw)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
+                shapes[l.tops[0]] = (n, co, conv_out(h, kh, sh, ph, d), conv_out(w, kw, sw, pw, d))
             elif t == "Deconvolution":
                 p = l.sub("convolution_param")
-                k, s, pad = kernel_stride_pad(p)
+                k, s, pad = _square(l)
                 g = int(p.get("group", 1))
                 co = int(p.get("num_output"))
                 n, c, h, w = bots[0]
@@ -278,7 +333,7 @@ class NetSpec:
                 if bool(p.get("global_pooling", False)):
                     shapes[l.tops[0]] = (n, c, 1, 1)
                 else:
-                    k, s, pad = kernel_stride_pad(p)
+                    k, s, pad = _square(l)
                     shapes[l.tops[0]] = (n, c, pool_out(h, k, s, pad), pool_out(w, k, s, pad))
             elif t == "Concat":
                 axis = int(l.sub("concat_param").get("axis", l.sub("concat_param").get("concat_dim", 1)))

@@ -693,6 +693,65 @@ int    fcn_dconv2d_f32(const fcn_dconv_plan* h_plan, fcn_stream_t s);
 size_t fcn_dconv2d_wgrad_workspace_floats(const fcn_dconv_desc* h_d);
 int    fcn_dconv2d_wgrad_f32(const fcn_dconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s);
 
+/* ---- rectangular convolution: Caffe ConvolutionLayer whose two spatial axes differ in kernel extent, pad or stride (kernel_h / kernel_w,
+ *      pad_h / pad_w, stride_h / stride_w: the 1x7 / 7x1 and 1x3 / 3x1 pairs of Inception-v3 / v4, the k x 1 + 1 x k pairs of ENet /
+ *      ERFNet), forward, data gradient and weight gradient, with one dilation for both axes.  NHWC float32, exact f32 on the matrix
+ *      cores (v_mfma_f32_32x32x2_f32).  With zeros outside the image:
+ *        y[n, oy, ox, co] = bias[co] + sum over ci, r, q of w[co][r][q][ci] * x[n, oy*stride_h - pad_h + r*dil, ox*stride_w - pad_w + q*dil, ci]
+ *        OH = (H + 2 pad_h - (dil*(kh-1) + 1)) / stride_h + 1     (floor)        OW likewise with kw, pad_w, stride_w
+ *      The contract is that of the dilated convolution above.  The bank is the Convolution's parameter blob as the engine keeps it,
+ *      [Cout][kh][kw][round4(Cin)] with Cin contiguous: no repacking.  All problems of a plan run in ONE launch.  Every output element
+ *      is written by exactly one lane, there are no float atomics, a second launch gives the same bits.
+ *      flags: FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK, applied in the order accumulate, ReLU, mask; y2 is only read
+ *      (FCN_CONV_MASK).  Channels Cin .. round4(Cin)-1 of `x` are padding and are never multiplied (they may hold anything); channels
+ *      of y outside [y_coffset, y_coffset + Cout) are not touched.  16-byte stores when y (y2) is 16-byte aligned with strides /
+ *      offsets in multiples of 4, scalar stores otherwise and for a last partial group.  dilation >= 1.  A square problem (equal
+ *      extents, pads and strides) is legal and equals the dense convolution.
+ *      The data gradient of a layer with stride_h == stride_w == 1 is the same kernel on dY with the flipped bank of
+ *      fcn_conv_weights_flip_batch_f32 (which takes kh and kw separately), pad_h' = dil*(kh-1) - pad_h, pad_w' = dil*(kw-1) - pad_w, the
+ *      same dilation, and FCN_CONV_ACCUM / FCN_CONV_MASK as the dense data-gradient passes use them.
+ *      Refused on the host before the first HIP call: FCN_E_ARG (null x / w / y, null descriptors / plan / workspace, n <= 0, unknown
+ *      cfg_request, non-positive extent or stride, negative pad, window larger than the padded image, OH / OW not the value above,
+ *      slice wider than its stride, FCN_CONV_MASK without y2 or with a y2 slice narrower than Cout, a plan that prepare() did not fill,
+ *      null dw, pixel splits without a workspace), FCN_E_ALIGN (x_cstride not a multiple of 4 or below round4(Cin); x / w / dw / the
+ *      workspace not 16-byte aligned; y / bias / db not 4-byte aligned), FCN_E_UNSUPPORTED (other flags, dilation < 1, more than 4096
+ *      taps, more than 65535 problems, tensors past 2^31 elements). ---- */
+typedef struct fcn_rconv_desc {
+    const float* x;      /* NHWC input, channel stride x_cstride (a multiple of 4, >= round4(Cin))               */
+    const float* w;      /* weights [Cout][kh][kw][round4(Cin)]  (OHWI, Cin contiguous, 16-byte aligned)         */
+    const float* bias;   /* [Cout] or NULL                                                                       */
+    float*       y;      /* NHWC output; channel co of pixel m at y[m*y_cstride + y_coffset + co]                */
+    float*       y2;     /* FCN_CONV_MASK: the activation whose sign masks the result (same indexing via y2_*)   */
+    int32_t N, H, W, Cin, x_cstride;
+    int32_t Cout, kh, kw, pad_h, pad_w, stride_h, stride_w, OH, OW;
+    int32_t y_cstride, y_coffset, y2_cstride, y2_coffset;
+    int32_t flags;
+    int32_t dilation;
+} fcn_rconv_desc;
+typedef struct fcn_rconv_plan {
+    void*   d_probs;
+    int32_t n;
+    int32_t cfg;          /* tile configuration chosen by prepare() */
+    int32_t grid_x, grid_y;
+    int32_t total_tiles;
+} fcn_rconv_plan;
+/* number of tile configurations (cfg_request: -1 = built-in choice, 0 .. count-1); one today: 64 pixels x 64 channels x 16 k */
+int    fcn_rconv2d_num_configs(void);
+size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n);
+/* validates and uploads n problems into d_workspace with a synchronous copy (plan time, not inside a graph capture); the
+ * workspace must stay alive as long as the plan is used */
+int    fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out);
+/* one pure kernel launch for all problems of the plan: capturable */
+int    fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s);
+/* Weight / bias gradient, the contract of fcn_dconv2d_wgrad_f32: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY
+ * (d->w, d->bias, d->y2 and d->flags are ignored).  dw is [Cout][kh][kw][round4(Cin)], 16-byte aligned, and is OVERWRITTEN; its pad
+ * columns Cin .. round4(Cin)-1 are written as exact zeros.  db is [Cout] or NULL.  With more than one pixel split every split writes a
+ * slab of the workspace (fcn_rconv2d_wgrad_workspace_floats() floats, 16-byte aligned; 0 = none needed, NULL allowed) and a second
+ * small launch adds the slabs in ascending order and sums db: bit-reproducible, no atomics.  Nothing outside dw / db / the workspace
+ * is written. */
+size_t fcn_rconv2d_wgrad_workspace_floats(const fcn_rconv_desc* h_d);
+int    fcn_rconv2d_wgrad_f32(const fcn_rconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s);
+
 /* ---- Crop (Caffe CropLayer: the skip connections and the final score map of the published FCN-32s / 16s / 8s nets): a window copy
  *      between two NHWC views with channel strides, and its adjoint.  x / dX is the N x H x W view, y / dY the N x OH x OW window at
  *      (off_y, off_x); a crop along the channel axis is the caller adding its offset to x_coffset.
