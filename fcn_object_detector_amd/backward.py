@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
 from . import storage as S
-from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, rconv_desc, tconv_desc
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
 from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, layer_dilation
 
 
@@ -22,7 +22,7 @@ class Dgrad:
     """One data-gradient launch, prepared once the whole plan is known: a group of stride-1 passes that write different buffers
     (ConvDesc, launch: L.ConvGroup), the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan) or the
     dilated / rectangular convolution of dY with the flipped bank of one dilated / rectangular layer (DConvDesc, launch: L.DConvPlan;
-    RConvDesc, launch: L.RConvPlan).
+    RConvDesc, launch: L.RConvPlan), or the gather of one depthwise layer (DwConvDesc, launch: None - nothing to prepare).
     targets[i]: the blob descs[i] writes."""
     name: str
     descs: list
@@ -59,7 +59,7 @@ class BackwardPlanner:
         self.skip_sigmoid_of = {m["sigmoid_top"]: name for name, m in eng._conv_layer_meta.items() if m.get("sigmoid_top")}
         nothing = lambda l: None
         # layer types that look at the plan state themselves ...
-        self.emitters = {"Convolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
+        self.emitters = {"Convolution": self._convolution, "DepthwiseConvolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
                          "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": self._concat,
                          "BatchNorm": self._batchnorm, "Scale": self._batchnorm,
                          "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
@@ -117,11 +117,10 @@ class BackwardPlanner:
         """A Convolution that csrc/rconv.hip runs (engine._rconv_task), whatever its dilation."""
         return l.type == "Convolution" and is_rectangular(l)
 
-    @staticmethod
-    def _dilated(l: Layer) -> bool:
-        """A Convolution that csrc/dconv.hip or csrc/rconv.hip runs (engine._dconv_task, engine._rconv_task): it stays out of the
-        grouped dense launches."""
-        return l.type == "Convolution" and (layer_dilation(l) > 1 or is_rectangular(l))
+    def _dilated(self, l: Layer) -> bool:
+        """A Convolution that csrc/dconv.hip, csrc/rconv.hip or csrc/dwconv.hip runs (engine._dconv_task, engine._rconv_task,
+        engine._dwconv_task): it stays out of the grouped dense launches."""
+        return self.spec.is_depthwise(l) or (l.type == "Convolution" and (layer_dilation(l) > 1 or is_rectangular(l)))
 
     def _find_concat_relu(self) -> None:
         """Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch."""
@@ -147,6 +146,8 @@ class BackwardPlanner:
         packs: List[Op] = []
         for l in self.spec.layers:
             if l.type != "Convolution" or self.G.get(l.bottoms[0]) is None or self.G.get(l.tops[0]) is None:
+                continue
+            if self.spec.is_depthwise(l):      # the data gradient gathers through the layer's own bank: nothing to flip or pack
                 continue
             if self._rect(l):      # the data gradient is the same rectangular kernel on the flipped bank: strides 1, pad' = d (k-1) - pad >= 0 per axis
                 r = e._rgeom(l)
@@ -270,11 +271,14 @@ class BackwardPlanner:
                 raise RuntimeError("the last writer of the gradient of %s does not name it among its targets" % x)
             for d, t in zip(rec.descs, rec.targets):      # (the groups of a grouped convolution each write their own channels of dX)
                 if t == x:
-                    first = d.b_coffset if isinstance(d, L.TConvDesc) else d.y_coffset
+                    # (a depthwise pass writes the whole view of dX through d.x: its mask starts where the activation's view does)
+                    first = d.b_coffset if isinstance(d, L.TConvDesc) else self.G[x].coffset if isinstance(d, L.DwConvDesc) else d.y_coffset
                     d.y2, d.y2_cstride, d.y2_coffset = act.buf.ptr, act.cstride, act.coffset + first - self.G[x].coffset
                     d.flags |= L.CONV_MASK
             self.ops.remove(rop)
         for rec in self.dgrad_records:
+            if rec.launch is None:      # a depthwise gather: one pure launch on its descriptor
+                continue
             if isinstance(rec.launch, L.DConvPlan):
                 d = rec.descs[0]
                 dws = DeviceBuffer(int(lib.fcn_dconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
@@ -452,10 +456,45 @@ class BackwardPlanner:
         e._keep.append(dd)
         self.mark(gbot, rec)
 
+    def _depthwise_convolution(self, l: Layer, gtop: Blob) -> None:
+        """Backward of a depthwise Convolution (csrc/dwconv.hip), the shape of _rect_convolution: the layer's own ReLU mask on dY, the
+        weight gradient on the second stream in the shared workspace (one form only: op.sel is None), and dX = the gather of dY through
+        the layer's own bank - any stride, no flipped bank - accumulating where dX already holds a gradient; _finish_dgrads may fold the
+        ReLU mask of the layer below into it, as for a dense pass."""
+        e, G, lib, top = self.e, self.G, self.lib, l.tops[0]
+        g, xb = e._dwgeom(l), self.B[l.bottoms[0]]
+        if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
+            rop = self.relu_bwd_op(l.name, self.B[top], gtop)
+            if top not in e.alias:
+                self.relu_ops[top] = rop
+            self.relu_done.add(top)
+        if e._learns(l) and l.name not in self.wgrad_done:
+            d = dwconv_desc(xb, gtop, g)
+            dw = e._grad_view(l.name, 0)
+            db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
+            e._keep.append(d)
+            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_dwconv2d_wgrad_f32(C.byref(d), dw.ptr, db, e._ws.ptr, 0, st)), g.flops, g.bytes)
+            # (the launch runs on the second stream behind the other weight gradients, never beside them: it shares their workspace)
+            self._book_wgrad(op, None, [l.name], [int(lib.fcn_dwconv2d_wgrad_workspace_floats(C.byref(d), 0))])
+        gbot = G.get(l.bottoms[0])
+        if gbot is None or l.name in self.dgrad_done:
+            return
+        if gbot.coffset % 4 or gbot.cstride % 4:
+            raise NotImplementedError("depthwise Convolution %s: the gradient view of %s is not 16-byte aligned" % (l.name, l.bottoms[0]))
+        dd = dwconv_desc(gbot, gtop, g, e.params_dev[l.name][0].ptr, flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
+        rec = Dgrad(l.name, [dd], [l.bottoms[0]], None)
+        rec.op = Op("dwconv_dgrad", "%s [%dx%d]" % (l.name, g.kh, g.kw), lambda st: L.check(lib.fcn_dwconv2d_dgrad_f32(C.byref(dd), -1, st)), g.flops, g.bytes)
+        self.ops.append(rec.op)
+        self.dgrad_records.append(rec)
+        e._keep.append(dd)
+        self.mark(gbot, rec)
+
     def _convolution(self, l: Layer) -> None:
         gtop = self._arrived(l)
         if gtop is None:
             return
+        if self.spec.is_depthwise(l):
+            return self._depthwise_convolution(l, gtop)
         if self._rect(l):
             return self._rect_convolution(l, gtop)
         if self._dilated(l):

@@ -157,6 +157,27 @@ def rconv_desc(x: "Blob", y: "Blob", g: RectGeom, w: Optional[int] = None, bias:
     return d
 
 
+class DwGeom(namedtuple("DwGeom", "n c h w oh ow kh kw sh sw ph pw d")):
+    """The geometry of a depthwise Convolution (csrc/dwconv.hip): n x c x h x w in, n x c x oh x ow out, kernel kh x kw at strides
+    (sh, sw) with pads (ph, pw) and one dilation d for both axes."""
+    __slots__ = ()
+
+    @property
+    def flops(self) -> float:
+        return 2.0 * self.n * self.oh * self.ow * self.c * self.kh * self.kw
+
+    @property
+    def bytes(self) -> float:
+        return 4.0 * (self.n * self.h * self.w * self.c + self.n * self.oh * self.ow * self.c + self.kh * self.kw * self.c + self.c)
+
+
+def dwconv_desc(x: "Blob", y: "Blob", g: DwGeom, w: Optional[int] = None, bias: Optional[int] = None, flags: int = 0) -> L.DwConvDesc:
+    """fcn_dwconv_desc of the FORWARD problem `g`: x the view of the layer's input (or of its gradient: the data-gradient pass writes
+    it), y the view of its output (or of dY), w the tap-major bank."""
+    return L.dwconv_desc(x.ptr, w, bias, y.buf.ptr, g.n, g.h, g.w, g.c, x.cstride, g.kh, g.kw, g.ph, g.pw, g.sh, g.sw, g.d,
+                         y.cstride, y.coffset, flags)
+
+
 class DeviceBuffer:
     """Owns one hipMalloc allocation."""
 
@@ -298,6 +319,7 @@ class OpTask:
     pool_desc: Optional[L.PoolDesc] = None
     dconv: Optional[L.DConvDesc] = None
     rconv: Optional[L.RConvDesc] = None      # a rectangular Convolution: as dconv, through csrc/rconv.hip
+    dwconv: Optional[L.DwConvDesc] = None    # a depthwise Convolution (csrc/dwconv.hip): the descriptor its one op launches
 
 
 Task = Union[ConvTask, OpTask]
@@ -537,6 +559,12 @@ class Engine:
         _, cout, oh, ow = self.blobs[l.tops[0]].shape
         return RectGeom(n, cin, h, w, cout, oh, ow, *layer_geometry(l), layer_dilation(l))
 
+    def _dwgeom(self, l: Layer) -> DwGeom:
+        """Per-axis geometry of a depthwise Convolution (NetSpec.is_depthwise) from its blobs and netspec.layer_geometry."""
+        n, c, h, w = self.blobs[l.bottoms[0]].shape
+        _, _, oh, ow = self.blobs[l.tops[0]].shape
+        return DwGeom(n, c, h, w, oh, ow, *layer_geometry(l), layer_dilation(l))
+
     def _conv_groups(self, l: Layer) -> int:
         """`group` of a Convolution (storage.conv_groups decided, and refused, when the parameters were laid out)."""
         return int(l.sub("convolution_param").get("group", 1)) if l.type == "Convolution" else 1
@@ -718,6 +746,9 @@ class Engine:
             t = l.type
             if t in ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data"):
                 continue
+            if spec.is_depthwise(l):
+                tasks.append(self._dwconv_task(li, l, skip))
+                continue
             if t == "Convolution" and is_rectangular(l):
                 tasks.append(self._rconv_task(li, l, skip))
                 continue
@@ -845,6 +876,27 @@ class Engine:
                 byts += 4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout)
             label = "%s [d%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join(str(it.dconv.dilation) for it in chunk), plan.total_tiles)
             self.ops.append(Op("dconv", label, lambda st, p=plan: L.check(lib.fcn_dconv2d_f32(C.byref(p), st)), flops, byts))
+
+    def _dwconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
+        """A depthwise Convolution (NetSpec.is_depthwise): one pure launch of csrc/dwconv.hip on the tap-major bank, never a ConvTask -
+        it stays out of the grouped launches and the tuner.  An in-place ReLU behind the layer rides in the epilogue.  In the
+        half-float engine the bottom holds halves and the top halves or float32; the bank and the bias are float32 in both."""
+        lib = L.load()
+        g = self._dwgeom(l)
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        eps = 16 // xb.esize
+        if xb.coffset % eps or xb.cstride % eps:
+            raise NotImplementedError("depthwise Convolution %s: input view is not 16-byte aligned" % l.name)
+        if xb.esize == 4 and yb.esize != 4:
+            raise NotImplementedError("f16 engine: depthwise Convolution %s reads the float32 blob %s and writes halves" % (l.name, l.bottoms[0]))
+        relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_dwconv_desc has no second output for a Sigmoid)
+        self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
+        pd = self.params_dev[l.name]
+        flags = (L.CONV_RELU if relu else 0) | (L.CONV_OUT_F32 if xb.esize == 2 and yb.esize == 4 else 0)
+        d = dwconv_desc(xb, yb, g, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, flags)
+        fn = lib.fcn_dwconv2d_fwd_f16 if xb.esize == 2 else lib.fcn_dwconv2d_fwd_f32
+        op = Op("dwconv", "%s [%dx%d]" % (l.name, g.kh, g.kw), lambda st: L.check(fn(C.byref(d), -1, st)), g.flops, g.bytes)
+        return OpTask(l, [op], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], dwconv=d)
 
     def _rconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
         """A Convolution whose axes differ in kernel, pad or stride (dilated or not): a problem of csrc/rconv.hip, never of the tiled

@@ -96,6 +96,33 @@ class RConvPlan(C.Structure):
                 ("total_tiles", C.c_int32)]
 
 
+class DwConvDesc(C.Structure):
+    """fcn_dwconv_desc: depthwise convolution, geometry per axis (forward f32 / f16, data gradient, weight gradient)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("x_cstride", C.c_int32),
+        ("kh", C.c_int32), ("kw", C.c_int32), ("pad_h", C.c_int32), ("pad_w", C.c_int32),
+        ("stride_h", C.c_int32), ("stride_w", C.c_int32), ("OH", C.c_int32), ("OW", C.c_int32),
+        ("y_cstride", C.c_int32), ("y_coffset", C.c_int32), ("y2_cstride", C.c_int32), ("y2_coffset", C.c_int32),
+        ("flags", C.c_int32), ("dilation", C.c_int32),
+    ]
+
+
+def dwconv_desc(x: int, w: Optional[int], bias: Optional[int], y: int, n: int, h: int, wd: int, c: int, x_cstride: int, kh: int, kw: int,
+                ph: int, pw: int, sh: int, sw: int, dilation: int, y_cstride: int, y_coffset: int, flags: int = 0) -> DwConvDesc:
+    """fcn_dwconv_desc of the forward problem n x c x h x wd under a kh x kw window (pads ph / pw, strides sh / sw, one dilation): x the
+    address of channel 0 of the input view, y the address of the output BUFFER (the slice starts y_coffset channels in); OH / OW by
+    Caffe's rule."""
+    d = DwConvDesc()
+    d.x, d.w, d.bias, d.y = x, w, bias, y
+    d.N, d.H, d.W, d.C, d.x_cstride = n, h, wd, c, x_cstride
+    d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w = kh, kw, ph, pw, sh, sw
+    d.OH = (h + 2 * ph - (dilation * (kh - 1) + 1)) // sh + 1
+    d.OW = (wd + 2 * pw - (dilation * (kw - 1) + 1)) // sw + 1
+    d.y_cstride, d.y_coffset, d.flags, d.dilation = y_cstride, y_coffset, flags, dilation
+    return d
+
+
 class SolverSeg(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("count", C.c_uint64), ("lr_mult", C.c_float), ("decay_mult", C.c_float)]
 
@@ -290,6 +317,12 @@ PROTOTYPES = {
     "fcn_rconv2d_f32": (_i, [C.POINTER(RConvPlan), _vp]),
     "fcn_rconv2d_wgrad_workspace_floats": (_sz, [C.POINTER(RConvDesc)]),
     "fcn_rconv2d_wgrad_f32": (_i, [C.POINTER(RConvDesc), _vp, _vp, _vp, _vp]),
+    "fcn_dwconv2d_num_configs": (_i, []),
+    "fcn_dwconv2d_fwd_f32": (_i, [C.POINTER(DwConvDesc), _i, _vp]),
+    "fcn_dwconv2d_fwd_f16": (_i, [C.POINTER(DwConvDesc), _i, _vp]),
+    "fcn_dwconv2d_dgrad_f32": (_i, [C.POINTER(DwConvDesc), _i, _vp]),
+    "fcn_dwconv2d_wgrad_workspace_floats": (_sz, [C.POINTER(DwConvDesc), _i]),
+    "fcn_dwconv2d_wgrad_f32": (_i, [C.POINTER(DwConvDesc), _vp, _vp, _vp, _i, _vp]),
     "fcn_crop_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),

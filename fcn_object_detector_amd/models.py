@@ -943,3 +943,107 @@ def inception_v3(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, wid
             w.layer("accuracy", "Accuracy", ["classifier", "label"], ["accuracy"])
         w.layer("loss", "SoftmaxWithLoss", ["classifier", "label"], ["loss"])
     return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# MobileNet v1 (Howard et al.: "MobileNets: Efficient Convolutional Neural Networks for Mobile Vision Applications") and v2 (Sandler et
+# al.: "MobileNetV2: Inverted Residuals and Linear Bottlenecks"): the structure of the papers.  The depthwise layers are written the way
+# the published Caffe ports write them - type "Convolution" with group == num_output and engine: CAFFE - so a NetSpec takes them with
+# depthwise=True (caffe.Net and the solvers pass it).
+# ----------------------------------------------------------------------
+
+def _mb_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, stride: int, phase: str, relu: Optional[str], group: int = 1) -> str:
+    """Convolution `<name>` (bias_term: false, pad k // 2; group > 1: depthwise) with BatchNorm `<name>/bn` and Scale `<name>/scale`
+    (bias_term: true) in place on its top and, with `relu`, a ReLU of that name; returns the top."""
+    geo = "    num_output: %d\n    bias_term: false\n    pad: %d\n    kernel_size: %d\n" % (num_output, k // 2, k)
+    if group > 1:
+        geo += "    group: %d\n    engine: CAFFE\n" % group
+    geo += "    stride: %d\n" % stride
+    fan = k * k * (1 if group > 1 else num_output)      # (a depthwise filter sees one channel)
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / fan) ** 0.5
+    w.layer(name, "Convolution", [bottom], [name], "  param { lr_mult: 1 decay_mult: 1 }\n  convolution_param {\n%s%s  }" % (geo, fill))
+    stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+    w.layer(name + "/bn", "BatchNorm", [name], [name], stats)
+    w.layer(name + "/scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
+    if relu:
+        w.layer(relu, "ReLU", [name], [name])
+    return name
+
+
+def _mb_tail(w: _Writer, phase: str, feat: str, classes: int) -> None:
+    """pool6 (global AVE), the 1x1 convolution classifier fc7 and prob (DEPLOY) / loss over an (N, 1, 1, 1) `label`, accuracy in TEST."""
+    w.layer("pool6", "Pooling", [feat], ["pool6"], "  pooling_param { pool: AVE global_pooling: true }")
+    w.layer("fc7", "Convolution", ["pool6"], ["fc7"], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  convolution_param {\n    num_output: %d\n    kernel_size: 1\n    weight_filler { type: \"gaussian\" std: 0.01 }\n"
+            "    bias_filler { type: \"constant\" value: 0 }\n  }" % classes)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["fc7"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["fc7", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["fc7", "label"], ["loss"])
+
+
+MOBILENET_V1 = (("2_1", 64, 1), ("2_2", 128, 2), ("3_1", 128, 1), ("3_2", 256, 2), ("4_1", 256, 1), ("4_2", 512, 2), ("5_1", 512, 1), ("5_2", 512, 1),
+                ("5_3", 512, 1), ("5_4", 512, 1), ("5_5", 512, 1), ("5_6", 1024, 2), ("6", 1024, 1))      # (tag, width of the 1x1, stride of the 3x3)
+MOBILENET_V2 = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))      # (t, c, n, s) of the paper
+
+
+def mobilenet_v1(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224, fillers: bool = True) -> str:
+    """MobileNet v1: the structure of the paper (no published prototxt was at hand).  The stem conv1 3x3 / 2 (32), thirteen pairs of a
+    depthwise 3x3 `conv<tag>/dw` and a 1x1 `conv<tag>/sep` with the strides 1, 2, 1, 2, 1, 2, 1 x 5, 2, 1 and the widths 64 .. 1024, every
+    convolution bias-free and followed by BatchNorm, Scale (bias_term: true) and ReLU in place; pool6 (global AVE), the 1x1 convolution
+    classifier fc7, and prob (DEPLOY), loss (SoftmaxWithLoss over an (N, 1, 1, 1) `label`; TRAIN and TEST) and accuracy (TEST).
+
+    Names: conv1, conv2_1/dw, conv2_1/sep ... conv5_6/dw, conv6/sep, pool6, fc7 and prob are those of the common Caffe port, as far as
+    remembered; `<conv>/bn`, `<conv>/scale` and the ReLUs `relu<tag>` are this project's.  A caffemodel from elsewhere maps only where
+    the names agree.  A depthwise layer is type "Convolution" with group == num_output and engine: CAFFE, as the ports write it.
+    width_div divides every convolution width, size is the image edge."""
+    _check_phase(phase)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "MobileNet-v1"')
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, 1, 1)))
+    x, c = _mb_conv(w, "conv1", "data", wd(32), 3, 2, phase, "relu1"), wd(32)
+    for tag, width, stride in MOBILENET_V1:
+        x = _mb_conv(w, "conv%s/dw" % tag, x, c, 3, stride, phase, "relu%s/dw" % tag, group=c)
+        x, c = _mb_conv(w, "conv%s/sep" % tag, x, wd(width), 1, 1, phase, "relu%s/sep" % tag), wd(width)
+    _mb_tail(w, phase, x, classes)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def _mb2_block(w: _Writer, tag: str, x: str, cin: int, cout: int, t: int, stride: int, phase: str) -> str:
+    """One inverted residual of MobileNet v2: 1x1 `<tag>/expand` to t * cin (left out at t == 1) + ReLU, depthwise 3x3 `<tag>/dwise` at
+    `stride` + ReLU, the linear 1x1 `<tag>/linear` to cout; with stride 1 and cin == cout the Eltwise sum `block_<tag>` with the input."""
+    y, mid = x, cin * t
+    if t != 1:
+        y = _mb_conv(w, "conv%s/expand" % tag, y, mid, 1, 1, phase, "relu%s/expand" % tag)
+    y = _mb_conv(w, "conv%s/dwise" % tag, y, mid, 3, stride, phase, "relu%s/dwise" % tag, group=mid)
+    y = _mb_conv(w, "conv%s/linear" % tag, y, cout, 1, 1, phase, None)
+    if stride == 1 and cin == cout:
+        w.layer("block_%s" % tag, "Eltwise", [x, y], ["block_%s" % tag], "  eltwise_param { operation: SUM }")
+        y = "block_%s" % tag
+    return y
+
+
+def mobilenet_v2(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224, fillers: bool = True) -> str:
+    """MobileNet v2: the structure of the paper (no published prototxt was at hand).  conv1 3x3 / 2 (32), the seven stages (t, c, n, s) =
+    (1,16,1,1), (6,24,2,2), (6,32,3,2), (6,64,4,2), (6,96,3,1), (6,160,3,2), (6,320,1,1) of inverted residuals - 17 depthwise layers,
+    linear bottlenecks, 10 Eltwise sums - the 1x1 convolution conv9 to 1280, pool6 (global AVE), the 1x1 classifier fc7 and the ends of
+    mobilenet_v1.  Plain ReLU, as the common Caffe port has it (the paper's ReLU6 is not a layer of this project).
+
+    Names: the spelling `conv<stage>_<block>/expand`, `/dwise`, `/linear`, `block_<stage>_<block>`, pool6 and fc7 is the common Caffe
+    port's; the numbering (stage 2 .. 8 of the paper's table, block 1 .. n) and conv9, `<conv>/bn`, `<conv>/scale` and the ReLUs are this
+    project's, and the first block has no expand layer (t = 1), as in the paper.  width_div divides every width, size is the image edge."""
+    _check_phase(phase)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "MobileNet-v2"')
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, 1, 1)))
+    x, c = _mb_conv(w, "conv1", "data", wd(32), 3, 2, phase, "relu1"), wd(32)
+    for stage, (t, width, n, s) in enumerate(MOBILENET_V2, 2):
+        for b in range(n):
+            x, c = _mb2_block(w, "%d_%d" % (stage, b + 1), x, c, wd(width), t, s if b == 0 else 1, phase), wd(width)
+    x = _mb_conv(w, "conv9", x, wd(1280), 1, 1, phase, "relu9")
+    _mb_tail(w, phase, x, classes)
+    return w.text() if fillers else _strip_fillers(w.text())

@@ -238,10 +238,15 @@ LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropy
 class NetSpec:
     """Phase-filtered layer list + blob/parameter shapes."""
 
-    def __init__(self, msg: proto.Msg, phase: str = "TEST"):
+    def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False):
+        """depthwise: a Convolution with group == bottom channels == num_output > 1 is a depthwise convolution (is_depthwise), the
+        same thing as a layer of type DepthwiseConvolution - the way the published MobileNet prototxts write it.  Off by default:
+        a bare NetSpec keeps refusing such a layer where its parameters are laid out (storage.conv_groups).  The public entry points
+        (caffe.Net, caffe.get_solver, `caffe train / test / time`) pass True."""
         if phase not in ("TRAIN", "TEST"):
             raise ValueError("phase must be 'TRAIN' or 'TEST'")
         self.phase = phase
+        self.depthwise = bool(depthwise)
         self.name = str(msg.get("name", ""))
         self.layers: List[Layer] = [Layer(m) for m in msg.getall("layer") if _phase_included(m, phase)]
         if msg.getall("layers"):
@@ -264,8 +269,21 @@ class NetSpec:
         self.param_shapes: Dict[str, List[Shape]] = {}
 
     @classmethod
-    def from_file(cls, path: str, phase: str = "TEST") -> "NetSpec":
-        return cls(proto.parse_file(path), phase)
+    def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False) -> "NetSpec":
+        return cls(proto.parse_file(path), phase, depthwise)
+
+    def is_depthwise(self, l: Layer) -> bool:
+        """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose
+        group equals its bottom's channels and its num_output (> 1).  The one predicate storage and both planners ask; it needs
+        infer() to have run."""
+        if l.type == "DepthwiseConvolution":
+            return True
+        if l.type != "Convolution" or not self.depthwise:
+            return False
+        p = l.sub("convolution_param")
+        g = int(p.get("group", 1))
+        shp = self.blob_shapes.get(l.bottoms[0]) if l.bottoms else None
+        return g > 1 and shp is not None and len(shp) == 4 and g == shp[1] == int(p.get("num_output"))
 
     # ------------------------------------------------------------------
     def data_tops(self) -> List[str]:
@@ -282,6 +300,7 @@ class NetSpec:
         if data_shapes:
             shapes.update({k: tuple(int(d) for d in v) for k, v in data_shapes.items()})
         self.param_shapes = {}
+        self.blob_shapes = shapes      # (filled as the layers are walked: is_depthwise reads a layer's bottom)
         for l in self.layers:
             t = l.type
             if t in DATA_TYPES:
@@ -301,10 +320,35 @@ class NetSpec:
                 n, c, h, w = bots[0]
                 d = layer_dilation(l)
                 rect = (kh, sh, ph) != (kw, sw, pw)
-                if (d > 1 or rect) and (conv_out(h, kh, sh, ph, d) < 1 or conv_out(w, kw, sw, pw, d) < 1):
+                if self.depthwise and g > 1 and g == c and co != c:
+                    raise NotImplementedError("layer %s: depthwise Convolution over %d channels with num_output %d (a channel multiplier of "
+                                              "%s is not supported: num_output must equal group)" % (l.name, c, co, co // c if co % c == 0 else "%d/%d" % (co, c)))
+                if (d > 1 or rect or self.is_depthwise(l)) and (conv_out(h, kh, sh, ph, d) < 1 or conv_out(w, kw, sw, pw, d) < 1):
                     raise ValueError("layer %s: the %dx%d window with dilation %d exceeds the padded %dx%d bottom" % (l.name, kh, kw, d, h + 2 * ph, w + 2 * pw))
                 self.param_shapes[l.name] = [(co, c // g, kh, kw)] + ([(co,)] if bool(p.get("bias_term", True)) else [])
                 shapes[l.tops[0]] = (n, co, conv_out(h, kh, sh, ph, d), conv_out(w, kw, sw, pw, d))
+            elif t == "DepthwiseConvolution":
+                # the common forks' DepthwiseConvolutionLayer (MobileNet-SSD deploy files): a convolution_param whose group, if written,
+                # equals the bottom's channels and num_output; the blob is Caffe's (C, 1, kh, kw)
+                p = l.sub("convolution_param")
+                if len(bots) != 1 or len(bots[0]) != 4 or len(l.tops) != 1:
+                    raise ValueError("layer %s: DepthwiseConvolution takes one 4-d bottom and has one top, got %s" % (l.name, bots))
+                kh, kw, sh, sw, ph, pw = layer_geometry(l)
+                n, c, h, w = bots[0]
+                if p.get("num_output") is None:
+                    raise ValueError("layer %s: DepthwiseConvolution without num_output" % l.name)
+                co, g = int(p.get("num_output")), int(p.get("group", c))
+                if g == c and co > c and co % c == 0:
+                    raise NotImplementedError("layer %s: DepthwiseConvolution over %d channels with num_output %d (a channel multiplier of "
+                                              "%d is not supported: num_output must equal the bottom's channels)" % (l.name, c, co, co // c))
+                if g != c or co != c:
+                    raise ValueError("layer %s: DepthwiseConvolution over %d channels with group %d, num_output %d (group, if written, and "
+                                     "num_output must equal the bottom's channels)" % (l.name, c, g, co))
+                d = layer_dilation(l)
+                if conv_out(h, kh, sh, ph, d) < 1 or conv_out(w, kw, sw, pw, d) < 1:
+                    raise ValueError("layer %s: the %dx%d window with dilation %d exceeds the padded %dx%d bottom" % (l.name, kh, kw, d, h + 2 * ph, w + 2 * pw))
+                self.param_shapes[l.name] = [(c, 1, kh, kw)] + ([(c,)] if bool(p.get("bias_term", True)) else [])
+                shapes[l.tops[0]] = (n, c, conv_out(h, kh, sh, ph, d), conv_out(w, kw, sw, pw, d))
             elif t == "Deconvolution":
                 p = l.sub("convolution_param")
                 k, s, pad = _square(l)

@@ -95,7 +95,7 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             pw = cons[0].sub("power_param")
             t = cons[0].tops[0]
             if (float(pw.get("power", 1.0)) != 1.0 or float(pw.get("scale", 1.0)) != 1.0 or t == d or t in outputs
-                    or [q.type for q in consumers.get(t, [])] != ["Convolution"]):
+                    or [q.type for q in consumers.get(t, [])] != ["Convolution"] or spec.is_depthwise(consumers[t][0])):
                 continue
             half_inputs[d] = (t, float(pw.get("shift", 0.0)))
     halves = set(half_inputs) | {t for t, _s in half_inputs.values()}
@@ -113,7 +113,7 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             if esize[name] == 4 and len(shapes[name]) in (2, 4) and name not in data_tops:
                 # (Softmax, Deconvolution and Interp read halves and store float32: the out_f32 forms of their half kernels)
                 bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct",
-                                                                                 "Interp")]
+                                                                                 "Interp", "DepthwiseConvolution")]
                 if bad:
                     raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 
@@ -217,7 +217,7 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
 
 
 # ---------------------------------------------------------------------- parameters
-CONV, INNER_PRODUCT, DECONV, PLAIN = "conv", "inner_product", "deconv", "plain"
+CONV, INNER_PRODUCT, DECONV, PLAIN, DEPTHWISE = "conv", "inner_product", "deconv", "plain", "depthwise"
 
 
 @dataclass(frozen=True)
@@ -228,6 +228,7 @@ class ParamSeg:
     kind: str                            # CONV: OHWI, Cin padded to whole 16-byte segments of the bottom's elements
     #                                      INNER_PRODUCT: [num_output][H*W*cstride], the columns in the order of a row of the NHWC bottom
     #                                      DECONV (group 1): [Cin][kh][kw][Cout padded to 4], an OHWI bank of Cin outputs over Cout inputs
+    #                                      DEPTHWISE: [kh][kw][C padded to whole 16-byte segments of the bottom's elements], always float32
     #                                      PLAIN: as it is (biases, the depthwise Deconvolution's filters)
     offset: int                          # in 4-byte words (= floats in the f32 engine, where the solver and RCCL index the buffer)
     count: int                           # elements on the device
@@ -250,7 +251,12 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
             continue
         for i, host_shape in enumerate(tuple(int(v) for v in s) for s in spec.param_shapes[l.name]):
             kind, shape, esize, bottom = PLAIN, host_shape, 4, None
-            if i == 0 and l.type == "Convolution":
+            if i == 0 and spec.is_depthwise(l):
+                # tap-major, channel-contiguous, float32 whatever the bottom holds: a lane that owns a 16-byte channel segment of the
+                # bottom fetches a tap's weights with one 16-byte load (csrc/dwconv.hip); conv_groups is not asked
+                c, _one, kh, kw = host_shape
+                kind, shape = DEPTHWISE, (kh, kw, _ra(c, views[l.bottoms[0]].esize))
+            elif i == 0 and l.type == "Convolution":
                 esize = views[l.bottoms[0]].esize          # element type of the layer's input: 16-byte segments of it
                 co, ci, kh, kw = host_shape
                 conv_groups(l, co, ci, esize)
@@ -303,7 +309,9 @@ def conv_groups(l: Layer, cout: int, cin_g: int, esize: int) -> int:
     if cin_g % eps or (cout // g) % eps:
         raise NotImplementedError("grouped Convolution %s: group %d leaves %d input and %d output channels per group, not whole 16-byte "
                                   "segments (%d %s)%s" % (l.name, g, cin_g, cout // g, eps, "floats" if esize == 4 else "halves",
-                                                          ": depthwise convolution has no kernel here" if cin_g == 1 else ""))
+                                                          ": depthwise convolution has no kernel here for a NetSpec built without "
+                                                          "depthwise=True (caffe.Net and the solvers pass it; type DepthwiseConvolution "
+                                                          "needs no keyword)" if cin_g == 1 else ""))
     return g
 
 
@@ -331,6 +339,10 @@ def pack(seg: ParamSeg, host_blob: np.ndarray, folded_shift: float = 0.0) -> np.
         return ip_pack_bank(a, *seg.bottom, dtype)
     if seg.kind == PLAIN:
         return np.ascontiguousarray(a.reshape(seg.shape))
+    if seg.kind == DEPTHWISE:               # Caffe's (C, 1, kh, kw) -> [kh][kw][C padded]
+        out = np.zeros(seg.shape, F32)
+        out[..., :seg.host_shape[0]] = a[:, 0].transpose(1, 2, 0)
+        return out
     n = seg.host_shape[1]                   # CONV: Cin; DECONV: Cout, which its data gradient (a forward convolution of dY) reads as Cin
     out = np.zeros(seg.shape, dtype)
     out[..., :n] = a.transpose(0, 2, 3, 1)
@@ -351,4 +363,6 @@ def unpack(seg: ParamSeg, raw: np.ndarray) -> np.ndarray:
         return ip_unpack_bank(a, *seg.bottom)
     if seg.kind in (CONV, DECONV):
         a = a[..., :seg.host_shape[1]].transpose(0, 3, 1, 2)
+    if seg.kind == DEPTHWISE:
+        a = a[..., :seg.host_shape[0]].transpose(2, 0, 1)
     return np.array(a.reshape(seg.host_shape), dtype=F32, order="C")

@@ -290,7 +290,7 @@ class TrainEngine(Engine):
             out = set()
             layers = self.spec.layers
             for li, l in enumerate(layers):
-                if l.type in ("Convolution", "InnerProduct") and self._conv_layer_meta.get(l.name, {}).get("relu"):
+                if l.type in ("Convolution", "DepthwiseConvolution", "InnerProduct") and self._conv_layer_meta.get(l.name, {}).get("relu"):
                     top = l.tops[0]
                     for nxt in layers[li + 1:]:
                         if top in nxt.bottoms or top in nxt.tops:

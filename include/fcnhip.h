@@ -752,6 +752,61 @@ int    fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s);
 size_t fcn_rconv2d_wgrad_workspace_floats(const fcn_rconv_desc* h_d);
 int    fcn_rconv2d_wgrad_f32(const fcn_rconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s);
 
+/* ---- depthwise convolution: Caffe ConvolutionLayer with group == channels == num_output (the 3x3 layers of MobileNet v1 / v2 and
+ *      MobileNet-SSD, the separable blocks of Xception / DeepLab-v3+), forward in float32 and in halves, data gradient and weight
+ *      gradient, per-axis kernel / pad / stride and one dilation for both axes.  NHWC, vector units (kh*kw multiply-adds per element
+ *      moved: bound by memory).  With zeros outside the image:
+ *        y[n, oy, ox, c] = bias[c] + sum over r, q of w[r][q][c] * x[n, oy*stride_h - pad_h + r*dil, ox*stride_w - pad_w + q*dil, c]
+ *        OH = (H + 2 pad_h - (dil*(kh-1) + 1)) / stride_h + 1     (floor)        OW likewise with kw, pad_w, stride_w
+ *      The bank is tap-major and channel-contiguous, [kh][kw][roundS(C)] float32 with S the bottom's 16-byte segment (4 floats, 8
+ *      halves), pad channels zero, 16-byte aligned; the bias is float32.  Every call is ONE pure kernel launch (capturable; the weight
+ *      gradient with pixel splits: two), needs no prepare step and, forward and data gradient, no workspace and no LDS.  Every output
+ *      element is written by exactly one lane, there are no float atomics, a second launch gives the same bits.
+ *      cfg_request: -1 = built-in choice (the strip form for stride_w 1 on large blobs), 0 = one output pixel per lane (every geometry), 1 = a strip of output pixels along x per lane
+ *      (4 in float32, 2 in halves): stride_w 1 or 2, dilation 1, kw 1 / 3 / 5 / 7, else FCN_E_UNSUPPORTED (a caller walking all
+ *      configurations skips it); forward only.
+ *      fwd_f32 flags: FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK, applied in the order accumulate, ReLU, mask; y2 is only read.
+ *      fwd_f16: x and y hold halves (8 channels per lane, float32 accumulation, bank and bias float32); flags FCN_CONV_RELU |
+ *      FCN_CONV_OUT_F32 (y is float32).
+ *      Channels C .. roundS(C)-1 of x are padding: they never reach a real channel of y (they may hold anything); channels of y outside
+ *      [y_coffset, y_coffset + C) are not touched.  16-byte stores when y (y2) is 16-byte aligned with strides / offsets in whole
+ *      16-byte runs, scalar stores otherwise and for a last partial group.
+ *      dgrad_f32: the descriptor is the FORWARD problem; y / y_cstride / y_coffset name dY (read) and x / x_cstride name dX (written,
+ *      channels 0 .. C-1 of every pixel): dx[n, iy, ix, c] = sum of w[r][q][c] * dy[n, oy, ox, c] over the taps with oy*stride_h ==
+ *      iy + pad_h - r*dil and ox*stride_w == ix + pad_w - q*dil in range - the same bank, no flip, any stride, any pad >= 0.  flags:
+ *      FCN_CONV_ACCUM | FCN_CONV_MASK as the other data-gradient passes use them, y2 indexed at dX's pixel; bias is ignored.
+ *      Refused on the host before the first HIP call: FCN_E_ARG (null descriptor / x / w / y / dw, non-positive extent or stride,
+ *      negative pad, window larger than the padded image, OH / OW not the value above, slice wider than its stride, FCN_CONV_MASK
+ *      without y2 or with a y2 slice narrower than C, unknown cfg_request, split_request outside 0 .. min(1024, N*OH*OW), pixel splits
+ *      without a workspace), FCN_E_ALIGN (x_cstride not a multiple of S or below roundS(C); x / w / dw / the workspace not 16-byte
+ *      aligned; y / bias / db not aligned to their elements), FCN_E_UNSUPPORTED (other flags, dilation < 1, more than 7 x 7 taps, a
+ *      configuration that does not take the geometry, tensors past 2^31 elements). ---- */
+typedef struct fcn_dwconv_desc {
+    void*        x;      /* NHWC input, channel stride x_cstride (a multiple of S, >= roundS(C)); dX for dgrad (written)   */
+    const float* w;      /* bank [kh][kw][roundS(C)] float32, 16-byte aligned                                              */
+    const float* bias;   /* [C] float32 or NULL                                                                            */
+    void*        y;      /* NHWC output; channel c of pixel m at y[m*y_cstride + y_coffset + c]; dY for dgrad / wgrad       */
+    float*       y2;     /* FCN_CONV_MASK: the activation whose sign masks the result (same indexing via y2_*)             */
+    int32_t N, H, W, C, x_cstride;
+    int32_t kh, kw, pad_h, pad_w, stride_h, stride_w, OH, OW;
+    int32_t y_cstride, y_coffset, y2_cstride, y2_coffset;
+    int32_t flags;
+    int32_t dilation;
+} fcn_dwconv_desc;
+int    fcn_dwconv2d_num_configs(void);
+int    fcn_dwconv2d_fwd_f32(const fcn_dwconv_desc* h_d, int cfg_request, fcn_stream_t s);
+int    fcn_dwconv2d_fwd_f16(const fcn_dwconv_desc* h_d, int cfg_request, fcn_stream_t s);
+int    fcn_dwconv2d_dgrad_f32(const fcn_dwconv_desc* h_d, int cfg_request, fcn_stream_t s);
+/* Weight / bias gradient: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY (d->w, d->bias, d->y2 and d->flags
+ * are ignored).  dw is [kh][kw][round4(C)], 16-byte aligned, and is OVERWRITTEN; its pad channels are written as exact zeros whatever
+ * the pad channels of x and dY hold.  db is [C] or NULL.  split_request: 0 = built-in choice, n > 0 = n pixel splits (fewer when a
+ * split would be empty).  With one split dw and db are written directly; otherwise every split writes a slab of the workspace
+ * (fcn_dwconv2d_wgrad_workspace_floats() floats for the same split_request - (kh*kw + 1) * round4(C) per split: the taps' rows, then
+ * db's - 16-byte aligned; 0 = none needed, NULL allowed) and a second small launch adds the slabs in a fixed order (64 lanes per column,
+ * each its slabs in ascending order, then a fold by halves): bit-reproducible, no atomics, 4 KiB of LDS in either launch. */
+size_t fcn_dwconv2d_wgrad_workspace_floats(const fcn_dwconv_desc* h_d, int split_request);
+int    fcn_dwconv2d_wgrad_f32(const fcn_dwconv_desc* h_d, float* dw, float* db, float* d_workspace, int split_request, fcn_stream_t s);
+
 /* ---- Crop (Caffe CropLayer: the skip connections and the final score map of the published FCN-32s / 16s / 8s nets): a window copy
  *      between two NHWC views with channel strides, and its adjoint.  x / dX is the N x H x W view, y / dY the N x OH x OW window at
  *      (off_y, off_x); a crop along the channel axis is the caller adding its offset to x_coffset.

@@ -1,0 +1,251 @@
+"""Depthwise Convolution as the forward and backward planners lay it out - without a GPU.
+
+As tests/test_rect_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by a counter
+of addresses and the library by one whose every entry point returns 0; what is checked is the arithmetic of the descriptors (pointers,
+extents, flags), the level and the read / write ranges of the task, how the weight gradient is booked, that every refusal names its
+layer - and that nets without a depthwise layer plan exactly the same with NetSpec(depthwise=True) as without it."""
+import ctypes as C
+import json
+import threading
+
+import pytest
+
+from fcn_object_detector_amd import backward as BW
+from fcn_object_detector_amd import engine as E
+from fcn_object_detector_amd import lib as L
+from fcn_object_detector_amd import models, proto
+from fcn_object_detector_amd import storage as S
+from fcn_object_detector_amd import train as T
+from fcn_object_detector_amd.netspec import NetSpec, fill_params
+
+FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
+NET = """
+input: "data" input_shape { dim: 2 dim: 3 dim: 12 dim: 14 }
+%s
+layer { name: "c0" type: "Convolution" bottom: "data" top: "c0" convolution_param { num_output: 6 kernel_size: 3 pad: 1 FILL } }
+layer { name: "r0" type: "ReLU" bottom: "c0" top: "c0" }
+layer { name: "dwa" type: "Convolution" bottom: "c0" top: "dwa" convolution_param { num_output: 6 group: 6 kernel_size: 3 pad: 1 stride: 2 engine: CAFFE FILL } }
+layer { name: "rdwa" type: "ReLU" bottom: "dwa" top: "dwa" }
+layer { name: "dwb" type: "DepthwiseConvolution" bottom: "c0" top: "dwb"
+        convolution_param { num_output: 6 kernel_h: 3 kernel_w: 5 pad_h: 2 pad_w: 4 stride: 2 dilation: 2 bias_term: false FILL } }
+layer { name: "sum" type: "Eltwise" bottom: "dwa" bottom: "dwb" top: "sum" }
+layer { name: "pw" type: "Convolution" bottom: "sum" top: "pw" convolution_param { num_output: 5 kernel_size: 1 FILL } }
+%s
+""".replace("FILL", FILL)
+TEST_NET = NET % ("", "")
+TRAIN_NET = NET % ('input: "target" input_shape { dim: 2 dim: 5 dim: 6 dim: 7 }',
+                   'layer { name: "loss" type: "EuclideanLoss" bottom: "pw" bottom: "target" top: "loss" }')
+
+
+class FakeBuffer:
+    next_ptr = 1 << 20
+
+    def __init__(self, nbytes, zero=True):
+        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
+        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
+
+    def free(self):
+        pass
+
+
+class FakeLib:
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def fn(*a):
+            self.calls.append(name)
+            return 0
+        return fn
+
+
+@pytest.fixture
+def stub(monkeypatch):
+    copies, lib = [], FakeLib()
+
+    def call(name, *a):
+        lib.calls.append(name)
+        if name == "fcn_memcpy_h2d_async":
+            copies.append((int(a[0]), C.string_at(a[1], a[2])))
+    for mod in (E, BW, T):
+        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
+    monkeypatch.setattr(L, "call", call)
+    monkeypatch.setattr(L, "load", lambda: lib)
+
+    def make(text, phase="TEST", f16=False, depthwise=True):
+        FakeBuffer.next_ptr = 1 << 20
+        spec = NetSpec(proto.parse_text(text), phase, depthwise=depthwise)
+        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
+        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
+        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
+        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
+        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
+        e.grad_blobs, e.stream, e.lock, e.copies, e.fake = {}, None, threading.RLock(), copies, lib
+        e._bn_chains, e._bn_ws_bytes = {}, 0
+        e._plan_buffers()
+        e._alloc_params(fill_params(spec, seed=1))
+        if phase == "TRAIN":
+            e.grad_flat = FakeBuffer(4 * e.param_count)
+        e.tasks = e._collect_tasks()
+        return e
+    return make
+
+
+def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
+    e = stub(TEST_NET)
+    assert [t.layer.name for t in e.tasks if isinstance(t, E.ConvTask)] == ["c0", "pw"]      # never a ConvTask: no grouped launch, no tuner
+    dt = {t.layer.name: t for t in e.tasks if isinstance(t, E.OpTask) and t.dwconv is not None}
+    assert sorted(dt) == ["dwa", "dwb"]
+    assert "rdwa" not in [t.layer.name for t in e.tasks]                    # the in-place ReLU rides in dwa's epilogue
+    assert e._conv_layer_meta["dwa"] == dict(relu=True, sigmoid_top=None) and e._conv_layer_meta["dwb"]["relu"] is False
+    x = e.blobs["c0"]
+    for nm, (kh, kw, ph, pw, dil), (oh, ow), relu in (("dwa", (3, 3, 1, 1, 1), (6, 7), True), ("dwb", (3, 5, 2, 4, 2), (6, 7), False)):
+        t, d, y, pd = dt[nm], dt[nm].dwconv, e.blobs[nm], e.params_dev[nm]
+        assert isinstance(d, L.DwConvDesc) and t.dconv is None and t.rconv is None and t.pool_desc is None and len(t.ops) == 1
+        assert (d.x, d.C, d.x_cstride, d.N, d.H, d.W) == (x.ptr, 6, 8, 2, 12, 14)
+        assert (d.y, d.y_coffset, d.y_cstride, d.OH, d.OW) == (y.buf.ptr, y.coffset, y.cstride, oh, ow)
+        assert (d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w, d.dilation) == (kh, kw, ph, pw, 2, 2, dil)
+        assert d.w == pd[0].ptr and d.bias == (pd[1].ptr if len(pd) > 1 else None) and d.flags == (L.CONV_RELU if relu else 0)
+        seg = e.param_segs[(nm, 0)]
+        assert (seg.kind, seg.shape, seg.esize, seg.host_shape) == (S.DEPTHWISE, (kh, kw, 8), 4, (6, 1, kh, kw))      # [kh][kw][round4(C)]
+        assert t.reads == [e._range("c0")] and t.writes == [e._range(nm)]
+        op = t.ops[0]
+        assert op.kind == "dwconv" and op.name == "%s [%dx%d]" % (nm, kh, kw)
+        assert op.flops == 2.0 * 2 * oh * ow * 6 * kh * kw                                   # 2 N OH OW C kh kw
+        assert op.bytes == 4.0 * (2 * 12 * 14 * 6 + 2 * oh * ow * 6 + kh * kw * 6 + 6)       # 4 (N H W C + N OH OW C + kh kw C + C)
+        del e.fake.calls[:]
+        op.run(None)
+        assert e.fake.calls == ["fcn_dwconv2d_fwd_f32"]
+    assert len(e.params_dev["dwb"]) == 1
+    # the bank as uploaded: tap-major, the channels of one tap contiguous, pad channels zero
+    import numpy as np
+    raw = [data for dst, data in e.copies if dst == e.params_dev["dwa"][0].ptr][-1]
+    bank = np.frombuffer(raw, np.float32).reshape(3, 3, 8)
+    assert np.array_equal(bank[..., :6], e.params_host["dwa"][0][:, 0].transpose(1, 2, 0)) and not bank[..., 6:].any()
+    # both read c0 and write different blobs: one level behind c0; the sum waits for both
+    lv = dict(zip([t.layer.name for t in e.tasks], E.task_levels(e.tasks)))
+    assert lv["dwa"] == lv["dwb"] == lv["c0"] + 1 and lv["pw"] > lv["sum"] > lv["dwa"]
+    # the whole plan: the two launches and nothing of the other convolution families for them
+    e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+    del e.fake.calls[:]
+    e._build_ops()
+    assert [op.name for op in e.ops if op.kind == "dwconv"] == ["dwa [3x3]", "dwb [3x5]"]
+    assert not any(c in e.fake.calls for c in ("fcn_rconv2d_prepare", "fcn_dconv2d_prepare")) and e.fake.calls.count("fcn_conv2d_group_prepare") + \
+        e.fake.calls.count("fcn_conv2d_group_prepare_fused") == 2
+
+
+def test_the_half_engine_runs_the_half_kernel_on_a_float32_bank(stub):
+    e = stub(TEST_NET, f16=True)
+    dt = {t.layer.name: t for t in e.tasks if isinstance(t, E.OpTask) and t.dwconv is not None}
+    x, y = e.blobs["c0"], e.blobs["dwa"]
+    assert x.esize == 2 and y.esize == 2
+    d = dt["dwa"].dwconv
+    assert (d.x, d.x_cstride, d.y, d.y_cstride, d.C, d.flags) == (x.ptr, 8, y.buf.ptr, 8, 6, L.CONV_RELU)
+    seg = e.param_segs[("dwa", 0)]
+    assert (seg.kind, seg.shape, seg.esize, seg.nbytes) == (S.DEPTHWISE, (3, 3, 8), 4, 3 * 3 * 8 * 4)      # round8(C) channels, float32
+    assert e.param_segs[("dwa", 1)].esize == 4 and e.param_segs[("pw", 0)].esize == 2
+    del e.fake.calls[:]
+    dt["dwa"].ops[0].run(None)
+    assert e.fake.calls == ["fcn_dwconv2d_fwd_f16"]
+    # a depthwise layer that is the net's output stores float32
+    out = stub(TEST_NET.split('layer { name: "rdwa"')[0], f16=True)
+    t = [t for t in out.tasks if isinstance(t, E.OpTask) and t.dwconv is not None][0]
+    assert out.outputs == ["dwa"] and out.blobs["dwa"].esize == 4 and t.dwconv.flags == L.CONV_OUT_F32 and t.dwconv.y_cstride == 8
+
+
+def test_backward_plan_of_depthwise_layers(stub):
+    e = stub(TRAIN_NET, "TRAIN")
+    B, G = e.blobs, e.grad_blobs
+    assert {"c0", "dwa", "dwb", "sum", "pw"} <= set(G)
+    plan = BW.BackwardPlanner(e)
+    plan._plan_banks()
+    assert plan.flip_layout == {"pw": 0} and not plan.tbank      # the depthwise layers need no flipped or re-packed bank, whatever their stride
+    by = {l.name: l for l in e.spec.layers}
+    e._ws = FakeBuffer(64)
+    plan.mark(G["pw"])
+    plan._convolution(by["pw"])
+    plan._eltwise(by["sum"])
+    n0 = len(plan.ops)
+    plan._convolution(by["dwb"])
+    plan._convolution(by["dwa"])
+    assert [(op.kind, op.name) for op in plan.ops[n0:]] == [("wgrad", "dwb"), ("dwconv_dgrad", "dwb [3x5]"), ("relu_bwd", "dwa"), ("wgrad", "dwa"),
+                                                            ("dwconv_dgrad", "dwa [3x3]")]
+    wop = plan.ops[n0]
+    assert wop.layers == ["dwb"] and wop.sel is None and {"dwa", "dwb"} <= plan.wgrad_done
+    assert wop.flops == 2.0 * 2 * 6 * 7 * 6 * 15 and wop.bytes == 4.0 * (2 * 12 * 14 * 6 + 2 * 6 * 7 * 6 + 15 * 6 + 6)
+    del e.fake.calls[:]
+    wop.run(None)
+    assert e.fake.calls == ["fcn_dwconv2d_wgrad_f32"]
+    first, last = plan.writers["c0"]
+    assert first.launch is None and first.targets == ["c0"] and isinstance(first.descs[0], L.DwConvDesc)
+    # the descriptor is the FORWARD problem: x names dX (the gradient view of c0), y names dY, the bank is the layer's own
+    d = first.descs[0]
+    assert (d.x, d.x_cstride, d.C, d.N, d.H, d.W) == (G["c0"].ptr, 8, 6, 2, 12, 14)
+    assert (d.y, d.y_cstride, d.y_coffset, d.OH, d.OW) == (G["dwb"].buf.ptr, 8, 0, 6, 7)
+    assert (d.w, d.bias, d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w, d.dilation, d.flags) == (e.params_dev["dwb"][0].ptr, None, 3, 5, 2, 4, 2, 2, 2, 0)
+    dl = last.descs[0]
+    assert (dl.kh, dl.kw, dl.stride_h, dl.flags, dl.w) == (3, 3, 2, L.CONV_ACCUM, e.params_dev["dwa"][0].ptr)      # dX already holds dwb's share
+    # c0's own ReLU mask is folded into the LAST pass that writes its gradient, as for a dense pass
+    plan._convolution(by["c0"])
+    del e.fake.calls[:]
+    e._group_workspaces = []
+    plan._finish_dgrads()
+    assert [c for c in e.fake.calls if "prepare" in c] == ["fcn_conv2d_group_prepare"]      # pw's dense pass; a depthwise gather has nothing to prepare
+    assert dl.flags == L.CONV_ACCUM | L.CONV_MASK and (dl.y2, dl.y2_cstride, dl.y2_coffset) == (B["c0"].buf.ptr, B["c0"].cstride, B["c0"].coffset)
+    assert first.descs[0].flags == 0 and ("relu_bwd", "c0") not in [(op.kind, op.name) for op in plan.ops]
+    last.op.run(None)
+    assert e.fake.calls[-1] == "fcn_dwconv2d_dgrad_f32"
+    assert "rdwa" in e._fused_relu_layers()
+
+
+ONE = """
+input: "data" input_shape { dim: 1 dim: 4 dim: 16 dim: 16 }
+layer { name: "c0" type: "Convolution" bottom: "data" top: "c0" convolution_param { num_output: 8 kernel_size: 3 pad: 1 FILL } }
+layer { name: "dw" type: "%s" bottom: "c0" top: "dw" convolution_param { num_output: %d group: 8 kernel_size: 3 pad: 1 FILL } }
+""".replace("FILL", FILL)
+
+
+def test_refusals_name_the_layer(stub):
+    with pytest.raises(NotImplementedError, match=r"grouped Convolution dw: group 8 .*depthwise convolution has no kernel here.*depthwise=True"):
+        stub(ONE % ("Convolution", 8), depthwise=False)
+    stub(ONE % ("Convolution", 8))
+    stub(ONE % ("DepthwiseConvolution", 8), depthwise=False)
+    with pytest.raises(NotImplementedError, match=r"layer dw: depthwise Convolution over 8 channels with num_output 16 \(a channel multiplier of 2"):
+        stub(ONE % ("Convolution", 16))
+    with pytest.raises(NotImplementedError, match=r"layer dw: DepthwiseConvolution over 8 channels with num_output 16 \(a channel multiplier of 2"):
+        stub(ONE % ("DepthwiseConvolution", 16))
+
+
+# ---------------------------------------------------------------- nets without a depthwise layer plan the same with the keyword
+def _fields(d):
+    return None if d is None else {n: getattr(d, n) for n, _ in d._fields_}
+
+
+def plan_signature(e):
+    out = []
+    for t, lv in zip(e.tasks, E.task_levels(e.tasks, e.group_convs)):
+        rec = {"task": type(t).__name__, "layer": t.layer.name, "level": lv, "reads": [list(r) for r in t.reads], "writes": [list(r) for r in t.writes]}
+        if isinstance(t, E.ConvTask):
+            rec.update(desc=_fields(t.desc), flops=t.flops, bytes=t.bytes)
+        else:
+            rec.update(ops=[[op.kind, op.name, op.flops, op.bytes] for op in t.ops], pool=_fields(t.pool_desc), dconv=_fields(t.dconv),
+                       rconv=_fields(t.rconv), dwconv=_fields(t.dwconv))
+        out.append(rec)
+    return out
+
+
+@pytest.mark.parametrize("name,text", [
+    ("googlenet_detectnet", lambda: models.googlenet_detectnet_deploy(batch=1, height=96, width=128, num_classes=2)),
+    ("resnet50", lambda: models.resnet("DEPLOY", depth=50, batch=1, num_classes=10, width_div=8, size=64)),
+    ("inception_v3", lambda: models.inception_v3("DEPLOY", batch=1, classes=10, width_div=8, size=139)),
+    ("caffenet", lambda: models.caffenet("DEPLOY", batch=1, num_classes=10, width_div=4, fc_div=8))])
+def test_nets_without_a_depthwise_layer_plan_the_same_with_the_keyword(stub, name, text):
+    text = text()
+    plain = stub(text, depthwise=False)
+    sig_plain = json.dumps(plan_signature(plain))
+    del plain.fake.calls[:]
+    keyed = stub(text, depthwise=True)
+    assert all(t.dwconv is None for t in keyed.tasks if isinstance(t, E.OpTask)), name
+    assert json.dumps(plan_signature(keyed)) == sig_plain, name
+    assert keyed.param_layout == plain.param_layout and keyed.param_count == plain.param_count, name
+    assert not any(c.startswith("fcn_dwconv2d") for c in keyed.fake.calls), name
