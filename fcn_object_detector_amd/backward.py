@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Tuple
 from . import lib as L
 from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, layer_dilation
+from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation
 
 
 @dataclass
@@ -74,7 +74,7 @@ class BackwardPlanner:
         # ... and the ones _one_bottom hands (layer, dY, dX, accumulate)
         self.one_bottom = {"Pooling": self._pooling, "LRN": self._lrn, "Dropout": self._dropout, "Eltwise": self._eltwise_prod,
                            "Deconvolution": self._depthwise_deconv, "Sigmoid": self._sigmoid_plain, "ReLU": self._relu_plain,
-                           "Crop": self._crop, "Interp": self._interp,
+                           "Crop": self._crop, "Interp": self._interp, "Upsample": self._upsample,
                            "Power": lambda l, gtop, gbot, acc: None}      # input transform: nothing upstream learns
 
     def run(self) -> None:
@@ -854,6 +854,19 @@ class BackwardPlanner:
         self.ops.append(Op("interp_bwd", l.name, lambda st: L.check(lib.fcn_interp_bwd_f32(
             gtop.buf.ptr, gbot.buf.ptr, n, h, w, c, gbot.cstride, gbot.coffset, pad_beg, pad_end, oh, ow, gtop.cstride, gtop.coffset, acc, st)),
             0.0, 4.0 * (gtop.pixels + gbot.pixels * (1 + acc)) * c))
+        self.mark(gbot)
+
+    def _upsample(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        """fcn_unpool_bwd_f32: dX of bottom 0 gathers dY at the pixels the mask names.  Bottom 1 is the mask: no gradient goes there."""
+        lib = self.lib
+        pool = self.spec.mask_blobs[l.bottoms[1]]
+        idx = self.e.aux_dev[pool.name]
+        k, s, pad = kernel_stride_pad(pool.sub("pooling_param"))
+        n, c, ph, pw = gbot.shape
+        _, _, h, w = gtop.shape
+        self.ops.append(Op("unpool_bwd", l.name, lambda st: L.check(lib.fcn_unpool_bwd_f32(
+            gtop.buf.ptr, idx.ptr, gbot.buf.ptr, n, ph, pw, c, gbot.cstride, gbot.coffset, k, s, pad, h, w, gtop.cstride, gtop.coffset, acc, st)),
+            0.0, 4.0 * gbot.pixels * c * (3 + acc)))
         self.mark(gbot)
 
     def _lrn(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:

@@ -427,7 +427,8 @@ class Engine:
         self.dropout_seed = 0
         self.dropout_index_offset = 0           # data-parallel rank r: r * (elements of the dropout blob)
         self.inputs = spec.data_tops()
-        self.outputs = [b for b in spec.output_blobs() if b in self.shapes]
+        # (a pooling mask that no Upsample consumes is no output: it is not an activation blob; read_blob() still returns it)
+        self.outputs = [b for b in spec.output_blobs() if b in self.shapes and b not in spec.mask_blobs]
         # autotuner: only tile configurations whose workgroup holds at most this much LDS (engines that share the GPU with
         # other streams: small footprints let workgroups of concurrent launches fit on a CU side by side)
         max_lds = int(tune_max_lds_kb if tune_max_lds_kb is not None else os.environ.get("FCN_TUNE_MAX_LDS_KB", "160")) * 1024
@@ -610,6 +611,9 @@ class Engine:
         return d
 
     def _range(self, name: str) -> Tuple[int, int, int]:
+        pool = self.spec.mask_blobs.get(name)
+        if pool is not None:      # a pooling mask: the layer's argmax buffer, written by the pooling and read by its Upsample layers
+            return (self.aux_dev[pool.name].ptr, 0, max(self.shapes[name][1], 1))
         b = self.blobs[name]
         return (b.buf.ptr, b.coffset, b.coffset + max(b.channels, 1))
 
@@ -1133,6 +1137,8 @@ class Engine:
     def _pool_lrn_op(self, la: Layer, lb: Layer) -> Optional[Op]:
         B, lib = self.blobs, L.load()
         pool, lrn = (la, lb) if la.type == "Pooling" else (lb, la)
+        if len(pool.tops) != 1:      # a pooling with a mask top: the fused launches write no argmax
+            return None
         mid = la.tops[0]
         if [q.name for q in self.consumers.get(mid, [])] != [lb.name] or len(self.producers.get(mid, [])) != 1 or mid in self.outputs:
             return None
@@ -1174,6 +1180,8 @@ class Engine:
         xb = self.blobs.get(l.bottoms[0])
         if self.f16 and xb is not None and xb.pixels >= 16384:
             return None
+        if self.f16 and len(l.tops) == 2:      # a masked pooling of halves: fcn_maxpool_idx_fwd_f16
+            return None
         return self._fusable_pool_desc_impl(l)
 
     def _fusable_pool_desc_impl(self, l: Layer) -> Optional[L.PoolDesc]:
@@ -1208,13 +1216,14 @@ class Engine:
         """The launches of one layer that is not a convolution."""
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp"):
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample"):
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
                 "Slice": self._fwd_slice, "Concat": self._fwd_concat, "Eltwise": self._fwd_eltwise,
-                "Deconvolution": self._fwd_deconvolution, "Crop": self._fwd_crop, "Interp": self._fwd_interp}.get(t)
+                "Deconvolution": self._fwd_deconvolution, "Crop": self._fwd_crop, "Interp": self._fwd_interp,
+                "Upsample": self._fwd_upsample}.get(t)
         if emit is None:
             raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
         return emit(l, halves)
@@ -1260,6 +1269,29 @@ class Engine:
                                                             yb.cstride, yb.coffset, st))
         return [Op("interp", l.name, run, 0.0, byts)]
 
+    def _fwd_upsample(self, l: Layer, halves: List[str]) -> List[Op]:
+        """Upsample: bottom 0 scattered to the pixels that the mask names - the argmax buffer of the MAX pooling whose second top the mask
+        is - as a gather over the top; everything else in the top is zero.  Halves are read as halves and stored as halves or - a net's
+        output - as float32; the argmax is int32 in both engines."""
+        lib = L.load()
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        pool = self.spec.mask_blobs[l.bottoms[1]]
+        idx = self.aux_dev[pool.name]
+        if xb.esize == 4 and yb.esize == 2:
+            raise NotImplementedError("f16 engine: Upsample %s reads the float32 blob %s and writes halves" % (l.name, l.bottoms[0]))
+        k, s, pad = kernel_stride_pad(pool.sub("pooling_param"))
+        n, c, ph, pw = xb.shape
+        _, _, h, w = yb.shape
+        byts = float(xb.esize + 4) * xb.pixels * c + float(yb.esize) * yb.pixels * c
+        if xb.esize == 2:
+            out_f32 = 1 if yb.esize == 4 else 0
+            run = lambda st: L.check(lib.fcn_unpool_fwd_f16(xb.buf.ptr, idx.ptr, yb.buf.ptr, n, ph, pw, c, xb.cstride, xb.coffset, k, s, pad, h, w,
+                                                            yb.cstride, yb.coffset, out_f32, st))
+        else:
+            run = lambda st: L.check(lib.fcn_unpool_fwd_f32(xb.buf.ptr, idx.ptr, yb.buf.ptr, n, ph, pw, c, xb.cstride, xb.coffset, k, s, pad, h, w,
+                                                            yb.cstride, yb.coffset, st))
+        return [Op("unpool", l.name, run, 0.0, byts)]
+
     def _fwd_pooling(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
@@ -1268,16 +1300,22 @@ class Engine:
         c = g.cin
         byts = float(xb.esize) * (xb.pixels * c + yb.pixels * c)
         is_max = str(pp.get("pool", "MAX")) == "MAX"
+        masked = len(l.tops) == 2      # (netspec: MAX only) the argmax is the mask blob: kept in TEST too, and written by the half engine
         if halves and (xb.esize != 2 or yb.esize != 2):
             raise NotImplementedError("f16 engine: pooling %s" % l.name)
-        if is_max and not halves:
+        if is_max and (masked or not halves):
             idx_ptr = None
-            if self.spec.phase == "TRAIN":      # backward routes the gradient to the argmax
+            if masked or self.spec.phase == "TRAIN":      # backward routes the gradient to the argmax; an Upsample scatters by it
                 ib = DeviceBuffer(yb.pixels * c * 4, zero=False)
                 self.aux_dev[l.name] = ib
                 idx_ptr = ib.ptr
-            run = lambda st: L.check(lib.fcn_maxpool_fwd_f32(
-                xb.ptr, yb.buf.ptr, idx_ptr, g.n, g.h, g.w, c, xb.cstride, g.k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, st))
+                byts += 4.0 * yb.pixels * c if masked else 0.0
+            if halves:
+                run = lambda st: L.check(lib.fcn_maxpool_idx_fwd_f16(
+                    xb.ptr, yb.buf.ptr, idx_ptr, g.n, g.h, g.w, c, xb.cstride, g.k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, st))
+            else:
+                run = lambda st: L.check(lib.fcn_maxpool_fwd_f32(
+                    xb.ptr, yb.buf.ptr, idx_ptr, g.n, g.h, g.w, c, xb.cstride, g.k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, st))
         else:
             fn = (lib.fcn_maxpool_fwd_f16 if is_max else lib.fcn_avepool_fwd_f16) if halves else lib.fcn_avepool_fwd_f32
             run = lambda st: L.check(fn(
@@ -1599,6 +1637,8 @@ class Engine:
 
     def read_blob(self, name: str) -> np.ndarray:
         """Synchronised NCHW float32 host copy of a blob (pycaffe ``net.blobs[name].data``)."""
+        if name in self.spec.mask_blobs:
+            return self._read_mask(name)
         with self.lock:
             L.call("fcn_init", self.device)
             b = self.blobs[name]
@@ -1611,6 +1651,23 @@ class Engine:
                 if b.lazy_shift:
                     host += F32(b.lazy_shift)
                 b.host_valid = True
+            return host
+
+    def _read_mask(self, name: str) -> np.ndarray:
+        """A pooling mask as Caffe holds it: NCHW float32, the flat iy * W + ix index of each window's maximum in the plane of the
+        pooling's bottom.  The device keeps the pooling's int32 argmax buffer; this converts a copy (fcn_pool_mask_to_nchw_f32)."""
+        with self.lock:
+            L.call("fcn_init", self.device)
+            n, c, ph, pw = self.shapes[name]
+            idx = self.aux_dev[self.spec.mask_blobs[name].name]
+            host = np.empty((n, c, ph, pw), F32)
+            tmp = DeviceBuffer(host.nbytes, zero=False)
+            try:
+                L.call("fcn_pool_mask_to_nchw_f32", idx.ptr, tmp.ptr, n, ph, pw, c, self.stream)
+                L.call("fcn_memcpy_d2h_async", host.ctypes.data, tmp.ptr, host.nbytes, self.stream)
+                L.call("fcn_stream_sync", self.stream)
+            finally:
+                tmp.free()
             return host
 
     # ------------------------------------------------------------------ label grids generated on the device

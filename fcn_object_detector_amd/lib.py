@@ -329,6 +329,11 @@ PROTOTYPES = {
     "fcn_interp_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_interp_fwd_f16": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_interp_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_unpool_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_unpool_fwd_f16": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
+    "fcn_unpool_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
+    "fcn_maxpool_idx_fwd_f16": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp]),
+    "fcn_pool_mask_to_nchw_f32": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
     "fcn_inner_product_workspace_bytes": (_sz, [_i, _i, _i]),
     "fcn_inner_product_fwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fcn_inner_product_fwd_f32": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),

@@ -1047,3 +1047,127 @@ def mobilenet_v2(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, wid
     x = _mb_conv(w, "conv9", x, wd(1280), 1, 1, phase, "relu9")
     _mb_tail(w, phase, x, classes)
     return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# SegNet and SegNet-Basic (Badrinarayanan, Kendall, Cipolla: "SegNet: A Deep Convolutional Encoder-Decoder Architecture for Image
+# Segmentation"): encoders whose MAX poolings keep their indices (a second top, the mask) and decoders that unpool by them (the SegNet
+# fork's Upsample layer).  The fork's `BN` layer is written as BatchNorm + Scale, its class-weighted loss as a plain SoftmaxWithLoss.
+# ----------------------------------------------------------------------
+
+def _hw(size) -> Tuple[int, int]:
+    return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+
+
+def _sn_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, phase: str, relu: Optional[str], bn: bool = True) -> str:
+    """Convolution `<name>` (pad k // 2, with a bias) and, with `bn`, BatchNorm `<name>_bn` and Scale `<name>_scale` (bias_term: true) in
+    place on its top; with `relu`, a ReLU of that name; returns the top."""
+    w.layer(name, "Convolution", [bottom], [name], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  convolution_param {\n    num_output: %d\n%s    kernel_size: %d\n    weight_filler { type: \"gaussian\" std: %g }\n"
+            "    bias_filler { type: \"constant\" value: 0 }\n  }" % (num_output, "    pad: %d\n" % (k // 2) if k > 1 else "", k,
+                                                                   (2.0 / (k * k * num_output)) ** 0.5))
+    if bn:
+        stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+        w.layer(name + "_bn", "BatchNorm", [name], [name], stats)
+        w.layer(name + "_scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
+    if relu:
+        w.layer(relu, "ReLU", [name], [name])
+    return name
+
+
+def _sn_pool(w: _Writer, name: str, bottom: str) -> str:
+    """2 x 2 / stride 2 MAX pooling with its mask: tops `<name>` and `<name>_mask`."""
+    w.layer(name, "Pooling", [bottom], [name, name + "_mask"], "  pooling_param { pool: MAX kernel_size: 2 stride: 2 }")
+    return name
+
+
+def _sn_upsample(w: _Writer, name: str, bottom: str, mask: str, hw: Tuple[int, int]) -> str:
+    """Upsample by `mask` to hw, the extents of the pooling's bottom: `scale: 2` where both are even, else upsample_h / upsample_w - the
+    way the published nets undo a ceil-mode pooling of an odd extent."""
+    body = "scale: 2" if hw[0] % 2 == 0 and hw[1] % 2 == 0 else "upsample_h: %d upsample_w: %d" % hw
+    w.layer(name, "Upsample", [bottom, mask], [name], "  upsample_param { %s }" % body)
+    return name
+
+
+def _sn_inputs(w: _Writer, phase: str, batch: int, hw: Tuple[int, int]) -> None:
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, hw[0], hw[1]))
+    if phase != "DEPLOY":
+        w.layer("label", "Input", [], ["label"], "  input_param { shape { dim: %d dim: 1 dim: %d dim: %d } }" % (batch, hw[0], hw[1]))
+
+
+def _sn_tail(w: _Writer, phase: str, score: str) -> None:
+    """prob (Softmax; DEPLOY) or loss (SoftmaxWithLoss, ignore_label 255; TRAIN and TEST) with accuracy in TEST."""
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", [score], ["prob"])
+        return
+    if phase == "TEST":
+        w.layer("accuracy", "Accuracy", [score, "label"], ["accuracy"], "  accuracy_param { ignore_label: 255 }")
+    w.layer("loss", "SoftmaxWithLoss", [score, "label"], ["loss"], "  loss_param { ignore_label: 255 }")
+
+
+def _halved(hw: Tuple[int, int]) -> Tuple[int, int]:
+    return (hw[0] + 1) // 2, (hw[1] + 1) // 2      # 2 x 2 / stride 2 in Caffe's ceil mode
+
+
+def segnet_basic(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1) -> str:
+    """SegNet-Basic: four encoder stages conv<i> 7x7 (64) + BatchNorm + ReLU + pool<i> 2x2 / 2 with the mask pool<i>_mask, four decoder
+    stages upsample<i> (by pool<i>_mask) + conv_decode<i> 7x7 (64) + BatchNorm without a ReLU, and the 1x1 conv_classifier.  DEPLOY ends
+    in prob (Softmax); TRAIN and TEST in loss (SoftmaxWithLoss over an (N, 1, H, W) `label`, ignore_label 255), TEST with accuracy.
+
+    Names: conv1 .. conv4, relu<i>, pool<i> / pool<i>_mask, upsample<i>, conv_decode<i>, conv_classifier, `<conv>_bn`, loss, accuracy and
+    prob are the published net's, as far as remembered.  `<conv>_bn` is a BatchNorm here (the fork's type is BN, which holds the scale and
+    shift as well) and `<conv>_scale` is this project's; the published input LRN (norm) is not emitted, and the loss is not weighted
+    by class frequencies.  An Upsample carries `scale: 2`, or upsample_h / upsample_w where the pooling's bottom has an odd extent.
+    width_div divides the 64; size is the image edge or (height, width)."""
+    _check_phase(phase)
+    hw, c = _hw(size), max(64 // width_div, 1)
+    w = _Writer()
+    w.raw('name: "SegNet-Basic"')
+    _sn_inputs(w, phase, batch, hw)
+    x, planes = "data", []
+    for i in range(1, 5):
+        x = _sn_conv(w, "conv%d" % i, x, c, 7, phase, "relu%d" % i)
+        planes.append(hw)
+        x, hw = _sn_pool(w, "pool%d" % i, x), _halved(hw)
+    for i in range(4, 0, -1):
+        x = _sn_upsample(w, "upsample%d" % i, x, "pool%d_mask" % i, planes[i - 1])
+        x = _sn_conv(w, "conv_decode%d" % i, x, c, 7, phase, None)
+    x = _sn_conv(w, "conv_classifier", x, classes, 1, phase, None, bn=False)
+    _sn_tail(w, phase, x)
+    return w.text()
+
+
+SEGNET_DECODER = ((5, (512, 512, 512)), (4, (512, 512, 256)), (3, (256, 256, 128)), (2, (128, 64)), (1, (64, 0)))      # widths of conv<b>_<n>_D .. conv<b>_1_D (0: the classes)
+
+
+def segnet(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1) -> str:
+    """SegNet: the 13 convolutions of VGG16 (3x3, pad 1) as the encoder, each with BatchNorm + ReLU, all five poolings 2x2 / 2 with a
+    mask; the mirrored decoder upsample<b> (by pool<b>_mask) + conv<b>_<n>_D .. conv<b>_1_D, each with BatchNorm + ReLU but the last,
+    conv1_1_D, which gives the class scores.  Ends as segnet_basic.
+
+    Names: conv1_1 .. conv5_3, relu<b>_<i>, pool<b> / pool<b>_mask, upsample5 .. upsample1, conv5_3_D .. conv1_1_D, relu<b>_<i>_D and
+    `<conv>_bn` are the published net's, as far as remembered; `<conv>_bn` is a BatchNorm here (the fork's BN also scales and shifts) and
+    `<conv>_scale` is this project's.  The loss is not weighted by class frequencies.  width_div divides every width; size is the
+    image edge or (height, width)."""
+    _check_phase(phase)
+    hw = _hw(size)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "SegNet"')
+    _sn_inputs(w, phase, batch, hw)
+    x, planes = "data", {}
+    for blk, convs, width_ in VGG16:
+        for i in range(1, convs + 1):
+            x = _sn_conv(w, "conv%d_%d" % (blk, i), x, wd(width_), 3, phase, "relu%d_%d" % (blk, i))
+        planes[blk] = hw
+        x, hw = _sn_pool(w, "pool%d" % blk, x), _halved(hw)
+    for blk, widths in SEGNET_DECODER:
+        x = _sn_upsample(w, "upsample%d" % blk, x, "pool%d_mask" % blk, planes[blk])
+        for j, width_ in enumerate(widths):
+            i = len(widths) - j
+            if (blk, i) == (1, 1):
+                x = _sn_conv(w, "conv1_1_D", x, classes, 3, phase, None, bn=False)
+            else:
+                x = _sn_conv(w, "conv%d_%d_D" % (blk, i), x, wd(width_), 3, phase, "relu%d_%d_D" % (blk, i))
+    _sn_tail(w, phase, x)
+    return w.text()

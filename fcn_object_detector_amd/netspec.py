@@ -202,6 +202,28 @@ def interp_size(l: "Layer", h: int, w: int) -> Tuple[int, int, int, int]:
     return oh, ow, pad_beg, pad_end
 
 
+def upsample_size(l: "Layer", h: int, w: int) -> Tuple[int, int]:
+    """The SegNet fork's UpsampleLayer: (height, width) of the top for an h x w bottom.  upsample_param's upsample_h AND upsample_w give the
+    extents as they are (the way the published nets undo a ceil-mode pooling of an odd extent); otherwise each axis is h * scale -
+    pad_out_h / w * scale - pad_out_w, scale defaulting to 2 and the pads to 0.  One of upsample_h / upsample_w alone is refused by
+    layer name."""
+    p = l.sub("upsample_param")
+    uh, uw = p.get("upsample_h"), p.get("upsample_w")
+    if (uh is None) != (uw is None):
+        raise ValueError("layer %s: Upsample with %s and no %s (both or neither)" % ((l.name, "upsample_h", "upsample_w") if uw is None
+                                                                                     else (l.name, "upsample_w", "upsample_h")))
+    if uh is not None:
+        oh, ow = int(uh), int(uw)
+    else:
+        scale = int(p.get("scale", 2))
+        if scale < 1:
+            raise ValueError("layer %s: Upsample scale %d is below 1" % (l.name, scale))
+        oh, ow = h * scale - int(p.get("pad_out_h", 0)), w * scale - int(p.get("pad_out_w", 0))
+    if oh < 1 or ow < 1:
+        raise ValueError("layer %s: Upsample to %d x %d: the output extents must be at least 1" % (l.name, oh, ow))
+    return oh, ow
+
+
 def as_nchw(shape: Shape) -> Optional[Tuple[int, int, int, int]]:
     """A blob's shape as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
     channels (H = W = 1); None for anything else.  Engine.Blob.nchw and the channel-axis layers (Concat, Slice) share this rule."""
@@ -267,6 +289,9 @@ class NetSpec:
                     self.input_shapes[t] = tuple(int(d) for d in s.getall("dim"))
         self.blob_shapes: Dict[str, Shape] = {}
         self.param_shapes: Dict[str, List[Shape]] = {}
+        # second top of a MAX Pooling (Caffe's mask: the flat iy * W + ix argmax as floats) -> that layer.  A mask has a shape and can be
+        # read, but it is no activation blob: on the device it is the pooling's int32 argmax buffer, and only an Upsample may consume it
+        self.mask_blobs: Dict[str, Layer] = {}
 
     @classmethod
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False) -> "NetSpec":
@@ -300,6 +325,7 @@ class NetSpec:
         if data_shapes:
             shapes.update({k: tuple(int(d) for d in v) for k, v in data_shapes.items()})
         self.param_shapes = {}
+        self.mask_blobs = {}
         self.blob_shapes = shapes      # (filled as the layers are walked: is_depthwise reads a layer's bottom)
         for l in self.layers:
             t = l.type
@@ -312,6 +338,11 @@ class NetSpec:
                 bots = [shapes[b] for b in l.bottoms]
             except KeyError as e:
                 raise KeyError("layer %s: unknown bottom blob %s" % (l.name, e)) from None
+            for bi, b in enumerate(l.bottoms):
+                if b in self.mask_blobs and not (t == "Upsample" and bi == 1):
+                    raise NotImplementedError("layer %s: the pooling mask %s (second top of %s) feeds %s (a mask may only be the second "
+                                              "bottom of an Upsample)" % (l.name, b, self.mask_blobs[b].name,
+                                                                          "the first bottom of an Upsample" if t == "Upsample" else "a layer of type %s" % t))
             if t == "Convolution":
                 p = l.sub("convolution_param")
                 kh, kw, sh, sw, ph, pw = layer_geometry(l)
@@ -374,11 +405,21 @@ class NetSpec:
             elif t == "Pooling":
                 p = l.sub("pooling_param")
                 n, c, h, w = bots[0]
+                if len(l.tops) > 2:
+                    raise ValueError("layer %s: Pooling has one top, or two (the pooled blob and the mask), got %d" % (l.name, len(l.tops)))
+                if len(l.tops) == 2 and (str(p.get("pool", "MAX")) != "MAX" or bool(p.get("global_pooling", False))):
+                    raise NotImplementedError("layer %s: a second top (the mask %s) on %s pooling: only pool: MAX without global_pooling writes one"
+                                              % (l.name, l.tops[1], "global" if bool(p.get("global_pooling", False)) else str(p.get("pool"))))
                 if bool(p.get("global_pooling", False)):
                     shapes[l.tops[0]] = (n, c, 1, 1)
                 else:
                     k, s, pad = _square(l)
                     shapes[l.tops[0]] = (n, c, pool_out(h, k, s, pad), pool_out(w, k, s, pad))
+                if len(l.tops) == 2:
+                    if l.tops[1] in (l.tops[0], l.bottoms[0]):
+                        raise ValueError("layer %s: the mask top %s must be a blob of its own" % (l.name, l.tops[1]))
+                    shapes[l.tops[1]] = shapes[l.tops[0]]
+                    self.mask_blobs[l.tops[1]] = l
             elif t == "Concat":
                 axis = int(l.sub("concat_param").get("axis", l.sub("concat_param").get("concat_dim", 1)))
                 if axis != 1:
@@ -456,6 +497,25 @@ class NetSpec:
                     raise ValueError("layer %s: Interp cannot run in place" % l.name)
                 oh, ow, _, _ = interp_size(l, bots[0][2], bots[0][3])
                 shapes[l.tops[0]] = (bots[0][0], bots[0][1], oh, ow)
+            elif t == "Upsample":
+                if len(bots) != 2 or any(len(b) != 4 for b in bots) or len(l.tops) != 1:
+                    raise ValueError("layer %s: Upsample takes two 4-d bottoms (the blob and the pooling mask) and has one top, got %s" % (l.name, bots))
+                if bots[0] != bots[1]:
+                    raise ValueError("layer %s: Upsample bottoms disagree: %s %s and mask %s %s" % (l.name, l.bottoms[0], bots[0], l.bottoms[1], bots[1]))
+                if l.tops[0] in l.bottoms:
+                    raise ValueError("layer %s: Upsample cannot run in place" % l.name)
+                oh, ow = upsample_size(l, bots[0][2], bots[0][3])
+                pool = self.mask_blobs.get(l.bottoms[1])
+                if pool is None:
+                    raise NotImplementedError("layer %s: the mask %s is not the second top of a MAX Pooling of this net (a mask fed from "
+                                              "outside, or computed by other layers, is not supported)" % (l.name, l.bottoms[1]))
+                ph, pw = shapes[pool.bottoms[0]][2:]
+                if (oh, ow) != (ph, pw):
+                    raise NotImplementedError("layer %s: Upsample to %d x %d, but the mask %s indexes the %d x %d bottom of %s: "
+                                              "upsample_h: %d upsample_w: %d would match" % (l.name, oh, ow, l.bottoms[1], ph, pw, pool.name, ph, pw))
+                shapes[l.tops[0]] = (bots[0][0], bots[0][1], oh, ow)
+            elif t == "BN":
+                raise NotImplementedError("layer type 'BN' (layer %s): the SegNet fork's BN layer is not supported: write BatchNorm + Scale" % l.name)
             elif t == "Eltwise":
                 for b in bots[1:]:
                     if b != bots[0]:

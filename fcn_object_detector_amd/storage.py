@@ -77,6 +77,8 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             producers.setdefault(t, []).append(l)
         for b in l.bottoms:
             consumers.setdefault(b, []).append(l)
+    # a pooling mask is no activation blob: it is the pooling's argmax buffer, which the engine allocates (no view, no buffer here)
+    shapes = {name: shp for name, shp in shapes.items() if name not in spec.mask_blobs}
     data_tops = set(inputs)
     # f16 mode: everything is stored as halves except what leaves the net towards the f32 decode kernel - the output
     # blobs and the input / output of a Sigmoid head (written by the convolution epilogue in f32)
@@ -111,9 +113,9 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     if f16:
         for name in shapes:
             if esize[name] == 4 and len(shapes[name]) in (2, 4) and name not in data_tops:
-                # (Softmax, Deconvolution and Interp read halves and store float32: the out_f32 forms of their half kernels)
+                # (Softmax, Deconvolution, Interp and Upsample read halves and store float32: the out_f32 forms of their half kernels)
                 bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct",
-                                                                                 "Interp", "DepthwiseConvolution")]
+                                                                                 "Interp", "DepthwiseConvolution", "Upsample")]
                 if bad:
                     raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 

@@ -181,7 +181,7 @@ class TrainEngine(Engine):
         for l in self.spec.layers:
             if l.type in DATA_TYPES:
                 continue
-            through = l.bottoms[:1] if l.type == "Crop" else l.bottoms      # a Crop's second bottom only lends its shape
+            through = l.bottoms[:1] if l.type in ("Crop", "Upsample") else l.bottoms      # a Crop's second bottom only lends its shape, an Upsample's is the mask
             if self._learns(l) or any(b in need for b in through):
                 need.update(l.tops)
         return need

@@ -856,6 +856,37 @@ int  fcn_interp_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int 
 int  fcn_interp_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset, int pad_beg, int pad_end,
                         int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
 
+/* ---- Upsample (the SegNet fork's UpsampleLayer: unpooling by the indices of an encoder's MAX pooling), its adjoint, and the pooling mask.
+ *      idx is the packed [N * PH * PW][C] int32 argmax that fcn_maxpool_fwd_f32 / fcn_maxpool_idx_fwd_f16 write: iy * W + ix in the H x W
+ *      plane of the pooling's bottom (-1: the window held no maximum).  x / dX is the pooled-size N x PH x PW view, y / dY the N x H x W
+ *      one; k, stride and pad are the POOLING's, and PH / PW must be its ceil-mode extents of H / W (FCN_E_ARG otherwise, as for null
+ *      pointers, non-positive extents and slices that leave their pixel).  Forward is a gather over y: y[n, idx[n, py, px, c], c] =
+ *      x[n, py, px, c] and every other element of channels y_coffset .. y_coffset + C - 1 is written as +0.0 - one launch, no memset in
+ *      front, no atomics, one writer per element.  Where windows overlap (k > stride) and several name one pixel, the window last in
+ *      ascending (py, px) order wins: what Caffe's serial scatter leaves.  Only the windows that cover a pixel are asked about it: an
+ *      index that lies outside its own window is never followed.  A lane moves 16 bytes of channels where C, the strides, the offsets and
+ *      the pointers allow and single elements otherwise; pad channels of x may be read and never reach a written value; channels of y
+ *      outside the slice are not written.  Pointers must be multiples of 4 bytes (FCN_E_ALIGN); a view of 2^31 elements or more is
+ *      FCN_E_UNSUPPORTED.  Every refusal precedes the first HIP call.  Floor: the bytes of x + idx + y. ---- */
+int  fcn_unpool_fwd_f32(const float* x, const int32_t* idx, float* y, int N, int PH, int PW, int C, int x_cstride, int x_coffset, int k, int stride,
+                        int pad, int H, int W, int y_cstride, int y_coffset, fcn_stream_t s);
+/* halves in (8-half segments: x 16-byte aligned, x_cstride and x_coffset multiples of 8, else FCN_E_ALIGN; C is free); halves out (out_f32
+ * 0: y likewise) or float32 out (out_f32 1: a net's output behind the layer; any 4-byte aligned view, 16-byte stores where it allows).
+ * idx stays int32. */
+int  fcn_unpool_fwd_f16(const void* x, const int32_t* idx, void* y, int N, int PH, int PW, int C, int x_cstride, int x_coffset, int k, int stride,
+                        int pad, int H, int W, int y_cstride, int y_coffset, int out_f32, fcn_stream_t s);
+/* Upsample backward, a pure gather: dx[n, py, px, c] = dy[n, idx[n, py, px, c], c] (accumulate 0; 0 where idx is outside the plane) or
+ * dx += the same in one float32 add (accumulate 1).  Every window that names a pixel receives its gradient, as in Caffe.  No half twin. */
+int  fcn_unpool_bwd_f32(const float* dy, const int32_t* idx, float* dx, int N, int PH, int PW, int C, int dx_cstride, int dx_coffset, int k,
+                        int stride, int pad, int H, int W, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);
+/* fcn_maxpool_fwd_f16 that also writes idx (required), by the rule of fcn_maxpool_fwd_f32: window clipped to the image, first maximum in
+ * raster order.  One kernel for every geometry; OH / OW must be the ceil-mode extents (FCN_E_ARG); C, the strides and y_coffset multiples
+ * of 8 and all three pointers 16-byte aligned (FCN_E_ALIGN).  y equals fcn_maxpool_fwd_f16's bit for bit. */
+int  fcn_maxpool_idx_fwd_f16(const void* x, void* y, int32_t* idx, int N, int H, int W, int C, int x_cstride, int k, int stride, int pad, int OH,
+                             int OW, int y_cstride, int y_coffset, fcn_stream_t s);
+/* the packed int32 argmax as Caffe's mask blob: dst (N x C x PH x PW float32, dense) = (float)idx.  For read-back only. */
+int  fcn_pool_mask_to_nchw_f32(const int32_t* idx, float* dst, int N, int PH, int PW, int C, fcn_stream_t s);
+
 /* ---- InnerProduct (Caffe InnerProductLayer) at M <= FCN_IP_MAX_ROWS input rows: y[m][n] = sum_k x[m][k] * w[n][k] + bias[n].
  *      x: M rows of K elements, x_rstride elements apart (a row of an NHWC blob of H*W*cstride elements IS such a row); w: the bank
  *      [N][K], K contiguous, in the order of the elements of a row of x (zero columns where x holds pad channels); y / dY: M pixels of
