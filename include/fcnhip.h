@@ -429,7 +429,9 @@ int  fcn_detect_decode_group(const float* cvg, const float* bbox, int batch,
  *      uint8 cast; the map is OR-ed into pmap (frame_h x frame_w bytes on the device, 4-byte aligned, zeroed by the caller) at the
  *      window's place, and out[(n * (C - 1) + c - 1) * 5 ..] = found, x, y, w, h: the bounding rectangle, in WINDOW coordinates, of the
  *      contour with the largest area (found = 0: no contour of positive area; the reference's 10-pixel padding and the window's origin
- *      are added by the caller).  d_workspace: fcn_score_masks_workspace_bytes() bytes. ---- */
+ *      are added by the caller).  d_workspace: fcn_score_masks_workspace_bytes() bytes, uninitialised.  pmap must be ALLOCATED up to a
+ *      multiple of 4 bytes: the OR is a 32-bit atomic on aligned words, and the up to three bytes behind frame_h * frame_w are read and
+ *      written back unchanged. ---- */
 size_t fcn_score_masks_workspace_bytes(int n_windows, int num_classes, int w, int h);
 int  fcn_score_masks(const float* score, int N, int C, int H, int W, int cstride, int coffset, const int32_t* h_rects, float prob_thresh,
                      uint8_t* pmap, int frame_h, int frame_w, void* d_workspace, int32_t* out, fcn_stream_t s);

@@ -2,6 +2,7 @@
 import ctypes as C
 
 import numpy as np
+import pytest
 
 from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd.engine import DeviceBuffer
@@ -281,3 +282,26 @@ def channels_untouched(full: np.ndarray, written: np.ndarray, poison="nan") -> b
     assert written.shape == (full.shape[-1],)
     want = _bits(np.array([poison_value(poison, full.dtype)]))[0]
     return bool(np.all(_bits(full)[..., ~written] == want))
+
+
+def complement(want: np.ndarray) -> np.ndarray:
+    """The prefill of a BYTE output: ~want, so that a byte the kernel never wrote cannot equal its expected value (every byte value is legitimate)."""
+    return np.bitwise_not(np.ascontiguousarray(want, np.uint8))
+
+
+@pytest.fixture
+def g(gpu):
+    """The Guards of one GPU test (`from gpu_util import g`): leaving the test checks every red zone and frees the allocations."""
+    with Guards() as guards:
+        yield guards
+
+
+def launched_twice(call, read):
+    """call(); read(); call(); read() on the same buffers: both reads (an array or a sequence of arrays) must hold the same bits.  -> the first."""
+    call()
+    a = read()
+    call()
+    b = read()
+    pairs = zip(a, b) if isinstance(a, (list, tuple)) else [(a, b)]
+    assert all(x.tobytes() == y.tobytes() for x, y in pairs), "two launches differ"
+    return a

@@ -29,21 +29,7 @@ NO_KERNEL = {
     "fcn_score_masks_workspace_bytes",
 }
 
-_BYTES = "byte / integer kernel family: its guarded tests are a separate piece of work"
-PENDING = {
-    "fcn_compose_scene_bgr8": _BYTES,
-    "fcn_compose_scene_view_bgr8": _BYTES,
-    "fcn_blur_gauss_bgr8": _BYTES,
-    "fcn_blur_box_bgr8": _BYTES,
-    "fcn_blur_median_bgr8": _BYTES,
-    "fcn_color_augment_bgr8": _BYTES,
-    "fcn_mask_to_label_f32": _BYTES,
-    "fcn_score_masks": _BYTES + "; score_mask_kernel's 32-bit atomicOr touches up to three bytes behind a frame_h * frame_w byte map that is "
-                       "not a multiple of 4 (it ORs zeros there, so poison cannot show it): needs a header sentence or a byte-wise tail",
-    "fcn_detect_decode_group": _BYTES,
-    "fcn_gen_targets": _BYTES,
-    "fcn_gen_targets_nhwc": _BYTES,
-}
+PENDING: dict = {}
 
 
 def declared():
@@ -97,3 +83,13 @@ def test_the_hot_path_of_this_ledger_is_guarded():
               "fcn_maxpool_lrn5_conv1x1_fwd_f16", "fcn_nchw_f32_to_nhwc_f16", "fcn_nhwc_f16_to_nchw_f32", "fcn_preprocess_bgr8_f16",
               "fcn_preprocess_bgr8_batch", "fcn_preprocess_bgr8_rois", "fcn_conv2d_wgrad_group_cfg_f32", "fcn_conv_weights_flip_batch_f32"):
         assert n in g, n
+
+
+def test_the_byte_and_integer_kernels_stay_guarded():
+    """What tests/test_gpu_guarded_{augment,scene,masks,detect}.py were written for stays guarded."""
+    g = guarded(declared())
+    for n in ("fcn_compose_scene_bgr8", "fcn_compose_scene_view_bgr8", "fcn_blur_gauss_bgr8", "fcn_blur_box_bgr8", "fcn_blur_median_bgr8",
+              "fcn_color_augment_bgr8", "fcn_mask_to_label_f32", "fcn_score_masks", "fcn_detect_decode_group", "fcn_gen_targets",
+              "fcn_gen_targets_nhwc"):
+        assert n in g, n
+    assert PENDING == {}

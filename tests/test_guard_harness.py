@@ -287,3 +287,70 @@ def test_ref64_pointwise_and_losses_match_the_oracle():
     dxd = ref64.deconv_depthwise_bwd(dy, wd[:, 0], k, st, pd, h, h)
     assert np.allclose(dxd, R.deconv2d_backward_data(dy, wd, pd, st, group=c), rtol=1e-5, atol=1e-5)
     assert np.isclose(float((yd * dy).sum()), float((dxd * xd).sum()), rtol=1e-10)
+
+
+# ---- byte kernels: what the guarded byte / integer tests (tests/test_gpu_guarded_{augment,scene,masks,detect}.py) rely on ----
+def invert_standin(src: GuardedBuffer, dst: GuardedBuffer, count: int, skip=(), extra=0):
+    """dst[i] = 255 - src[i] for i < count + extra, except the indices in `skip`: a byte kernel that forgets elements / runs past the end."""
+    s = src.handle[src.offset:src.offset + count + extra]
+    d = dst.handle[dst.offset:dst.offset + count + extra]
+    keep = np.ones(count + extra, bool)
+    keep[list(skip)] = False
+    d[keep] = 255 - s[keep]
+
+
+def test_a_byte_written_just_behind_a_byte_payload_is_reported():
+    from gpu_util import complement
+    img = np.arange(35, dtype=np.uint8)                       # 35 bytes at the end of their allocation: an odd start address
+    want = 255 - img
+    with Guards(mem=HOST) as g:
+        src, dst = g.put(img, at_end=True), g.put(complement(want), at_end=True)
+        assert src.ptr % 2 == 1
+        invert_standin(src, dst, img.size)
+        assert np.array_equal(dst.read(img.shape, np.uint8), want) and src.unchanged()
+    with pytest.raises(GuardError, match=r"behind the payload \(35 bytes\): first modified byte at \+35, last at \+35"):
+        with Guards(mem=HOST) as g:
+            src, dst = g.put(img, at_end=True), g.put(complement(want), at_end=True, name="dst")
+            invert_standin(src, dst, img.size, extra=1)       # (the source's red zone holds 0xC0 there: 255 - 0xC0 is stored)
+
+
+def test_an_unwritten_byte_fails_the_equality_because_of_the_complement_prefill():
+    """0xC0, the poison byte, is a legitimate pixel: an output prefilled with poison would PASS where the expected byte is 0xC0 and was never
+    written.  Prefilled with ~want, no unwritten byte can equal its expected value."""
+    from gpu_util import complement
+    img = np.full(64, 255 - 0xC0, np.uint8)                   # every expected byte is the poison byte
+    want = 255 - img
+    assert np.all(want == poison_value("nan", np.uint8))
+    with Guards(mem=HOST) as g:
+        src, dst = g.put(img, at_end=True), g.put(want.nbytes)                    # poison prefill (C0 7F C0 7F ..): the forgotten byte 16 goes unnoticed
+        invert_standin(src, dst, img.size, skip=(16,))
+        assert np.array_equal(dst.read(img.shape, np.uint8), want)
+    with Guards(mem=HOST) as g:
+        src, dst = g.put(img, at_end=True), g.put(complement(want))
+        invert_standin(src, dst, img.size, skip=(16,))
+        got = dst.read(img.shape, np.uint8)
+        assert np.nonzero(got != want)[0].tolist() == [16]
+    assert np.all(complement(np.arange(256, dtype=np.uint8)) != np.arange(256, dtype=np.uint8))
+
+
+def test_a_nan_score_reads_as_background_and_3e38_as_foreground():
+    """fcn_score_masks' chain - threshold, x 255, clamp, truncating cast through int32, low byte - on numpy stand-ins: a consumed NaN
+    gives byte 0 (background: nothing to see), 3e38 gives 128.  Hence poison='huge' for score maps; `NaN >= thresh` is false as well, so
+    the same holds for the coverage maps of fcn_detect_decode_group."""
+    def fmaxf(a, b):                                                               # C semantics: a NaN operand yields the other one
+        return b if np.isnan(a) else a if np.isnan(b) else max(a, b)
+
+    def fminf(a, b):
+        return b if np.isnan(a) else a if np.isnan(b) else min(a, b)
+
+    def chain(v, thresh=np.float32(0.5)):
+        v = np.float32(v)
+        with np.errstate(over="ignore", invalid="ignore"):
+            v = np.float32(0) if v < thresh else v                                 # (NaN < thresh is false: the NaN is kept)
+            v = np.float32(v * np.float32(255))
+        v = fminf(fmaxf(v, np.float32(-2147483648.0)), np.float32(2147483520.0))
+        return int(np.trunc(np.float64(v))) & 0xFF
+
+    assert chain(poison_value("nan", np.float32)) == 0                             # -2147483648 & 0xFF
+    assert chain(poison_value("huge", np.float32)) == 128 and chain(1.0) == 255 and chain(1.5) == 126 and chain(0.49) == 0
+    assert not (poison_value("nan", np.float32) >= np.float32(0.5)) and poison_value("huge", np.float32) >= np.float32(0.5)
