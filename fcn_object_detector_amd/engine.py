@@ -28,6 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import lib as L
+from . import ssd as SSD
 from . import storage as S
 from . import tune as T
 from .netspec import Layer, NetSpec, bn_global_stats, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation, layer_geometry
@@ -452,17 +453,39 @@ class Engine:
         self.producers, self.consumers = plan.producers, plan.consumers
         self.alias, self.shift, self.copy_concats, self.copy_slices = plan.alias, plan.shift, plan.copy_concats, plan.copy_slices
         self._half_inputs = plan.half_inputs      # data top -> (Power top, shift)
+        self.permutes, self.gathers, self.detections = plan.permutes, plan.gathers, plan.detections      # SSD heads (storage.BlobPlan)
         bufs = {root: DeviceBuffer(nbytes) for root, nbytes in plan.root_bytes.items()}
         for name, v in plan.views.items():
             b = self.blobs[name] = Blob(name, v.shape)
             b.esize, b.rows, b.is_input = v.esize, v.rows, name in self.inputs
             b.buf, b.coffset, b.cstride = bufs[v.root], v.coffset, v.cstride
             b.upload_shift, b.lazy_shift = v.upload_shift, v.lazy_shift
+        self._upload_priors()
         for d in self._half_inputs:                 # the two constant-1 channels, once: every writer of the image touches channels 0..2 only
             b = self.blobs[d]
             ones = np.zeros((b.pixels, b.cstride), np.float16)
             ones[:, 3:5] = 1.0
             L.call("fcn_memcpy_h2d_async", b.buf.ptr, ones.ctypes.data, ones.nbytes, None)
+            L.call("fcn_device_sync")
+
+    def _upload_priors(self) -> None:
+        """The tops of the PriorBox layers and of their Concat(axis 2) are constants of the plan: computed here by ssd.prior_boxes, uploaded
+        once, never touched by forward().  prior_consts keeps the host copies (read_blob returns them)."""
+        self.prior_consts: Dict[str, np.ndarray] = {}
+        for name, l in self.spec.prior_blobs.items():
+            if l.type == "PriorBox":
+                _, _, fh, fw = self.shapes[l.bottoms[0]]
+                _, _, dh, dw = self.shapes[l.bottoms[1]]
+                a = SSD.prior_boxes(SSD.priorbox_params(l), fh, fw, dh, dw)
+            else:
+                a = np.concatenate([self.prior_consts[b] for b in l.bottoms], axis=2)
+            if a.shape != tuple(self.shapes[name]):
+                raise RuntimeError("layer %s: %s prior constants for the blob %s" % (l.name, a.shape, self.shapes[name]))
+            self.prior_consts[name] = a = np.ascontiguousarray(a, F32)
+            b = self.blobs[name]
+            if b.coffset or b.cstride != a.size:
+                raise NotImplementedError("layer %s: the prior blob %s is a window of another buffer" % (l.name, name))
+            L.call("fcn_memcpy_h2d_async", b.buf.ptr, a.ctypes.data, a.nbytes, None)
             L.call("fcn_device_sync")
 
     def _alloc_params(self, params: Optional[Dict[str, List[np.ndarray]]]) -> None:
@@ -783,6 +806,10 @@ class Engine:
                 ch = self._bn_chain_after(li, l, skip)
                 tasks.append(OpTask(l, self._fwd_batchnorm(ch), reads=[self._range(ch.x)], writes=[self._range(ch.y)]))
                 continue
+            if t in SSD.HEAD_TYPES or l.name in self.gathers or (l.tops and l.tops[0] in spec.prior_blobs) or \
+                    (t == "Softmax" and len(self.shapes[l.bottoms[0]]) == 3 and int(l.sub("softmax_param").get("axis", 1)) in (2, -1)):
+                tasks.extend(self._ssd_tasks(l))
+                continue
             if t == "Concat" and l.name not in self.copy_concats:
                 continue      # producers already wrote their slices
             if t == "Slice" and l.name not in self.copy_slices:
@@ -841,6 +868,107 @@ class Engine:
         self.levels = max(levels) + 1 if levels else 0
         if self.score_outputs:
             self._emit_score_ops()
+
+    # ------------------------------------------------------------------ SSD detection head (csrc/ssd.hip)
+    def _ssd_tasks(self, l: Layer) -> List[OpTask]:
+        """The launches of one layer of an SSD head.  Permute, Reshape, the Flatten layers that are views, PriorBox and the priors' Concat emit
+        nothing: views and constants of the plan (storage.plan_blobs).  A Concat of Permute + Flatten heads (or such a Flatten on its own) is
+        one fcn_ssd_gather_f32 launch per 16 heads; Normalize, the row Softmax and DetectionOutput are one op each."""
+        lib, B, t = L.load(), self.blobs, l.type
+        need = getattr(self, "need_grad", None)
+        if need is not None and any(b in need for b in l.bottoms + l.tops):
+            raise NotImplementedError("layer %s: %s below a layer that learns in a TRAIN-phase net (the SSD head has no backward pass: "
+                                      "deploy nets only)" % (l.name, t))
+        if l.name in self.gathers:
+            top, cols = self.gathers[l.name]
+            db = B[top]
+            n, width = db.shape[0], db.shape[1]
+            out: List[OpTask] = []
+            for g0 in range(0, len(cols), L.SSD_MAX_HEADS):
+                part = cols[g0:g0 + L.SSD_MAX_HEADS]
+                arr = (L.SsdHead * len(part))()
+                byts = 0.0
+                for h, (_flat, src, col) in zip(arr, part):
+                    sb = B[src]
+                    if sb.esize != 4 or sb.nchw is None or sb.shape[0] != n:
+                        raise NotImplementedError("layer %s: the head %s is no float32 4-d blob of %d images" % (l.name, src, n))
+                    h.src, h.pixels, h.C, h.cstride, h.coffset, h.dst_col = sb.buf.ptr, sb.shape[2] * sb.shape[3], sb.shape[1], sb.cstride, sb.coffset, col
+                    byts += 8.0 * n * h.pixels * h.C
+                self._keep.append(arr)
+                label = l.name + ":" + "+".join(src for _f, src, _c in part)
+                run = lambda st, arr=arr, k=len(part): L.check(lib.fcn_ssd_gather_f32(arr, k, n, db.buf.ptr + 4 * db.coffset, db.cstride, width, st))
+                out.append(OpTask(l, [Op("ssd_gather", label, run, 0.0, byts)], reads=[self._range(src) for _f, src, _c in part],
+                                  writes=[(db.buf.ptr, db.coffset + part[0][2], db.coffset + part[-1][2] + B[part[-1][0]].channels)]))
+            return out
+        if t in ("Permute", "Reshape", "Flatten", "PriorBox") or (t == "Concat" and l.tops[0] in self.spec.prior_blobs):
+            return []
+        if t == "Normalize":
+            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+            npar = l.sub("norm_param")
+            shared, eps = int(bool(npar.get("channel_shared", True))), float(npar.get("eps", 1e-10))
+            scale = self.params_dev[l.name][0]
+            if yb.cstride < yb.coffset + _r4(yb.channels):
+                raise NotImplementedError("layer %s: the top %s is a channel window that ends inside a 16-byte group" % (l.name, l.tops[0]))
+            pix, c = xb.pixels, xb.channels
+            run = lambda st: L.check(lib.fcn_normalize_fwd_f32(xb.buf.ptr, yb.buf.ptr, scale.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride,
+                                                               yb.coffset, shared, eps, st))
+            return [OpTask(l, [Op("normalize", l.name, run, 4.0 * pix * c, 8.0 * pix * c)], reads=[self._range(l.bottoms[0])],
+                           writes=[self._range(l.tops[0])])]
+        if t == "Softmax":
+            # over the last axis of an (N, P, C) blob: P rows of C contiguous floats per image - fcn_softmax_fwd_f32 with pixels = P and both
+            # strides C (its lanes load and store single floats: C = 21 needs no alignment), one launch per image (the images' rows start
+            # a row stride apart, which is no multiple of C)
+            xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+            if len(xb.shape) != 3 or not xb.rows or xb.shape != yb.shape:
+                raise NotImplementedError("Softmax over an axis other than channels (layer %s)" % l.name)
+            n, pr, c = xb.shape
+            def run(st):
+                for i in range(n):
+                    L.check(lib.fcn_softmax_fwd_f32(xb.ptr + 4 * i * xb.cstride, yb.ptr + 4 * i * yb.cstride, pr, c, c, c, st))
+            return [OpTask(l, [Op("softmax", l.name, run, 0.0, 8.0 * n * pr * c)], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])])]
+        if t == "DetectionOutput":
+            dp = SSD.detection_params(l)
+            (_, _, cap, _), priors = SSD.detection_shapes(l, [self.shapes[b] for b in l.bottoms])
+            lb, cb, pb, ob = (B[b] for b in l.bottoms + l.tops[:1])
+            if pb.coffset or pb.cstride != 8 * priors or any(x.esize != 4 for x in (lb, cb, pb)):
+                raise NotImplementedError("layer %s: the priors %s are a window of another buffer" % (l.name, l.bottoms[2]))
+            kmax = min(dp.top_k, priors) if dp.top_k > -1 else priors
+            if kmax > L.DETOUT_MAX_TOPK:
+                raise NotImplementedError("layer %s: DetectionOutput with %d candidates per class (top_k %d over %d priors): the NMS kernel "
+                                          "holds at most %d" % (l.name, kmax, dp.top_k, priors, L.DETOUT_MAX_TOPK))
+            par = L.DetOutParams()
+            par.N, par.P, par.num_classes, par.background = lb.shape[0], priors, dp.num_classes, dp.background
+            par.code_type, par.variance_encoded, par.top_k, par.keep_top_k = dp.code_type, int(dp.variance_encoded), dp.top_k, dp.keep_top_k
+            par.conf_threshold, par.nms_threshold = dp.confidence_threshold, dp.nms_threshold
+            par.loc_rstride, par.conf_rstride, par.capacity = lb.cstride, cb.cstride, cap
+            nbytes = int(lib.fcn_detection_output_workspace_bytes(C.byref(par)))
+            if nbytes <= 0:
+                L.check(lib.fcn_detection_output_f32(None, None, None, C.byref(par), None, None, None, 0, None))      # (raises with the library's text)
+                raise RuntimeError("layer %s: DetectionOutput has no plan" % l.name)
+            ws = DeviceBuffer(nbytes, zero=True)
+            self._keep.extend([ws, par])
+            n, nc = par.N, dp.num_classes
+            run = lambda st: L.check(lib.fcn_detection_output_f32(lb.ptr, cb.ptr, pb.ptr, C.byref(par), ob.buf.ptr, ob.buf.ptr + 4 * 7 * cap,
+                                                                  ws.ptr, nbytes, st))
+            return [OpTask(l, [Op("detection_output", l.name, run, 30.0 * n * priors + 20.0 * n * nc * kmax * kmax / 2,
+                                  4.0 * n * priors * (4 + nc + 4) + 28.0 * cap)],
+                           reads=[self._range(b) for b in l.bottoms], writes=[self._range(l.tops[0])])]
+        raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
+
+    def blob_shape(self, name: str) -> Tuple[int, ...]:
+        """A blob's shape as pycaffe reports it: the inferred one - for the top of a DetectionOutput after a forward, (1, 1, K, 7) with the
+        K rows that forward found (the inferred shape is the capacity)."""
+        if name in self.detections and self.blobs[name].host is not None and getattr(self, "_ran", False):
+            return self._compose_detections(name).shape
+        return tuple(self.shapes[name])
+
+    def _compose_detections(self, name: str) -> np.ndarray:
+        """Caffe's top of a DetectionOutput from the downloaded buffer (rows, then the count): composed on the host, nothing waits here."""
+        raw = self.blobs[name].host
+        cap = self.detections[name]
+        count = int(raw[7 * cap:7 * cap + 1].view(np.int32)[0])
+        l = self.spec.detection_blobs[name]
+        return SSD.compose_detections(raw, min(max(count, 0), cap), self.shapes[l.bottoms[0]][0])
 
     def _dconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
         """A Convolution with dilation > 1: a problem of csrc/rconv.hip through fcn_dconv2d_*, not of the tiled family.  The bank is the
@@ -1403,7 +1531,8 @@ class Engine:
     def _fwd_softmax(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        if int(l.sub("softmax_param").get("axis", 1)) != 1:
+        if int(l.sub("softmax_param").get("axis", 1)) != 1 or len(xb.shape) == 3:
+            # (an (N, P, C) blob lies as rows of P * C floats: only its last axis, _ssd_tasks, has a kernel - axis 1 would be over P)
             raise NotImplementedError("Softmax over an axis other than channels (layer %s)" % l.name)
         if halves and (xb.esize != 2 or xb.coffset % 8 or yb.coffset % (16 // yb.esize)):
             raise NotImplementedError("f16 engine: Softmax %s from a float32 blob / on an unaligned channel slice" % l.name)
@@ -1639,6 +1768,20 @@ class Engine:
         """Synchronised NCHW float32 host copy of a blob (pycaffe ``net.blobs[name].data``)."""
         if name in self.spec.mask_blobs:
             return self._read_mask(name)
+        if name in self.permutes:      # Caffe's (N, H, W, C) array, read from the bottom's buffer
+            return np.ascontiguousarray(self.read_blob(self.permutes[name]).transpose(0, 2, 3, 1))
+        if name in self.spec.prior_blobs:
+            return self.prior_consts[name]
+        if name in self.detections:
+            with self.lock:
+                L.call("fcn_init", self.device)
+                b = self.blobs[name]
+                self.host_array(name)
+                if not b.host_valid:
+                    self._enqueue_download(name, self.stream)
+                    L.call("fcn_stream_sync", self.stream)
+                    b.host_valid = True
+                return self._compose_detections(name)
         with self.lock:
             L.call("fcn_init", self.device)
             b = self.blobs[name]
@@ -1851,9 +1994,10 @@ class Engine:
                 if b.lazy_shift:
                     b.host += F32(b.lazy_shift)
                 b.host_valid = True
-                out[nm] = b.host
+                out[nm] = b.host if nm not in self.detections else self._compose_detections(nm)
             for nm in self.inputs:
                 self.blobs[nm].host_valid = nm not in self.device_fed
+            self._ran = True
             return out
 
     def forward_begin(self) -> None:
@@ -1883,9 +2027,10 @@ class Engine:
                 if b.lazy_shift:
                     b.host += F32(b.lazy_shift)
                 b.host_valid = True
-                out[nm] = b.host
+                out[nm] = b.host if nm not in self.detections else self._compose_detections(nm)
             for nm in self.inputs:
                 self.blobs[nm].host_valid = nm not in self.device_fed
+            self._ran = True
             return out
 
     def upload_inputs(self) -> None:
@@ -1906,6 +2051,7 @@ class Engine:
             for b in self.blobs.values():
                 if not b.is_input:
                     b.host_valid = False
+            self._ran = True
 
     def forward_resident(self, iters: int = 1, use_graph: bool = True) -> float:
         """Run the layer stack ``iters`` times on inputs already in HBM; returns HIP-event ms for all iterations."""

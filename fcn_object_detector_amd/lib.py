@@ -164,6 +164,20 @@ class DetectParams(C.Structure):
     ]
 
 
+class SsdHead(C.Structure):
+    """fcn_ssd_head: one head of the Permute + Flatten + Concat gather."""
+    _fields_ = [("src", C.c_void_p)] + [(k, C.c_int32) for k in ("pixels", "C", "cstride", "coffset", "dst_col", "reserved")]
+
+
+class DetOutParams(C.Structure):
+    """fcn_detout_params: DetectionOutput."""
+    _fields_ = [(k, C.c_int32) for k in ("N", "P", "num_classes", "background", "code_type", "variance_encoded", "top_k", "keep_top_k")] + [
+        ("conf_threshold", C.c_float), ("nms_threshold", C.c_float)] + [(k, C.c_int32) for k in ("loc_rstride", "conf_rstride", "capacity", "reserved")]
+
+
+SSD_MAX_HEADS = 16             # FCN_SSD_MAX_HEADS
+DETOUT_MAX_TOPK = 1024         # FCN_DETOUT_MAX_TOPK
+CODE_CORNER, CODE_CENTER_SIZE = 1, 2
 CONV_RELU, CONV_SIGMOID2, CONV_ACCUM, CONV_OUT_F32, CONV_F16, CONV_OUT_F16, CONV_MASK = 1, 2, 4, 8, 16, 32, 64
 IP_MAX_ROWS = 32               # FCN_IP_MAX_ROWS: rows the InnerProduct streaming kernels take
 IP_WEIGHTS_NT = 256            # FCN_IP_WEIGHTS_NT
@@ -346,6 +360,10 @@ PROTOTYPES = {
     "fcn_batchnorm_apply_f16": (_i, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
     "fcn_batchnorm_bwd_reduce_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _vp]),
     "fcn_batchnorm_bwd_apply_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp]),
+    "fcn_ssd_gather_f32": (_i, [C.POINTER(SsdHead), _i, _i, _vp, _i, _i, _vp]),
+    "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
+    "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),
+    "fcn_detection_output_f32": (_i, [_vp, _vp, _vp, C.POINTER(DetOutParams), _vp, _vp, _vp, _sz, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

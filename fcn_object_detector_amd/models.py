@@ -1171,3 +1171,142 @@ def segnet(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 
                 x = _sn_conv(w, "conv%d_%d_D" % (blk, i), x, wd(width_), 3, phase, "relu%d_%d_D" % (blk, i))
     _sn_tail(w, phase, x)
     return w.text()
+
+
+# ----------------------------------------------------------------------
+# SSD (Liu et al.: "SSD: Single Shot MultiBox Detector") deploy nets: the detection head of Caffe-SSD (the weiliu89 fork) on MobileNet v1
+# (the common Caffe port) and on VGG16 (SSD300).  Layer and blob names are the published ones, as remembered.
+# ----------------------------------------------------------------------
+
+def _ssd_refuse_training(phase: str) -> None:
+    _check_phase(phase)
+    if phase != "DEPLOY":
+        raise NotImplementedError("SSD %s net: MultiBoxLoss (and AnnotatedData / DetectionEvaluate) are not built - only the DEPLOY net" % phase)
+
+
+def _ssd_head(w: _Writer, feat: str, priors: int, classes: int, k: int, box: str, norm_from: Optional[str] = None) -> None:
+    """One head over the blob `feat`: <feat>_mbox_loc / _mbox_conf (k x k convolutions with 4 / `classes` outputs per prior), each
+    through Permute(0, 2, 3, 1) and Flatten, and <feat>_mbox_priorbox over (feat, data) with the prior_box_param `box`."""
+    for kind, per in (("loc", 4), ("conf", classes)):
+        nm = "%s_mbox_%s" % (feat, kind)
+        _dl_conv(w, nm, feat, priors * per, k, pad=k // 2)
+        w.layer(nm + "_perm", "Permute", [nm], [nm + "_perm"], "  permute_param { order: 0 order: 2 order: 3 order: 1 }")
+        w.layer(nm + "_flat", "Flatten", [nm + "_perm"], [nm + "_flat"], "  flatten_param { axis: 1 }")
+    w.layer(feat + "_mbox_priorbox", "PriorBox", [norm_from or feat, "data"], [feat + "_mbox_priorbox"], "  prior_box_param {\n%s\n  }" % box)
+
+
+def _ssd_tail(w: _Writer, feats: Sequence[str], classes: int, conf_thr: float, top_k: int, keep_top_k: int) -> None:
+    """mbox_loc / mbox_conf / mbox_priorbox (the Concats), mbox_conf_reshape -> mbox_conf_softmax -> mbox_conf_flatten, detection_out."""
+    for kind, axis in (("loc", 1), ("conf", 1)):
+        w.layer("mbox_" + kind, "Concat", ["%s_mbox_%s_flat" % (f, kind) for f in feats], ["mbox_" + kind], "  concat_param { axis: %d }" % axis)
+    w.layer("mbox_priorbox", "Concat", [f + "_mbox_priorbox" for f in feats], ["mbox_priorbox"], "  concat_param { axis: 2 }")
+    w.layer("mbox_conf_reshape", "Reshape", ["mbox_conf"], ["mbox_conf_reshape"],
+            "  reshape_param { shape { dim: 0 dim: -1 dim: %d } }" % classes)
+    w.layer("mbox_conf_softmax", "Softmax", ["mbox_conf_reshape"], ["mbox_conf_softmax"], "  softmax_param { axis: 2 }")
+    w.layer("mbox_conf_flatten", "Flatten", ["mbox_conf_softmax"], ["mbox_conf_flatten"], "  flatten_param { axis: 1 }")
+    w.layer("detection_out", "DetectionOutput", ["mbox_loc", "mbox_conf_flatten", "mbox_priorbox"], ["detection_out"],
+            "  include { phase: TEST }\n  detection_output_param {\n    num_classes: %d\n    share_location: true\n    background_label_id: 0\n"
+            "    nms_param { nms_threshold: 0.45 top_k: %d }\n    code_type: CENTER_SIZE\n    keep_top_k: %d\n    confidence_threshold: %g\n  }"
+            % (classes, top_k, keep_top_k, conf_thr))
+
+
+def _ssd_box(sizes: Tuple[float, Optional[float]], ratios: Sequence[float], scale: float, step: Optional[int] = None) -> str:
+    s = ["    min_size: %g" % (sizes[0] * scale)] + (["    max_size: %g" % (sizes[1] * scale)] if sizes[1] is not None else [])
+    s += ["    aspect_ratio: %g" % r for r in ratios]
+    s += ["    flip: true", "    clip: false"] + ["    variance: %g" % v for v in (0.1, 0.1, 0.2, 0.2)]
+    if step is not None:
+        s.append("    step: %d" % step)
+    return "\n".join(s + ["    offset: 0.5"])
+
+
+MOBILENET_SSD_BODY = ((1, 64, 1), (2, 128, 2), (3, 128, 1), (4, 256, 2), (5, 256, 1), (6, 512, 2), (7, 512, 1), (8, 512, 1), (9, 512, 1),
+                      (10, 512, 1), (11, 512, 1), (12, 1024, 2), (13, 1024, 1))      # (n of conv<n>/dw + conv<n>, width, stride of the 3x3)
+MOBILENET_SSD_EXTRAS = ((14, 256, 512), (15, 128, 256), (16, 128, 256), (17, 64, 128))      # conv<n>_1 1x1, conv<n>_2 3x3 / 2
+MOBILENET_SSD_BOXES = (("conv11", (60.0, None), (2.0,)), ("conv13", (105.0, 150.0), (2.0, 3.0)), ("conv14_2", (150.0, 195.0), (2.0, 3.0)),
+                       ("conv15_2", (195.0, 240.0), (2.0, 3.0)), ("conv16_2", (240.0, 285.0), (2.0, 3.0)), ("conv17_2", (285.0, 300.0), (2.0, 3.0)))
+
+
+def mobilenet_ssd(phase: str = "DEPLOY", classes: int = 21, size: int = 300, width_div: int = 1, batch: int = 1, fillers: bool = True) -> str:
+    """MobileNet-SSD, the common Caffe port, as remembered: the MobileNet v1 body conv0, conv1/dw, conv1 .. conv13/dw, conv13 (every
+    convolution bias-free with BatchNorm, Scale and ReLU, as models.mobilenet_v1 writes them - the published deploy file has them merged
+    into biased convolutions), the extras conv14_1 (1x1) / conv14_2 (3x3 / 2) .. conv17_2, and six heads: conv11 with 3 priors per cell
+    (min_size 60, aspect ratio 2), conv13 and conv14_2 .. conv17_2 with 6 (min / max 105 / 150 .. 285 / 300, ratios 2 and 3) - 1917 priors
+    at 300 x 300.  Heads are 1x1 convolutions; offset 0.5, variances .1 .1 .2 .2, CENTER_SIZE, confidence_threshold 0.25, nms_threshold
+    0.45, top_k 100, keep_top_k 100.  width_div divides the body's and the extras' widths, size is the image edge (the box sizes scale
+    with it).  TRAIN and TEST are refused: MultiBoxLoss is not built."""
+    _ssd_refuse_training(phase)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "MobileNet-SSD"')
+    _inputs(w, phase, batch, ["data"], size, None)
+    x, c = _mb_conv(w, "conv0", "data", wd(32), 3, 2, phase, "conv0/relu"), wd(32)
+    for n, width, stride in MOBILENET_SSD_BODY:
+        x = _mb_conv(w, "conv%d/dw" % n, x, c, 3, stride, phase, "conv%d/dw/relu" % n, group=c)
+        x, c = _mb_conv(w, "conv%d" % n, x, wd(width), 1, 1, phase, "conv%d/relu" % n), wd(width)
+    for n, mid, out in MOBILENET_SSD_EXTRAS:
+        x = _mb_conv(w, "conv%d_1" % n, x, wd(mid), 1, 1, phase, "conv%d_1/relu" % n)
+        x = _mb_conv(w, "conv%d_2" % n, x, wd(out), 3, 2, phase, "conv%d_2/relu" % n)
+    for feat, sizes, ratios in MOBILENET_SSD_BOXES:
+        _ssd_head(w, feat, (1 + 2 * len(ratios)) + (1 if sizes[1] is not None else 0), classes, 1, _ssd_box(sizes, ratios, size / 300.0))
+    _ssd_tail(w, [f for f, _s, _r in MOBILENET_SSD_BOXES], classes, 0.25, 100, 100)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+SSD300_BOXES = (("conv4_3_norm", (30.0, 60.0), (2.0,), 8), ("fc7", (60.0, 111.0), (2.0, 3.0), 16), ("conv6_2", (111.0, 162.0), (2.0, 3.0), 32),
+                ("conv7_2", (162.0, 213.0), (2.0, 3.0), 64), ("conv8_2", (213.0, 264.0), (2.0,), 100), ("conv9_2", (264.0, 315.0), (2.0,), 300))
+
+
+def ssd300_vgg(phase: str = "DEPLOY", classes: int = 21, size: int = 300, width_div: int = 1, batch: int = 1, heads: int = 6,
+               fillers: bool = True) -> str:
+    """SSD300 on VGG16, as remembered: conv1_1 .. conv5_3 with 2x2 / 2 poolings (Caffe's ceil mode: 300 -> 150 -> 75 -> 38 -> 19), pool5
+    3x3 / 1 / pad 1, fc6 as a 3x3 convolution with dilation 6 (pad 6) and fc7 1x1 (1024 each), the extras conv6_1 (1x1, 256) / conv6_2
+    (3x3 / 2, 512), conv7_1 / conv7_2 (128 / 256, / 2), conv8_1 / conv8_2 and conv9_1 / conv9_2 (128 / 256, 3x3 without pad), and six heads
+    of 3x3 convolutions: conv4_3_norm - Normalize(across_spatial: false, channel_shared: false, scale_filler 20) of conv4_3 - with 4 priors
+    per cell, fc7, conv6_2 and conv7_2 with 6, conv8_2 and conv9_2 with 4: 8732 priors at 300 x 300.  confidence_threshold 0.01,
+    nms_threshold 0.45, top_k 400, keep_top_k 200.  width_div divides every width, size is the image edge (box sizes scale with it; the
+    published `step` values are written at 300 only), heads keeps the first `heads` heads and drops the layers behind the last one (a small
+    test net).  TRAIN and TEST are refused: MultiBoxLoss is not built."""
+    _ssd_refuse_training(phase)
+    if not 1 <= heads <= len(SSD300_BOXES):
+        raise ValueError("ssd300_vgg: heads must be 1 .. %d" % len(SSD300_BOXES))
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "VGG_VOC0712_SSD_300x300_deploy"')
+    _inputs(w, phase, batch, ["data"], size, None)
+    boxes = SSD300_BOXES[:heads]
+    last = boxes[-1][0]
+    prev = "data"
+
+    def body() -> None:
+        nonlocal prev
+        for blk, convs, width_ in VGG16:
+            for i in range(1, convs + 1):
+                prev = _dl_conv(w, "conv%d_%d" % (blk, i), prev, wd(width_), 3, 1, relu="relu%d_%d" % (blk, i))
+                if (blk, i) == (4, 3):
+                    w.layer("conv4_3_norm", "Normalize", ["conv4_3"], ["conv4_3_norm"], "  norm_param {\n    across_spatial: false\n"
+                            "    scale_filler { type: \"constant\" value: 20 }\n    channel_shared: false\n  }")
+                    if last == "conv4_3_norm":
+                        return
+            if blk < 5:
+                w.layer("pool%d" % blk, "Pooling", [prev], ["pool%d" % blk], "  pooling_param { pool: MAX kernel_size: 2 stride: 2 }")
+            else:
+                w.layer("pool5", "Pooling", [prev], ["pool5"], "  pooling_param { pool: MAX kernel_size: 3 stride: 1 pad: 1 }")
+            prev = "pool%d" % blk
+        prev = _dl_conv(w, "fc6", prev, wd(1024), 3, 6, 6, relu="relu6")
+        prev = _dl_conv(w, "fc7", prev, wd(1024), 1, relu="relu7")
+        for n, mid, out, stride, pad in ((6, 256, 512, 2, 1), (7, 128, 256, 2, 1), (8, 128, 256, 1, 0), (9, 128, 256, 1, 0)):
+            if last == prev:
+                return
+            prev = _dl_conv(w, "conv%d_1" % n, prev, wd(mid), 1, relu="conv%d_1_relu" % n)
+            nm = "conv%d_2" % n
+            w.layer(nm, "Convolution", [prev], [nm], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+                    "  convolution_param {\n    num_output: %d\n    pad: %d\n    kernel_size: 3\n    stride: %d\n    weight_filler { type: \"xavier\" }\n"
+                    "    bias_filler { type: \"constant\" value: 0 }\n  }" % (wd(out), pad, stride))
+            w.layer(nm + "_relu", "ReLU", [nm], [nm])
+            prev = nm
+
+    body()
+    for feat, sizes, ratios, step in boxes:
+        _ssd_head(w, feat, (1 + 2 * len(ratios)) + 1, classes, 3, _ssd_box(sizes, ratios, size / 300.0, step if size == 300 else None))
+    _ssd_tail(w, [f for f, _s, _r, _st in boxes], classes, 0.01, 400, 200)
+    return w.text() if fillers else _strip_fillers(w.text())

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import proto
+from . import proto, ssd
 
 Shape = Tuple[int, ...]
 
@@ -292,6 +292,10 @@ class NetSpec:
         # second top of a MAX Pooling (Caffe's mask: the flat iy * W + ix argmax as floats) -> that layer.  A mask has a shape and can be
         # read, but it is no activation blob: on the device it is the pooling's int32 argmax buffer, and only an Upsample may consume it
         self.mask_blobs: Dict[str, Layer] = {}
+        # SSD: tops of PriorBox layers and of their Concat(axis 2) -> that layer (constants of the net, computed when it is planned), and the
+        # top of a DetectionOutput -> that layer (its shape is a capacity: a forward says how many rows it holds)
+        self.prior_blobs: Dict[str, Layer] = {}
+        self.detection_blobs: Dict[str, Layer] = {}
 
     @classmethod
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False) -> "NetSpec":
@@ -326,6 +330,7 @@ class NetSpec:
             shapes.update({k: tuple(int(d) for d in v) for k, v in data_shapes.items()})
         self.param_shapes = {}
         self.mask_blobs = {}
+        self.prior_blobs, self.detection_blobs = {}, {}
         self.blob_shapes = shapes      # (filled as the layers are walked: is_depthwise reads a layer's bottom)
         for l in self.layers:
             t = l.type
@@ -422,6 +427,11 @@ class NetSpec:
                     self.mask_blobs[l.tops[1]] = l
             elif t == "Concat":
                 axis = int(l.sub("concat_param").get("axis", l.sub("concat_param").get("concat_dim", 1)))
+                if axis == 2 and bots and all(len(b) == 3 and b[:2] == (1, 2) for b in bots) and all(b in self.prior_blobs for b in l.bottoms):
+                    # SSD's mbox_priorbox: the PriorBox tops side by side, a constant of the net like them
+                    shapes[l.tops[0]] = (1, 2, sum(b[2] for b in bots))
+                    self.prior_blobs[l.tops[0]] = l
+                    continue
                 if axis != 1:
                     raise NotImplementedError("Concat along axis %d" % axis)
                 g4 = _channel_axis_bottoms(l, bots)
@@ -514,6 +524,41 @@ class NetSpec:
                     raise NotImplementedError("layer %s: Upsample to %d x %d, but the mask %s indexes the %d x %d bottom of %s: "
                                               "upsample_h: %d upsample_w: %d would match" % (l.name, oh, ow, l.bottoms[1], ph, pw, pool.name, ph, pw))
                 shapes[l.tops[0]] = (bots[0][0], bots[0][1], oh, ow)
+            elif t == "Permute":
+                if len(bots) != 1 or len(l.tops) != 1 or l.tops[0] == l.bottoms[0]:
+                    raise ValueError("layer %s: Permute takes one bottom and has one top of its own" % l.name)
+                order = ssd.permute_order(l, len(bots[0]))
+                shapes[l.tops[0]] = tuple(bots[0][a] for a in order)
+            elif t == "Flatten":
+                if len(bots) != 1 or len(l.tops) != 1 or l.tops[0] == l.bottoms[0]:
+                    raise ValueError("layer %s: Flatten takes one bottom and has one top of its own" % l.name)
+                shapes[l.tops[0]] = ssd.flatten_shape(l, bots[0])
+            elif t == "Reshape":
+                if len(bots) != 1 or len(l.tops) != 1 or l.tops[0] == l.bottoms[0]:
+                    raise ValueError("layer %s: Reshape takes one bottom and has one top of its own" % l.name)
+                shapes[l.tops[0]] = ssd.reshape_shape(l, bots[0])
+            elif t == "PriorBox":
+                if len(bots) != 2 or any(len(b) != 4 for b in bots) or len(l.tops) != 1:
+                    raise ValueError("layer %s: PriorBox takes two 4-d bottoms (the feature map and the image) and has one top, got %s" % (l.name, bots))
+                shapes[l.tops[0]] = (1, 2, bots[0][2] * bots[0][3] * ssd.priorbox_params(l).per_cell * 4)
+                self.prior_blobs[l.tops[0]] = l
+            elif t == "Normalize":
+                np_ = l.sub("norm_param")
+                if len(bots) != 1 or len(bots[0]) != 4 or len(l.tops) != 1:
+                    raise ValueError("layer %s: Normalize takes one 4-d bottom and has one top, got %s" % (l.name, bots))
+                if bool(np_.get("across_spatial", True)):
+                    raise NotImplementedError("layer %s: Normalize with across_spatial: true (one norm per image; only the per-pixel form "
+                                              "across_spatial: false)" % l.name)
+                self.param_shapes[l.name] = [(1,) if bool(np_.get("channel_shared", True)) else (bots[0][1],)]
+                shapes[l.tops[0]] = bots[0]
+            elif t == "DetectionOutput":
+                if len(l.tops) != 1:
+                    raise ValueError("layer %s: DetectionOutput has one top" % l.name)
+                shapes[l.tops[0]] = ssd.detection_shapes(l, bots)[0]
+                self.detection_blobs[l.tops[0]] = l
+            elif t in ssd.TRAINING_TYPES:
+                raise NotImplementedError("layer type %r (layer %s): SSD's training and evaluation layers (MultiBoxLoss, AnnotatedData, "
+                                          "DetectionEvaluate, VideoData) are not built: deploy nets only" % (t, l.name))
             elif t == "BN":
                 raise NotImplementedError("layer type 'BN' (layer %s): the SegNet fork's BN layer is not supported: write BatchNorm + Scale" % l.name)
             elif t == "Eltwise":
@@ -592,6 +637,10 @@ def fill_params(spec: NetSpec, seed: int = 0) -> Dict[str, List[np.ndarray]]:
             if len(shapes) > 1:
                 blobs.append(fill_blob(shapes[1], p.get("bias_filler"), rng))
             out[l.name] = blobs
+            continue
+        if l.type == "Normalize":      # NormalizeLayer: scale_filler defaults to constant 1
+            f = l.sub("norm_param").get("scale_filler")
+            out[l.name] = [fill_blob(shapes[0], f if f is not None else one, rng)]
             continue
         p = l.sub("inner_product_param" if l.type == "InnerProduct" else "convolution_param")
         blobs = [fill_blob(shapes[0], p.get("weight_filler"), rng)]

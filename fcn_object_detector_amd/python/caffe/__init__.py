@@ -189,7 +189,7 @@ class Net(object):
                 inst.bind_device(self._engine, [t.name for t in tops])
 
     def _shape(self, name: str):
-        return self._engine.shapes[name]
+        return self._engine.blob_shape(name)      # (the top of a DetectionOutput: as many rows as the last forward found)
 
     def _reshape_blob(self, name: str, dims) -> None:
         with self._lock:

@@ -6,11 +6,12 @@ environment.  :class:`Engine` does that, from what these functions return (DESIG
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
+from . import ssd
 from .netspec import Layer, NetSpec, as_nchw
 
 F32 = np.float32
@@ -28,10 +29,13 @@ def _ra(c: int, esize: int) -> int:
 
 def blob_nchw(shape: Sequence[int], rows: bool) -> Optional[Tuple[int, int, int, int]]:
     """A blob as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
-    channels (H = W = 1); an (N,) label that pairs with such score rows (`rows`) as N pixels of one channel; None for anything else
-    (scalars, per-class vectors: dense floats outside that machinery).  netspec.as_nchw is the rule."""
+    channels (H = W = 1); an (N,) label that pairs with such score rows (`rows`) as N pixels of one channel, and an (N, P, C) blob of an
+    SSD head (`rows` as well) as N pixels of P * C channels - the row of its (N, P * C) twin; None for anything else (scalars, per-class
+    vectors, the rows of a DetectionOutput: dense floats outside that machinery).  netspec.as_nchw is the rule."""
     if rows and len(shape) == 1:
         return (shape[0], 1, 1, 1)
+    if rows and len(shape) == 3:
+        return (shape[0], shape[1] * shape[2], 1, 1)
     return as_nchw(shape)
 
 
@@ -46,7 +50,8 @@ class BlobView:
     cstride: int
     upload_shift: float        # value added while the blob is uploaded (device copy = host + upload_shift)
     lazy_shift: float          # value added when the blob is read back (Power layer folded into the upload)
-    rows: bool                 # an (N,) label blob of a loss / Accuracy over N score rows: N pixels of one channel
+    rows: bool                 # an (N,) label blob of a loss / Accuracy over N score rows: N pixels of one channel; an (N, P, C) blob of
+    #                            an SSD head: N pixels of P * C channels
 
     @property
     def nchw(self) -> Optional[Tuple[int, int, int, int]]:
@@ -66,6 +71,12 @@ class BlobPlan:
     rows: Set[str]
     producers: Dict[str, List[Layer]]
     consumers: Dict[str, List[Layer]]
+    # SSD heads.  permutes: top of a Permute(0, 2, 3, 1) -> its bottom (the top owns no buffer: the bottom's NHWC buffer IS that order).
+    # gathers: Concat (or lone Flatten) layer -> (top that receives the columns, [(Flatten top, head blob, first column)]): one launch of
+    # fcn_ssd_gather_f32 per 16 heads.  detections: top of a DetectionOutput -> rows of capacity (its buffer: 7 floats a row, then the count)
+    permutes: Dict[str, str] = field(default_factory=dict)
+    gathers: Dict[str, Tuple[str, List[Tuple[str, str, int]]]] = field(default_factory=dict)
+    detections: Dict[str, int] = field(default_factory=dict)
 
 
 def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequence[str], outputs: Sequence[str],
@@ -77,8 +88,27 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             producers.setdefault(t, []).append(l)
         for b in l.bottoms:
             consumers.setdefault(b, []).append(l)
+    heads = [l for l in spec.layers if l.type in ssd.HEAD_TYPES]
+    if f16 and heads:
+        raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (heads[0].type, heads[0].name))
+    # the top of a Permute(0, 2, 3, 1) owns nothing: its bottom's NHWC buffer, minus the pad channels, is Caffe's memory order of it
+    permutes: Dict[str, str] = {}
+    for l in spec.layers:
+        if l.type == "Permute":
+            order = ssd.permute_order(l, len(shapes[l.bottoms[0]]))
+            if len(shapes[l.bottoms[0]]) != 4 or order != (0, 2, 3, 1):
+                raise NotImplementedError("layer %s: Permute of a %d-d blob to order %s (only order 0 2 3 1 of a 4-d blob: channels last, "
+                                          "the layout the device keeps)" % (l.name, len(shapes[l.bottoms[0]]), list(order)))
+            bad = [q.name for q in consumers.get(l.tops[0], []) if q.type != "Flatten"]
+            if bad or l.tops[0] in outputs:
+                raise NotImplementedError("layer %s: the Permute top %s %s (only Flatten layers may read it)"
+                                          % (l.name, l.tops[0], "feeds %s" % bad if bad else "is an output of the net"))
+            permutes[l.tops[0]] = l.bottoms[0]
+    # the top of a DetectionOutput is dense floats: `capacity` rows of 7, then the int32 count in a 16-byte tail
+    detections: Dict[str, int] = {name: int(shapes[name][2]) for name in spec.detection_blobs}
     # a pooling mask is no activation blob: it is the pooling's argmax buffer, which the engine allocates (no view, no buffer here)
-    shapes = {name: shp for name, shp in shapes.items() if name not in spec.mask_blobs}
+    shapes = {name: ((detections[name] * 7 + 4,) if name in detections else shp) for name, shp in shapes.items()
+              if name not in spec.mask_blobs and name not in permutes}
     data_tops = set(inputs)
     # f16 mode: everything is stored as halves except what leaves the net towards the f32 decode kernel - the output
     # blobs and the input / output of a Sigmoid head (written by the convolution epilogue in f32)
@@ -123,7 +153,39 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     shift: Dict[str, float] = {}
     copy_concats: Set[str] = set()
     copy_slices: Set[str] = set()
+    gathers: Dict[str, Tuple[str, List[Tuple[str, str, int]]]] = {}
     for l in spec.layers:
+        if l.type == "Concat" and l.tops[0] in spec.prior_blobs:
+            continue      # SSD's mbox_priorbox: a constant with a buffer of its own, like the PriorBox tops beside it
+        if l.type == "Flatten":
+            top, bot = l.tops[0], l.bottoms[0]
+            bshape = spec.blob_shapes[bot]
+            if bot in permutes:
+                # Caffe's memory order of the Permute top, per image: the head's pixels x real channels.  One Concat(axis 1) that is the only
+                # reader of all its Flatten bottoms receives them directly (below); any other Flatten of this kind is a gather of one head
+                gathers[l.name] = (top, [(top, permutes[bot], 0)])
+            elif len(bshape) == 3 or (len(bshape) == 4 and bshape[2] == bshape[3] == 1):
+                alias[top] = (bot, 0)      # the same floats per image, at the same row stride
+            else:
+                raise NotImplementedError("layer %s: Flatten of the %s blob %s (Caffe's C x H x W order of a row is not the device's: Flatten "
+                                          "the top of a Permute(0, 2, 3, 1), an (N, P, C) blob or a blob with H = W = 1)" % (l.name, tuple(bshape), bot))
+        elif l.type == "Reshape":
+            top, bot = l.tops[0], l.bottoms[0]
+            a, b = spec.blob_shapes[bot], spec.blob_shapes[top]
+            if not ((len(a), len(b)) in ((2, 3), (3, 2)) and a[0] == b[0]) or bot in data_tops:
+                raise NotImplementedError("layer %s: Reshape of %s to %s (only between (N, K) and (N, P, C) with P * C == K)" % (l.name, tuple(a), tuple(b)))
+            alias[top] = (bot, 0)
+        if l.type == "Concat" and l.bottoms and all(
+                len(producers.get(b, [])) == 1 and producers[b][0].name in gathers and [q.name for q in consumers.get(b, [])] == [l.name]
+                and b not in outputs for b in l.bottoms) and len(set(l.bottoms)) == len(l.bottoms):
+            # the mbox_loc / mbox_conf form: every bottom is the Flatten of a Permute top and nothing else reads it
+            off, cols = 0, []
+            for b in l.bottoms:
+                cols.append((b, gathers.pop(producers[b][0].name)[1][0][1], off))
+                alias[b] = (l.tops[0], off)
+                off += shapes[b][1]
+            gathers[l.name] = (l.tops[0], cols)
+            continue
         if l.type == "Concat":
             off = 0
             ok = True
@@ -176,6 +238,10 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             score, lab = shapes[l.bottoms[0]], shapes[l.bottoms[1]]
             if len(score) == 2 and tuple(lab) == (score[0],):
                 rows.add(l.bottoms[1])
+        # an SSD head's 3-d blobs - (N, P, C) scores, (1, 2, P * 4) priors - are rows of P * C floats per image, like their 2-d twins
+        if (l.type in ("Reshape", "PriorBox") or l.tops[:1] and l.tops[0] in spec.prior_blobs
+                or l.type == "Softmax" and l.bottoms[0] in rows) and len(shapes.get(l.tops[0], ())) == 3:
+            rows.add(l.tops[0])
 
     # roots own a buffer; every other blob resolves through its chain of parents to a channel window of one
     cstride: Dict[str, int] = {}
@@ -215,7 +281,8 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     views = {name: BlobView(tuple(shp), esize[name], window[name][0], window[name][1], cstride[window[name][0]],
                             upload_shift.get(name, 0.0), lazy_shift.get(name, 0.0), name in rows)
              for name, shp in shapes.items()}
-    return BlobPlan(views, root_bytes, esize, alias, shift, copy_concats, copy_slices, half_inputs, rows, producers, consumers)
+    return BlobPlan(views, root_bytes, esize, alias, shift, copy_concats, copy_slices, half_inputs, rows, producers, consumers,
+                    permutes, gathers, detections)
 
 
 # ---------------------------------------------------------------------- parameters
@@ -286,7 +353,7 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
                     raise NotImplementedError("f16 engine: layer type Deconvolution with group 1 (%s) has no half-float kernel" % l.name)
                 else:
                     kind, shape = DECONV, (c, kh, kw, _r4(cog))
-            elif i == 0 and l.type not in ("BatchNorm", "Scale"):      # (their blobs are per-channel vectors as they are: PLAIN)
+            elif i == 0 and l.type not in ("BatchNorm", "Scale", "Normalize"):      # (their blobs are per-channel vectors as they are: PLAIN)
                 raise NotImplementedError(l.type)
             count = int(np.prod(shape))
             lr, decay = float(l.lr_mult[i] if i < len(l.lr_mult) else 1.0), float(l.decay_mult[i] if i < len(l.decay_mult) else 1.0)

@@ -961,6 +961,66 @@ int  fcn_batchnorm_bwd_apply_f32(const float* dy, const float* xhat, const float
                                  const float* save, const float* blob_var, const float* blob_factor, float eps, const float* gamma,
                                  const float* sum_dy, const float* sum_dyx, int accumulate, fcn_stream_t s);
 
+/* ---- SSD detection head (Caffe-SSD's Permute + Flatten + Concat, Normalize and DetectionOutput; csrc/ssd.hip).  Float32, inference.
+ *      Common contract: every output element has exactly one writer lane (no float atomics anywhere), so a second launch on the same
+ *      inputs gives the same bytes; nothing outside the named outputs and the workspace is written; every refusal is made on the host
+ *      before the first HIP call (null pointers, non-positive extents, ranges that leave their row or pixel FCN_E_ARG; pointers off their
+ *      alignment FCN_E_ALIGN; extents past 2^31 elements and sizes beyond a kernel's plan FCN_E_UNSUPPORTED); all launches are capturable.
+ *      The file is compiled without fused multiply-add contraction: a rebuild does not move a decision of the NMS. ---- */
+#define FCN_SSD_MAX_HEADS 16
+typedef struct fcn_ssd_head {
+    const float* src;          /* channel 0 of pixel 0 of image 0 of the head's NHWC buffer                                      */
+    int32_t pixels;            /* H * W per image                                                                                */
+    int32_t C;                 /* real channels per pixel                                                                        */
+    int32_t cstride;           /* floats per pixel in src                                                                        */
+    int32_t coffset;           /* the head's first channel inside a pixel                                                        */
+    int32_t dst_col;           /* column of a destination row where the head's pixels * C floats start (any value, odd included) */
+    int32_t reserved;          /* 0                                                                                              */
+} fcn_ssd_head;
+/* Permute(0,2,3,1) + Flatten + Concat(axis 1) of up to FCN_SSD_MAX_HEADS heads in ONE launch:
+ *   dst[n * dst_rstride + dst_col + p * C + c] = src[(n * pixels + p) * cstride + coffset + c]      for every head, n < N, p < pixels, c < C.
+ * A head whose source runs and destination runs are all 16-byte aligned (C, cstride, coffset, dst_col, dst_rstride multiples of 4, both
+ * pointers on 16 bytes) moves 16 bytes per lane, any other head one float per lane.  Pad channels of a source pixel are never read;
+ * columns of dst outside the heads' ranges are never written.  Heads whose column ranges overlap, or leave dst_cols, are FCN_E_ARG. */
+int  fcn_ssd_gather_f32(const fcn_ssd_head* h_heads, int n_heads, int N, float* dst, int dst_rstride, int dst_cols, fcn_stream_t s);
+/* Normalize (across_spatial: false): y[c] = scale[c] * (x[c] / sqrt(sum_c x[c]^2 + eps)) per pixel; channel_shared: scale[0] for every c.
+ * One wave per pixel.  The sum is taken in a fixed order: lane l adds x[c]^2 for c = l, l + 64, l + 128, .. ascending, then the 64 lanes
+ * fold by halves (partner lane ^ 32, ^ 16, .. ^ 1).  Pad channels of x are never read; channels C .. r4(C) - 1 of the y view are written
+ * as zeros (y_cstride >= y_coffset + r4(C)).  y may be x. */
+int  fcn_normalize_fwd_f32(const float* x, float* y, const float* scale, int pixels, int C, int x_cstride, int x_coffset, int y_cstride,
+                           int y_coffset, int channel_shared, float eps, fcn_stream_t s);
+/* DetectionOutput (share_location: true, eta 1).  loc: N rows of P * 4 floats, conf: N rows of P * num_classes floats (row strides in
+ * floats), priors: P * 4 corners followed by P * 4 variances, as a PriorBox top lies in memory.  The order of steps is the contract:
+ *   1. decode every prior once per image.  FCN_CODE_CENTER_SIZE: cx = v0 l0 pw + pcx, cy = v1 l1 ph + pcy, w = exp(v2 l2) pw,
+ *      h = exp(v3 l3) ph, corners c -+ size / 2; FCN_CODE_CORNER: corner_i = prior_i + v_i l_i; v = 1 under variance_encoded.  No clipping.
+ *   2. per image and class c != background: the priors with conf > conf_threshold (strictly), by score descending, ties by prior index
+ *      ascending, cut to top_k when top_k > -1.
+ *   3. greedy NMS in that order: a candidate is kept iff its Jaccard overlap with every box kept so far is <= nms_threshold.  The overlap
+ *      is 0 when the boxes do not intersect, else inter / (a1 + a2 - inter); a box with xmax < xmin or ymax < ymin has area 0; no +1.
+ *   4. per image, when keep_top_k > -1 and more survive: the keep_top_k highest scores; ties by label ascending, then prior index
+ *      ascending (Caffe's std::sort leaves them unspecified; this order is fixed here).
+ *   5. rows [image, label, score, xmin, ymin, xmax, ymax] by image ascending, label ascending and within a label in NMS order, into
+ *      out_rows; their number into *out_count.  Rows at and past the count are not written.
+ * One workgroup per (image, class) selects (compaction, ranking of the 64-bit keys (score bits, ~index) through LDS tiles) and sweeps;
+ * one per image cuts and writes.  top_k (or P when top_k is -1) above FCN_DETOUT_MAX_TOPK and products past 2^31 are FCN_E_UNSUPPORTED;
+ * `capacity` rows below what N images can yield is FCN_E_CAPACITY; a workspace below fcn_detection_output_workspace_bytes() FCN_E_ARG,
+ * off 16 bytes FCN_E_ALIGN.  The size query returns 0 for parameters the launch would refuse. */
+#define FCN_DETOUT_MAX_TOPK 1024
+#define FCN_CODE_CORNER 1
+#define FCN_CODE_CENTER_SIZE 2
+typedef struct fcn_detout_params {
+    int32_t N, P, num_classes, background;       /* background: label that is never emitted (-1: none)      */
+    int32_t code_type, variance_encoded;
+    int32_t top_k, keep_top_k;                   /* -1: no cut                                             */
+    float conf_threshold, nms_threshold;
+    int32_t loc_rstride, conf_rstride;           /* floats between the rows of two images                  */
+    int32_t capacity;                            /* rows that out_rows holds                               */
+    int32_t reserved;                            /* 0                                                      */
+} fcn_detout_params;
+size_t fcn_detection_output_workspace_bytes(const fcn_detout_params* h_params);
+int  fcn_detection_output_f32(const float* loc, const float* conf, const float* priors, const fcn_detout_params* h_params, float* out_rows,
+                              int32_t* out_count, void* d_workspace, size_t workspace_bytes, fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
