@@ -28,6 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import lib as L
+from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
@@ -454,6 +455,12 @@ class Engine:
         self.alias, self.shift, self.copy_concats, self.copy_slices = plan.alias, plan.shift, plan.copy_concats, plan.copy_slices
         self._half_inputs = plan.half_inputs      # data top -> (Power top, shift)
         self.permutes, self.gathers, self.detections = plan.permutes, plan.gathers, plan.detections      # SSD heads (storage.BlobPlan)
+        self.pair_softmax, self.rpn_views = plan.pair_softmax, plan.rpn_views                            # the RPN softmax chain
+        # Proposal layer -> the device int32 that holds how many of its post_nms_topn rows the last forward found, and its host copy
+        self.roi_counts: Dict[str, DeviceBuffer] = {}
+        self._roi_count_host: Dict[str, "PinnedArray"] = {}
+        self._roi_caps: Dict[str, int] = {}
+        self._counts_valid = False
         bufs = {root: DeviceBuffer(nbytes) for root, nbytes in plan.root_bytes.items()}
         for name, v in plan.views.items():
             b = self.blobs[name] = Blob(name, v.shape)
@@ -806,6 +813,9 @@ class Engine:
                 ch = self._bn_chain_after(li, l, skip)
                 tasks.append(OpTask(l, self._fwd_batchnorm(ch), reads=[self._range(ch.x)], writes=[self._range(ch.y)]))
                 continue
+            if t in RG.REGION_TYPES or l.name in self.pair_softmax or (t == "Reshape" and (l.tops[0] in self.rpn_views or l.bottoms[0] in self.rpn_views)):
+                tasks.extend(self._region_tasks(l))
+                continue
             if t in SSD.HEAD_TYPES or l.name in self.gathers or (l.tops and l.tops[0] in spec.prior_blobs) or \
                     (t == "Softmax" and len(self.shapes[l.bottoms[0]]) == 3 and int(l.sub("softmax_param").get("axis", 1)) in (2, -1)):
                 tasks.extend(self._ssd_tasks(l))
@@ -957,10 +967,105 @@ class Engine:
 
     def blob_shape(self, name: str) -> Tuple[int, ...]:
         """A blob's shape as pycaffe reports it: the inferred one - for the top of a DetectionOutput after a forward, (1, 1, K, 7) with the
-        K rows that forward found (the inferred shape is the capacity)."""
+        K rows that forward found (the inferred shape is the capacity), and for a blob on the ROI axis of a Proposal after a forward, the
+        rows that Proposal found in front of the other extents."""
         if name in self.detections and self.blobs[name].host is not None and getattr(self, "_ran", False):
             return self._compose_detections(name).shape
+        if name in self.spec.roi_blobs and getattr(self, "_ran", False):
+            return (self._roi_count(self.spec.roi_blobs[name].name),) + tuple(self.shapes[name][1:])
         return tuple(self.shapes[name])
+
+    # ------------------------------------------------------------------ region stage (csrc/region.hip)
+    def _region_tasks(self, l: Layer) -> List[OpTask]:
+        """The launches of one layer of a region stage.  The two Reshape layers of the RPN softmax chain emit nothing: its Softmax layer is
+        ONE fcn_pair_softmax_f32 launch from the first Reshape's bottom into the second one's top.  Proposal, ROIPooling and PSROIPooling
+        are one op each; Proposal's op is five launches that never wait for the host."""
+        lib, B, t = L.load(), self.blobs, l.type
+        need = getattr(self, "need_grad", None)
+        if need is not None and any(b in need for b in l.bottoms + l.tops):
+            raise NotImplementedError("layer %s: %s below a layer that learns in a TRAIN-phase net (the region stage has no backward pass: "
+                                      "AnchorTarget, ProposalTarget and the poolings' gradients are not built; deploy nets only)" % (l.name, t))
+        if t == "Reshape":
+            return []
+        if t == "Softmax":
+            src, dst, a = self.pair_softmax[l.name]
+            xb, yb = B[src], B[dst]
+            if xb.esize != 4 or yb.esize != 4 or yb.cstride < yb.coffset + _r4(2 * a):
+                raise NotImplementedError("layer %s: the top %s is a channel window that ends inside a 16-byte group" % (l.name, dst))
+            pix = xb.pixels
+            run = lambda st: L.check(lib.fcn_pair_softmax_f32(xb.buf.ptr, yb.buf.ptr, pix, a, xb.cstride, xb.coffset, yb.cstride, yb.coffset, st))
+            return [OpTask(l, [Op("pair_softmax", l.name, run, 0.0, 16.0 * pix * a)], reads=[self._range(src)], writes=[self._range(dst)])]
+        if t == "Proposal":
+            pp = RG.proposal_params(l)
+            RG.proposal_shapes(l, [self.shapes[b] for b in l.bottoms])
+            sb, db, ib = (B[b] for b in l.bottoms)
+            rb = B[l.tops[0]]
+            tb = B[l.tops[1]] if len(l.tops) > 1 else None
+            if any(x.esize != 4 for x in (sb, db, ib)) or rb.cstride < rb.coffset + 8 or (tb is not None and tb.cstride < tb.coffset + 4):
+                raise NotImplementedError("layer %s: a top of Proposal is a channel window that ends inside a 16-byte group" % l.name)
+            base = RG.anchors(pp.base_size, pp.ratios, pp.scales).astype(F32).reshape(-1)
+            par = L.ProposalParams()
+            par.H, par.W, par.A, par.feat_stride = sb.shape[2], sb.shape[3], base.size // 4, pp.feat_stride
+            par.pre_nms_topn, par.post_nms_topn, par.min_size, par.nms_thresh = pp.pre_nms_topn, pp.post_nms_topn, pp.min_size, pp.nms_thresh
+            par.score_cstride, par.score_coffset, par.delta_cstride, par.delta_coffset = sb.cstride, sb.coffset, db.cstride, db.coffset
+            par.rois_cstride, par.rois_coffset = rb.cstride, rb.coffset
+            par.top_score_cstride, par.top_score_coffset = (tb.cstride, tb.coffset) if tb is not None else (0, 0)
+            for i, v in enumerate(base):
+                par.anchors[i] = float(v)
+            nbytes = int(lib.fcn_proposal_workspace_bytes(C.byref(par)))
+            if nbytes <= 0:
+                L.check(lib.fcn_proposal_f32(None, None, None, C.byref(par), None, None, None, None, 0, None))      # (raises with the library's text)
+                raise RuntimeError("layer %s: Proposal has no plan" % l.name)
+            ws, cnt = DeviceBuffer(nbytes, zero=True), DeviceBuffer(16, zero=True)
+            self.roi_counts[l.name], self._roi_caps[l.name] = cnt, pp.post_nms_topn
+            self._keep.extend([ws, par])
+            m, k = par.H * par.W * par.A, min(pp.pre_nms_topn, par.H * par.W * par.A)
+            run = lambda st: L.check(lib.fcn_proposal_f32(sb.buf.ptr, db.buf.ptr, ib.ptr, C.byref(par), rb.buf.ptr, tb.buf.ptr if tb is not None else None,
+                                                          cnt.ptr, ws.ptr, nbytes, st))
+            return [OpTask(l, [Op("proposal", l.name, run, 30.0 * m + 2.0 * m * m + 20.0 * k * k / 2, 24.0 * m + 8.0 * m * ((m + 255) // 256) + k * k / 4.0)],
+                           reads=[self._range(b) for b in l.bottoms], writes=[self._range(tp) for tp in l.tops])]
+        xb, rb, yb = B[l.bottoms[0]], B[l.bottoms[1]], B[l.tops[0]]
+        if any(x.esize != 4 for x in (xb, rb, yb)) or yb.cstride < yb.coffset + _r4(yb.channels):
+            raise NotImplementedError("layer %s: the top %s is a channel window that ends inside a 16-byte group" % (l.name, l.tops[0]))
+        n, c, h, w = xb.nchw
+        r = rb.shape[0]
+        if t == "ROIPooling":
+            rp = RG.roi_pool_params(l)
+            run = lambda st: L.check(lib.fcn_roi_pool_fwd_f32(xb.buf.ptr, rb.buf.ptr, yb.buf.ptr, None, n, h, w, c, xb.cstride, xb.coffset, r, rb.cstride,
+                                                              rb.coffset, rp.pooled_h, rp.pooled_w, rp.spatial_scale, yb.cstride, yb.coffset, st))
+            return [OpTask(l, [Op("roi_pool", l.name, run, 0.0, 4.0 * (n * h * w * c + r * rp.pooled_h * rp.pooled_w * c))],
+                           reads=[self._range(b) for b in l.bottoms], writes=[self._range(l.tops[0])])]
+        if t == "PSROIPooling":
+            sp = RG.psroi_pool_params(l)
+            RG.psroi_pool_shape(l, [self.shapes[b] for b in l.bottoms])
+            run = lambda st: L.check(lib.fcn_psroi_pool_fwd_f32(xb.buf.ptr, rb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset, r, rb.cstride,
+                                                                rb.coffset, sp.output_dim, sp.group_size, sp.spatial_scale, yb.cstride, yb.coffset, st))
+            return [OpTask(l, [Op("psroi_pool", l.name, run, 1.0 * r * c * 4, 4.0 * (n * h * w * c + r * c))],
+                           reads=[self._range(b) for b in l.bottoms], writes=[self._range(l.tops[0])])]
+        raise NotImplementedError("layer type %r (layer %s) has no forward kernel yet" % (t, l.name))
+
+    def _download_counts(self, stream: Optional[int]) -> None:
+        """The Proposal layers' row counts to the host, enqueued behind the layers (and behind the graph that holds them)."""
+        for name, cnt in self.roi_counts.items():
+            host = self._roi_count_host.get(name)
+            if host is None:
+                host = self._roi_count_host[name] = PinnedArray((4,))
+            L.check(L.load().fcn_memcpy_d2h_async(host.array.ctypes.data, cnt.ptr, 4, stream))
+
+    def _roi_count(self, name: str) -> int:
+        """How many rows the Proposal layer `name` found in the last forward (copied now if that forward left the count on the device)."""
+        if not self._counts_valid:
+            with self.lock:
+                self._download_counts(self.stream)
+                L.call("fcn_stream_sync", self.stream)
+                self._counts_valid = True
+        return min(max(int(self._roi_count_host[name].array.view(np.int32)[0]), 0), self._roi_caps[name])
+
+    def _cut_rois(self, name: str, a: np.ndarray) -> np.ndarray:
+        """A blob on the ROI axis of a Proposal as Caffe would shape it: the rows the last forward found."""
+        if name not in self.spec.roi_blobs or not getattr(self, "_ran", False):
+            return a
+        return a[:self._roi_count(self.spec.roi_blobs[name].name)]
 
     def _compose_detections(self, name: str) -> np.ndarray:
         """Caffe's top of a DetectionOutput from the downloaded buffer (rows, then the count): composed on the host, nothing waits here."""
@@ -1768,6 +1873,8 @@ class Engine:
         """Synchronised NCHW float32 host copy of a blob (pycaffe ``net.blobs[name].data``)."""
         if name in self.spec.mask_blobs:
             return self._read_mask(name)
+        if name in self.rpn_views:     # a middle blob of the RPN softmax chain: its neighbour's NCHW array in Caffe's memory order
+            return np.ascontiguousarray(self.read_blob(self.rpn_views[name])).reshape(self.shapes[name])
         if name in self.permutes:      # Caffe's (N, H, W, C) array, read from the bottom's buffer
             return np.ascontiguousarray(self.read_blob(self.permutes[name]).transpose(0, 2, 3, 1))
         if name in self.spec.prior_blobs:
@@ -1794,7 +1901,7 @@ class Engine:
                 if b.lazy_shift:
                     host += F32(b.lazy_shift)
                 b.host_valid = True
-            return host
+            return self._cut_rois(name, host)
 
     def _read_mask(self, name: str) -> np.ndarray:
         """A pooling mask as Caffe holds it: NCHW float32, the flat iy * W + ix index of each window's maximum in the plane of the
@@ -1966,6 +2073,7 @@ class Engine:
         L.call("fcn_graph_launch", self.graph_io, self.stream)
         for nm in self.outputs:
             self._download_copy(nm, self.stream)
+        self._download_counts(self.stream)
 
     def forward(self, use_graph: bool = True) -> Dict[str, np.ndarray]:
         """Upload inputs, run every layer, download the output blobs (synchronous, like Net.forward())."""
@@ -1985,19 +2093,20 @@ class Engine:
                 self.run_ops(self.stream)
                 for nm in self.outputs:
                     self._enqueue_download(nm, self.stream)
+                self._download_counts(self.stream)
             L.call("fcn_stream_sync", self.stream)
             for b in self.blobs.values():
                 b.host_valid = False
+            self._ran = self._counts_valid = True      # (the Proposal counts came down behind the layers)
             out = {}
             for nm in self.outputs:
                 b = self.blobs[nm]
                 if b.lazy_shift:
                     b.host += F32(b.lazy_shift)
                 b.host_valid = True
-                out[nm] = b.host if nm not in self.detections else self._compose_detections(nm)
+                out[nm] = self._cut_rois(nm, b.host) if nm not in self.detections else self._compose_detections(nm)
             for nm in self.inputs:
                 self.blobs[nm].host_valid = nm not in self.device_fed
-            self._ran = True
             return out
 
     def forward_begin(self) -> None:
@@ -2015,22 +2124,23 @@ class Engine:
                 self.run_ops(self.stream)
                 for nm in self.outputs:
                     self._enqueue_download(nm, self.stream)
+                self._download_counts(self.stream)
 
     def forward_end(self) -> Dict[str, np.ndarray]:
         with self.lock:
             L.call("fcn_stream_sync", self.stream)
             for b in self.blobs.values():
                 b.host_valid = False
+            self._ran = self._counts_valid = True      # (the Proposal counts came down behind the layers)
             out = {}
             for nm in self.outputs:
                 b = self.blobs[nm]
                 if b.lazy_shift:
                     b.host += F32(b.lazy_shift)
                 b.host_valid = True
-                out[nm] = b.host if nm not in self.detections else self._compose_detections(nm)
+                out[nm] = self._cut_rois(nm, b.host) if nm not in self.detections else self._compose_detections(nm)
             for nm in self.inputs:
                 self.blobs[nm].host_valid = nm not in self.device_fed
-            self._ran = True
             return out
 
     def upload_inputs(self) -> None:
@@ -2051,7 +2161,7 @@ class Engine:
             for b in self.blobs.values():
                 if not b.is_input:
                     b.host_valid = False
-            self._ran = True
+            self._ran, self._counts_valid = True, False
 
     def forward_resident(self, iters: int = 1, use_graph: bool = True) -> float:
         """Run the layer stack ``iters`` times on inputs already in HBM; returns HIP-event ms for all iterations."""
@@ -2078,6 +2188,7 @@ class Engine:
             for b in self.blobs.values():
                 if not b.is_input:
                     b.host_valid = False
+            self._counts_valid = False
             return float(ms.value)
 
     def time_ops(self, reps: int = 20, ops: Optional[Sequence["Op"]] = None) -> List[Tuple[str, str, float, float, float]]:

@@ -175,6 +175,17 @@ class DetOutParams(C.Structure):
         ("conf_threshold", C.c_float), ("nms_threshold", C.c_float)] + [(k, C.c_int32) for k in ("loc_rstride", "conf_rstride", "capacity", "reserved")]
 
 
+class ProposalParams(C.Structure):
+    """fcn_proposal_params: Proposal."""
+    _fields_ = [(k, C.c_int32) for k in ("H", "W", "A", "feat_stride", "pre_nms_topn", "post_nms_topn")] + [
+        ("min_size", C.c_float), ("nms_thresh", C.c_float)] + [(k, C.c_int32) for k in (
+            "score_cstride", "score_coffset", "delta_cstride", "delta_coffset", "rois_cstride", "rois_coffset", "top_score_cstride",
+            "top_score_coffset")] + [("anchors", C.c_float * 128)]
+
+
+PROPOSAL_MAX_ANCHORS = 32      # FCN_PROPOSAL_MAX_ANCHORS
+PROPOSAL_MAX_CANDIDATES = 65536    # FCN_PROPOSAL_MAX_CANDIDATES
+PROPOSAL_MAX_PRE_NMS = 6144    # FCN_PROPOSAL_MAX_PRE_NMS
 SSD_MAX_HEADS = 16             # FCN_SSD_MAX_HEADS
 DETOUT_MAX_TOPK = 1024         # FCN_DETOUT_MAX_TOPK
 CODE_CORNER, CODE_CENTER_SIZE = 1, 2
@@ -364,6 +375,11 @@ PROTOTYPES = {
     "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
     "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),
     "fcn_detection_output_f32": (_i, [_vp, _vp, _vp, C.POINTER(DetOutParams), _vp, _vp, _vp, _sz, _vp]),
+    "fcn_pair_softmax_f32": (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
+    "fcn_proposal_workspace_bytes": (_sz, [C.POINTER(ProposalParams)]),
+    "fcn_proposal_f32": (_i, [_vp, _vp, _vp, C.POINTER(ProposalParams), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fcn_roi_pool_fwd_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_f, _i, _i, _vp]),
+    "fcn_psroi_pool_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 11 + [_f, _i, _i, _vp]),
 }
 
 HW_QUEUES: dict = {}      # what load() found / did about GPU_MAX_HW_QUEUES

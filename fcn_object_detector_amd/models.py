@@ -628,12 +628,14 @@ def _resnet_block_names(count: int, numbered: bool) -> List[str]:
 
 
 def _rn_conv_bn(w: _Writer, tag: str, bottom: str, num_output: int, k: int, pad: int, stride: int, phase: str, relu: bool,
-                conv_name: Optional[str] = None, bias: bool = False) -> str:
+                conv_name: Optional[str] = None, bias: bool = False, dilation: int = 1) -> str:
     """Convolution `res<tag>` (bias_term: false but for conv1) with BatchNorm `bn<tag>`, Scale `scale<tag>` (bias_term: true) and ReLU
     `res<tag>_relu` in place on its top; returns the top."""
     name = conv_name or "res" + tag
     sfx = tag if conv_name is None else "_" + conv_name
     geo = "    num_output: %d\n    kernel_size: %d\n    pad: %d\n    stride: %d\n" % (num_output, k, pad, stride)
+    if dilation != 1:
+        geo += "    dilation: %d\n" % dilation
     fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / (k * k * num_output)) ** 0.5
     if bias:
         fill += "    bias_filler { type: \"constant\" value: 0 }\n"
@@ -1309,4 +1311,83 @@ def ssd300_vgg(phase: str = "DEPLOY", classes: int = 21, size: int = 300, width_
     for feat, sizes, ratios, step in boxes:
         _ssd_head(w, feat, (1 + 2 * len(ratios)) + 1, classes, 3, _ssd_box(sizes, ratios, size / 300.0, step if size == 300 else None))
     _ssd_tail(w, [f for f, _s, _r, _st in boxes], classes, 0.01, 400, 200)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# R-FCN (Dai, Li, He, Sun: "R-FCN: Object Detection via Region-based Fully Convolutional Networks") on ResNet-50 / 101: the deploy net of
+# the py-R-FCN release (class-agnostic boxes), layer and blob names as remembered
+# ----------------------------------------------------------------------
+
+def rfcn_resnet(phase: str = "DEPLOY", depth: int = 50, classes: int = 21, size=(600, 1000), width_div: int = 1, batch: int = 1,
+                pre_nms_topn: int = 6000, post_nms_topn: int = 300, scales: Sequence[float] = (8, 16, 32), fillers: bool = True) -> str:
+    """The R-FCN deploy net on the ResNet body of models.resnet (published names: conv1 .. res4f / res4b22 at stride 16, res5a .. res5c
+    at stride 1 with dilation 2 in their 3x3 convolutions).  RPN over the last res4 block: rpn_conv/3x3 (512) with rpn_relu/3x3,
+    rpn_cls_score (2 x 9) and rpn_bbox_pred (4 x 9), the softmax chain rpn_cls_score_reshape -> rpn_cls_prob -> rpn_cls_prob_reshape, and
+    `proposal` over (rpn_cls_prob_reshape, rpn_bbox_pred, im_info) with the top rois.  Region stage over res5c: conv_new_1 (1x1, 1024) with
+    conv_new_1_relu, rfcn_cls (classes x 49) and rfcn_bbox (8 x 49), psroipooled_cls_rois / psroipooled_loc_rois (PSROIPooling,
+    spatial_scale 0.0625, group_size 7), ave_cls_score_rois -> cls_score and ave_bbox_pred_rois -> bbox_pred (AVE 7 x 7), cls_prob.
+    Inputs: data (batch, 3, h, w) and im_info (1, 3).  `size` is the image edge or (height, width).
+
+    With the default pre / post_nms_topn and scales the proposal layer is written as the published files write it, a Python layer naming
+    rpn.proposal_layer.ProposalLayer with param_str "'feat_stride': 16"; with others as `type: "Proposal"` with a proposal_param.  This
+    project's own: the published files end in cls_prob_reshape / bbox_pred_reshape, two Reshape layers from (R, C, 1, 1) to (R, C) that
+    are left out here - cls_prob and bbox_pred are (R, classes, 1, 1) and (R, 8, 1, 1); width_div, scales and the two topn arguments
+    (small test nets).  DEPLOY only: TRAIN and TEST need AnchorTarget / ProposalTarget and a backward pass through the poolings, which
+    are not built."""
+    _check_phase(phase)
+    if phase != "DEPLOY":
+        raise NotImplementedError("R-FCN %s net: AnchorTarget / ProposalTarget and the backward pass of PSROIPooling are not built - only "
+                                  "the DEPLOY net" % phase)
+    if depth not in (50, 101):
+        raise ValueError("rfcn_resnet: depth must be 50 or 101")
+    if batch != 1:
+        raise NotImplementedError("rfcn_resnet: batch %d (the Proposal layer takes one image a forward)" % batch)
+    h, wdt = _hw(size)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "ResNet-%d-RFCN"' % depth)
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, h, wdt))
+    w.layer("im_info", "Input", [], ["im_info"], "  input_param { shape { dim: 1 dim: 3 } }")
+    _rn_conv_bn(w, "", "data", wd(64), 7, 3, 2, phase, True, conv_name="conv1", bias=True)
+    w.layer("pool1", "Pooling", ["conv1"], ["pool1"], "  pooling_param { pool: MAX kernel_size: 3 stride: 2 }")
+    feat, res4 = "pool1", ""
+    for stage, count in zip((2, 3, 4, 5), RESNET_BLOCKS[depth]):
+        mid, out = wd(64 << (stage - 2)), wd(256 << (stage - 2))
+        dil = 2 if stage == 5 else 1
+        for bi, letter in enumerate(_resnet_block_names(count, depth > 50 and stage in (3, 4))):
+            tag = "%d%s" % (stage, letter)
+            stride = 2 if bi == 0 and stage in (3, 4) else 1
+            short = feat if bi else _rn_conv_bn(w, tag + "_branch1", feat, out, 1, 0, stride, phase, False)
+            x = _rn_conv_bn(w, tag + "_branch2a", feat, mid, 1, 0, stride, phase, True)
+            x = _rn_conv_bn(w, tag + "_branch2b", x, mid, 3, dil, 1, phase, True, dilation=dil)
+            x = _rn_conv_bn(w, tag + "_branch2c", x, out, 1, 0, 1, phase, False)
+            feat = "res" + tag
+            w.layer(feat, "Eltwise", [short, x], [feat])
+            w.layer(feat + "_relu", "ReLU", [feat], [feat])
+        if stage == 4:
+            res4 = feat
+    a = 3 * len(scales)
+    _dl_conv(w, "rpn_conv/3x3", res4, wd(512), 3, 1, relu="rpn_relu/3x3", std=0.01)
+    _dl_conv(w, "rpn_cls_score", "rpn_conv/3x3", 2 * a, 1, std=0.01)
+    _dl_conv(w, "rpn_bbox_pred", "rpn_conv/3x3", 4 * a, 1, std=0.01)
+    w.layer("rpn_cls_score_reshape", "Reshape", ["rpn_cls_score"], ["rpn_cls_score_reshape"], "  reshape_param { shape { dim: 0 dim: 2 dim: -1 dim: 0 } }")
+    w.layer("rpn_cls_prob", "Softmax", ["rpn_cls_score_reshape"], ["rpn_cls_prob"])
+    w.layer("rpn_cls_prob_reshape", "Reshape", ["rpn_cls_prob"], ["rpn_cls_prob_reshape"],
+            "  reshape_param { shape { dim: 0 dim: %d dim: -1 dim: 0 } }" % (2 * a))
+    bottoms = ["rpn_cls_prob_reshape", "rpn_bbox_pred", "im_info"]
+    if (pre_nms_topn, post_nms_topn, tuple(float(v) for v in scales)) == (6000, 300, (8.0, 16.0, 32.0)):
+        w.layer("proposal", "Python", bottoms, ["rois"], "  python_param {\n    module: 'rpn.proposal_layer'\n    layer: 'ProposalLayer'\n"
+                "    param_str: \"'feat_stride': 16\"\n  }")
+    else:
+        w.layer("proposal", "Proposal", bottoms, ["rois"], "  proposal_param {\n    feat_stride: 16\n%s\n    pre_nms_topn: %d\n    post_nms_topn: %d\n  }"
+                % ("\n".join("    scale: %g" % v for v in scales), pre_nms_topn, post_nms_topn))
+    _dl_conv(w, "conv_new_1", feat, wd(1024), 1, relu="conv_new_1_relu", std=0.01)
+    for name, dim, pooled, ave, top in (("rfcn_cls", classes, "psroipooled_cls_rois", "ave_cls_score_rois", "cls_score"),
+                                        ("rfcn_bbox", 8, "psroipooled_loc_rois", "ave_bbox_pred_rois", "bbox_pred")):
+        _dl_conv(w, name, "conv_new_1", dim * 49, 1, std=0.01)
+        w.layer(pooled, "PSROIPooling", [name, "rois"], [pooled], "  psroi_pooling_param {\n    spatial_scale: 0.0625\n    output_dim: %d\n"
+                "    group_size: 7\n  }" % dim)
+        w.layer(ave, "Pooling", [pooled], [top], "  pooling_param { pool: AVE kernel_size: 7 stride: 7 }")
+    w.layer("cls_prob", "Softmax", ["cls_score"], ["cls_prob"])
     return w.text() if fillers else _strip_fillers(w.text())

@@ -13,13 +13,13 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import proto, ssd
+from . import proto, region, ssd
 
 Shape = Tuple[int, ...]
 
 
 class Layer:
-    __slots__ = ("name", "type", "bottoms", "tops", "msg", "lr_mult", "decay_mult", "loss_weight")
+    __slots__ = ("name", "type", "bottoms", "tops", "msg", "lr_mult", "decay_mult", "loss_weight", "python_alias")
 
     def __init__(self, msg: proto.Msg):
         self.msg = msg
@@ -31,6 +31,11 @@ class Layer:
         self.lr_mult = [float(p.get("lr_mult", 1.0)) for p in params]
         self.decay_mult = [float(p.get("decay_mult", 1.0)) for p in params]
         self.loss_weight = [float(w) for w in msg.getall("loss_weight")]
+        # the published Faster R-CNN / R-FCN deploy files write Proposal as a Python layer (rpn.proposal_layer.ProposalLayer): the same
+        # built-in layer, its parameters in param_str; no module is imported.  Every other Python layer stays a Python layer
+        self.python_alias: bool = region.is_python_proposal(self)
+        if self.python_alias:
+            self.type = "Proposal"
 
     def sub(self, key: str) -> proto.Msg:
         m = self.msg.get(key)
@@ -296,6 +301,9 @@ class NetSpec:
         # top of a DetectionOutput -> that layer (its shape is a capacity: a forward says how many rows it holds)
         self.prior_blobs: Dict[str, Layer] = {}
         self.detection_blobs: Dict[str, Layer] = {}
+        # region stage: blobs whose axis 0 is the ROI axis of a Proposal - its tops and everything downstream that keeps that axis - ->
+        # the Proposal layer whose count says how many of the post_nms_topn rows a forward found (rois fed through an Input are not here)
+        self.roi_blobs: Dict[str, Layer] = {}
 
     @classmethod
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False) -> "NetSpec":
@@ -331,6 +339,7 @@ class NetSpec:
         self.param_shapes = {}
         self.mask_blobs = {}
         self.prior_blobs, self.detection_blobs = {}, {}
+        self.roi_blobs = {}
         self.blob_shapes = shapes      # (filled as the layers are walked: is_depthwise reads a layer's bottom)
         for l in self.layers:
             t = l.type
@@ -348,6 +357,8 @@ class NetSpec:
                     raise NotImplementedError("layer %s: the pooling mask %s (second top of %s) feeds %s (a mask may only be the second "
                                               "bottom of an Upsample)" % (l.name, b, self.mask_blobs[b].name,
                                                                           "the first bottom of an Upsample" if t == "Upsample" else "a layer of type %s" % t))
+            # the ROI axis travels with the rois through the poolings (and with the first bottom through every other layer: below)
+            governs = self.roi_blobs.get(l.bottoms[1]) if t in ("ROIPooling", "PSROIPooling") and len(l.bottoms) > 1 else None
             if t == "Convolution":
                 p = l.sub("convolution_param")
                 kh, kw, sh, sw, ph, pw = layer_geometry(l)
@@ -556,6 +567,21 @@ class NetSpec:
                     raise ValueError("layer %s: DetectionOutput has one top" % l.name)
                 shapes[l.tops[0]] = ssd.detection_shapes(l, bots)[0]
                 self.detection_blobs[l.tops[0]] = l
+            elif t == "Proposal":
+                for tp, shp in zip(l.tops, region.proposal_shapes(l, bots)):
+                    shapes[tp] = shp
+                    self.roi_blobs[tp] = l
+            elif t == "ROIPooling":
+                shapes[l.tops[0]] = region.roi_pool_shape(l, bots)
+                if governs is not None:
+                    self.roi_blobs[l.tops[0]] = governs
+            elif t == "PSROIPooling":
+                shapes[l.tops[0]] = region.psroi_pool_shape(l, bots)
+                if governs is not None:
+                    self.roi_blobs[l.tops[0]] = governs
+            elif t in region.TRAINING_TYPES:
+                raise NotImplementedError("layer type %r (layer %s): training the region stage (AnchorTarget, ProposalTarget and a backward "
+                                          "pass through the ROI poolings) is not built: deploy nets only" % (t, l.name))
             elif t in ssd.TRAINING_TYPES:
                 raise NotImplementedError("layer type %r (layer %s): SSD's training and evaluation layers (MultiBoxLoss, AnnotatedData, "
                                           "DetectionEvaluate, VideoData) are not built: deploy nets only" % (t, l.name))
@@ -568,6 +594,12 @@ class NetSpec:
                 shapes[l.tops[0]] = bots[0]
             else:
                 raise NotImplementedError("layer type %r (layer %s)" % (t, l.name))
+        for l in self.layers:      # downstream of the poolings: a top that keeps its first bottom's axis 0 keeps its count
+            src = self.roi_blobs.get(l.bottoms[0]) if l.bottoms and l.type not in region.REGION_TYPES else None
+            if src is not None:
+                for tp in l.tops:
+                    if len(shapes.get(tp, ())) >= 1 and shapes[tp][0] == shapes[l.bottoms[0]][0]:
+                        self.roi_blobs[tp] = src
         self.blob_shapes = shapes
         return shapes
 

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
-from . import ssd
+from . import region, ssd
 from .netspec import Layer, NetSpec, as_nchw
 
 F32 = np.float32
@@ -77,6 +77,10 @@ class BlobPlan:
     permutes: Dict[str, str] = field(default_factory=dict)
     gathers: Dict[str, Tuple[str, List[Tuple[str, str, int]]]] = field(default_factory=dict)
     detections: Dict[str, int] = field(default_factory=dict)
+    # region stage.  pair_softmax: Softmax layer of an RPN chain Reshape -> Softmax -> Reshape -> (blob the one launch reads, blob it
+    # writes, A).  rpn_views: a middle blob of such a chain (it owns nothing) -> (the neighbour whose NCHW array, reshaped, it is)
+    pair_softmax: Dict[str, Tuple[str, str, int]] = field(default_factory=dict)
+    rpn_views: Dict[str, str] = field(default_factory=dict)
 
 
 def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequence[str], outputs: Sequence[str],
@@ -91,6 +95,30 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     heads = [l for l in spec.layers if l.type in ssd.HEAD_TYPES]
     if f16 and heads:
         raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (heads[0].type, heads[0].name))
+    stage = [l for l in spec.layers if l.type in region.REGION_TYPES]
+    if f16 and stage:
+        raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (stage[0].type, stage[0].name))
+    # the RPN's two-class softmax: Reshape(0, 2, -1, 0) -> Softmax(axis 1) -> Reshape(0, 2A, -1, 0).  In Caffe's memory order the middle
+    # blobs pair channel a with channel a + A at every pixel; on the NHWC device that is no view, so the chain is ONE launch that reads the
+    # first Reshape's bottom and writes the second one's top, and the two middle blobs own nothing
+    pair_softmax: Dict[str, Tuple[str, str, int]] = {}
+    rpn_views: Dict[str, str] = {}
+    chain_reshapes: Set[str] = set()
+    for l in spec.layers:
+        if l.type != "Softmax" or len(l.bottoms) != 1 or int(l.sub("softmax_param").get("axis", 1)) != 1 or f16:
+            continue
+        r1, r2 = producers.get(l.bottoms[0], []), consumers.get(l.tops[0], [])
+        only = [q.name for q in consumers.get(l.bottoms[0], []) if q is not l]
+        if len(r1) != 1 or r1[0].type != "Reshape" or len(r2) != 1 or r2[0].type != "Reshape" or only or l.tops[0] in outputs or l.bottoms[0] in outputs:
+            continue
+        src, dst = r1[0].bottoms[0], r2[0].tops[0]
+        a = region.rpn_softmax_anchors(shapes[src], shapes[l.bottoms[0]], shapes[dst])
+        if a is None or len(producers.get(l.tops[0], [])) != 1:
+            continue
+        pair_softmax[l.name] = (src, dst, a)
+        rpn_views[l.bottoms[0]] = src
+        rpn_views[l.tops[0]] = dst
+        chain_reshapes.update((r1[0].name, r2[0].name))
     # the top of a Permute(0, 2, 3, 1) owns nothing: its bottom's NHWC buffer, minus the pad channels, is Caffe's memory order of it
     permutes: Dict[str, str] = {}
     for l in spec.layers:
@@ -108,7 +136,7 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
     detections: Dict[str, int] = {name: int(shapes[name][2]) for name in spec.detection_blobs}
     # a pooling mask is no activation blob: it is the pooling's argmax buffer, which the engine allocates (no view, no buffer here)
     shapes = {name: ((detections[name] * 7 + 4,) if name in detections else shp) for name, shp in shapes.items()
-              if name not in spec.mask_blobs and name not in permutes}
+              if name not in spec.mask_blobs and name not in permutes and name not in rpn_views}
     data_tops = set(inputs)
     # f16 mode: everything is stored as halves except what leaves the net towards the f32 decode kernel - the output
     # blobs and the input / output of a Sigmoid head (written by the convolution epilogue in f32)
@@ -169,11 +197,15 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             else:
                 raise NotImplementedError("layer %s: Flatten of the %s blob %s (Caffe's C x H x W order of a row is not the device's: Flatten "
                                           "the top of a Permute(0, 2, 3, 1), an (N, P, C) blob or a blob with H = W = 1)" % (l.name, tuple(bshape), bot))
+        elif l.type == "Reshape" and l.name in chain_reshapes:
+            pass      # the RPN softmax chain: its Softmax layer launches for all three
         elif l.type == "Reshape":
             top, bot = l.tops[0], l.bottoms[0]
             a, b = spec.blob_shapes[bot], spec.blob_shapes[top]
             if not ((len(a), len(b)) in ((2, 3), (3, 2)) and a[0] == b[0]) or bot in data_tops:
-                raise NotImplementedError("layer %s: Reshape of %s to %s (only between (N, K) and (N, P, C) with P * C == K)" % (l.name, tuple(a), tuple(b)))
+                raise NotImplementedError("layer %s: Reshape of %s to %s (only between (N, K) and (N, P, C) with P * C == K, or the RPN's chain "
+                                          "Reshape(0, 2, -1, 0) -> Softmax -> Reshape(0, 2A, -1, 0) whose middle blobs nothing else reads)"
+                                          % (l.name, tuple(a), tuple(b)))
             alias[top] = (bot, 0)
         if l.type == "Concat" and l.bottoms and all(
                 len(producers.get(b, [])) == 1 and producers[b][0].name in gathers and [q.name for q in consumers.get(b, [])] == [l.name]
@@ -282,7 +314,7 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
                             upload_shift.get(name, 0.0), lazy_shift.get(name, 0.0), name in rows)
              for name, shp in shapes.items()}
     return BlobPlan(views, root_bytes, esize, alias, shift, copy_concats, copy_slices, half_inputs, rows, producers, consumers,
-                    permutes, gathers, detections)
+                    permutes, gathers, detections, pair_softmax, rpn_views)
 
 
 # ---------------------------------------------------------------------- parameters

@@ -1021,6 +1021,67 @@ size_t fcn_detection_output_workspace_bytes(const fcn_detout_params* h_params);
 int  fcn_detection_output_f32(const float* loc, const float* conf, const float* priors, const fcn_detout_params* h_params, float* out_rows,
                               int32_t* out_count, void* d_workspace, size_t workspace_bytes, fcn_stream_t s);
 
+/* ---- Region stage of the two-stage detectors (Faster R-CNN / R-FCN: the RPN's two-class softmax, Proposal, ROIPooling, PSROIPooling;
+ *      csrc/region.hip).  Float32, inference.  The common contract of the SSD head above holds: one writer lane per output element, no
+ *      atomics at all, a second launch on the same inputs gives the same bytes, every refusal is made on the host before the first HIP
+ *      call, all launches are capturable, the file is compiled without fused multiply-add contraction.  Blobs are NHWC: a pixel is
+ *      `cstride` floats of which the blob's channels start at `coffset`; channels C .. r4(C) - 1 of every top are written as zeros. ---- */
+/* The RPN softmax, Reshape(0, 2, -1, 0) -> Softmax(axis 1) -> Reshape(0, 2A, -1, 0) of an (N, 2A, H, W) blob, in one launch: at every
+ * pixel and for every a < A the pair (x[a], x[a + A]) is normalised: m = max of the two, e = exp(x - m), y = e / (e_a + e_{a+A}).
+ * One lane per (pixel, a).  y may be x. */
+int  fcn_pair_softmax_f32(const float* x, float* y, int pixels, int A, int x_cstride, int x_coffset, int y_cstride, int y_coffset, fcn_stream_t s);
+/* Proposal (py-faster-rcnn's rpn/proposal_layer.py at TEST settings), one image.  scores: H x W pixels of 2A channels (a < A background,
+ * A + a foreground), deltas: H x W pixels of 4A channels (4a .. 4a + 3: dx, dy, dw, dh of anchor a), im_info: 3 floats on the device
+ * (height, width, scale).  Candidate i = (y W + x) A + a is anchors[a] shifted by (x, y) * feat_stride.  The order of steps is the contract:
+ *   1. decode: w = x2 - x1 + 1, cx = x1 + 0.5 w, pcx = dx w + cx, pw = exp(dw) w, box (pcx - 0.5 pw, .., pcx + 0.5 pw, ..); y likewise.
+ *   2. clip x to [0, im_w - 1], y to [0, im_h - 1].
+ *   3. a candidate stays iff x2 - x1 + 1 >= min_size * im_scale and the same for y (a NaN score or corner is no candidate).
+ *   4. order by foreground score descending, TIES BY CANDIDATE INDEX ASCENDING (numpy's argsort()[::-1] leaves them unspecified; this order
+ *      is fixed here); the first pre_nms_topn go on.
+ *   5. greedy NMS in that order with the +1 extents: area (x2 - x1 + 1)(y2 - y1 + 1), intersection extents max(0, min(x2) - max(x1) + 1),
+ *      a later box is suppressed iff inter / (a_i + a_j - inter) > nms_thresh.
+ *   6. the first post_nms_topn survivors are the rows [0, x1, y1, x2, y2] of rois (and their scores the rows of top_scores, which may be
+ *      NULL); their number goes to *out_count; rows at and past the count, and the pad channels 5 .. 7 (1 .. 3), are written as ZEROS on
+ *      every call: all post_nms_topn rows are defined.
+ * Five launches: decode (a key per candidate: score bits, ~index, or 0 for a dropped one - nothing is compacted), rank (a workgroup per
+ * 256 candidates and eighth of the keys counts the keys above its own through LDS tiles), place (the eight counts summed are the place
+ * in the order), the suppression bit matrix (a wave per 64 x 64 block), one wave that sweeps it a word at a time and writes the rows.  More than FCN_PROPOSAL_MAX_ANCHORS anchors, H * W * A above FCN_PROPOSAL_MAX_CANDIDATES, min(pre_nms_topn, H * W * A)
+ * or post_nms_topn above FCN_PROPOSAL_MAX_PRE_NMS are FCN_E_UNSUPPORTED; a workspace below fcn_proposal_workspace_bytes() FCN_E_ARG, off
+ * 16 bytes FCN_E_ALIGN.  The size query returns 0 for parameters the launch would refuse. */
+#define FCN_PROPOSAL_MAX_ANCHORS 32
+#define FCN_PROPOSAL_MAX_CANDIDATES 65536
+#define FCN_PROPOSAL_MAX_PRE_NMS 6144
+typedef struct fcn_proposal_params {
+    int32_t H, W, A, feat_stride;
+    int32_t pre_nms_topn, post_nms_topn;
+    float min_size, nms_thresh;
+    int32_t score_cstride, score_coffset;        /* floats per pixel of the bottoms, first channel inside a pixel     */
+    int32_t delta_cstride, delta_coffset;
+    int32_t rois_cstride, rois_coffset;          /* rois_cstride >= rois_coffset + 8                                  */
+    int32_t top_score_cstride, top_score_coffset;/* 0, 0 without a scores top; else cstride >= coffset + 4            */
+    float anchors[4 * FCN_PROPOSAL_MAX_ANCHORS]; /* x1, y1, x2, y2 of each base anchor                                */
+} fcn_proposal_params;
+size_t fcn_proposal_workspace_bytes(const fcn_proposal_params* h_params);
+int  fcn_proposal_f32(const float* scores, const float* deltas, const float* im_info, const fcn_proposal_params* h_params, float* rois,
+                      float* top_scores, int32_t* out_count, void* d_workspace, size_t workspace_bytes, fcn_stream_t s);
+/* ROIPooling.  x: N images of H x W pixels; rois: R rows [b, x1, y1, x2, y2] (row stride rois_cstride); y: R images of pooled_h x pooled_w
+ * pixels of C channels.  Per roi: start = round(x * spatial_scale) (halves away from zero), roi_w = max(end_w - start_w + 1, 1),
+ * bin_w = (float)roi_w / pooled_w; bin (ph, pw) covers rows floor(ph bin_h) + start_h .. ceil((ph + 1) bin_h) + start_h (exclusive), both
+ * clipped to [0, H], columns likewise; the value is the maximum over the bin of image b (the first maximum in raster order; a NaN never
+ * wins), 0 for an empty bin or an image index outside [0, N).  argmax (NULL, or R * pooled_h * pooled_w * C dense int32 in the top's
+ * order): h * W + w of the maximum, -1 for an empty bin.  One wave per (roi, bin), lanes over channels. */
+int  fcn_roi_pool_fwd_f32(const float* x, const float* rois, float* y, int32_t* argmax, int N, int H, int W, int C, int x_cstride, int x_coffset,
+                          int R, int rois_cstride, int rois_coffset, int pooled_h, int pooled_w, float spatial_scale, int y_cstride, int y_coffset,
+                          fcn_stream_t s);
+/* PSROIPooling (R-FCN).  x has C = output_dim * group_size^2 channels (anything else is FCN_E_ARG); y: R images of group_size x group_size
+ * pixels of output_dim channels.  start_w = round(x1) * spatial_scale, end_w = (round(x2) + 1) * spatial_scale, roi_w = max(end_w - start_w,
+ * 0.1), bin_w = roi_w / group_size, wstart = floor(pw bin_w + start_w), wend = ceil((pw + 1) bin_w + start_w), both clipped to [0, W]; rows
+ * likewise.  Top channel ct of bin (ph, pw) is the mean of input channel (ct * group_size + ph) * group_size + pw over the bin: the sum
+ * in raster order divided by the bin's pixel count; 0 for an empty bin or an image index outside [0, N). */
+int  fcn_psroi_pool_fwd_f32(const float* x, const float* rois, float* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int R,
+                            int rois_cstride, int rois_coffset, int output_dim, int group_size, float spatial_scale, int y_cstride, int y_coffset,
+                            fcn_stream_t s);
+
 /* ---- data-parallel exchange (new capability; the reference trains with --gpu=0 only, train/train.sh:26):
  *      sum of the flat gradient buffer over all ranks with RCCL on the caller's stream ---- */
 int  fcn_comm_unique_id(char* h_id128);                                    /* rank 0: ncclGetUniqueId (128 bytes)   */
