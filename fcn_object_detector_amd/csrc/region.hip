@@ -128,15 +128,19 @@ __global__ __launch_bounds__(256) void prop_decode_kernel(const float* __restric
     const float cx = ax1 + 0.5f * w, cy = ay1 + 0.5f * h;
     const float pcx = dl[0] * w + cx, pcy = dl[1] * h + cy;
     const float pw = expf(dl[2]) * w, ph = expf(dl[3]) * h;
+    const float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
     V4 b;
-    b.x = fminf(fmaxf(pcx - 0.5f * pw, 0.f), im_w - 1.f);
-    b.y = fminf(fmaxf(pcy - 0.5f * ph, 0.f), im_h - 1.f);
-    b.z = fminf(fmaxf(pcx + 0.5f * pw, 0.f), im_w - 1.f);
-    b.w = fminf(fmaxf(pcy + 0.5f * ph, 0.f), im_h - 1.f);
+    b.x = fminf(fmaxf(x1, 0.f), im_w - 1.f);
+    b.y = fminf(fmaxf(y1, 0.f), im_h - 1.f);
+    b.z = fminf(fmaxf(x2, 0.f), im_w - 1.f);
+    b.w = fminf(fmaxf(y2, 0.f), im_h - 1.f);
     boxes[t] = b;
     const float sc = scores[(size_t)pix * d.p.score_cstride + d.p.score_coffset + A + a];
     const float ms = d.p.min_size * im_scale;
-    const bool ok = (b.z - b.x + 1.f >= ms) && (b.w - b.y + 1.f >= ms) && sc == sc;      // (a NaN corner fails the comparisons)
+    // fmaxf / fminf return their other operand for a NaN: the clip turns a NaN corner into 0, a box one pixel wide that a min_size of
+    // 1 or less lets through.  So the corners are asked before the clip.
+    const bool number = x1 == x1 && y1 == y1 && x2 == x2 && y2 == y2 && sc == sc;
+    const bool ok = number && (b.z - b.x + 1.f >= ms) && (b.w - b.y + 1.f >= ms);
     keys[t] = ok ? (((u64)ordered_bits(sc) << 32) | (u64)(0xFFFFFFFFu - (unsigned)t)) : 0ull;
 }
 

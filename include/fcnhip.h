@@ -994,7 +994,8 @@ int  fcn_normalize_fwd_f32(const float* x, float* y, const float* scale, int pix
  *   1. decode every prior once per image.  FCN_CODE_CENTER_SIZE: cx = v0 l0 pw + pcx, cy = v1 l1 ph + pcy, w = exp(v2 l2) pw,
  *      h = exp(v3 l3) ph, corners c -+ size / 2; FCN_CODE_CORNER: corner_i = prior_i + v_i l_i; v = 1 under variance_encoded.  No clipping.
  *   2. per image and class c != background: the priors with conf > conf_threshold (strictly), by score descending, ties by prior index
- *      ascending, cut to top_k when top_k > -1.
+ *      ascending, cut to top_k when top_k > -1.  Scores and threshold are any floats (logits, Caffe's default threshold -FLT_MAX: every
+ *      prior of a class goes in); -0 and +0 are one score, a NaN score is above no threshold.
  *   3. greedy NMS in that order: a candidate is kept iff its Jaccard overlap with every box kept so far is <= nms_threshold.  The overlap
  *      is 0 when the boxes do not intersect, else inter / (a1 + a2 - inter); a box with xmax < xmin or ymax < ymin has area 0; no +1.
  *   4. per image, when keep_top_k > -1 and more survive: the keep_top_k highest scores; ties by label ascending, then prior index
@@ -1035,11 +1036,14 @@ int  fcn_pair_softmax_f32(const float* x, float* y, int pixels, int A, int x_cst
  * (height, width, scale).  Candidate i = (y W + x) A + a is anchors[a] shifted by (x, y) * feat_stride.  The order of steps is the contract:
  *   1. decode: w = x2 - x1 + 1, cx = x1 + 0.5 w, pcx = dx w + cx, pw = exp(dw) w, box (pcx - 0.5 pw, .., pcx + 0.5 pw, ..); y likewise.
  *   2. clip x to [0, im_w - 1], y to [0, im_h - 1].
- *   3. a candidate stays iff x2 - x1 + 1 >= min_size * im_scale and the same for y (a NaN score or corner is no candidate).
+ *   3. a candidate stays iff x2 - x1 + 1 >= min_size * im_scale and the same for y (a NaN score or corner is no candidate).  The corners
+ *      are asked for a NaN as step 1 leaves them, before the clip, so the rule holds whatever min_size is, 0 included.  Every other float
+ *      is a score: the infinities and the denormals order as floats do, -0 and +0 are one score.
  *   4. order by foreground score descending, TIES BY CANDIDATE INDEX ASCENDING (numpy's argsort()[::-1] leaves them unspecified; this order
  *      is fixed here); the first pre_nms_topn go on.
  *   5. greedy NMS in that order with the +1 extents: area (x2 - x1 + 1)(y2 - y1 + 1), intersection extents max(0, min(x2) - max(x1) + 1),
- *      a later box is suppressed iff inter / (a_i + a_j - inter) > nms_thresh.
+ *      a later box is suppressed iff inter / (a_i + a_j - inter) > nms_thresh.  nms_thresh is any float but a NaN: at 1 or above nothing is
+ *      suppressed, below 0 every later box is, boxes that do not meet included (their overlap is 0).
  *   6. the first post_nms_topn survivors are the rows [0, x1, y1, x2, y2] of rois (and their scores the rows of top_scores, which may be
  *      NULL); their number goes to *out_count; rows at and past the count, and the pad channels 5 .. 7 (1 .. 3), are written as ZEROS on
  *      every call: all post_nms_topn rows are defined.

@@ -5,7 +5,8 @@ softmax.  Blobs are NCHW.
 Like tests/ref_ssd64.py every function that decides something also returns the MARGIN of its decisions:
   proposal   the smallest gap between two neighbouring, distinct scores of the order (the pre_nms_topN cut is the gap between two such
              neighbours), the smallest |overlap - nms_thresh| over every comparison the greedy NMS makes, and the smallest distance of a
-             box extent from the min_size bound;
+             box extent from the min_size bound (a candidate with a NaN score or a NaN corner is no candidate and has no extent to
+             measure);
   poolings   the smallest distance of an argument of round / floor / ceil from a breakpoint of that function.  An argument that float32
              arithmetic (IEEE, no contraction) computes to the very same value as float64 is decided alike in both formats whatever its
              distance and is left out: 0.0625 * 32, 1.25 * 4 and (1 / 3) * 3 are such values.
@@ -56,10 +57,21 @@ def overlaps(b, others):
     return inter / (area(b) + area(o) - inter)
 
 
-def proposal(scores, deltas, im_info, base_anchors, feat_stride=16, pre_nms_topn=6000, post_nms_topn=300, nms_thresh=0.7, min_size=16):
+def proposal(scores, deltas, im_info, base_anchors, feat_stride=16, pre_nms_topn=6000, post_nms_topn=300, nms_thresh=0.7, min_size=16,
+             score_gaps=True):
     """scores (1, 2A, H, W), deltas (1, 4A, H, W), im_info (1, 3) or (3,) -> dict with
     rois (post_nms_topn, 5) float64 (rows at and past `count` are zeros), scores (post_nms_topn, 1), count, index (the candidates of the
-    rows, in order), suppressed (boxes the NMS dropped before it stopped), filtered (candidates the size filter dropped), margin."""
+    rows, in order), suppressed (boxes the NMS dropped before it stopped), filtered (candidates the size filter dropped), margin; and for
+    the tests that say which path a case walks: order (the candidates that went into the NMS, place by place), places (the place of each
+    row's candidate in that order), suppressors ((place of a dropped box, place of the kept box that dropped it) for each dropped box),
+    raw (the boxes before the clip), boxes (after it) and alive (the candidates that pass step 3).
+
+    A NaN is no number to compare: a candidate whose score is a NaN, or whose box has a NaN corner (a NaN delta), is not alive - it is
+    counted in `filtered` - and the min_size margin is taken over the other candidates only.
+
+    score_gaps=False leaves the gaps between neighbouring scores out of the margin.  It is for inputs whose scores are the layer's own
+    bottom and are compared as they are, bit for bit, with no arithmetic in front of the comparison that could round: a case that is about
+    the spacing of the floats themselves (denormals beside the two zeros) then keeps a margin over what IS computed - extents and overlaps."""
     scores, deltas = np.asarray(scores, F64), np.asarray(deltas, F64)
     im = np.asarray(im_info, F64).reshape(-1)
     assert scores.shape[0] == 1 and deltas.shape[0] == 1
@@ -69,23 +81,28 @@ def proposal(scores, deltas, im_info, base_anchors, feat_stride=16, pre_nms_topn
     assert c2 == 2 * a and deltas.shape == (1, 4 * a, h, w)
     fg = scores[0, a:].transpose(1, 2, 0).reshape(-1)                      # (y, x, a) order
     dl = deltas[0].reshape(a, 4, h, w).transpose(2, 3, 0, 1).reshape(-1, 4)
-    boxes = decode(all_anchors(base, h, w, feat_stride), dl)
+    with np.errstate(invalid="ignore", over="ignore"):
+        raw = decode(all_anchors(base, h, w, feat_stride), dl)
+    number = ~(np.isnan(fg) | np.isnan(raw).any(axis=1))
+    boxes = raw.copy()
     boxes[:, 0::2] = np.clip(boxes[:, 0::2], 0.0, im[1] - 1)
     boxes[:, 1::2] = np.clip(boxes[:, 1::2], 0.0, im[0] - 1)
     bound = min_size * im[2]
     ext = np.stack([boxes[:, 2] - boxes[:, 0] + 1, boxes[:, 3] - boxes[:, 1] + 1], axis=1)
-    margin = float(np.min(np.abs(ext - bound)))
-    alive = np.nonzero((ext[:, 0] >= bound) & (ext[:, 1] >= bound))[0]
+    margin = float(np.min(np.abs(ext[number] - bound))) if number.any() else np.inf
+    with np.errstate(invalid="ignore"):
+        alive = np.nonzero(number & (ext[:, 0] >= bound) & (ext[:, 1] >= bound))[0]
     order = alive[np.lexsort((alive, -fg[alive]))]                        # score descending, ties by candidate index ascending
     # every neighbouring pair of the order up to and across the cut
     upto = min(len(order), pre_nms_topn + 1)
-    gaps = -np.diff(fg[order[:upto]])
+    with np.errstate(invalid="ignore"):
+        gaps = -np.diff(fg[order[:upto]])                                 # (two infinities of one sign: a NaN, which is no gap)
     gaps = gaps[gaps > 0]
-    if gaps.size:
+    if gaps.size and score_gaps:
         margin = min(margin, float(gaps.min()))
     order = order[:pre_nms_topn]
-    kept, suppressed = [], 0
-    for i in order:
+    kept, places, suppressors = [], [], []
+    for place, i in enumerate(order):
         if len(kept) == post_nms_topn:
             break
         if kept:
@@ -94,15 +111,16 @@ def proposal(scores, deltas, im_info, base_anchors, feat_stride=16, pre_nms_topn
             seen = ov if over.size == 0 else ov[:over[0] + 1]          # the greedy loop stops at the first box that suppresses
             margin = min(margin, float(np.min(np.abs(seen - nms_thresh))))
             if over.size:
-                suppressed += 1
+                suppressors.append((place, places[over[0]]))
                 continue
         kept.append(int(i))
+        places.append(place)
     rois = np.zeros((post_nms_topn, 5), F64)
     sc = np.zeros((post_nms_topn, 1), F64)
     rois[:len(kept), 1:] = boxes[kept]
     sc[:len(kept), 0] = fg[kept]
-    return dict(rois=rois, scores=sc, count=len(kept), index=kept, suppressed=suppressed, filtered=int(fg.size - alive.size), margin=margin,
-                boxes=boxes)
+    return dict(rois=rois, scores=sc, count=len(kept), index=kept, suppressed=len(suppressors), filtered=int(fg.size - alive.size),
+                margin=margin, boxes=boxes, raw=raw, alive=alive, order=order, places=places, suppressors=suppressors)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- poolings

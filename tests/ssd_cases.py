@@ -27,7 +27,23 @@ CASES = {
                              high=1100, spread=True, seed=39),
     "ssd300_shape":     dict(P=8732, classes=21, N=1, code=R.CENTER_SIZE, var_enc=False, top_k=400, keep_top_k=200, thr=0.01, nms=0.45, bg=0, high=30,
                              seed=8),
+    # ---- signed scores, no background, more than 256 classes (tests/test_ssd_ref.py asserts what each of them reaches)
+    # scores as logits: 100 per (image, class) above a threshold of -4, 0.05 apart in -3.95 .. 0.5 (at most 30 rows of an image can be positive), every other one below it; the ties
+    # of p300_center and one more lie among negative scores
+    "logits":           dict(P=300, classes=4, code=R.CENTER_SIZE, var_enc=False, top_k=64, keep_top_k=40, thr=-4.0, nms=0.45, bg=0, high=90,
+                             ties=True, logits=True, seed=9),
+    # Caffe's default confidence_threshold: every prior of every class is a candidate; scores 0.01 apart, the best nine positive, then
+    # the two zeros on two priors (one score: the lower prior index first), then negative ones
+    "no_threshold":     dict(P=600, classes=3, code=R.CENTER_SIZE, var_enc=False, top_k=400, keep_top_k=200, thr=-float(np.finfo(np.float32).max),
+                             nms=0.45, bg=0, high=0, ladder=590, seed=10),
+    "no_background":    dict(P=70, classes=3, code=R.CORNER, var_enc=False, top_k=16, keep_top_k=-1, thr=0.25, nms=0.45, bg=-1, high=40, seed=11),
+    # the per-image scan over the classes' counts runs two chunks of 256; image 1 has survivors in the second chunk only
+    "c300":             dict(P=12, classes=300, code=R.CENTER_SIZE, var_enc=False, top_k=-1, keep_top_k=200, thr=0.25, nms=0.45, bg=150, high=2,
+                             first_class={1: 256}, seed=12),
 }
+# cases that run a second time with `capacity` exactly what the images can yield (N * keep_top_k here) and the rows ending on the last byte
+# in front of the red zone
+EXACT_CAPACITY = ("p300_center", "p70_nothing")
 
 
 def make(name):
@@ -52,13 +68,28 @@ def make(name):
         pr = priors[0].reshape(2, p, 4)
         pr[:, smothered, :] = pr[:, smothered[0], :][:, None, :]
     thr = c["thr"]
-    conf = rng.uniform(0.0, thr * 0.8, (n, p, nc))
+    if c.get("ladder"):
+        conf = np.empty((n, p, nc))
+        for i in range(n):
+            for cl in range(nc):
+                step = rng.permutation(p)
+                conf[i, :, cl] = (step - c["ladder"]) * 0.01
+                conf[i, step == c["ladder"] - 1, cl] = -0.0
+    elif c.get("logits"):
+        conf = thr - 0.05 - np.abs(rng.normal(0.0, 3.0, (n, p, nc)))
+    else:
+        conf = rng.uniform(0.0, thr * 0.8, (n, p, nc))
     for i in range(n):
         if i in c.get("empty", ()):
             continue
         for cl in range(nc):
+            if cl < c.get("first_class", {}).get(i, 0):
+                continue
             at = rng.choice(p, min(c["high"], p), replace=False)
-            conf[i, at, cl] = rng.uniform(thr + 0.05, 0.99, at.size)
+            if c.get("logits"):
+                conf[i, at, cl] = thr + 0.05 * (1 + rng.permutation(at.size))
+            else:
+                conf[i, at, cl] = rng.uniform(thr + 0.05, 0.99, at.size)
             if c.get("smother") == cl and at.size:
                 # every candidate of this class decodes to (nearly) the best one's box: the same priors in both images (the priors are
                 # shared), the first of them with the best score, all on its prior and its loc
@@ -71,6 +102,8 @@ def make(name):
             if c.get("ties") and at.size > 20:
                 srt = at[np.argsort(-conf[i, at, cl])]
                 conf[i, srt[3], cl] = conf[i, srt[2], cl]                                  # a tie inside the kept range
+                if c.get("logits"):
+                    conf[i, srt[41], cl] = conf[i, srt[40], cl]                            # ... and one between two negative scores
                 if c["top_k"] > 1:
                     conf[i, srt[c["top_k"]], cl] = conf[i, srt[c["top_k"] - 1], cl]          # a tie across the top_k cut
         if c.get("ties") and nc - (1 if c["bg"] >= 0 else 0) >= 2:

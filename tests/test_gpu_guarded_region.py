@@ -4,7 +4,9 @@ Proposal is held to the float64 reference's count, order and batch column exactl
 extent: a corner passes through about six roundings and an exp, on boxes the cases keep below twice the image before they are clipped.
 ROIPooling is a maximum of inputs and is held to equality, argmax included; PSROIPooling to the allowance of an n-term float32 sum with n
 the largest bin, as Normalize's sum is held; the pair softmax to the bound tests/test_gpu_guarded.py uses for the channel softmax.  All
-on inputs whose decision margins tests/test_region_ref.py asserts without a GPU.  Every case is launched twice on the same buffers."""
+on inputs whose decision margins tests/test_region_ref.py asserts without a GPU - as it asserts which path each Proposal case walks (the
+upper half of the sweep's suppressed set, the capacity limits, signed, infinite and NaN scores, an image that is not the map's extent).
+Every case is launched twice on the same buffers."""
 import ctypes as C
 
 import numpy as np
@@ -59,13 +61,17 @@ def proposal_params(c, base, score_cs, score_co, delta_cs, delta_co, rois_cs, ro
     return par
 
 
-@pytest.mark.parametrize("name", list(RC.PROPOSALS))
-def test_proposal(g, name):
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def run_proposal(g, name, with_scores=True, workspace=None):
+    """One case on guard-banded, poisoned buffers of its own, launched twice, held to its reference; `workspace` (a guarded buffer and its
+    size) is used as it is, whatever an earlier run left in it, else the case gets a fresh, poisoned one of exactly the size it asks for."""
     lib = L.load()
     c, base, scores, deltas, im_info, ref = RC.proposal_reference(name)
     assert ref["margin"] >= RC.MARGIN      # (tests/test_region_ref.py asserts the same without a GPU)
     a, post = len(base), c["post"]
-    with_scores = name != "post_cut"       # (one case without the optional second top)
     s_cs, s_co, d_cs, d_co = 2 * a + 6, 2, 4 * a + 4, 4
     r_cs, r_co = 12, 4
     t_cs, t_co = (8, 4) if with_scores else (0, 0)
@@ -74,10 +80,12 @@ def test_proposal(g, name):
     assert nbytes > 0
     sd, dd = g.put(poisoned_nhwc(scores, s_cs, s_co), name="scores"), g.put(poisoned_nhwc(deltas, d_cs, d_co), name="deltas")
     imd = g.put(im_info, at_end=True, name="im_info")
-    rd, cd, ws = g.put(poisoned((post, r_cs)), name="rois"), g.put(poisoned(1), at_end=True, name="count"), g.put(nbytes, name="workspace")
+    rd, cd = g.put(poisoned((post, r_cs)), name="rois"), g.put(poisoned(1), at_end=True, name="count")
+    ws, ws_bytes = workspace or (g.put(nbytes, name="workspace"), nbytes)
+    assert ws_bytes >= nbytes
     td = g.put(poisoned((post, t_cs)), name="top scores") if with_scores else None
     rows, top, cnt = launched_twice(
-        lambda: L.call("fcn_proposal_f32", sd.ptr, dd.ptr, imd.ptr, C.byref(par), rd.ptr, td.ptr if td else None, cd.ptr, ws.ptr, nbytes, None),
+        lambda: L.call("fcn_proposal_f32", sd.ptr, dd.ptr, imd.ptr, C.byref(par), rd.ptr, td.ptr if td else None, cd.ptr, ws.ptr, ws_bytes, None),
         lambda: (rd.read((post, r_cs)), td.read((post, t_cs)) if td else np.zeros(1, np.float32), cd.read((1,), np.int32)))
     k = int(cnt[0])
     print("PROPOSAL %s count %d (reference %d) margin %.3g" % (name, k, ref["count"], ref["margin"]))
@@ -89,14 +97,45 @@ def test_proposal(g, name):
     if with_scores:
         ts = top[:, t_co:t_co + 4]
         assert np.all(is_poison(top[:, :t_co])) and np.all(ts[:, 1:] == 0) and np.all(ts[k:] == 0)
-        assert np.array_equal(ts[:k, 0], ref["scores"][:k, 0].astype(np.float32)), "the rows' scores, hence their order"
+        # bit for bit (a -0.0 is not a +0.0 here, an infinity is itself): the rows' scores, hence their order
+        assert np.array_equal(bits(ts[:k, 0]), bits(ref["scores"][:k, 0])), "the rows' scores, hence their order"
+    if k == 0:
+        return
     limit = 32 * float(np.spacing(np.float32(max(im_info[0, 0], im_info[0, 1]))))
     err = float(np.max(np.abs(got[:k, 1:5].astype(np.float64) - ref["rois"][:k, 1:])))
     print("PROPOSAL %s worst |error| %.3g of %.3g" % (name, err, limit))
     assert err <= limit
     # the order, read off the boxes as well: every row is nearer to its own reference row than to any other
-    far = np.abs(got[:k, None, 1:5].astype(np.float64) - ref["rois"][None, :k, 1:]).max(axis=2)
-    assert np.array_equal(np.argmin(far, axis=1), np.arange(k))
+    for lo in range(0, k, 512):
+        hi = min(lo + 512, k)
+        far = np.abs(got[lo:hi, None, 1:5].astype(np.float64) - ref["rois"][None, :k, 1:]).max(axis=2)
+        assert np.array_equal(np.argmin(far, axis=1), np.arange(lo, hi))
+
+
+@pytest.mark.parametrize("name", list(RC.PROPOSALS))
+def test_proposal(g, name):
+    run_proposal(g, name, with_scores=name != "post_cut")      # (one case without the optional second top)
+
+
+@pytest.mark.parametrize("name", ["deep_sweep", "signed_scores"])
+def test_proposal_without_the_scores_top(g, name):
+    """top_scores NULL: the order of the rows is read off the boxes alone."""
+    run_proposal(g, name, with_scores=False)
+
+
+@pytest.mark.parametrize("big_first", [True, False])
+def test_proposal_on_a_stale_workspace(g, big_first):
+    """One workspace, sized for deep_sweep and never poisoned again, under different problems with their own parameter blocks, as the
+    engine reuses one workspace from frame to frame: what a larger problem left in the keys, the slices' counts, the order or the matrix
+    must not reach a smaller one (few_survive: 81 places; none_survive: no place at all), nor the other way round."""
+    lib = L.load()
+    c, base = RC.proposal_inputs("deep_sweep")[:2]
+    par = proposal_params(c, base, 2 * len(base) + 6, 2, 4 * len(base) + 4, 4, 12, 4, 8, 4)
+    nbytes = int(lib.fcn_proposal_workspace_bytes(C.byref(par)))
+    shared = (g.put(nbytes, name="shared workspace"), nbytes)
+    names = ["deep_sweep", "few_survive", "none_survive"]
+    for name in names if big_first else names[::-1]:
+        run_proposal(g, name, workspace=shared)
 
 
 @pytest.mark.parametrize("with_argmax", [True, False])

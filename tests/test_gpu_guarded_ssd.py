@@ -2,7 +2,9 @@
 
 The gather is a copy and is held to exact equality; Normalize to the allowance of a C-term float32 sum; the row softmax to the bound
 tests/test_gpu_guarded.py uses for the channel softmax; DetectionOutput to the same rows as the float64 reference - the same count, the
-same (image, label) in the same order, score and corners within 1e-5 - on inputs whose decision margin tests/test_ssd_ref.py asserts."""
+same (image, label) in the same order, score and corners within 1e-5 (the score, a copy of the bottom's, also bit for bit) - on inputs
+whose decision margin tests/test_ssd_ref.py asserts, with what each case reaches: negative scores, no threshold, no background label,
+300 classes.  Two cases run again with `capacity` exactly what the images can yield and the rows against the red zone."""
 import ctypes as C
 
 import numpy as np
@@ -111,8 +113,12 @@ def det_params(c, n, loc_rs, conf_rs, cap):
     return par
 
 
-@pytest.mark.parametrize("name", list(ssd_cases.CASES))
-def test_detection_output(g, name):
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def run_detection_output(g, name, exact=False):
+    """exact: `capacity` is what the images can yield and not a row more, and the rows end on the last byte in front of the red zone."""
     lib = L.load()
     c, loc, conf, priors, want, margin, count = ssd_cases.reference(name)
     assert margin >= ssd_cases.MARGIN      # (tests/test_ssd_ref.py asserts the same without a GPU)
@@ -120,13 +126,18 @@ def test_detection_output(g, name):
     loc_rs, conf_rs = p * 4 + 4, (p * nc + 3) // 4 * 4 + 4
     wl, wc = poisoned((n, loc_rs)), poisoned((n, conf_rs))
     wl[:, :p * 4], wc[:, :p * nc] = loc, conf
-    keep = c["keep_top_k"] if c["keep_top_k"] > -1 else (nc - 1) * c["top_k"]
-    cap = n * keep + 3
+    per_class = min(c["top_k"], p) if c["top_k"] > -1 else p
+    keep = c["keep_top_k"] if c["keep_top_k"] > -1 else (nc - (1 if c["bg"] >= 0 else 0)) * per_class
+    cap = n * keep + (0 if exact else 3)
     par = det_params(c, n, loc_rs, conf_rs, cap)
     nbytes = int(lib.fcn_detection_output_workspace_bytes(C.byref(par)))
     assert nbytes > 0
+    if exact:      # one row less is refused, so `cap` is the bound itself
+        par.capacity = cap - 1
+        assert int(lib.fcn_detection_output_workspace_bytes(C.byref(par))) == 0
+        par.capacity = cap
     ld, cd, pd = g.put(wl, name="loc"), g.put(wc, name="conf"), g.put(priors, at_end=True, name="priors")
-    od, nd, ws = g.put(poisoned((cap, 7)), name="rows"), g.put(poisoned(1), at_end=True, name="count"), g.put(nbytes, name="workspace")
+    od, nd, ws = g.put(poisoned((cap, 7)), at_end=exact, name="rows"), g.put(poisoned(1), at_end=True, name="count"), g.put(nbytes, name="workspace")
     rows, cnt = launched_twice(lambda: L.call("fcn_detection_output_f32", ld.ptr, cd.ptr, pd.ptr, C.byref(par), od.ptr, nd.ptr, ws.ptr, nbytes, None),
                                lambda: (od.read((cap, 7)), nd.read((1,), np.int32)))
     k = int(cnt[0])
@@ -141,3 +152,15 @@ def test_detection_output(g, name):
         err = float(np.max(np.abs(got[:, 2:].astype(np.float64) - want[:, 2:])))
         print("DETOUT %s worst |error| %.3g" % (name, err))
         assert err <= 1e-5
+        # a score is copied, not computed: the sign of a zero is the bottom's
+        assert np.array_equal(bits(got[:, 2]), bits(want[:, 2])), "the rows' scores, bit for bit"
+
+
+@pytest.mark.parametrize("name", list(ssd_cases.CASES))
+def test_detection_output(g, name):
+    run_detection_output(g, name)
+
+
+@pytest.mark.parametrize("name", ssd_cases.EXACT_CAPACITY)
+def test_detection_output_at_exact_capacity(g, name):
+    run_detection_output(g, name, exact=True)

@@ -90,12 +90,96 @@ def test_psroi_pooling_bins_by_hand():
 @pytest.mark.parametrize("name", list(RC.PROPOSALS))
 def test_margin_of_the_gpu_proposal_cases(name):
     """Every Proposal case the GPU test runs decides, in float64, at least MARGIN away from each threshold, bound and neighbouring score: the
-    float32 kernel, off by rounding, then has to decide the same.  A condition on the inputs (the seeds), not a skip."""
-    c, base, scores, _deltas, _im, out = RC.proposal_reference(name)
+    float32 kernel, off by rounding, then has to decide the same.  A condition on the inputs (the seeds), not a skip.
+
+    Beside each case stands what it is for, computed from the reference's order, places, suppressors and scores: the depth of the walk
+    (the last place of the order the greedy NMS looks at), boxes kept and dropped in the upper half of the sweep's suppressed set (places
+    from 4096 on), a full matrix, a cut that hides leaders, an image that is not the map's extent ...  An edit of a seed that moves a case
+    off its path fails here."""
+    c, base, scores, deltas, im, out = RC.proposal_reference(name)
     assert out["margin"] >= RC.MARGIN, "case %s: margin %.3g" % (name, out["margin"])
     m = scores.shape[2] * scores.shape[3] * len(base)
-    assert float(np.abs(out["boxes"]).max()) < 2 * max(c["H"], c["W"]) * RC.FEAT_STRIDE
-    if name == "m12x10_tiles":
+    assert float(np.nanmax(np.abs(out["boxes"]))) < 2 * max(c["H"], c["W"]) * RC.FEAT_STRIDE
+    places = np.array(out["places"], np.int64)
+    drops = np.array(out["suppressors"], np.int64).reshape(-1, 2)            # (place of the dropped box, place of the kept box that dropped it)
+    depth, k, fg = RC.depth(out), len(out["order"]), scores[0, len(base):].transpose(1, 2, 0).reshape(-1)
+    print("PROPOSAL-REF %s: %d candidates, %d into the NMS (%d words), count %d, depth %d, %d kept at places >= 4096"
+          % (name, m, k, (k + 63) // 64, out["count"], depth, int((places >= 4096).sum())))
+    # the corner tolerance of the GPU test (32 float32 ulps of the larger image extent) is justified here, against the reference and not
+    # against the kernel: the contract's decode in numpy float32 is off by at most a quarter of it
+    number = ~np.isnan(out["boxes"]).any(axis=1)
+    err = float(np.max(np.abs(RC.decode32(c, base, deltas, im)[number].astype(np.float64) - out["boxes"][number])))
+    limit = 32 * float(np.spacing(np.float32(max(im[0, 0], im[0, 1]))))
+    print("PROPOSAL-REF %s: a float32 decode is off by at most %.3g, the tolerance is %.3g" % (name, err, limit))
+    assert err <= 0.25 * limit
+    if "placed" in c:
+        assert np.array_equal(out["boxes"], out["raw"]) and float(np.abs(deltas).max()) > 50, "every box inside the image; deltas far above 1"
+        assert drops.size and np.all(fg[out["order"][:-1]] >= fg[out["order"][1:]])
+    if name == "deep_sweep":
+        assert k == m == 5184 and out["count"] == c["post"] and depth >= 4096 + 128 and int((places >= 4096).sum()) >= 64
+        late = drops[drops[:, 0] >= 4096]
+        assert np.any(late[:, 1] < 4096), "a box in the upper half of the set dropped by a box kept in the lower half"
+        assert np.any(late[:, 1] >= 4096), "... and one dropped by a box kept in the upper half"
+        assert np.any(places % 64 == 63) and np.any(places[places % 64 == 63] >= 4096), "a kept box at bit 63 of its word"
+        assert int((out["scores"][:out["count"], 0] < 0).sum()) >= 64 and np.all(fg != 0)
+    elif name == "pre_6144":
+        assert m == 26 * 27 * 9 > c["pre"] == k == 6144 and (k + 63) // 64 == 96 and places[-1] > 6080 and out["count"] < c["post"]
+        # past the cut lie leaders of sites the order has not seen: with them the count would be another one
+        more = R.proposal(scores, deltas, im, base, RC.FEAT_STRIDE, m, c["post"], c["nms"], c["min_size"])
+        assert more["count"] > out["count"] + 10 and more["index"][:out["count"]] == out["index"]
+        # the tie across the cut: the two candidates have one score, both are leaders, the smaller index is in
+        order_all = more["order"]
+        inside, outside = int(order_all[c["pre"] - 1]), int(order_all[c["pre"]])
+        assert fg[inside] == fg[outside] and inside < outside and out["index"][-1] == inside and outside in more["index"]
+    elif name in ("keep_everything", "suppress_everything"):
+        assert k == m >= 4200 and out["filtered"] == 0 and c["post"] == 6144 and (k + 63) // 64 > 64
+        assert out["count"] == (k if name == "keep_everything" else 1)
+        if name == "suppress_everything":
+            far = R.overlaps(out["boxes"][out["index"][0]], out["boxes"])
+            assert int((far == 0).sum()) > 1000, "pairs that do not meet at all are dropped as well: 0 > -1"
+    elif name == "max_candidates":
+        assert m == 65536 and len(base) == 16 and m - out["filtered"] > c["pre"] == k and out["filtered"] > 0 and out["count"] == c["post"]
+        assert out["index"][:4] == [2047, 2048, 8191, 8192] and fg[2047] == fg[2048] > fg[8191] == fg[8192] > np.delete(fg, [2047, 2048, 8191, 8192]).max()
+    elif name == "a32":
+        assert (m, len(base)) == (480, 32) and out["count"] > 0 and out["suppressed"] > 0 and out["filtered"] > 0
+    elif name == "a1":
+        assert (m, len(base)) == (63, 1) and out["count"] > 0 and out["suppressed"] > 0
+    elif name == "one":
+        assert m == 1 and (c["pre"], c["post"], out["count"], out["index"]) == (1, 1, 1, [0])
+    elif name == "one_filtered":
+        assert m == 1 and (out["count"], out["filtered"]) == (0, 1) and np.all(out["rois"] == 0)
+    elif name == "none_survive":
+        assert (out["count"], out["filtered"], k) == (0, m, 0) and np.all(out["rois"] == 0) and np.all(out["scores"] == 0)
+    elif name == "scaled_image":
+        assert tuple(im[0]) == (43, 91, np.float32(1.6)) and out["count"] > 0 and out["suppressed"] > 0
+        unit = R.proposal(scores, deltas, [im[0, 0], im[0, 1], 1.0], base, RC.FEAT_STRIDE, c["pre"], c["post"], c["nms"], c["min_size"])
+        ext = np.stack([out["boxes"][:, 2] - out["boxes"][:, 0] + 1, out["boxes"][:, 3] - out["boxes"][:, 1] + 1], axis=1).min(axis=1)
+        fate = int(((ext >= 16) & (ext < 16 * 1.6)).sum())                  # alive at scale 1, dropped at scale 1.6
+        assert fate >= 10 and unit["filtered"] == out["filtered"] - fate and unit["index"] != out["index"]
+        raw, box = out["raw"], out["boxes"]
+        by_image = int(((raw[:, 2] > 90) & (raw[:, 2] <= 7 * 16 - 1)).sum()) + int(((raw[:, 3] > 42) & (raw[:, 3] <= 5 * 16 - 1)).sum())
+        assert by_image >= 10 and np.any(box[:, 2] == 90) and np.any(box[:, 3] == 42), "corners the image clips and the map's extent would not"
+        on_map = R.proposal(scores, deltas, [5 * 16, 7 * 16, im[0, 2]], base, RC.FEAT_STRIDE, c["pre"], c["post"], c["nms"], c["min_size"])
+        assert on_map["index"] != out["index"]
+    elif name == "signed_scores":
+        s = out["scores"][:out["count"], 0]
+        assert s[0] == np.inf and s[-1] == -np.inf and np.all(np.isfinite(s[1:-1])) and out["count"] <= c["post"] and k < c["pre"]
+        assert int(((s < 0) & (s > -1e30)).sum()) >= 10 and np.any((s > 0) & (s < 1e-38)) and np.any((s < 0) & (s > -1e-38))
+        zero = np.nonzero(s == 0)[0]
+        assert np.any(np.signbit(s[zero])) and np.any(~np.signbit(s[zero]))
+        tied = np.array(out["index"])[zero]
+        assert len(zero) >= 2 and np.all(np.diff(zero) == 1) and np.all(np.diff(tied) > 0), "the zeros are one score: smaller index first"
+        assert np.any(np.diff(np.signbit(s[zero]).astype(int)) < 0), "a -0.0 in front of a +0.0: the sign does not order them"
+    elif name in ("nan_inputs", "nan_min0"):
+        clean = c["clean"]
+        assert int(np.isnan(fg).sum()) == 5 and int(np.isnan(deltas).sum()) == 5 and int(np.isnan(out["raw"]).any(axis=1).sum()) == 5
+        lost = set(c["no_score"] + c["no_delta"])
+        assert len(lost & set(clean["index"])) >= 6 and not lost & set(out["index"]) and not lost & set(out["order"].tolist())
+        assert out["index"] != clean["index"] and out["count"] == c["post"]
+        assert out["filtered"] == m - len(set(clean["alive"].tolist()) - lost) > clean["filtered"], "`filtered` counts them"
+        if name == "nan_min0":
+            assert c["min_size"] == 0 and clean["filtered"] == 0 and out["filtered"] == 10, "no size bound drops a box here: the NaN rule alone does"
+    elif name == "m12x10_tiles":
         assert m == 1080 and c["pre"] == 150 and out["suppressed"] > 0            # more than one ranking tile, three words of NMS matrix
     elif name == "filter_clip":
         assert out["filtered"] > m // 2 and np.any(out["boxes"] == 0) and np.any(out["boxes"][:, 2] == c["W"] * RC.FEAT_STRIDE - 1)

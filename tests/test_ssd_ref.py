@@ -116,6 +116,32 @@ def test_margin_of_the_gpu_cases(name):
         assert [int(((rows[:, 0] == i) & (rows[:, 1] == 1)).sum()) for i in range(2)] == [1, 1]      # the smothered class: one box survives
     elif name in ("p2000_multipass", "ssd300_shape", "p1200_full_tile"):
         assert per_image == [c["keep_top_k"]] * c["N"]                                                # keep_top_k cuts
+    elif name == "logits":
+        negative = rows[rows[:, 2] < 0]
+        print("DETOUT-REF logits: %d of %d rows have a negative score" % (len(negative), count))
+        assert c["thr"] < 0 and len(negative) >= 10 and per_image == [c["keep_top_k"]] * 2
+        conf = _conf.reshape(2, c["P"], c["classes"])
+        assert all(int((conf[i, :, cl] > c["thr"]).sum()) > c["top_k"] for i in range(2) for cl in (1, 2, 3))      # top_k cuts, among negative scores
+    elif name == "no_threshold":
+        conf = _conf.reshape(2, c["P"], c["classes"])
+        assert c["thr"] == -float(np.finfo(np.float32).max) and np.all(conf > c["thr"]) and c["top_k"] < c["P"]      # every prior is a candidate
+        for i in range(2):
+            for cl in (1, 2):
+                z = np.nonzero(conf[i, :, cl] == 0)[0]
+                assert len(z) == 2 and sorted(np.signbit(conf[i, z, cl]).tolist()) == [False, True]
+                assert int((conf[i, :, cl] > 0).sum()) + 2 <= c["top_k"]                              # both zeros inside the top_k
+        zero_rows = rows[rows[:, 2] == 0]
+        assert np.any(np.signbit(zero_rows[:, 2])) and np.any(~np.signbit(zero_rows[:, 2])) and int((rows[:, 2] < 0).sum()) >= 10
+    elif name == "no_background":
+        assert c["bg"] == -1 and np.any(rows[:, 1] == 0)
+    elif name == "c300":
+        # before the keep_top_k cut: at least 260 classes of image 0 have a survivor, image 1 has survivors in classes >= 256 only
+        uncut, _m, _n = R.detection_output(_loc, _conf, _priors, c["classes"], c["bg"], c["nms"], c["top_k"], c["code"], c["var_enc"], -1, c["thr"])
+        lab0, lab1 = uncut[uncut[:, 0] == 0, 1], uncut[uncut[:, 0] == 1, 1]
+        print("DETOUT-REF c300: survivors %d in %d classes (image 0), %d in %d classes (image 1)" % (len(lab0), len(set(lab0)), len(lab1), len(set(lab1))))
+        assert c["classes"] == 300 and len(set(lab0)) >= 260 and len(lab0) > c["keep_top_k"] and len(lab1) > 0 and lab1.min() >= 256
+        cut0 = rows[rows[:, 0] == 0, 1]
+        assert len(cut0) == c["keep_top_k"] and np.any(cut0 < 256) and np.any(cut0 >= 256) and c["bg"] not in set(uncut[:, 1])
     else:
         assert count > 0
 
