@@ -304,12 +304,12 @@ class BackwardPlanner:
             rec.op.name = "%s [cfg%d %dwg]" % (rec.name, rec.launch.cfg, rec.launch.total_tiles)
 
     # ------------------------------------------------------------------ weight gradients, ReLU masks
-    def relu_bwd_op(self, name: str, y: Blob, dy: Blob, dx: Optional[Blob] = None) -> Op:
-        """dX = dY where the activation y is positive, else 0.  dx None: in place on dY, the mask of a ReLU fused into its
-        convolution (its traffic is booked; the ReLU layer's own never was)."""
-        lib, byts = self.lib, 12.0 * y.pixels * y.channels if dx is None else 0.0
-        dx = dy if dx is None else dx
-        op = Op("relu_bwd", name, lambda st: L.check(lib.fcn_relu_bwd_f32(dy.ptr, y.ptr, dx.ptr, y.pixels, y.channels, y.cstride, st)), 0.0, byts)
+    def relu_bwd_op(self, name: str, y: Blob, dy: Blob) -> Op:
+        """dY = dY where the activation y is positive, else 0, in place: the mask of a ReLU fused into its convolution (slope 0 always:
+        engine._relu_after fuses no other; a ReLU layer of its own goes through _relu_plain)."""
+        lib = self.lib
+        op = Op("relu_bwd", name, lambda st: L.check(lib.fcn_relu_bwd_f32(dy.ptr, y.ptr, dy.ptr, y.pixels, y.channels, y.cstride, st)), 0.0,
+                12.0 * y.pixels * y.channels)
         self.ops.append(op)
         return op
 
@@ -646,7 +646,7 @@ class BackwardPlanner:
         if l.bottoms[1] in self.e.need_grad:
             raise NotImplementedError("loss layer %s: gradient w.r.t. the second bottom" % l.name)
         if self.state(g) != "none":
-            raise NotImplementedError("loss gradient would have to accumulate into %s" % l.bottoms[0])
+            raise NotImplementedError("loss gradient would have to accumulate into %s (%s)" % (l.bottoms[0], l.name))
         self.mark(g)                      # written by the forward loss kernel (da)
 
     def _sigmoid(self, l: Layer) -> None:
@@ -659,7 +659,7 @@ class BackwardPlanner:
         lib, acc = self.lib, 1 if self.state(gbot) == "full" else 0
         count = yb.pixels * yb.cstride
         if yb.coffset or gtop.coffset or gbot.coffset or yb.cstride != gbot.cstride:
-            raise NotImplementedError("sigmoid backward on channel slices")
+            raise NotImplementedError("sigmoid backward on channel slices (%s)" % l.name)
         self.ops.append(Op("sigmoid_bwd", l.name, lambda st: L.check(lib.fcn_sigmoid_bwd_f32(yb.ptr, gtop.ptr, gbot.ptr, count, acc, st))))
         self.mark(gbot)
 
@@ -684,7 +684,7 @@ class BackwardPlanner:
                 continue
             if self.state(gb) == "full":
                 if gtop.coffset or gb.coffset or gb.cstride != gtop.cstride:
-                    raise NotImplementedError("Eltwise SUM backward accumulating into a channel slice")
+                    raise NotImplementedError("Eltwise SUM backward accumulating into a channel slice (%s)" % l.name)
                 run = lambda st, a=gtop, b=gb: L.check(lib.fcn_eltwise_fwd_f32(a.ptr, b.ptr, b.ptr, a.pixels * a.cstride, L.ELT_SUM, 1.0, 1.0, st))
             else:
                 run = lambda st, a=gtop, b=gb: L.check(lib.fcn_copy_channels_f32(
@@ -875,14 +875,14 @@ class BackwardPlanner:
         ls, al, be = int(p.get("local_size", 5)), float(p.get("alpha", 1.0)), float(p.get("beta", 0.75))
         lib, sc = self.lib, self.e.aux_dev[l.name]
         if gtop.coffset or gbot.coffset or xb.coffset or yb.coffset:
-            raise NotImplementedError("LRN backward on channel slices")
+            raise NotImplementedError("LRN backward on channel slices (%s)" % l.name)
         self.ops.append(Op("lrn_bwd", l.name, lambda st: L.check(lib.fcn_lrn_bwd_f32(
             xb.ptr, yb.ptr, sc.ptr, gtop.ptr, gbot.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, acc, st))))
         self.mark(gbot)
 
     def _dropout(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
         if acc:
-            raise NotImplementedError("dropout backward into an already written gradient")
+            raise NotImplementedError("dropout backward into an already written gradient (%s)" % l.name)
         e, lib = self.e, self.lib
         ratio = float(l.sub("dropout_param").get("dropout_ratio", 0.5))
         n, c, h, w = self.B[l.bottoms[0]].nchw
@@ -899,7 +899,7 @@ class BackwardPlanner:
         if l.bottoms[1] in self.e.need_grad:
             raise NotImplementedError("Eltwise PROD backward w.r.t. both bottoms (%s)" % l.name)
         if acc:
-            raise NotImplementedError("Eltwise backward into an already written gradient")
+            raise NotImplementedError("Eltwise backward into an already written gradient (%s)" % l.name)
         lib, other = self.lib, self.B[l.bottoms[1]]
         count = gtop.pixels * gtop.cstride
         if gtop.coffset or gbot.coffset or other.coffset or other.cstride != gtop.cstride:
@@ -925,5 +925,14 @@ class BackwardPlanner:
         self.mark(gbot)
 
     def _relu_plain(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
-        self.relu_bwd_op(l.name, self.B[l.tops[0]], gtop, gbot)
+        """A ReLU layer of its own (engine._relu_after and _bn_chain_after leave every ReLU with a slope to this one): dX (+)= dY where the
+        output is positive and negative_slope dY elsewhere.  The stored output stands in for the input - their signs agree for a slope
+        >= 0, in place too; below 0 they do not, and nothing here keeps the input."""
+        lib, yb = self.lib, self.B[l.tops[0]]
+        slope = float(l.sub("relu_param").get("negative_slope", 0.0))
+        if slope < 0.0:
+            raise NotImplementedError("ReLU %s: backward with negative_slope %g (below 0 the sign of the output is not the sign of the input)"
+                                      % (l.name, slope))
+        self.ops.append(Op("relu_bwd", l.name, lambda st: L.check(lib.fcn_relu_bwd_slope_f32(
+            gtop.ptr, yb.ptr, gbot.ptr, yb.pixels, yb.channels, yb.cstride, slope, acc, st))))
         self.mark(gbot)

@@ -960,6 +960,18 @@ __global__ __launch_bounds__(256) void relu_bwd_view_kernel(const float* __restr
     }
 }
 
+// a ReLU layer of its own, any slope: dx (+)= y > 0 ? dy : slope * dy over the C real channels of every pixel (cstride == C: one run);
+// dx may be dy (in place, without accumulate), so neither is __restrict__
+__global__ __launch_bounds__(256) void relu_bwd_slope_kernel(const float* dy, const float* __restrict__ y, float* dx,
+                                                             long long pixels, int C, int cstride, float slope, int accumulate) {
+    const long long total = pixels * C;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const size_t o = cstride == C ? (size_t)t : (size_t)(t / C) * cstride + (t % C);
+        const float g = y[o] > 0.f ? dy[o] : slope * dy[o];
+        dx[o] = accumulate ? dx[o] + g : g;
+    }
+}
+
 __global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
                                                           size_t count, int accumulate) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -1980,6 +1992,17 @@ int fcn_relu_bwd_f32(const float* dy, const float* y, float* dx, int pixels, int
         hipLaunchKernelGGL(relu_bwd_view_kernel, dim3(stream_grid((long long)pixels * C, 256)), dim3(256), 0, st, dy, y, dx, (long long)pixels, C,
                            cstride);
     FCN_LAUNCH_CHECK("relu_bwd");
+    return 0;
+}
+
+int fcn_relu_bwd_slope_f32(const float* dy, const float* y, float* dx, int pixels, int C, int cstride, float negative_slope, int accumulate,
+                           fcn_stream_t s) {
+    FCN_REQUIRE(dy && y && dx && pixels > 0 && C > 0 && cstride >= C, FCN_E_ARG, "relu_bwd_slope: bad args");
+    FCN_REQUIRE(negative_slope >= 0.f, FCN_E_ARG, "relu_bwd_slope: a negative slope (the sign of y is not the sign of x)");
+    FCN_REQUIRE(!(accumulate && dx == dy), FCN_E_ARG, "relu_bwd_slope: accumulate in place");
+    hipLaunchKernelGGL(relu_bwd_slope_kernel, dim3(stream_grid((long long)pixels * C, 256)), dim3(256), 0, as_stream(s), dy, y, dx,
+                       (long long)pixels, C, cstride, negative_slope, accumulate);
+    FCN_LAUNCH_CHECK("relu_bwd_slope");
     return 0;
 }
 

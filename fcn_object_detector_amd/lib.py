@@ -302,6 +302,7 @@ PROTOTYPES = {
     "fcn_deconv_depthwise_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_conv_weights_flip_batch_f32": (_i, [_vp, _vp, _vp, _i, _vp]),
     "fcn_relu_bwd_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "fcn_relu_bwd_slope_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "fcn_sigmoid_bwd_f32": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     "fcn_maxpool_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     "fcn_maxpool_bwd_mask_f32": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp, _i, _i, _vp]),

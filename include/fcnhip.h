@@ -485,6 +485,11 @@ int  fcn_conv_weights_flip_f32(const float* w, float* wt, int Cout, int kh, int 
 typedef struct fcn_flip_seg { uint64_t w_offset, wt_offset; int32_t Cout, kh, kw, Cin, Cin4, Cout4; } fcn_flip_seg;
 int  fcn_conv_weights_flip_batch_f32(const float* w_base, float* wt_base, const fcn_flip_seg* d_segs, int nseg, fcn_stream_t s);
 int  fcn_relu_bwd_f32(const float* dy, const float* y, float* dx, int pixels, int C, int cstride, fcn_stream_t s);
+/* Backward of a ReLU layer of its own: dx (+)= y > 0 ? dy : negative_slope * dy over the C real channels of pixels of cstride floats
+ * (pad channels are left alone).  negative_slope >= 0 only: then the sign of the output y is the sign of the input.  dx == dy (in
+ * place) is allowed without accumulate. */
+int  fcn_relu_bwd_slope_f32(const float* dy, const float* y, float* dx, int pixels, int C, int cstride, float negative_slope, int accumulate,
+                            fcn_stream_t s);
 int  fcn_sigmoid_bwd_f32(const float* y, const float* dy, float* dx, size_t count, int accumulate, fcn_stream_t s);
 int  fcn_maxpool_bwd_f32(const float* dy, const int32_t* idx, float* dx, int N, int H, int W, int C, int dx_cstride, int dx_coffset,
                          int k, int stride, int pad, int OH, int OW, int dy_cstride, int dy_coffset, int accumulate, fcn_stream_t s);

@@ -577,6 +577,48 @@ def test_relu_and_sigmoid_backward(g):
             within(od.read((count,)), want, 4 * ref64.U32 * (np.abs(want) + np.abs(base) * acc + np.abs(gr)), "sigmoid bwd")
 
 
+@pytest.mark.parametrize("slope", [0.0, 0.1])
+@pytest.mark.parametrize("acc", [0, 1])
+def test_relu_backward_with_slope_and_accumulate(g, acc, slope):
+    """fcn_relu_bwd_slope_f32, dx (+)= y > 0 ? dy : slope * dy: the packed form (cstride == C) at every count, the channel-stride view
+    (10 channels in pixels of 12: the pad channels of dx keep their poison), and in place on dy without accumulate.  y is what the
+    forward stores: slope * x on the negative side, so its sign is the input's; some outputs are exact zeros."""
+    rng = np.random.default_rng(44 + acc)
+    sl = np.float32(slope)
+
+    def case(shape):
+        x = rng.standard_normal(shape).astype(np.float32)
+        x.flat[::7] = 0.0
+        y = np.where(x > 0, x, sl * x).astype(np.float32)
+        dy, base = rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape).astype(np.float32)
+        want = np.where(y > 0, dy.astype(np.float64), float(sl) * dy) + (base if acc else 0)
+        return y, dy, base, want, 2 * ref64.U32 * (np.abs(want) + np.abs(base) * acc + np.abs(dy))
+
+    for count in COUNTS:
+        y, dy, base, want, allow = case((count,))
+        yd, dyd = g.put(y, at_end=True, name="y"), g.put(dy, at_end=True, name="dy")
+        dxd = g.put(base if acc else poisoned(count), at_end=True, name="dx")
+        L.call("fcn_relu_bwd_slope_f32", dyd.ptr, yd.ptr, dxd.ptr, count, 1, 1, float(sl), acc, None)
+        within(dxd.read((count,)), want, allow, "relu bwd packed %d" % count)
+    n, c, h, w, cs = 2, 10, 3, 5, 12
+    y, dy, base, want, allow = case((n, c, h, w))
+    yd, dyd = g.put(poisoned_nhwc(y, cs), at_end=True, name="y"), g.put(poisoned_nhwc(dy, cs), at_end=True, name="dy")
+    dxd = g.put(poisoned_nhwc(base, cs) if acc else poisoned((n, h, w, cs)), at_end=True, name="dx")
+    L.call("fcn_relu_bwd_slope_f32", dyd.ptr, yd.ptr, dxd.ptr, n * h * w, c, cs, float(sl), acc, None)
+    full = dxd.read((n, h, w, cs))
+    assert poison_free(nchw(full, c)) and slice_untouched(full, 0, c)
+    within(nchw(full, c), want, allow, "relu bwd view")
+    if not acc:
+        L.call("fcn_relu_bwd_slope_f32", dyd.ptr, yd.ptr, dyd.ptr, n * h * w, c, cs, float(sl), 0, None)
+        full = dyd.read((n, h, w, cs))
+        assert slice_untouched(full, 0, c)
+        within(nchw(full, c), want, allow, "relu bwd in place")
+    else:      # `+=` into its own dY would be dY + f(dY): refused, like a slope below 0
+        lib = L.load()
+        assert lib.fcn_relu_bwd_slope_f32(dyd.ptr, yd.ptr, dyd.ptr, n * h * w, c, cs, float(sl), 1, None) == 1
+        assert lib.fcn_relu_bwd_slope_f32(dyd.ptr, yd.ptr, dxd.ptr, n * h * w, c, cs, -0.1, 0, None) == 1
+
+
 @pytest.mark.parametrize("c,cs_dy,co_dy,cs_dx,co_dx", [(8, 16, 8, 12, 4), (6, 9, 2, 7, 1)])
 @pytest.mark.parametrize("k,s,p,h,w", [(3, 2, 0, 7, 6), (3, 1, 1, 4, 5), (2, 2, 0, 5, 3), (3, 3, 0, 7, 7)])
 def test_maxpool_backward(g, k, s, p, h, w, c, cs_dy, co_dy, cs_dx, co_dx):
