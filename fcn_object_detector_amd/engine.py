@@ -1592,8 +1592,17 @@ class Engine:
             return [Op("relu", l.name, lambda st: L.check(lib.fcn_batchnorm_apply_f16(
                 xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, None, None, None, 0.0, None, None, 1, st)),
                 0.0, 4.0 * pix * c)]
-        if xb.coffset or yb.coffset or xb.cstride != yb.cstride:
-            raise NotImplementedError("%s on a channel slice (layer %s)" % (t, l.name))
+        if not all(b.coffset == 0 and (b.nchw is None or b.cstride == _r4(b.channels)) for b in (xb, yb)):
+            # a channel window of another blob's buffer (a Pooling top that a Concat view holds, with its ReLU in place): the flat
+            # kernels below run over whole pixels - at offset 0 they would rewrite the neighbours' channels as well.  A plain ReLU
+            # takes the BatchNorm / Scale apply launch with every operand NULL, y = relu(x) exactly, which keeps to its window
+            plain = t == "ReLU" and float(l.sub("relu_param").get("negative_slope", 0.0)) == 0.0 and self.spec.phase == "TEST"
+            if not plain or xb.nchw is None or xb.shape != yb.shape or any(b.coffset % 4 or b.cstride % 4 for b in (xb, yb)):
+                raise NotImplementedError("%s on a channel slice (layer %s)" % (t, l.name))
+            pix, c = xb.pixels, xb.channels
+            return [Op("relu", l.name, lambda st: L.check(lib.fcn_batchnorm_apply_f32(
+                xb.buf.ptr, yb.buf.ptr, None, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), None, None, None, None, 0.0, None, None,
+                1, st)), 0.0, 8.0 * pix * c)]
         count = xb.pixels * xb.cstride
         if t == "ReLU":
             ns = float(l.sub("relu_param").get("negative_slope", 0.0))
