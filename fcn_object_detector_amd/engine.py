@@ -774,6 +774,7 @@ class Engine:
         spec = self.spec
         skip: set = set()
         tasks: List[Task] = []
+        self._conv_flags: Dict[str, int] = {}      # Convolution layer of the tiled family -> the CONV_* flags of its descriptor(s)
         for li, l in enumerate(spec.layers):
             if l.name in skip:
                 continue
@@ -803,6 +804,7 @@ class Engine:
                                           reads=[(xp, xlo + i * cin_g, xlo + (i + 1) * cin_g)],
                                           writes=[(yp, ylo + i * cout_g, ylo + (i + 1) * cout_g)] + ([self._range(sig_top)] if sig_top else [])))
                 self._conv_layer_meta[l.name] = dict(relu=fused_relu, sigmoid_top=sig_top)
+                self._conv_flags[l.name] = int(tasks[-1].desc.flags)
                 continue
             if t == "InnerProduct":
                 relu = self._relu_after(li, l, skip)
@@ -1536,6 +1538,8 @@ class Engine:
         masked = len(l.tops) == 2      # (netspec: MAX only) the argmax is the mask blob: kept in TEST too, and written by the half engine
         if halves and (xb.esize != 2 or yb.esize != 2):
             raise NotImplementedError("f16 engine: pooling %s" % l.name)
+        if halves and is_max and c % 8:      # (fcn_maxpool_fwd_f16 / fcn_maxpool_idx_fwd_f16 would refuse at the first forward)
+            raise NotImplementedError("f16 engine: MAX pooling %s over %d channels (the half-float kernels take whole 8-channel segments)" % (l.name, c))
         if is_max and (masked or not halves):
             idx_ptr = None
             if masked or self.spec.phase == "TRAIN":      # backward routes the gradient to the argmax; an Upsample scatters by it
@@ -1572,6 +1576,10 @@ class Engine:
         if halves:
             if xb.esize != 2 or yb.esize != 2 or xb.coffset:
                 raise NotImplementedError("f16 engine: LRN %s" % l.name)
+            if ls != 5:      # (fcn_lrn_fwd_f16 would refuse at the first forward, inside the graph capture)
+                raise NotImplementedError("f16 engine: LRN %s with local_size %d (the half-float kernel takes 5 only)" % (l.name, ls))
+            if xb.channels % 8:
+                raise NotImplementedError("f16 engine: LRN %s over %d channels (the half-float kernel takes whole 8-channel segments)" % (l.name, xb.channels))
             return [Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f16(
                 xb.ptr, yb.ptr, xb.pixels, xb.channels, xb.cstride, yb.cstride, ls, al, be, kk, st)), 0.0, 4.0 * xb.pixels * xb.channels)]
         return [Op("lrn", l.name, lambda st: L.check(lib.fcn_lrn_fwd_f32(
