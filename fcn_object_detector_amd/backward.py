@@ -13,28 +13,27 @@ from typing import Dict, List, Optional, Tuple
 
 from . import lib as L
 from . import storage as S
-from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dconv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
+from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
 from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation
 
 
 @dataclass
 class Dgrad:
     """One data-gradient launch, prepared once the whole plan is known: a group of stride-1 passes that write different buffers
-    (ConvDesc, launch: L.ConvGroup), the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan) or the
-    dilated / rectangular convolution of dY with the flipped bank of one dilated / rectangular layer (DConvDesc, launch: L.DConvPlan;
-    RConvDesc, launch: L.RConvPlan), or the gather of one depthwise layer (DwConvDesc, launch: None - nothing to prepare).
-    targets[i]: the blob descs[i] writes."""
+    (ConvDesc, launch: L.ConvGroup), the transposed convolution of one strided layer (TConvDesc, launch: L.TConvPlan), the
+    convolution of dY with the flipped bank of one dilated or rectangular layer (RConvDesc, launch: L.RConvPlan), or the gather of one
+    depthwise layer (DwConvDesc, launch: None - nothing to prepare).
+    targets[i]: the blob descs[i] writes.  shows: what the op's label shows of the geometry once the launch is prepared."""
     name: str
     descs: list
     targets: List[str]
     launch: object
     op: Optional[Op] = None
+    shows: str = ""
 
 
-# the plan class of a one-problem data-gradient launch -> (prefix of its entry points, what the op's label shows of the geometry)
-_SINGLE_DGRAD = {L.DConvPlan: ("fcn_dconv2d", lambda d: "d%d " % d.dilation),
-                 L.RConvPlan: ("fcn_rconv2d", lambda d: "%dx%d " % (d.kh, d.kw)),
-                 L.TConvPlan: ("fcn_tconv2d", lambda d: "")}
+# the plan class of a one-problem data-gradient launch -> prefix of its entry points
+_SINGLE_DGRAD = {L.RConvPlan: "fcn_rconv2d", L.TConvPlan: "fcn_tconv2d"}
 
 
 @dataclass
@@ -118,15 +117,14 @@ class BackwardPlanner:
     def _conv_of(self, blob: str) -> Layer:
         return [q for q in self.e.producers.get(blob, []) if q.type == "Convolution"][0]
 
-    @staticmethod
-    def _rect(l: Layer) -> bool:
-        """A Convolution that csrc/rconv.hip runs (engine._rconv_task), whatever its dilation."""
-        return l.type == "Convolution" and is_rectangular(l)
+    def _rconv(self, l: Layer) -> bool:
+        """A Convolution that csrc/rconv.hip runs (engine._rconv_task): rectangular, or square with dilation > 1."""
+        return l.type == "Convolution" and not self.spec.is_depthwise(l) and (layer_dilation(l) > 1 or is_rectangular(l))
 
-    def _dilated(self, l: Layer) -> bool:
-        """A Convolution that csrc/rconv.hip (dilated or rectangular) or csrc/dwconv.hip runs (engine._dconv_task, engine._rconv_task,
-        engine._dwconv_task): it stays out of the grouped dense launches."""
-        return self.spec.is_depthwise(l) or (l.type == "Convolution" and (layer_dilation(l) > 1 or is_rectangular(l)))
+    def _own_kernel(self, l: Layer) -> bool:
+        """A Convolution that csrc/rconv.hip or csrc/dwconv.hip runs (engine._rconv_task, engine._dwconv_task): it stays out of the
+        grouped dense launches."""
+        return self.spec.is_depthwise(l) or self._rconv(l)
 
     def _find_concat_relu(self) -> None:
         """Concat outputs all of whose members are convolutions with a fused in-place ReLU: their ReLU backward is one launch."""
@@ -136,7 +134,7 @@ class BackwardPlanner:
                 self.concat_members.setdefault(parent, []).append(child)
         for parent, members in self.concat_members.items():
             prods = [[q for q in e.producers.get(m, []) if q.type == "Convolution"] for m in members]
-            if all(len(pr) == 1 and e._conv_layer_meta.get(pr[0].name, {}).get("relu") and not self._dilated(pr[0]) for pr in prods) and \
+            if all(len(pr) == 1 and e._conv_layer_meta.get(pr[0].name, {}).get("relu") and not self._own_kernel(pr[0]) for pr in prods) and \
                     sum(B[m].channels for m in members) == B[parent].channels and B[parent].coffset == 0:
                 for m in members:
                     self.concat_relu[m] = parent
@@ -155,29 +153,24 @@ class BackwardPlanner:
                 continue
             if self.spec.is_depthwise(l):      # the data gradient gathers through the layer's own bank: nothing to flip or pack
                 continue
-            if self._rect(l):      # the data gradient is the same rectangular kernel on the flipped bank: strides 1, pad' = d (k-1) - pad >= 0 per axis
+            if self._rconv(l):      # the data gradient is the same kernel on the flipped bank: strides 1, pad' = d (k-1) - pad >= 0 per axis
                 r = e._rgeom(l)
+                rect = is_rectangular(l)      # (a square layer is named as a dilated one, with one stride and one pad)
+                kind = "rectangular" if rect else "dilated"
+                axes = (("_h", r.ph, r.kh), ("_w", r.pw, r.kw)) if rect else (("", r.ph, r.kh),)
                 if r.sh != 1 or r.sw != 1:
-                    raise NotImplementedError("rectangular Convolution %s: the data gradient of a rectangular layer with stride %dx%d (its "
-                                              "bottom %s needs a gradient)" % (l.name, r.sh, r.sw, l.bottoms[0]))
-                for axis, pad, k in (("h", r.ph, r.kh), ("w", r.pw, r.kw)):
+                    raise NotImplementedError("%s Convolution %s: the data gradient of a %s layer with stride %s (its bottom %s needs a gradient)"
+                                              % (kind, l.name, kind, "%dx%d" % (r.sh, r.sw) if rect else r.sh, l.bottoms[0]))
+                for axis, pad, k in axes:
                     if pad > r.d * (k - 1):
-                        raise NotImplementedError("rectangular Convolution %s: the data gradient with pad_%s %d above dilation * (kernel_%s - 1) = "
-                                                  "%d (its bottom %s needs a gradient)" % (l.name, axis, pad, axis, r.d * (k - 1), l.bottoms[0]))
+                        raise NotImplementedError("%s Convolution %s: the data gradient with pad%s %d above dilation * (kernel%s - 1) = %d (its "
+                                                  "bottom %s needs a gradient)" % (kind, l.name, axis, pad, axis, r.d * (k - 1), l.bottoms[0]))
                 self.flip_layout[l.name] = flip_floats
                 wdev = e.params_dev[l.name][0].ptr
                 flip_segs.append(L.FlipSeg((wdev - e.param_flat.ptr) // 4, flip_floats, r.cout, r.kh, r.kw, r.cin, _r4(r.cin), _r4(r.cout)))
                 flip_floats += _r4(r.cin * r.kh * r.kw * _r4(r.cout))
                 continue
             g, ng = e._geom(l), e._conv_groups(l)
-            if self._dilated(l):      # the data gradient is the same dilated kernel on the flipped bank: stride 1, pad' = dil (k-1) - pad >= 0
-                dil = layer_dilation(l)
-                if g.s != 1:
-                    raise NotImplementedError("dilated Convolution %s: the data gradient of a dilated layer with stride %d (its bottom %s "
-                                              "needs a gradient)" % (l.name, g.s, l.bottoms[0]))
-                if g.pad > dil * (g.k - 1):
-                    raise NotImplementedError("dilated Convolution %s: the data gradient with pad %d above dilation * (kernel - 1) = %d (its "
-                                              "bottom %s needs a gradient)" % (l.name, g.pad, dil * (g.k - 1), l.bottoms[0]))
             cin, cout, k = g.cin // ng, g.cout // ng, g.k      # of one group: its bank is rows i*cout .. of the layer's (storage.conv_groups)
             if g.s == 1:
                 self.flip_layout[l.name] = flip_floats
@@ -285,14 +278,13 @@ class BackwardPlanner:
         for rec in self.dgrad_records:
             if rec.launch is None:      # a depthwise gather: one pure launch on its descriptor
                 continue
-            single = _SINGLE_DGRAD.get(type(rec.launch))
-            if single is not None:
-                prefix, geometry = single
+            prefix = _SINGLE_DGRAD.get(type(rec.launch))
+            if prefix is not None:
                 d = rec.descs[0]
                 ws = DeviceBuffer(int(getattr(lib, prefix + "_workspace_bytes")(C.byref(d), 1)), zero=False)
                 L.call(prefix + "_prepare", C.byref(d), 1, ws.ptr, -1, C.byref(rec.launch))
                 e._keep.extend([ws, rec.launch])
-                rec.op.name = "%s [%s%dwg]" % (rec.name, geometry(d), rec.launch.total_tiles)
+                rec.op.name = "%s [%s%dwg]" % (rec.name, rec.shows, rec.launch.total_tiles)
                 continue
             n_ = len(rec.descs)
             arr = (L.ConvDesc * n_)(*rec.descs)
@@ -336,7 +328,7 @@ class BackwardPlanner:
     def wgrad_items(self, l: Layer, gtop: Blob) -> List[Tuple[L.ConvDesc, DevView, Optional[DevView], float]]:
         """(descriptor with y = dY of the layer, dW view, db view or None, flops) of a layer that learns: one per group, dW and db at
         the group's rows."""
-        if self._dilated(l):
+        if self._own_kernel(l):
             raise RuntimeError("wgrad_items is the dense path; dilated and rectangular layers have emitters of their own (%s)" % l.name)
         e, g, xb, ng = self.e, self.e._geom(l), self.B[l.bottoms[0]], self.e._conv_groups(l)
         if gtop.coffset % 4 or gtop.cstride % 4:
@@ -389,43 +381,12 @@ class BackwardPlanner:
                 self.relu_ops[top] = rop
             self.relu_done.add(top)
 
-    def _dilated_convolution(self, l: Layer, gtop: Blob) -> None:
-        """Backward of a Convolution with dilation > 1 (fcn_dconv2d_*, csrc/rconv.hip): the layer's own ReLU mask on dY, the weight
-        gradient on the second stream (one form only: op.sel is None), and dX = the dilated convolution of dY with the flipped bank,
-        stride 1, pad' = dil (k-1) - pad, accumulating where dX already holds a gradient; _finish_dgrads may fold the ReLU mask of the
-        layer below into it, as for a dense pass."""
-        e, G, lib, top = self.e, self.G, self.lib, l.tops[0]
-        g, dil, xb = e._geom(l), layer_dilation(l), self.B[l.bottoms[0]]
-        self._own_relu_mask(l, gtop)
-        if e._learns(l) and l.name not in self.wgrad_done:
-            d = dconv_desc(xb, gtop, g, dil)
-            dw = e._grad_view(l.name, 0)
-            db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
-            e._keep.append(d)
-            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_dconv2d_wgrad_f32(C.byref(d), dw.ptr, db, e._ws.ptr, st)), g.flops,
-                    4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout))
-            # (the launch runs on the second stream behind the other weight gradients, never beside them: it shares their workspace)
-            self._book_wgrad(op, None, [l.name], [int(lib.fcn_dconv2d_wgrad_workspace_floats(C.byref(d)))])
-        gbot = G.get(l.bottoms[0])
-        if gbot is None or l.name in self.dgrad_done:
-            return
-        if gtop.coffset % 4 or gtop.cstride % 4 or gtop.cstride - gtop.coffset < _r4(g.cout):
-            raise NotImplementedError("gradient view of %s is not a 16-byte aligned run of whole channel groups" % top)
-        wt = self.flip_flat.ptr + 4 * self.flip_layout[l.name]
-        dd = dconv_desc(gtop, gbot, g.swapped()._replace(s=1, pad=dil * (g.k - 1) - g.pad), dil, wt,
-                        flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
-        rec = Dgrad(l.name, [dd], [l.bottoms[0]], L.DConvPlan())
-        rec.op = Op("dconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_dconv2d_f32(C.byref(pl), st)), g.flops)
-        self.ops.append(rec.op)
-        self.dgrad_records.append(rec)
-        e._keep.append(dd)
-        self.mark(gbot, rec)
-
-    def _rect_convolution(self, l: Layer, gtop: Blob) -> None:
-        """Backward of a rectangular Convolution (csrc/rconv.hip), the shape of _dilated_convolution: the layer's own ReLU mask on dY,
-        the weight gradient on the second stream (one form only: op.sel is None), and dX = the rectangular convolution of dY with
-        the flipped bank, strides 1, pad_h' = d (kh-1) - pad_h, pad_w' = d (kw-1) - pad_w, accumulating where dX already holds a
-        gradient; _finish_dgrads may fold the ReLU mask of the layer below into it, as for a dense pass."""
+    def _rconv_convolution(self, l: Layer, gtop: Blob) -> None:
+        """Backward of a dilated or rectangular Convolution (csrc/rconv.hip): the layer's own ReLU mask on dY, the weight gradient on
+        the second stream (one form only: op.sel is None), and dX = the same convolution of dY with the flipped bank, strides 1,
+        pad_h' = d (kh-1) - pad_h, pad_w' = d (kw-1) - pad_w, accumulating where dX already holds a gradient; _finish_dgrads may fold
+        the ReLU mask of the layer below into it, as for a dense pass.  The op of a square layer is a "dconv_dgrad" whose label shows
+        the dilation, that of a rectangular one an "rconv_dgrad" that shows the kernel."""
         e, G, lib, top = self.e, self.G, self.lib, l.tops[0]
         g, xb = e._rgeom(l), self.B[l.bottoms[0]]
         self._own_relu_mask(l, gtop)
@@ -445,15 +406,16 @@ class BackwardPlanner:
         wt = self.flip_flat.ptr + 4 * self.flip_layout[l.name]
         dd = rconv_desc(gtop, gbot, g.swapped()._replace(sh=1, sw=1, ph=g.d * (g.kh - 1) - g.ph, pw=g.d * (g.kw - 1) - g.pw), wt,
                         flags=L.CONV_ACCUM if self.state(gbot) == "full" else 0)
-        rec = Dgrad(l.name, [dd], [l.bottoms[0]], L.RConvPlan())
-        rec.op = Op("rconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_rconv2d_f32(C.byref(pl), st)), g.flops)
+        rect = is_rectangular(l)
+        rec = Dgrad(l.name, [dd], [l.bottoms[0]], L.RConvPlan(), shows="%dx%d " % (g.kh, g.kw) if rect else "d%d " % g.d)
+        rec.op = Op("rconv_dgrad" if rect else "dconv_dgrad", rec.name, lambda st, pl=rec.launch: L.check(lib.fcn_rconv2d_f32(C.byref(pl), st)), g.flops)
         self.ops.append(rec.op)
         self.dgrad_records.append(rec)
         e._keep.append(dd)
         self.mark(gbot, rec)
 
     def _depthwise_convolution(self, l: Layer, gtop: Blob) -> None:
-        """Backward of a depthwise Convolution (csrc/dwconv.hip), the shape of _rect_convolution: the layer's own ReLU mask on dY, the
+        """Backward of a depthwise Convolution (csrc/dwconv.hip), the shape of _rconv_convolution: the layer's own ReLU mask on dY, the
         weight gradient on the second stream in the shared workspace (one form only: op.sel is None), and dX = the gather of dY through
         the layer's own bank - any stride, no flipped bank - accumulating where dX already holds a gradient; _finish_dgrads may fold the
         ReLU mask of the layer below into it, as for a dense pass."""
@@ -487,10 +449,8 @@ class BackwardPlanner:
             return
         if self.spec.is_depthwise(l):
             return self._depthwise_convolution(l, gtop)
-        if self._rect(l):
-            return self._rect_convolution(l, gtop)
-        if self._dilated(l):
-            return self._dilated_convolution(l, gtop)
+        if self._rconv(l):
+            return self._rconv_convolution(l, gtop)
         e, G, top = self.e, self.G, l.tops[0]
         if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
             whole = self.concat_relu.get(top)
@@ -555,7 +515,7 @@ class BackwardPlanner:
                 continue
             prods = [q for q in e.producers.get(lm.bottoms[0], []) if q.type == "Convolution"]
             cons = [q for q in e.consumers.get(lm.bottoms[0], []) if not (q.type in ("ReLU", "Dropout") and q.bottoms == q.tops)]
-            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in e.alias and lm.bottoms[0] in self.G and not self._dilated(prods[0]):
+            if len(prods) == 1 and len(cons) == 1 and lm.bottoms[0] not in e.alias and lm.bottoms[0] in self.G and not self._own_kernel(prods[0]):
                 sibs.append(prods[0])
         if len(sibs) > 1:
             for q in sibs:

@@ -5,8 +5,8 @@
 //
 //   y[n, oy, ox, co] = bias[co] + sum over ci, r, q of w[co][r][q][ci] * x[n, oy*sh - ph + r*dil, ox*sw - pw + q*dil, ci]
 //
-// One kernel family behind two ABIs: the geometry is kept per axis, fcn_rconv2d_* takes it as it is, and
-// fcn_dconv2d_* (one pad, one stride) widens its descriptor to equal axes and runs the same kernels.
+// One kernel family behind one ABI: fcn_rconv2d_* keeps the geometry per axis, and a square dilated layer is
+// its case with equal axes.
 //
 // Forward / data gradient (rconv_f32_kernel): a workgroup (256 threads, four waves as 2 x 2) computes 64 output pixels x 64 output
 // channels as out^T = W . act^T with v_mfma_f32_32x32x2_f32 (exact f32, a k-ordered fma chain): A = 32 filters x 2 k, B = 2 k x 32
@@ -294,39 +294,38 @@ __global__ __launch_bounds__(256) void rconv_wgrad_finish_kernel(const float* __
     if (threadIdx.x == 0) db[c] = part[0];
 }
 
-// fam: "dconv" / "rconv", the ABI the caller came through, which every refusal names.
-// wgrad = true: the descriptor of fcn_*2d_wgrad_f32 (w, bias, y2 and flags are not looked at; y names dY)
-int validate(const char* fam, const fcn_rconv_desc& d, bool wgrad) {
-    FCN_REQUIRE(d.x && d.y && (wgrad || d.w), FCN_E_ARG, "%s: null x/w/y", fam);
+// wgrad = true: the descriptor of fcn_rconv2d_wgrad_f32 (w, bias, y2 and flags are not looked at; y names dY)
+int validate(const fcn_rconv_desc& d, bool wgrad) {
+    FCN_REQUIRE(d.x && d.y && (wgrad || d.w), FCN_E_ARG, "rconv: null x/w/y");
     FCN_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.kh > 0 && d.kw > 0 && d.stride_h > 0 && d.stride_w > 0 &&
                     d.pad_h >= 0 && d.pad_w >= 0,
                 FCN_E_ARG,
-                "%s: non-positive extent", fam);
-    FCN_REQUIRE(d.dilation >= 1, FCN_E_UNSUPPORTED, "%s: dilation %d below 1", fam, d.dilation);
-    FCN_REQUIRE(d.kh * (long long)d.kw <= 4096, FCN_E_UNSUPPORTED, "%s: kernel window %dx%d too large", fam, d.kh, d.kw);
+                "rconv: non-positive extent");
+    FCN_REQUIRE(d.dilation >= 1, FCN_E_UNSUPPORTED, "rconv: dilation %d below 1", d.dilation);
+    FCN_REQUIRE(d.kh * (long long)d.kw <= 4096, FCN_E_UNSUPPORTED, "rconv: kernel window %dx%d too large", d.kh, d.kw);
     const int ci4 = (d.Cin + 3) & ~3;
-    FCN_REQUIRE(d.x_cstride % 4 == 0 && d.x_cstride >= ci4, FCN_E_ALIGN, "%s: x_cstride (%d) must be a multiple of 4 holding Cin (%d) padded to 4", fam,
+    FCN_REQUIRE(d.x_cstride % 4 == 0 && d.x_cstride >= ci4, FCN_E_ALIGN, "rconv: x_cstride (%d) must be a multiple of 4 holding Cin (%d) padded to 4",
                 d.x_cstride, d.Cin);
-    FCN_REQUIRE(((uintptr_t)d.x & 15) == 0 && (wgrad || ((uintptr_t)d.w & 15) == 0), FCN_E_ALIGN, "%s: x / w must be 16-byte aligned", fam);
-    FCN_REQUIRE(((uintptr_t)d.y & 3) == 0 && (wgrad || !d.bias || ((uintptr_t)d.bias & 3) == 0), FCN_E_ALIGN, "%s: y / bias must be 4-byte aligned", fam);
+    FCN_REQUIRE(((uintptr_t)d.x & 15) == 0 && (wgrad || ((uintptr_t)d.w & 15) == 0), FCN_E_ALIGN, "rconv: x / w must be 16-byte aligned");
+    FCN_REQUIRE(((uintptr_t)d.y & 3) == 0 && (wgrad || !d.bias || ((uintptr_t)d.bias & 3) == 0), FCN_E_ALIGN, "rconv: y / bias must be 4-byte aligned");
     const long long eh = (long long)d.dilation * (d.kh - 1) + 1, ew = (long long)d.dilation * (d.kw - 1) + 1;
     const long long nh = (long long)d.H + 2ll * d.pad_h - eh, nw = (long long)d.W + 2ll * d.pad_w - ew;
-    FCN_REQUIRE(nh >= 0 && nw >= 0, FCN_E_ARG, "%s: the window (%lldx%lld) exceeds the padded image", fam, eh, ew);
+    FCN_REQUIRE(nh >= 0 && nw >= 0, FCN_E_ARG, "rconv: the window (%lldx%lld) exceeds the padded image", eh, ew);
     FCN_REQUIRE(d.OH == nh / d.stride_h + 1 && d.OW == nw / d.stride_w + 1, FCN_E_ARG,
-                "%s: OH/OW (%d,%d) is not (H + 2 pad - (dil (k-1) + 1)) / stride + 1 per axis = (%lld,%lld)", fam, d.OH, d.OW, nh / d.stride_h + 1,
+                "rconv: OH/OW (%d,%d) is not (H + 2 pad - (dil (k-1) + 1)) / stride + 1 per axis = (%lld,%lld)", d.OH, d.OW, nh / d.stride_h + 1,
                 nw / d.stride_w + 1);
-    FCN_REQUIRE(d.y_coffset >= 0 && d.y_cstride >= d.y_coffset + d.Cout, FCN_E_ARG, "%s: output slice exceeds y_cstride", fam);
+    FCN_REQUIRE(d.y_coffset >= 0 && d.y_cstride >= d.y_coffset + d.Cout, FCN_E_ARG, "rconv: output slice exceeds y_cstride");
     if (!wgrad) {
         FCN_REQUIRE((d.flags & ~(FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK)) == 0, FCN_E_UNSUPPORTED,
-                    "%s: flags 0x%x outside FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK (float32 only)", fam, d.flags);
+                    "rconv: flags 0x%x outside FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK (float32 only)", d.flags);
         if (d.flags & FCN_CONV_MASK)
             FCN_REQUIRE(d.y2 && ((uintptr_t)d.y2 & 3) == 0 && d.y2_coffset >= 0 && d.y2_cstride >= d.y2_coffset + d.Cout, FCN_E_ARG,
-                        "%s: FCN_CONV_MASK needs y2 with a slice of Cout channels", fam);
+                        "rconv: FCN_CONV_MASK needs y2 with a slice of Cout channels");
     }
     FCN_REQUIRE((long long)d.N * d.H * d.W * d.x_cstride < (1ll << 31) && (long long)d.N * d.OH * d.OW * d.y_cstride < (1ll << 31) &&
                     (long long)d.kh * d.kw * d.Cout * ci4 < (1ll << 31) &&
                     (wgrad || !(d.flags & FCN_CONV_MASK) || (long long)d.N * d.OH * d.OW * d.y2_cstride < (1ll << 31)),
-                FCN_E_UNSUPPORTED, "%s: tensor too large for 32-bit element offsets", fam);
+                FCN_E_UNSUPPORTED, "rconv: tensor too large for 32-bit element offsets");
     return 0;
 }
 
@@ -355,27 +354,35 @@ WgradPlan wgrad_plan(const fcn_rconv_desc& d) {
     return wp;
 }
 
-// ---- the host side, shared by both ABIs: every refusal is made here, before the first HIP call, under the caller's family name
+}  // namespace
+}  // namespace fcn
 
-// the refusals of prepare() that look at no descriptor
-int prepare_args(const char* fam, const void* h_descs, const void* h_out, int n, int cfg_request) {
-    FCN_REQUIRE(h_descs && h_out && n > 0, FCN_E_ARG, "%s prepare: null descriptors / plan or n <= 0", fam);
-    FCN_REQUIRE(n <= 65535, FCN_E_UNSUPPORTED, "%s prepare: more than 65535 problems", fam);
-    FCN_REQUIRE(cfg_request >= -1 && cfg_request < RC_CONFIGS, FCN_E_ARG, "%s prepare: unknown configuration %d", fam, cfg_request);
-    return 0;
+using namespace fcn;
+
+// ---- the host side: every refusal is made here, before the first HIP call
+extern "C" {
+
+int fcn_rconv2d_num_configs(void) { return RC_CONFIGS; }
+
+size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n) {
+    (void)h_descs;
+    return n > 0 ? (size_t)n * sizeof(RConvP) : 0;
 }
 
-int prepare(const char* fam, const fcn_rconv_desc* h_descs, int n, void* d_workspace, fcn_rconv_plan* h_out) {
+int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out) {
+    FCN_REQUIRE(h_descs && h_out && n > 0, FCN_E_ARG, "rconv prepare: null descriptors / plan or n <= 0");
+    FCN_REQUIRE(n <= 65535, FCN_E_UNSUPPORTED, "rconv prepare: more than 65535 problems");
+    FCN_REQUIRE(cfg_request >= -1 && cfg_request < RC_CONFIGS, FCN_E_ARG, "rconv prepare: unknown configuration %d", cfg_request);
     long long gx = 0, total = 0;
     for (int i = 0; i < n; ++i) {
-        const int rc = validate(fam, h_descs[i], false);
+        const int rc = validate(h_descs[i], false);
         if (rc) return rc;
         const long long tx = tiles_x(h_descs[i]);
         gx = tx > gx ? tx : gx;
         total += tx;
     }
-    FCN_REQUIRE(gx < (1ll << 31) && total < (1ll << 31), FCN_E_UNSUPPORTED, "%s prepare: too many tiles for one launch", fam);
-    FCN_REQUIRE(d_workspace, FCN_E_ARG, "%s prepare: null workspace", fam);
+    FCN_REQUIRE(gx < (1ll << 31) && total < (1ll << 31), FCN_E_UNSUPPORTED, "rconv prepare: too many tiles for one launch");
+    FCN_REQUIRE(d_workspace, FCN_E_ARG, "rconv prepare: null workspace");
     std::vector<RConvP> ps((size_t)n);
     for (int i = 0; i < n; ++i) {
         const fcn_rconv_desc& d = h_descs[i];
@@ -398,35 +405,34 @@ int prepare(const char* fam, const fcn_rconv_desc* h_descs, int n, void* d_works
     return 0;
 }
 
-// (a null plan arrives as an empty one and is refused with it)
-int launch(const char* fam, const fcn_rconv_plan& plan, fcn_stream_t s) {
-    FCN_REQUIRE(plan.d_probs && plan.n > 0 && plan.grid_x > 0 && plan.grid_y == 1 && plan.n <= 65535 && plan.cfg == 0, FCN_E_ARG,
-                "%s: the plan was not filled by fcn_%s2d_prepare", fam, fam);
-    hipLaunchKernelGGL(rconv_f32_kernel, dim3((unsigned)plan.grid_x, 1u, (unsigned)plan.n), dim3(RC_THREADS), 0, as_stream(s),
-                       (const RConvP*)plan.d_probs);
+int fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s) {
+    FCN_REQUIRE(h_plan && h_plan->d_probs && h_plan->n > 0 && h_plan->grid_x > 0 && h_plan->grid_y == 1 && h_plan->n <= 65535 && h_plan->cfg == 0,
+                FCN_E_ARG, "rconv: the plan was not filled by fcn_rconv2d_prepare");
+    hipLaunchKernelGGL(rconv_f32_kernel, dim3((unsigned)h_plan->grid_x, 1u, (unsigned)h_plan->n), dim3(RC_THREADS), 0, as_stream(s),
+                       (const RConvP*)h_plan->d_probs);
     FCN_LAUNCH_CHECK("rconv_f32_kernel");
     return 0;
 }
 
-size_t wgrad_workspace_floats(const char* fam, const fcn_rconv_desc* h_d) {
-    if (!h_d || validate(fam, *h_d, true)) return 0;
+size_t fcn_rconv2d_wgrad_workspace_floats(const fcn_rconv_desc* h_d) {
+    if (!h_d || validate(*h_d, true)) return 0;
     const WgradPlan wp = wgrad_plan(*h_d);
     if (wp.splits <= 1) return 0;
     return (size_t)wp.splits * h_d->Cout * h_d->kh * h_d->kw * ((h_d->Cin + 3) & ~3);
 }
 
-int wgrad(const char* fam, const fcn_rconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s) {
-    FCN_REQUIRE(h_d && dw, FCN_E_ARG, "%s wgrad: null descriptor / dw", fam);
+int fcn_rconv2d_wgrad_f32(const fcn_rconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s) {
+    FCN_REQUIRE(h_d && dw, FCN_E_ARG, "rconv wgrad: null descriptor / dw");
     const fcn_rconv_desc& d = *h_d;
-    const int rc = validate(fam, d, true);
+    const int rc = validate(d, true);
     if (rc) return rc;
-    FCN_REQUIRE(((uintptr_t)dw & 15) == 0 && (!db || ((uintptr_t)db & 3) == 0), FCN_E_ALIGN, "%s wgrad: dw must be 16-byte, db 4-byte aligned", fam);
+    FCN_REQUIRE(((uintptr_t)dw & 15) == 0 && (!db || ((uintptr_t)db & 3) == 0), FCN_E_ALIGN, "rconv wgrad: dw must be 16-byte, db 4-byte aligned");
     const WgradPlan wp = wgrad_plan(d);
     const int ci4 = (d.Cin + 3) & ~3, taps = d.kh * d.kw;
     const unsigned long long slab = (unsigned long long)d.Cout * taps * ci4;
-    FCN_REQUIRE(wp.splits == 1 || d_workspace, FCN_E_ARG, "%s wgrad: %d pixel splits need a workspace", fam, wp.splits);
-    FCN_REQUIRE(wp.splits == 1 || ((uintptr_t)d_workspace & 15) == 0, FCN_E_ALIGN, "%s wgrad: the workspace must be 16-byte aligned", fam);
-    FCN_REQUIRE((long long)wp.nblk_co * wp.nblk_ci < (1ll << 31) && taps <= 65535, FCN_E_UNSUPPORTED, "%s wgrad: too many tiles for one launch", fam);
+    FCN_REQUIRE(wp.splits == 1 || d_workspace, FCN_E_ARG, "rconv wgrad: %d pixel splits need a workspace", wp.splits);
+    FCN_REQUIRE(wp.splits == 1 || ((uintptr_t)d_workspace & 15) == 0, FCN_E_ALIGN, "rconv wgrad: the workspace must be 16-byte aligned");
+    FCN_REQUIRE((long long)wp.nblk_co * wp.nblk_ci < (1ll << 31) && taps <= 65535, FCN_E_UNSUPPORTED, "rconv wgrad: too many tiles for one launch");
     RWgradP p;
     p.x = d.x; p.dy = d.y; p.out = wp.splits == 1 ? dw : d_workspace;
     p.N = d.N; p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.x_cstride = d.x_cstride; p.Cout = d.Cout; p.kh = d.kh; p.kw = d.kw;
@@ -446,70 +452,6 @@ int wgrad(const char* fam, const fcn_rconv_desc* h_d, float* dw, float* db, floa
         FCN_LAUNCH_CHECK("rconv_wgrad_finish_kernel");
     }
     return 0;
-}
-
-// the dilated ABI: one pad and one stride are the per-axis problem with equal axes
-fcn_rconv_desc widen(const fcn_dconv_desc& d) {
-    return fcn_rconv_desc{d.x, d.w, d.bias, d.y, d.y2, d.N, d.H, d.W, d.Cin, d.x_cstride, d.Cout, d.kh, d.kw, d.pad, d.pad, d.stride, d.stride,
-                          d.OH, d.OW, d.y_cstride, d.y_coffset, d.y2_cstride, d.y2_coffset, d.flags, d.dilation};
-}
-
-}  // namespace
-}  // namespace fcn
-
-using namespace fcn;
-
-extern "C" {
-
-int fcn_rconv2d_num_configs(void) { return RC_CONFIGS; }
-int fcn_dconv2d_num_configs(void) { return RC_CONFIGS; }
-
-size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n) {
-    (void)h_descs;
-    return n > 0 ? (size_t)n * sizeof(RConvP) : 0;
-}
-size_t fcn_dconv2d_workspace_bytes(const fcn_dconv_desc* h_descs, int n) {
-    (void)h_descs;
-    return n > 0 ? (size_t)n * sizeof(RConvP) : 0;
-}
-
-int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out) {
-    const int rc = prepare_args("rconv", h_descs, h_out, n, cfg_request);
-    return rc ? rc : prepare("rconv", h_descs, n, d_workspace, h_out);
-}
-int fcn_dconv2d_prepare(const fcn_dconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_dconv_plan* h_out) {
-    int rc = prepare_args("dconv", h_descs, h_out, n, cfg_request);
-    if (rc) return rc;
-    std::vector<fcn_rconv_desc> wide;
-    wide.reserve((size_t)n);
-    for (int i = 0; i < n; ++i) wide.push_back(widen(h_descs[i]));
-    fcn_rconv_plan plan;
-    rc = prepare("dconv", wide.data(), n, d_workspace, &plan);
-    if (rc) return rc;
-    *h_out = fcn_dconv_plan{plan.d_probs, plan.n, plan.cfg, plan.grid_x, plan.grid_y, plan.total_tiles};
-    return 0;
-}
-
-int fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s) { return launch("rconv", h_plan ? *h_plan : fcn_rconv_plan{}, s); }
-int fcn_dconv2d_f32(const fcn_dconv_plan* h_plan, fcn_stream_t s) {
-    const fcn_dconv_plan p = h_plan ? *h_plan : fcn_dconv_plan{};
-    return launch("dconv", fcn_rconv_plan{p.d_probs, p.n, p.cfg, p.grid_x, p.grid_y, p.total_tiles}, s);
-}
-
-size_t fcn_rconv2d_wgrad_workspace_floats(const fcn_rconv_desc* h_d) { return wgrad_workspace_floats("rconv", h_d); }
-size_t fcn_dconv2d_wgrad_workspace_floats(const fcn_dconv_desc* h_d) {
-    if (!h_d) return 0;
-    const fcn_rconv_desc wide = widen(*h_d);
-    return wgrad_workspace_floats("dconv", &wide);
-}
-
-int fcn_rconv2d_wgrad_f32(const fcn_rconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s) {
-    return wgrad("rconv", h_d, dw, db, d_workspace, s);
-}
-int fcn_dconv2d_wgrad_f32(const fcn_dconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s) {
-    if (!h_d) return wgrad("dconv", nullptr, dw, db, d_workspace, s);
-    const fcn_rconv_desc wide = widen(*h_d);
-    return wgrad("dconv", &wide, dw, db, d_workspace, s);
 }
 
 }  // extern "C"

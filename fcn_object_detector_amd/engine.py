@@ -116,22 +116,9 @@ def tconv_desc(a: "Blob", b: "Blob", g: ConvGeom, bank: int, bias: Optional[int]
     return d
 
 
-def dconv_desc(x: "Blob", y: "Blob", g: ConvGeom, dilation: int, w: Optional[int] = None, bias: Optional[int] = None,
-               flags: int = 0) -> L.DConvDesc:
-    """fcn_dconv_desc: the dilated convolution `g` reading the view x through the OHWI bank w and writing the view y - activations
-    (forward) or gradients (the data-gradient pass on the flipped bank, the weight gradient with y = dY)."""
-    d = L.DConvDesc()
-    d.x, d.w, d.bias, d.y = x.ptr, w, bias, y.buf.ptr
-    d.N, d.H, d.W, d.Cin, d.x_cstride = g.n, g.h, g.w, g.cin, x.cstride
-    d.Cout, d.kh, d.kw, d.pad, d.stride, d.OH, d.OW = g.cout, g.k, g.k, g.pad, g.s, g.oh, g.ow
-    d.y_cstride, d.y_coffset = y.cstride, y.coffset
-    d.flags, d.dilation = flags, dilation
-    return d
-
-
 class RectGeom(namedtuple("RectGeom", "n cin h w cout oh ow kh kw sh sw ph pw d")):
-    """The geometry of a rectangular Convolution (csrc/rconv.hip): input n x cin x h x w, output n x cout x oh x ow, kernel kh x kw at
-    strides (sh, sw) with pads (ph, pw) and one dilation d for both axes."""
+    """The geometry of a rectangular or dilated Convolution (csrc/rconv.hip): input n x cin x h x w, output n x cout x oh x ow, kernel
+    kh x kw at strides (sh, sw) with pads (ph, pw) and one dilation d for both axes.  A square dilated layer has equal axes."""
     __slots__ = ()
 
     @property
@@ -148,7 +135,7 @@ class RectGeom(namedtuple("RectGeom", "n cin h w cout oh ow kh kw sh sw ph pw d"
 
 
 def rconv_desc(x: "Blob", y: "Blob", g: RectGeom, w: Optional[int] = None, bias: Optional[int] = None, flags: int = 0) -> L.RConvDesc:
-    """fcn_rconv_desc: the rectangular convolution `g` reading the view x through the OHWI bank w and writing the view y - activations
+    """fcn_rconv_desc: the rectangular or dilated convolution `g` reading the view x through the OHWI bank w and writing the view y - activations
     (forward) or gradients (the data-gradient pass on the flipped bank, the weight gradient with y = dY)."""
     d = L.RConvDesc()
     d.x, d.w, d.bias, d.y = x.ptr, w, bias, y.buf.ptr
@@ -312,15 +299,14 @@ class ConvTask:
 @dataclass(eq=False)
 class OpTask:
     """Any other layer (or fused run of layers) that launches something: its ops; pool_desc if it is a MAX pooling that can
-    ride in a convolution launch; dconv if it is a dilated Convolution (its ops are made when its level is emitted: the dilated
-    convolutions of one level that read one bottom share a launch)."""
+    ride in a convolution launch; rconv if it is a dilated or rectangular Convolution (its ops are made when its level is emitted:
+    those of one level that read one bottom share a launch, _emit_rconvs)."""
     layer: Layer
     ops: List[Op]
     reads: List[Range]
     writes: List[Range]
     pool_desc: Optional[L.PoolDesc] = None
-    dconv: Optional[L.DConvDesc] = None
-    rconv: Optional[L.RConvDesc] = None      # a rectangular Convolution: as dconv, through csrc/rconv.hip
+    rconv: Optional[L.RConvDesc] = None      # a dilated or rectangular Convolution (csrc/rconv.hip)
     dwconv: Optional[L.DwConvDesc] = None    # a depthwise Convolution (csrc/dwconv.hip): the descriptor its one op launches
 
 
@@ -784,11 +770,8 @@ class Engine:
             if spec.is_depthwise(l):
                 tasks.append(self._dwconv_task(li, l, skip))
                 continue
-            if t == "Convolution" and is_rectangular(l):
+            if t == "Convolution" and (is_rectangular(l) or layer_dilation(l) > 1):
                 tasks.append(self._rconv_task(li, l, skip))
-                continue
-            if t == "Convolution" and layer_dilation(l) > 1:
-                tasks.append(self._dconv_task(li, l, skip))
                 continue
             if t == "Convolution":
                 top = l.tops[0]
@@ -853,28 +836,23 @@ class Engine:
         order = sorted(range(len(tasks)), key=lambda i: (levels[i], 1 if isinstance(tasks[i], ConvTask) else 0, i))
         pending: List[ConvTask] = []
         pending_pools: List[OpTask] = []
-        pending_dconvs: List[OpTask] = []
         pending_rconvs: List[OpTask] = []
         cur = None
         for i in order:
             if levels[i] != cur:
-                self._emit_dconvs(pending_dconvs)
                 self._emit_rconvs(pending_rconvs)
                 self._emit_convs(pending, pending_pools, tail)
-                pending, pending_dconvs, pending_rconvs, cur = [], [], [], levels[i]
+                pending, pending_rconvs, cur = [], [], levels[i]
             if tail is not None and any(tasks[i] is ht for ht in tail["heads"]):
                 continue      # evaluated by the launches that produce its input
             if isinstance(tasks[i], ConvTask):
                 pending.append(tasks[i])
             elif tasks[i].pool_desc is not None and self.fuse and self.group_convs:
                 pending_pools.append(tasks[i])
-            elif tasks[i].dconv is not None:
-                pending_dconvs.append(tasks[i])
             elif tasks[i].rconv is not None:
                 pending_rconvs.append(tasks[i])
             else:
                 self.ops.extend(tasks[i].ops)
-        self._emit_dconvs(pending_dconvs)
         self._emit_rconvs(pending_rconvs)
         self._emit_convs(pending, pending_pools, tail)
         self.levels = max(levels) + 1 if levels else 0
@@ -1077,45 +1055,6 @@ class Engine:
         l = self.spec.detection_blobs[name]
         return SSD.compose_detections(raw, min(max(count, 0), cap), self.shapes[l.bottoms[0]][0])
 
-    def _dconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
-        """A Convolution with dilation > 1: a problem of csrc/rconv.hip through fcn_dconv2d_*, not of the tiled family.  The bank is the
-        layer's parameter blob where it lies; an in-place ReLU behind the layer rides in the epilogue."""
-        dil = layer_dilation(l)
-        if self.f16:
-            raise NotImplementedError("f16 engine: Convolution %s with dilation %d has no half-float kernel" % (l.name, dil))
-        if self._conv_groups(l) > 1:
-            raise NotImplementedError("Convolution %s: group %d together with dilation %d" % (l.name, self._conv_groups(l), dil))
-        g = self._geom(l)
-        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        if xb.coffset % 4 or xb.cstride % 4:
-            raise NotImplementedError("dilated Convolution %s: input view is not 16-byte aligned" % l.name)
-        relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_dconv_desc has no second output for a Sigmoid)
-        self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
-        pd = self.params_dev[l.name]
-        d = dconv_desc(xb, yb, g, dil, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, L.CONV_RELU if relu else 0)
-        return OpTask(l, [], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], dconv=d)
-
-    def _emit_dconvs(self, items: List[OpTask]) -> None:
-        """The dilated convolutions of one level: those that read the same bottom (the four branches of an ASPP head) share ONE
-        fcn_dconv2d_prepare plan and launch.  FLOPs and bytes are booked as a ConvTask's."""
-        lib = L.load()
-        by_bottom: Dict[Range, List[OpTask]] = {}
-        for it in items:
-            by_bottom.setdefault(it.reads[0], []).append(it)
-        for chunk in by_bottom.values():
-            arr = (L.DConvDesc * len(chunk))(*[it.dconv for it in chunk])
-            ws = DeviceBuffer(int(lib.fcn_dconv2d_workspace_bytes(arr, len(chunk))), zero=False)
-            plan = L.DConvPlan()
-            L.call("fcn_dconv2d_prepare", arr, len(chunk), ws.ptr, -1, C.byref(plan))
-            self._keep.extend([arr, ws, plan])
-            flops = byts = 0.0
-            for it in chunk:
-                g = self._geom(it.layer)
-                flops += g.flops
-                byts += 4.0 * (g.n * g.cin * g.h * g.w + g.n * g.cout * g.oh * g.ow + g.cout * g.cin * g.k * g.k + g.cout)
-            label = "%s [d%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join(str(it.dconv.dilation) for it in chunk), plan.total_tiles)
-            self.ops.append(Op("dconv", label, lambda st, p=plan: L.check(lib.fcn_dconv2d_f32(C.byref(p), st)), flops, byts))
-
     def _dwconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
         """A depthwise Convolution (NetSpec.is_depthwise): one pure launch of csrc/dwconv.hip on the tap-major bank, never a ConvTask -
         it stays out of the grouped launches and the tuner.  An in-place ReLU behind the layer rides in the epilogue.  In the
@@ -1138,19 +1077,20 @@ class Engine:
         return OpTask(l, [op], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], dwconv=d)
 
     def _rconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
-        """A Convolution whose axes differ in kernel, pad or stride (dilated or not): a problem of csrc/rconv.hip, never of the tiled
-        family or the tuner.  The bank is the layer's parameter blob where it lies; an in-place ReLU behind the layer rides in the
-        epilogue."""
-        kh, kw, sh, sw, ph, pw = layer_geometry(l)
-        what = "%dx%d stride %dx%d pad %dx%d" % (kh, kw, sh, sw, ph, pw)
+        """A Convolution whose axes differ in kernel, pad or stride (dilated or not), or a square one with dilation > 1 (the case with
+        equal axes): a problem of csrc/rconv.hip, never of the tiled family or the tuner.  The bank is the layer's parameter blob where
+        it lies; an in-place ReLU behind the layer rides in the epilogue."""
+        rect, dil, ng = is_rectangular(l), layer_dilation(l), self._conv_groups(l)
+        who = "rectangular Convolution %s (%dx%d stride %dx%d pad %dx%d)" % (l.name, *layer_geometry(l)) if rect else \
+            "Convolution %s with dilation %d" % (l.name, dil)
         if self.f16:
-            raise NotImplementedError("f16 engine: rectangular Convolution %s (%s) has no half-float kernel" % (l.name, what))
-        if self._conv_groups(l) > 1:
-            raise NotImplementedError("rectangular Convolution %s (%s): group %d" % (l.name, what, self._conv_groups(l)))
+            raise NotImplementedError("f16 engine: %s has no half-float kernel" % who)
+        if ng > 1:
+            raise NotImplementedError("%s: group %d" % (who, ng) if rect else "Convolution %s: group %d together with dilation %d" % (l.name, ng, dil))
         g = self._rgeom(l)
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
         if xb.coffset % 4 or xb.cstride % 4:
-            raise NotImplementedError("rectangular Convolution %s: input view is not 16-byte aligned" % l.name)
+            raise NotImplementedError("%s Convolution %s: input view is not 16-byte aligned" % ("rectangular" if rect else "dilated", l.name))
         relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_rconv_desc has no second output for a Sigmoid)
         self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
         pd = self.params_dev[l.name]
@@ -1158,21 +1098,24 @@ class Engine:
         return OpTask(l, [], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], rconv=d)
 
     def _emit_rconvs(self, items: List[OpTask]) -> None:
-        """The rectangular convolutions of one level: those that read the same bottom (the 1x3 / 3x1 pair of an 8-grid Inception
-        module) share ONE fcn_rconv2d_prepare plan and launch.  FLOPs are booked as 2 N OH OW Cin Cout kh kw."""
+        """The dilated and rectangular convolutions of one level: the square dilated ones that read the same bottom (the four branches
+        of an ASPP head) share ONE fcn_rconv2d_prepare plan and launch, op kind "dconv", the label shows the dilations; so do the
+        rectangular ones (the 1x3 / 3x1 pair of an 8-grid Inception module), op kind "rconv", the label shows the kernels.  Square
+        launches come first.  FLOPs are booked as 2 N OH OW Cin Cout kh kw."""
         lib = L.load()
-        by_bottom: Dict[Range, List[OpTask]] = {}
+        groups: Dict[Tuple[bool, Range], List[OpTask]] = {}
         for it in items:
-            by_bottom.setdefault(it.reads[0], []).append(it)
-        for chunk in by_bottom.values():
+            groups.setdefault((is_rectangular(it.layer), it.reads[0]), []).append(it)
+        for (rect, _), chunk in sorted(groups.items(), key=lambda kv: kv[0][0]):
             arr = (L.RConvDesc * len(chunk))(*[it.rconv for it in chunk])
             ws = DeviceBuffer(int(lib.fcn_rconv2d_workspace_bytes(arr, len(chunk))), zero=False)
             plan = L.RConvPlan()
             L.call("fcn_rconv2d_prepare", arr, len(chunk), ws.ptr, -1, C.byref(plan))
             self._keep.extend([arr, ws, plan])
             geoms = [self._rgeom(it.layer) for it in chunk]
-            label = "%s [%s %dwg]" % ("+".join(it.layer.name for it in chunk), ",".join("%dx%d" % (g.kh, g.kw) for g in geoms), plan.total_tiles)
-            self.ops.append(Op("rconv", label, lambda st, p=plan: L.check(lib.fcn_rconv2d_f32(C.byref(p), st)),
+            shows = ",".join("%dx%d" % (g.kh, g.kw) for g in geoms) if rect else "d" + ",".join(str(g.d) for g in geoms)
+            label = "%s [%s %dwg]" % ("+".join(it.layer.name for it in chunk), shows, plan.total_tiles)
+            self.ops.append(Op("rconv" if rect else "dconv", label, lambda st, p=plan: L.check(lib.fcn_rconv2d_f32(C.byref(p), st)),
                                sum(g.flops for g in geoms), sum(g.bytes for g in geoms)))
 
     def _emit_group(self, chunk: List[ConvTask], fused: List[OpTask], tail: Optional[dict]) -> None:

@@ -62,25 +62,8 @@ class TConvPlan(C.Structure):
                 ("total_tiles", C.c_int32)]
 
 
-class DConvDesc(C.Structure):
-    """fcn_dconv_desc: dilated convolution (forward, data gradient on the flipped bank, weight gradient)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p),
-        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("x_cstride", C.c_int32),
-        ("Cout", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32), ("pad", C.c_int32), ("stride", C.c_int32),
-        ("OH", C.c_int32), ("OW", C.c_int32),
-        ("y_cstride", C.c_int32), ("y_coffset", C.c_int32), ("y2_cstride", C.c_int32), ("y2_coffset", C.c_int32),
-        ("flags", C.c_int32), ("dilation", C.c_int32),
-    ]
-
-
-class DConvPlan(C.Structure):
-    _fields_ = [("d_probs", C.c_void_p), ("n", C.c_int32), ("cfg", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32),
-                ("total_tiles", C.c_int32)]
-
-
 class RConvDesc(C.Structure):
-    """fcn_rconv_desc: rectangular convolution, geometry per axis (forward, data gradient on the flipped bank, weight gradient)."""
+    """fcn_rconv_desc: rectangular or dilated convolution, geometry per axis (forward, data gradient on the flipped bank, weight gradient)."""
     _fields_ = [
         ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p),
         ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("x_cstride", C.c_int32),
@@ -331,12 +314,6 @@ PROTOTYPES = {
     "fcn_tconv_bank_floats": (_sz, [_i, _i, _i, _i]),
     "fcn_tconv_bank_pack_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fcn_channel_sum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "fcn_dconv2d_num_configs": (_i, []),
-    "fcn_dconv2d_workspace_bytes": (_sz, [C.POINTER(DConvDesc), _i]),
-    "fcn_dconv2d_prepare": (_i, [C.POINTER(DConvDesc), _i, _vp, _i, C.POINTER(DConvPlan)]),
-    "fcn_dconv2d_f32": (_i, [C.POINTER(DConvPlan), _vp]),
-    "fcn_dconv2d_wgrad_workspace_floats": (_sz, [C.POINTER(DConvDesc)]),
-    "fcn_dconv2d_wgrad_f32": (_i, [C.POINTER(DConvDesc), _vp, _vp, _vp, _vp]),
     "fcn_rconv2d_num_configs": (_i, []),
     "fcn_rconv2d_workspace_bytes": (_sz, [C.POINTER(RConvDesc), _i]),
     "fcn_rconv2d_prepare": (_i, [C.POINTER(RConvDesc), _i, _vp, _i, C.POINTER(RConvPlan)]),

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FCN_ABI_VERSION 1
+#define FCN_ABI_VERSION 2
 
 /* argument-validation codes (positive returns) */
 #define FCN_E_ARG       1   /* null pointer / non-positive extent            */
@@ -643,11 +643,14 @@ int    fcn_tconv_bank_pack_f32(const float* w, float* packed, int Ca, int Cb, in
  * sums ITS y, which after the role swap is the layer's input).  One workgroup per channel, fixed order: bit-reproducible. */
 int    fcn_channel_sum_f32(const float* dy, float* db, int pixels, int C, int cstride, int coffset, fcn_stream_t s);
 
-/* ---- dilated ("atrous") convolution: Caffe ConvolutionLayer with convolution_param { dilation: d } (DeepLab-LargeFOV conv5_* / fc6,
- *      the DeepLab-v2 ASPP branches), forward, data gradient and weight gradient.  NHWC float32, exact f32 on the matrix cores
- *      (v_mfma_f32_32x32x2_f32).  With zeros outside the image:
- *        y[n, oy, ox, co] = bias[co] + sum over ci, r, q of w[co][r][q][ci] * x[n, oy*stride - pad + r*dil, ox*stride - pad + q*dil, ci]
- *        OH = (H + 2 pad - (dil*(kh-1) + 1)) / stride + 1     (floor; likewise OW)
+/* ---- per-axis ("rectangular") and dilated ("atrous") convolution: Caffe ConvolutionLayer whose two spatial axes differ in kernel
+ *      extent, pad or stride (kernel_h / kernel_w, pad_h / pad_w, stride_h / stride_w: the 1x7 / 7x1 and 1x3 / 3x1 pairs of
+ *      Inception-v3 / v4, the k x 1 + 1 x k pairs of ENet / ERFNet), and Caffe ConvolutionLayer with convolution_param { dilation: d }
+ *      (DeepLab-LargeFOV conv5_* / fc6, the DeepLab-v2 ASPP branches): a square dilated layer is the case with equal axes (kh = kw,
+ *      pad_h = pad_w, stride_h = stride_w).  Forward, data gradient and weight gradient, with one dilation for both axes.  NHWC
+ *      float32, exact f32 on the matrix cores (v_mfma_f32_32x32x2_f32).  With zeros outside the image:
+ *        y[n, oy, ox, co] = bias[co] + sum over ci, r, q of w[co][r][q][ci] * x[n, oy*stride_h - pad_h + r*dil, ox*stride_w - pad_w + q*dil, ci]
+ *        OH = (H + 2 pad_h - (dil*(kh-1) + 1)) / stride_h + 1     (floor)        OW likewise with kw, pad_w, stride_w
  *      The bank is the Convolution's parameter blob as the engine keeps it, [Cout][kh][kw][round4(Cin)] with Cin contiguous: no
  *      repacking.  All problems of a plan run in ONE launch (the four ASPP branches read one blob with four dilations).  Every output
  *      element is written by exactly one lane, the contraction is never split across lanes that meet in memory, there are no float
@@ -656,64 +659,8 @@ int    fcn_channel_sum_f32(const float* dy, float* db, int pixels, int C, int cs
  *      fcn_tconv_desc; y2 is only read (FCN_CONV_MASK).  Channels Cin .. round4(Cin)-1 of `x` are padding and are never multiplied
  *      (they may hold anything: the rule of fcn_tconv_desc, not of the dense kernels); channels of y outside [y_coffset, y_coffset + Cout)
  *      are not touched.  16-byte stores when y (y2) is 16-byte aligned with strides / offsets in multiples of 4, scalar stores otherwise
- *      and for a last partial group.  dilation >= 1; dilation == 1 is legal and equals the dense convolution.
- *      The data gradient of a stride-1 layer is the same kernel on dY with the flipped bank of fcn_conv_weights_flip_batch_f32 (the flip
- *      does not depend on the dilation), pad' = dil*(k-1) - pad, the same dilation, and FCN_CONV_ACCUM / FCN_CONV_MASK as the dense
- *      data-gradient passes use them.
- *      Refused on the host before any launch: FCN_E_ARG (null pointer, non-positive extent, OH / OW not the value above, slice wider
- *      than its stride, FCN_CONV_MASK without y2), FCN_E_ALIGN (x_cstride not a multiple of 4 or below round4(Cin); x / w not 16-byte
- *      aligned), FCN_E_UNSUPPORTED (other flags, dilation < 1, tensors past 2^31 elements). ---- */
-typedef struct fcn_dconv_desc {
-    const float* x;      /* NHWC input, channel stride x_cstride (a multiple of 4, >= round4(Cin))               */
-    const float* w;      /* weights [Cout][kh][kw][round4(Cin)]  (OHWI, Cin contiguous, 16-byte aligned)         */
-    const float* bias;   /* [Cout] or NULL                                                                       */
-    float*       y;      /* NHWC output; channel co of pixel m at y[m*y_cstride + y_coffset + co]                */
-    float*       y2;     /* FCN_CONV_MASK: the activation whose sign masks the result (same indexing via y2_*)   */
-    int32_t N, H, W, Cin, x_cstride;
-    int32_t Cout, kh, kw, pad, stride, OH, OW;
-    int32_t y_cstride, y_coffset, y2_cstride, y2_coffset;
-    int32_t flags;
-    int32_t dilation;
-} fcn_dconv_desc;
-typedef struct fcn_dconv_plan {
-    void*   d_probs;
-    int32_t n;
-    int32_t cfg;          /* tile configuration chosen by prepare() */
-    int32_t grid_x, grid_y;
-    int32_t total_tiles;
-} fcn_dconv_plan;
-/* number of tile configurations (cfg_request: -1 = built-in choice, 0 .. count-1); one today: 64 pixels x 64 channels x 16 k */
-int    fcn_dconv2d_num_configs(void);
-size_t fcn_dconv2d_workspace_bytes(const fcn_dconv_desc* h_descs, int n);
-/* validates and uploads n problems into d_workspace with a synchronous copy (plan time, not inside a graph capture); the
- * workspace must stay alive as long as the plan is used */
-int    fcn_dconv2d_prepare(const fcn_dconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_dconv_plan* h_out);
-/* one pure kernel launch for all problems of the plan: capturable */
-int    fcn_dconv2d_f32(const fcn_dconv_plan* h_plan, fcn_stream_t s);
-/* Weight / bias gradient, the contract of fcn_conv2d_wgrad_f32: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY
- * (d->w, d->bias, d->y2 and d->flags are ignored).  dw is [Cout][kh][kw][round4(Cin)], 16-byte aligned, and is OVERWRITTEN; its pad
- * columns Cin .. round4(Cin)-1 are written as exact zeros (the solver, clipping and weight decay run over the packed buffer as it is).
- * db is [Cout] or NULL.  The reduction runs over the pixels on the matrix cores; with more than one pixel split every split writes a
- * slab of the workspace (fcn_dconv2d_wgrad_workspace_floats() floats, 16-byte aligned; 0 = none needed, NULL allowed) and a second
- * small launch adds the slabs in ascending order and sums db: bit-reproducible, no atomics.  Nothing outside dw / db / the workspace
- * is written. */
-size_t fcn_dconv2d_wgrad_workspace_floats(const fcn_dconv_desc* h_d);
-int    fcn_dconv2d_wgrad_f32(const fcn_dconv_desc* h_d, float* dw, float* db, float* d_workspace, fcn_stream_t s);
-
-/* ---- rectangular convolution: Caffe ConvolutionLayer whose two spatial axes differ in kernel extent, pad or stride (kernel_h / kernel_w,
- *      pad_h / pad_w, stride_h / stride_w: the 1x7 / 7x1 and 1x3 / 3x1 pairs of Inception-v3 / v4, the k x 1 + 1 x k pairs of ENet /
- *      ERFNet), forward, data gradient and weight gradient, with one dilation for both axes.  NHWC float32, exact f32 on the matrix
- *      cores (v_mfma_f32_32x32x2_f32).  With zeros outside the image:
- *        y[n, oy, ox, co] = bias[co] + sum over ci, r, q of w[co][r][q][ci] * x[n, oy*stride_h - pad_h + r*dil, ox*stride_w - pad_w + q*dil, ci]
- *        OH = (H + 2 pad_h - (dil*(kh-1) + 1)) / stride_h + 1     (floor)        OW likewise with kw, pad_w, stride_w
- *      The contract is that of the dilated convolution above.  The bank is the Convolution's parameter blob as the engine keeps it,
- *      [Cout][kh][kw][round4(Cin)] with Cin contiguous: no repacking.  All problems of a plan run in ONE launch.  Every output element
- *      is written by exactly one lane, there are no float atomics, a second launch gives the same bits.
- *      flags: FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK, applied in the order accumulate, ReLU, mask; y2 is only read
- *      (FCN_CONV_MASK).  Channels Cin .. round4(Cin)-1 of `x` are padding and are never multiplied (they may hold anything); channels
- *      of y outside [y_coffset, y_coffset + Cout) are not touched.  16-byte stores when y (y2) is 16-byte aligned with strides /
- *      offsets in multiples of 4, scalar stores otherwise and for a last partial group.  dilation >= 1.  A square problem (equal
- *      extents, pads and strides) is legal and equals the dense convolution.
+ *      and for a last partial group.  dilation >= 1; a square problem (equal extents, pads and strides) with dilation == 1 is legal
+ *      and equals the dense convolution.
  *      The data gradient of a layer with stride_h == stride_w == 1 is the same kernel on dY with the flipped bank of
  *      fcn_conv_weights_flip_batch_f32 (which takes kh and kw separately), pad_h' = dil*(kh-1) - pad_h, pad_w' = dil*(kw-1) - pad_w, the
  *      same dilation, and FCN_CONV_ACCUM / FCN_CONV_MASK as the dense data-gradient passes use them.
@@ -750,9 +697,10 @@ size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n);
 int    fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out);
 /* one pure kernel launch for all problems of the plan: capturable */
 int    fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s);
-/* Weight / bias gradient, the contract of fcn_dconv2d_wgrad_f32: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY
+/* Weight / bias gradient, the contract of fcn_conv2d_wgrad_f32: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY
  * (d->w, d->bias, d->y2 and d->flags are ignored).  dw is [Cout][kh][kw][round4(Cin)], 16-byte aligned, and is OVERWRITTEN; its pad
- * columns Cin .. round4(Cin)-1 are written as exact zeros.  db is [Cout] or NULL.  With more than one pixel split every split writes a
+ * columns Cin .. round4(Cin)-1 are written as exact zeros (the solver, clipping and weight decay run over the packed buffer as it is).
+ * db is [Cout] or NULL.  The reduction runs over the pixels on the matrix cores; with more than one pixel split every split writes a
  * slab of the workspace (fcn_rconv2d_wgrad_workspace_floats() floats, 16-byte aligned; 0 = none needed, NULL allowed) and a second
  * small launch adds the slabs in ascending order and sums db: bit-reproducible, no atomics.  Nothing outside dw / db / the workspace
  * is written. */

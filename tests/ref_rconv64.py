@@ -1,5 +1,6 @@
-"""float64 reference of the rectangular convolution, its data gradient and its weight gradient, written from the definition (a loop
-over the filter taps, einsum over the channels).  It shares no code with csrc/rconv.hip, which it checks.
+"""float64 reference of the rectangular (and, with equal axes, the square dilated) convolution, its data gradient and its weight
+gradient, written from the definition (a loop over the filter taps, einsum over the channels).  It shares no code with
+csrc/rconv.hip, which it checks.
 
     y[n, o, i, j] = b[o] + sum over c, r, q of w[o, c, r, q] * x[n, c, i*sh - ph + r*d, j*sw - pw + q*d],   zeros outside the image
     OH = (H + 2 ph - (d (kh - 1) + 1)) // sh + 1,   OW = (W + 2 pw - (d (kw - 1) + 1)) // sw + 1

@@ -24,7 +24,7 @@ def test_symbol_and_prototype():
     res, args = L.PROTOTYPES["fcn_avepool_bwd_f32"]
     mres, margs = L.PROTOTYPES["fcn_maxpool_bwd_f32"]
     assert res is mres and args == margs[:1] + margs[2:]      # the argument list of fcn_maxpool_bwd_f32 minus idx
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
 
 
 def test_the_sample_geometry_is_a_valid_one():

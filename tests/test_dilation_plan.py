@@ -89,34 +89,34 @@ def stub(monkeypatch):
 def test_forward_tasks_and_the_shared_launch(stub):
     e = stub(TEST_NET)
     assert [t.layer.name for t in e.tasks if isinstance(t, E.ConvTask)] == ["c0"]
-    dt = {t.layer.name: t for t in e.tasks if isinstance(t, E.OpTask) and t.dconv is not None}
+    dt = {t.layer.name: t for t in e.tasks if isinstance(t, E.OpTask) and t.rconv is not None}
     assert sorted(dt) == ["a2", "a4", "b3"] and all(t.ops == [] for t in dt.values())
     assert "ra2" not in [t.layer.name for t in e.tasks]                     # the in-place ReLU rides in a2's epilogue
     assert e._conv_layer_meta["a2"] == dict(relu=True, sigmoid_top=None) and e._conv_layer_meta["a4"]["relu"] is False
     x = e.blobs["c0"]
     for nm, dil, relu in (("a2", 2, True), ("a4", 4, False)):
-        d, y, pd = dt[nm].dconv, e.blobs[nm], e.params_dev[nm]
+        d, y, pd = dt[nm].rconv, e.blobs[nm], e.params_dev[nm]
         assert (d.x, d.Cin, d.x_cstride, d.N, d.H, d.W) == (x.ptr, 6, 8, 2, 12, 14)
         assert (d.y, d.Cout, d.y_coffset, d.y_cstride, d.OH, d.OW) == (y.buf.ptr, 8, y.coffset, y.cstride, 12, 14)
-        assert (d.kh, d.kw, d.pad, d.stride, d.dilation) == (3, 3, dil, 1, dil)
+        assert (d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w, d.dilation) == (3, 3, dil, dil, 1, 1, dil)
         assert d.w == pd[0].ptr and d.bias == (pd[1].ptr if len(pd) > 1 else None)      # the parameter blob where it lies: no repacking
         assert d.flags == (L.CONV_RELU if relu else 0)
         assert e.param_segs[(nm, 0)].shape == (8, 3, 3, 8)                               # [Cout][kh][kw][round4(Cin)]
-    d = dt["b3"].dconv
-    assert (d.stride, d.dilation, d.pad, d.OH, d.OW, d.Cin, d.Cout) == (2, 3, 1, 4, 5, 8, 5)      # (12 + 2 - 7) // 2 + 1, (14 + 2 - 7) // 2 + 1
+    d = dt["b3"].rconv
+    assert (d.stride_h, d.stride_w, d.dilation, d.pad_h, d.pad_w, d.OH, d.OW, d.Cin, d.Cout) == (2, 2, 3, 1, 1, 4, 5, 8, 5)      # (12 + 2 - 7) // 2 + 1, (14 + 2 - 7) // 2 + 1
     # a2 and a4 read one blob and wait for the same launch: one level, ONE prepare and one op; b3 waits for both
     lv = dict(zip([t.layer.name for t in e.tasks], E.task_levels(e.tasks)))
     assert lv["a2"] == lv["a4"] == lv["c0"] + 1 and lv["b3"] > lv["sum"] > lv["a2"]
     del e.fake.calls[:]
-    e._emit_dconvs([dt["a2"], dt["a4"]])
-    assert e.fake.calls.count("fcn_dconv2d_prepare") == 1 and len(e.ops) == 1
+    e._emit_rconvs([dt["a2"], dt["a4"]])
+    assert e.fake.calls.count("fcn_rconv2d_prepare") == 1 and len(e.ops) == 1
     op = e.ops[0]
     assert op.kind == "dconv" and op.name.startswith("a2+a4 [d2,4 ")
     assert op.flops == 2 * (2.0 * 2 * 12 * 14 * 6 * 8 * 9)                               # 2 N OH OW Cin Cout k k, each
     assert op.bytes == 4.0 * (2 * (2 * 6 * 168 + 2 * 8 * 168 + 8 * 6 * 9) + 8 + 8)
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_dconv2d_f32"
-    e._emit_dconvs([dt["b3"]])
+    assert e.fake.calls[-1] == "fcn_rconv2d_f32"
+    e._emit_rconvs([dt["b3"]])
     assert len(e.ops) == 2 and e.ops[1].flops == 2.0 * 2 * 4 * 5 * 8 * 5 * 9
 
 
@@ -141,13 +141,14 @@ def test_backward_plan_of_dilated_layers(stub):
     assert wop.layers == ["b3"] and wop.sel is None and "b3" in plan.wgrad_done
     assert wop.flops == 2.0 * 2 * 8 * 10 * 8 * 5 * 9                               # b3: pad 1, dilation 3 on 12 x 14 gives 8 x 10
     rec = plan.last_writer("sum")
-    assert isinstance(rec.launch, L.DConvPlan) and rec.targets == ["sum"]
+    assert isinstance(rec.launch, L.RConvPlan) and rec.targets == ["sum"]
     d = rec.descs[0]
     assert (d.x, d.Cin, d.x_cstride, d.H, d.W) == (G["b3"].ptr, 5, 8, 8, 10)             # dY of b3
     assert (d.y, d.Cout, d.y_coffset, d.y_cstride, d.OH, d.OW) == (G["sum"].buf.ptr, 8, 0, 8, 12, 14)
-    assert (d.w, d.kh, d.stride, d.dilation, d.pad, d.flags) == (plan.flip_flat.ptr + 4 * 2 * 6 * 9 * 8, 3, 1, 3, 3 * 2 - 1, 0)      # pad' = dil (k-1) - pad
+    assert (d.w, d.kh, d.kw, d.stride_h, d.stride_w, d.dilation, d.pad_h, d.pad_w, d.flags) == \
+        (plan.flip_flat.ptr + 4 * 2 * 6 * 9 * 8, 3, 3, 1, 1, 3, 3 * 2 - 1, 3 * 2 - 1, 0)      # pad' = dil (k-1) - pad
     wop.run(None)
-    assert e.fake.calls[-1] == "fcn_dconv2d_wgrad_f32"
+    assert e.fake.calls[-1] == "fcn_rconv2d_wgrad_f32"
     # a2 (fused ReLU: its mask first) and a4 both write the gradient of c0: the second one accumulates
     plan._eltwise(by["sum"])
     n0 = len(plan.ops)
@@ -156,13 +157,13 @@ def test_backward_plan_of_dilated_layers(stub):
     assert [(op.kind, op.name) for op in plan.ops[n0:]] == [("wgrad", "a4"), ("dconv_dgrad", "a4"), ("relu_bwd", "a2"), ("wgrad", "a2"),
                                                             ("dconv_dgrad", "a2")]
     first, last = plan.writers["c0"]
-    assert (first.descs[0].dilation, first.descs[0].pad, first.descs[0].flags) == (4, 4, 0)
-    assert (last.descs[0].dilation, last.descs[0].pad, last.descs[0].flags) == (2, 2, L.CONV_ACCUM)
+    assert (first.descs[0].dilation, first.descs[0].pad_h, first.descs[0].pad_w, first.descs[0].flags) == (4, 4, 4, 0)
+    assert (last.descs[0].dilation, last.descs[0].pad_h, last.descs[0].pad_w, last.descs[0].flags) == (2, 2, 2, L.CONV_ACCUM)
     # c0's own ReLU mask is folded into the LAST pass that writes its gradient, as for a dense pass
     plan._convolution(by["c0"])
     del e.fake.calls[:]
     plan._finish_dgrads()
-    assert e.fake.calls.count("fcn_dconv2d_prepare") == 3
+    assert e.fake.calls.count("fcn_rconv2d_prepare") == 3
     dl = last.descs[0]
     assert dl.flags == L.CONV_ACCUM | L.CONV_MASK and (dl.y2, dl.y2_cstride, dl.y2_coffset) == (B["c0"].buf.ptr, B["c0"].cstride, B["c0"].coffset)
     assert first.descs[0].flags == 0 and ("relu_bwd", "c0") not in [(op.kind, op.name) for op in plan.ops]

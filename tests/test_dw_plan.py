@@ -101,7 +101,7 @@ def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
     x = e.blobs["c0"]
     for nm, (kh, kw, ph, pw, dil), (oh, ow), relu in (("dwa", (3, 3, 1, 1, 1), (6, 7), True), ("dwb", (3, 5, 2, 4, 2), (6, 7), False)):
         t, d, y, pd = dt[nm], dt[nm].dwconv, e.blobs[nm], e.params_dev[nm]
-        assert isinstance(d, L.DwConvDesc) and t.dconv is None and t.rconv is None and t.pool_desc is None and len(t.ops) == 1
+        assert isinstance(d, L.DwConvDesc) and t.rconv is None and t.pool_desc is None and len(t.ops) == 1
         assert (d.x, d.C, d.x_cstride, d.N, d.H, d.W) == (x.ptr, 6, 8, 2, 12, 14)
         assert (d.y, d.y_coffset, d.y_cstride, d.OH, d.OW) == (y.buf.ptr, y.coffset, y.cstride, oh, ow)
         assert (d.kh, d.kw, d.pad_h, d.pad_w, d.stride_h, d.stride_w, d.dilation) == (kh, kw, ph, pw, 2, 2, dil)
@@ -130,7 +130,7 @@ def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
     del e.fake.calls[:]
     e._build_ops()
     assert [op.name for op in e.ops if op.kind == "dwconv"] == ["dwa [3x3]", "dwb [3x5]"]
-    assert not any(c in e.fake.calls for c in ("fcn_rconv2d_prepare", "fcn_dconv2d_prepare")) and e.fake.calls.count("fcn_conv2d_group_prepare") + \
+    assert "fcn_rconv2d_prepare" not in e.fake.calls and e.fake.calls.count("fcn_conv2d_group_prepare") + \
         e.fake.calls.count("fcn_conv2d_group_prepare_fused") == 2
 
 
@@ -228,8 +228,8 @@ def plan_signature(e):
         if isinstance(t, E.ConvTask):
             rec.update(desc=_fields(t.desc), flops=t.flops, bytes=t.bytes)
         else:
-            rec.update(ops=[[op.kind, op.name, op.flops, op.bytes] for op in t.ops], pool=_fields(t.pool_desc), dconv=_fields(t.dconv),
-                       rconv=_fields(t.rconv), dwconv=_fields(t.dwconv))
+            rec.update(ops=[[op.kind, op.name, op.flops, op.bytes] for op in t.ops], pool=_fields(t.pool_desc), rconv=_fields(t.rconv),
+                       dwconv=_fields(t.dwconv))
         out.append(rec)
     return out
 

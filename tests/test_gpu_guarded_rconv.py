@@ -1,10 +1,10 @@
-"""Guard-banded, poisoned-buffer parity of the rectangular convolution (csrc/rconv.hip) against the float64 reference
-(tests/ref_rconv64.py), -m gpu.  As in tests/test_gpu_guarded_dconv.py: every tensor lives in a guarded allocation, inputs are
+"""Guard-banded, poisoned-buffer parity of the rectangular and dilated convolution (csrc/rconv.hip) against the float64 reference
+(tests/ref_rconv64.py), -m gpu.  As in tests/test_gpu_guarded_tconv.py: every tensor lives in a guarded allocation, inputs are
 channel windows of wider pixels whose other channels (the pad channels Cin .. round4(Cin)-1 included) hold NaN, outputs are slices of
 poison-filled buffers; a case passes when the result meets the element-wise bound c * eps * K * magnitude, carries no poison, the
 neighbouring channels and the red zones are bit-identical afterwards, and a second launch gives the same bits.  Every case runs under
-every configuration 0 .. fcn_rconv2d_num_configs() - 1 as well as the built-in choice.  The dilated ABI (fcn_dconv2d_*) is a converter
-onto the same kernels: the last tests hold a square problem to the same bytes through either ABI."""
+every configuration 0 .. fcn_rconv2d_num_configs() - 1 as well as the built-in choice.  The rectangular cases come first; the square
+dilated ones (equal axes: the conv5 / fc6 layers of DeepLab-LargeFOV, the ASPP branches) follow."""
 import ctypes as C
 
 import numpy as np
@@ -14,7 +14,6 @@ import ref64
 import ref_rconv64 as R
 from fcn_object_detector_amd import lib as L
 from gpu_util import Guards, nchw, pack_ohwi, poison_free, poisoned, poisoned_nhwc, slice_untouched
-from test_gpu_guarded_dconv import dconv_desc, launch as dconv_launch
 
 pytestmark = pytest.mark.gpu
 
@@ -199,12 +198,10 @@ def flipped_on_device(g, wt):
     return td
 
 
-@pytest.mark.parametrize("k,pad,dil,flags", [((1, 7), (0, 3), 1, ""), ((7, 1), (3, 0), 1, "MASK"), ((1, 7), (0, 2), 1, "ACCUM"),
-                                             ((3, 1), (2, 0), 2, "ACCUM+MASK"), ((2, 3), (0, 2), 2, "")])
-def test_data_gradient_through_the_flipped_bank(g, k, pad, dil, flags):
+def run_dgrad(g, seed, k, pad, dil, flags):
     """dX of a stride-1 layer: the same kernel on dY with the flipped bank, ph' = d (kh-1) - ph, pw' = d (kw-1) - pw, the same dilation;
     MASK reads the activation of the blob below from a slice with poisoned neighbours and leaves it bit-identical."""
-    rng = np.random.default_rng(11 + dil + k[0])
+    rng = np.random.default_rng(seed)
     n, ci, co, h, w = 2, 6, 9, 12, 10
     wt = rng.standard_normal((co, ci) + k).astype(np.float32)
     oh, ow = R.out_hw(h, w, k[0], k[1], pad, (1, 1), dil)
@@ -234,6 +231,12 @@ def test_data_gradient_through_the_flipped_bank(g, k, pad, dil, flags):
         if "MASK" in flags:
             assert np.array_equal(y2d.read(y2_img.shape).view(np.uint32), y2_img.view(np.uint32)), "y2 was written"
     assert dyd.unchanged(), "dY was written"
+
+
+@pytest.mark.parametrize("k,pad,dil,flags", [((1, 7), (0, 3), 1, ""), ((7, 1), (3, 0), 1, "MASK"), ((1, 7), (0, 2), 1, "ACCUM"),
+                                             ((3, 1), (2, 0), 2, "ACCUM+MASK"), ((2, 3), (0, 2), 2, "")])
+def test_data_gradient_through_the_flipped_bank(g, k, pad, dil, flags):
+    run_dgrad(g, 11 + dil + k[0], k, pad, dil, flags)
 
 
 def run_wgrad(g, seed, n, ci, co, h, w, k, s, pad, dil, dycs=None, dyco=0, xcs=None, xco=0, with_db=True, min_splits=1, max_splits=None):
@@ -296,83 +299,102 @@ def test_weight_gradient_over_several_pixel_splits(g):
     run_wgrad(g, 42, 2, 6, 5, 23, 25, (3, 1), (1, 1), (2, 0), 2, dycs=12, dyco=4, min_splits=2)
 
 
-# ---- one kernel family behind two ABIs: a square problem gives the same bytes through fcn_dconv2d_* and through fcn_rconv2d_* with
-#      equal axes.  N = 2 on 9 x 11 is 198 pixels: four pixel blocks, the last one partial, tiles crossing row ends and the image
-#      boundary; Cout 70 is a second channel tile whose last group holds two channels; Cin 6 leaves two pad channels of NaN.
-def same_bytes_forward(g, xd, wd, bd, y0, n, h, w, ci, xcs, co, k, pad, s, dil, ycs, yco, flags=0, y2d=None, y2cs=0, y2co=0):
-    """The same device inputs through both ABIs, each into a fresh guarded copy of the image y0; whole pixels are compared, the
-    channels outside the slice included."""
-    oh, ow = R.out_hw(h, w, k, k, (pad, pad), (s, s), dil)
-    assert y0.shape == (n, oh, ow, ycs)
-    head = (xd.ptr, wd.ptr, bd.ptr if bd is not None else None)
-    tail = (dil, oh, ow, ycs, yco, flags, y2d.ptr if y2d is not None else None, y2cs, y2co)
-    yd = g.put(y0, at_end=True, name="y through dconv")
-    dconv_launch(g, [dconv_desc(*head, yd.ptr, n, h, w, ci, xcs, co, k, pad, s, *tail)])
-    yr = g.put(y0, at_end=True, name="y through rconv")
-    launch(g, [rconv_desc(*head, yr.ptr, n, h, w, ci, xcs, co, (k, k), (pad, pad), (s, s), *tail)])
-    got_d, got_r = yd.read(y0.shape), yr.read(y0.shape)
-    assert poison_free(nchw(got_d, co, yco)) and slice_untouched(got_d, yco, co)
-    assert got_d.tobytes() == got_r.tobytes(), "a square problem differs between fcn_dconv2d_f32 and fcn_rconv2d_f32"
-    assert xd.unchanged() and wd.unchanged()
+# ---- square dilated layers: the problem with equal axes.  sq_fwd / sq_wgrad take one kernel extent, pad and stride for both.
+def sq_fwd(g, seed, n, ci, co, h, w, k, s, pad, dil, **kw):
+    run_fwd(g, seed, n, ci, co, h, w, (k, k), (s, s), (pad, pad), dil, **kw)
 
 
-@pytest.mark.parametrize("s,flags,ycs,yco", [(1, "", 72, 0), (2, "", 72, 0), (1, "RELU+ACCUM+MASK", 80, 4)], ids=["s1", "s2", "s1-relu-accum-mask-slice"])
-def test_square_forward_same_bytes_through_either_abi(g, s, flags, ycs, yco):
-    rng = np.random.default_rng(50 + s + len(flags))
-    n, h, w, ci, co, k, dil, pad = 2, 9, 11, 6, 70, 3, 2, 2
+def sq_wgrad(g, seed, n, ci, co, h, w, k, s, pad, dil, **kw):
+    run_wgrad(g, seed, n, ci, co, h, w, (k, k), (s, s), (pad, pad), dil, **kw)
+
+
+# k, dilation, pad, stride, (H, W)
+SQUARE_GEOMETRIES = [(3, 2, 2, 1, (7, 9)), (3, 12, 12, 1, (5, 6)), (3, 4, 0, 1, (11, 13)), (5, 2, 4, 1, (9, 10)), (2, 3, 0, 1, (8, 7)),
+                     (1, 3, 0, 1, (6, 5)), (3, 2, 1, 2, (11, 9)), (3, 3, 2, 2, (13, 11))]
+
+
+@pytest.mark.parametrize("k,dil,pad,s,hw", SQUARE_GEOMETRIES)
+def test_square_dilated_forward_geometries(g, k, dil, pad, s, hw):
+    """Cin 5 (a pad channel of NaN), Cout 7 (a scalar tail); the far taps of d12 lie in the padding for most pixels."""
+    sq_fwd(g, 7 * k + dil, 1, 5, 7, hw[0], hw[1], k, s, pad, dil)
+    sq_fwd(g, 9 * k + dil, 2, 3, 6, hw[0], hw[1], k, s, pad, dil, xcs=12, xco=4, ycs=16, yco=4)
+
+
+def test_dilation_one_equals_the_dense_convolution(g):
+    """(equal axes and dilation 1: the launches of test_a_square_problem_equals_the_dense_convolution, kept as the dilated cases' own)"""
+    sq_fwd(g, 1, 2, 5, 7, 7, 9, 3, 1, 1, 1, ref=lambda x, w, b: ref64.conv2d(x, w, b, 1, 1))
+    sq_fwd(g, 2, 1, 4, 8, 9, 8, 3, 2, 0, 1, ref=lambda x, w, b: ref64.conv2d(x, w, b, 0, 2))
+
+
+def test_square_dilated_tile_crosses_a_row_end_and_the_image_boundary(g):
+    """N = 2 on 9 x 11: 99 pixels per image, so the second 64-pixel tile holds the end of image 0 and the start of image 1."""
+    sq_fwd(g, 3, 2, 5, 7, 9, 11, 3, 1, 2, 2)
+    sq_fwd(g, 4, 2, 8, 4, 9, 11, 3, 1, 3, 3, flags="RELU")
+
+
+@pytest.mark.parametrize("ci,co", [(1, 1), (17, 65), (72, 40), (130, 70)])
+def test_square_dilated_channel_counts_across_tiles_and_chunks(g, ci, co):
+    """1 channel; Cin past one 16-channel chunk and off 4; Cout past one 64-channel block."""
+    sq_fwd(g, ci + co, 2, ci, co, 9, 11, 3, 1, 2, 2)
+    sq_fwd(g, ci * co, 1, ci, co, 5, 6, 3, 1, 4, 4, flags="ACCUM")
+
+
+@pytest.mark.parametrize("flags", ["", "RELU", "ACCUM", "MASK", "ACCUM+MASK"])
+def test_square_dilated_epilogues_in_a_channel_slice(g, flags):
+    """bias / ReLU / accumulate / mask; x a channel window of a wider pixel, y at coffset 8 and 4 of wider pixels, with and without bias."""
+    sq_fwd(g, 5, 2, 6, 10, 7, 9, 3, 1, 2, 2, flags=flags, xcs=16, xco=4, ycs=24, yco=8)
+    sq_fwd(g, 6, 1, 4, 3, 5, 4, 3, 1, 2, 2, flags=flags, ycs=8, yco=4, bias=False)
+
+
+def test_four_dilations_of_one_input_in_one_launch(g):
+    """The ASPP head: four problems read the same 17 x 19 blob with dilations 2, 4, 6, 8 (pad == dilation) in one launch."""
+    rng = np.random.default_rng(9)
+    n, ci, h, w, k = 1, 6, 17, 19, 3
     x = rng.standard_normal((n, ci, h, w)).astype(np.float32)
-    wt = (rng.standard_normal((co, ci, k, k)) / np.sqrt(ci)).astype(np.float32)
-    oh, ow = R.out_hw(h, w, k, k, (pad, pad), (s, s), dil)
-    base = rng.standard_normal((n, co, oh, ow)).astype(np.float32)
-    act = np.maximum(rng.standard_normal((n, co, oh, ow)), 0).astype(np.float32)
     xd = g.put(poisoned_nhwc(x, r4(ci), 0), at_end=True, name="x")
-    wd = g.put(pack_ohwi(wt), at_end=True, name="bank")
-    bd = g.put(rng.standard_normal(co).astype(np.float32), at_end=True, name="bias")
-    y2_img = poisoned_nhwc(act, ycs + 4, 4)
-    y2d = g.put(y2_img, at_end=True, name="y2") if "MASK" in flags else None
-    y0 = poisoned_nhwc(base, ycs, yco) if "ACCUM" in flags else poisoned((n, oh, ow, ycs))
-    same_bytes_forward(g, xd, wd, bd, y0, n, h, w, ci, r4(ci), co, k, pad, s, dil, ycs, yco, sum(FLAGS[f] for f in flags.split("+") if f),
-                       y2d, ycs + 4, 4)
-    assert y2d is None or y2d.unchanged(), "y2 was written"
+    banks = []
+    for dil, co in zip((2, 4, 6, 8), (7, 70, 4, 9)):
+        wt = rng.standard_normal((co, ci, k, k)).astype(np.float32)
+        b = rng.standard_normal(co).astype(np.float32)
+        banks.append((dil, co, wt, b, g.put(pack_ohwi(wt), at_end=True), g.put(b, at_end=True)))
+    for cfg in configs():
+        descs, outs = [], []
+        for dil, co, wt, b, wd, bd in banks:
+            ycs = r4(co) + 4
+            yd = g.put(poisoned((n, h, w, ycs)), at_end=True)
+            descs.append(rconv_desc(xd.ptr, wd.ptr, bd.ptr, yd.ptr, n, h, w, ci, r4(ci), co, (k, k), (dil, dil), (1, 1), dil, h, w, ycs, 4))
+            outs.append((yd, ycs, wt, b, dil, co))
+        plan = launch(g, descs, cfg)
+        assert plan.n == 4 and plan.grid_y == 1
+        for yd, ycs, wt, b, dil, co in outs:
+            full = yd.read((n, h, w, ycs))
+            y = nchw(full, co, 4)
+            assert poison_free(y) and slice_untouched(full, 4, co)
+            pad = (dil, dil)
+            within(y, R.conv2d(x, wt, b, pad, (1, 1), dil), ref64.dot_bound(k * k * ci, R.conv2d_mag(x, wt, b, pad, (1, 1), dil)), "aspp d%d" % dil)
+    assert xd.unchanged()
 
 
-def test_square_data_gradient_same_bytes_through_either_abi(g):
-    """dX of the layer above at stride 1: dY (70 channels) with the flipped bank, pad' = dil (k-1) - pad.  The flip still runs on the
-    device and is held to the host's (inside flipped_on_device); the two launches read an UPLOADED copy of those same bits, because
-    same_bytes_forward asks unchanged() of the bank and unchanged() compares an allocation with its upload - a buffer that a launch
-    of the test itself has filled can never pass it."""
-    rng = np.random.default_rng(60)
-    n, h, w, ci, co, k, dil, pad = 2, 9, 11, 6, 70, 3, 2, 2
-    wt = rng.standard_normal((co, ci, k, k)).astype(np.float32)
-    dy = rng.standard_normal((n, co, h, w)).astype(np.float32)      # (pad == dil: the output is as large as the input)
-    dyd = g.put(poisoned_nhwc(dy, r4(co), 0), at_end=True, name="dy")
-    flipped_on_device(g, wt)      # (asserts that the device's flip is pack_ohwi(R.flipped_bank(wt)), bit for bit)
-    td = g.put(pack_ohwi(R.flipped_bank(wt)), at_end=True, name="flipped bank")
-    same_bytes_forward(g, dyd, td, None, poisoned((n, h, w, r4(ci))), n, h, w, co, r4(co), ci, k, dil * (k - 1) - pad, 1, dil, r4(ci), 0)
+@pytest.mark.parametrize("k,dil,pad,flags", [(3, 2, 2, ""), (3, 4, 1, ""), (3, 2, 2, "MASK"), (3, 4, 1, "ACCUM+MASK")])
+def test_square_dilated_data_gradient_through_the_flipped_bank(g, k, dil, pad, flags):
+    run_dgrad(g, 11 + dil, (k, k), (pad, pad), dil, flags)
 
 
-def test_square_weight_gradient_same_bytes_through_either_abi(g):
-    """N = 2 on 12 x 14: 336 pixels, two pixel splits; dw with its pad columns, and db."""
-    rng = np.random.default_rng(70)
-    lib = L.load()
-    n, h, w, ci, co, k, dil, pad = 2, 12, 14, 6, 70, 3, 2, 2
-    x = rng.standard_normal((n, ci, h, w)).astype(np.float32)
-    dy = rng.standard_normal((n, co, h, w)).astype(np.float32)
-    xd = g.put(poisoned_nhwc(x, r4(ci), 0), at_end=True, name="x")
-    dyd = g.put(poisoned_nhwc(dy, r4(co), 0), at_end=True, name="dy")
-    head, tail = (xd.ptr, None, None, dyd.ptr, n, h, w, ci, r4(ci), co), (dil, h, w, r4(co), 0)
-    descs = {"dconv": dconv_desc(*head, k, pad, 1, *tail), "rconv": rconv_desc(*head, (k, k), (pad, pad), (1, 1), *tail)}
-    got = {}
-    for fam, d in descs.items():
-        floats = int(getattr(lib, "fcn_%s2d_wgrad_workspace_floats" % fam)(C.byref(d)))
-        assert floats > 0, "%s: 336 pixels over 18 tiles are two pixel splits and need a workspace" % fam
-        dwd, dbd = g.put(co * k * k * r4(ci) * 4, name="dw " + fam), g.put(co * 4, at_end=True, name="db " + fam)
-        wsd = g.put(floats * 4, name="wgrad workspace " + fam)
-        L.call("fcn_%s2d_wgrad_f32" % fam, C.byref(d), dwd.ptr, dbd.ptr, wsd.ptr, None)
-        L.call("fcn_device_sync")
-        got[fam] = (floats, dwd.read((co, k, k, r4(ci))), dbd.read((co,)))
-    assert got["dconv"][0] == got["rconv"][0] == 2 * co * k * k * r4(ci)
-    assert poison_free(got["dconv"][1]) and poison_free(got["dconv"][2])
-    assert got["dconv"][1].tobytes() == got["rconv"][1].tobytes(), "dw differs between fcn_dconv2d_wgrad_f32 and fcn_rconv2d_wgrad_f32"
-    assert got["dconv"][2].tobytes() == got["rconv"][2].tobytes(), "db differs between fcn_dconv2d_wgrad_f32 and fcn_rconv2d_wgrad_f32"
-    assert xd.unchanged() and dyd.unchanged()
+@pytest.mark.parametrize("k,dil,pad,s,hw", [SQUARE_GEOMETRIES[i] for i in (0, 1, 2, 7)])
+def test_square_dilated_weight_gradient_geometries(g, k, dil, pad, s, hw):
+    sq_wgrad(g, 20 + dil, 1, 5, 7, hw[0], hw[1], k, s, pad, dil)
+    sq_wgrad(g, 30 + dil, 2, 3, 6, hw[0], hw[1], k, s, pad, dil, dycs=16, dyco=4, xcs=12, xco=4, with_db=False)
+
+
+@pytest.mark.parametrize("ci,co", [(17, 65), (130, 70)])
+def test_square_dilated_weight_gradient_channel_counts(g, ci, co):
+    sq_wgrad(g, ci + co, 2, ci, co, 9, 11, 3, 1, 2, 2)
+
+
+def test_square_dilated_weight_gradient_over_several_pixel_splits(g):
+    """N = 2 on 23 x 25: 1150 pixels, more than one pixel split; dY a channel slice at an offset that keeps it off 16 bytes too."""
+    sq_wgrad(g, 40, 2, 5, 7, 23, 25, 3, 1, 2, 2, min_splits=2)
+    sq_wgrad(g, 41, 2, 6, 5, 23, 25, 3, 1, 4, 4, dycs=12, dyco=3, min_splits=2, with_db=False)
+    sq_wgrad(g, 42, 2, 6, 5, 23, 25, 3, 1, 4, 4, dycs=12, dyco=4, min_splits=2)
+
+

@@ -19,7 +19,7 @@ def test_symbols_are_exported_and_bound():
     lib = L.load()
     for n in NAMES + ("fcn_inner_product_workspace_bytes", "fcn_inner_product_fwd_workspace_bytes"):
         assert hasattr(lib, n) and n in L.PROTOTYPES, n
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
 
 
 def test_prototypes_match_the_header():

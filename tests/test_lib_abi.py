@@ -24,7 +24,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), "libfcnhip.so lacks %s" % n
         assert n in L.PROTOTYPES, "lib.py has no prototype for %s" % n
     assert sorted(L.PROTOTYPES) == names
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
 
 
 def test_struct_layouts_match_header():

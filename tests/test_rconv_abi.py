@@ -1,4 +1,4 @@
-"""C ABI of the rectangular convolution: symbols, descriptor layout, host-side refusal of bad descriptors (no GPU: every call here
+"""C ABI of the rectangular and dilated convolution: symbols, descriptor layout, host-side refusal of bad descriptors (no GPU: every call here
 returns before anything touches a device)."""
 import ctypes as C
 import os
@@ -16,7 +16,7 @@ def test_symbols_are_exported_and_bound():
     lib = L.load()
     for n in NAMES:
         assert hasattr(lib, n) and n in L.PROTOTYPES, n
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
     assert int(lib.fcn_rconv2d_num_configs()) >= 1
 
 
@@ -42,13 +42,30 @@ def test_descriptor_layout_matches_the_header():
         assert (ct is C.c_void_p) == ptr and getattr(L.RConvDesc, n).offset == off, n
         off += 8 if ptr else 4
     assert C.sizeof(L.RConvDesc) == 5 * 8 + 20 * 4
-    # fcn_dconv_desc with pad and stride kept per axis
-    want = []
-    for f in L.DConvDesc._fields_:
-        want += {"pad": ["pad_h", "pad_w"], "stride": ["stride_h", "stride_w"]}.get(f[0], [f[0]])
-    assert [f[0] for f in L.RConvDesc._fields_] == want
-    assert [n for n, _ in _header_fields("fcn_rconv_plan")] == [f[0] for f in L.RConvPlan._fields_] == [f[0] for f in L.DConvPlan._fields_]
+    assert [n for n, _ in _header_fields("fcn_rconv_plan")] == [f[0] for f in L.RConvPlan._fields_]
     assert C.sizeof(L.RConvPlan) == 8 + 5 * 4 + 4 and L.RConvPlan.total_tiles.offset == 24
+
+
+def test_the_descriptor_is_the_dense_one_per_axis_plus_the_dilation():
+    """What the retired fcn_dconv_desc / fcn_dconv_plan promised, of the one descriptor that is left: the fields of fcn_conv_desc without
+    in_shift, pad and stride kept per axis, plus the dilation; the plan field for field fcn_tconv_plan."""
+    want = []
+    for f in L.ConvDesc._fields_:
+        want += {"pad": ["pad_h", "pad_w"], "stride": ["stride_h", "stride_w"], "in_shift": []}.get(f[0], [f[0]])
+    assert [f[0] for f in L.RConvDesc._fields_] == want + ["dilation"]
+    assert [f[0] for f in L.RConvPlan._fields_] == [f[0] for f in L.TConvPlan._fields_]
+    assert C.sizeof(L.RConvPlan) == C.sizeof(L.TConvPlan)
+
+
+def test_the_dilated_symbols_are_gone():
+    """ABI version 2: no fcn_dconv* name is exported, bound or declared any more."""
+    lib = L.load()
+    assert lib.fcn_abi_version() == 2
+    for n in NAMES:
+        gone = n.replace("rconv", "dconv")
+        assert not hasattr(lib, gone) and gone not in L.PROTOTYPES, gone
+    assert not [n for n in L.PROTOTYPES if "dconv" in n] and not hasattr(L, "DConvDesc") and not hasattr(L, "DConvPlan")
+    assert "dconv" not in open(os.path.join(ROOT, "include", "fcnhip.h")).read()
 
 
 def _desc(**kw):
@@ -60,6 +77,16 @@ def _desc(**kw):
     d.y_cstride, d.y_coffset, d.y2_cstride, d.y2_coffset, d.flags, d.dilation = 8, 0, 0, 0, 0, 1
     for k, v in kw.items():
         setattr(d, k, v)
+    return d
+
+
+def _square(**kw):
+    """A consistent square k3 d2 p2 s1 problem (a dilated layer: equal axes); pad= / stride= set both axes."""
+    both = {"pad": ("pad_h", "pad_w"), "stride": ("stride_h", "stride_w")}
+    d = _desc(kh=3, kw=3, pad_h=2, pad_w=2, dilation=2)
+    for k, v in kw.items():
+        for f in both.get(k, (k,)):
+            setattr(d, f, v)
     return d
 
 
@@ -81,6 +108,12 @@ BAD_ARG = (dict(x=None), dict(y=None), dict(kh=0), dict(kw=0), dict(stride_h=0),
            dict(stride_h=2), dict(stride_w=2), dict(pad_h=1), dict(pad_w=2),      # each changes one extent only
            dict(dilation=3, OH=7, OW=1),                                    # the window (1 x 19) exceeds the padded image (7 x 15)
            dict(y_cstride=4), dict(y_coffset=4), dict(y_coffset=-1))        # slice wider than the pixel
+SQUARE_BAD_ARG = (dict(x=None), dict(y=None), dict(kh=0), dict(kw=0), dict(stride=0), dict(pad=-1), dict(N=0), dict(H=0), dict(W=-1), dict(Cin=0),
+                  dict(Cout=0),
+                  dict(OH=6), dict(OH=8), dict(OW=8), dict(OW=10),          # not (H + 2 pad - (dil (k-1) + 1)) / stride + 1 = (7, 9)
+                  dict(dilation=6, OH=1, OW=1),                             # the dilated window (13) exceeds the padded image (11)
+                  dict(y_cstride=4), dict(y_coffset=4), dict(y_coffset=-1)) # slice wider than the pixel
+SQUARE_BAD_UNSUPPORTED = (dict(dilation=0), dict(dilation=-1), dict(N=1 << 20, H=64, W=64, OH=64, OW=64))
 BAD_ALIGN = (dict(x_cstride=6), dict(x_cstride=0), dict(Cin=5), dict(x=0x10004), dict(y=0x40002))
 BAD_UNSUPPORTED = (dict(dilation=0), dict(dilation=-1), dict(N=1 << 20, H=64, W=64, OH=64, OW=64),
                    dict(kh=65, kw=65, pad_h=32, pad_w=32, H=64, W=64, OH=64, OW=64))      # more than 4096 taps
@@ -117,6 +150,41 @@ def test_bad_descriptors_are_refused_on_the_host():
         assert rc == E_UNSUPPORTED and msg.startswith("rconv"), (bad, rc, msg)
     assert int(lib.fcn_rconv2d_workspace_bytes(C.byref(_desc()), 3)) >= 3 * C.sizeof(L.RConvDesc)
     assert int(lib.fcn_rconv2d_workspace_bytes(C.byref(_desc()), 0)) == 0
+
+
+def test_bad_square_dilated_descriptors_are_refused_on_the_host():
+    assert int(L.load().fcn_rconv2d_wgrad_workspace_floats(C.byref(_square(N=2, H=23, W=25, OH=23, OW=25)))) > 0      # the problem itself is accepted
+    for bad in SQUARE_BAD_ARG + (dict(w=None), dict(flags=L.CONV_MASK), dict(flags=L.CONV_MASK, y2=0x60000, y2_cstride=4)):
+        rc, msg = _prepare(_square(**bad))
+        assert rc == E_ARG and msg.startswith("rconv"), (bad, rc, msg)
+    for bad in BAD_ALIGN + (dict(w=0x20008),):
+        rc, msg = _prepare(_square(**bad))
+        assert rc == E_ALIGN and msg.startswith("rconv"), (bad, rc, msg)
+    for bad in SQUARE_BAD_UNSUPPORTED + (dict(flags=L.CONV_SIGMOID2), dict(flags=L.CONV_F16), dict(flags=L.CONV_OUT_F16)):
+        rc, msg = _prepare(_square(**bad))
+        assert rc == E_UNSUPPORTED and msg.startswith("rconv"), (bad, rc, msg)
+
+
+def test_the_weight_gradient_refuses_square_dilated_problems_on_the_host():
+    lib = L.load()
+    assert _wgrad(_square(), dw=None)[0] == E_ARG
+    for bad in SQUARE_BAD_ARG:
+        rc, msg = _wgrad(_square(**bad))
+        assert rc == E_ARG and msg.startswith("rconv"), (bad, rc, msg)
+    for bad in BAD_ALIGN:
+        rc, msg = _wgrad(_square(**bad))
+        assert rc == E_ALIGN and msg.startswith("rconv"), (bad, rc, msg)
+    assert _wgrad(_square(), dw=0x60004)[0] == E_ALIGN
+    for bad in SQUARE_BAD_UNSUPPORTED:
+        rc, msg = _wgrad(_square(**bad))
+        assert rc == E_UNSUPPORTED and msg.startswith("rconv"), (bad, rc, msg)
+    # more than one pixel split (2 x 23 x 25 pixels, nine small tiles) needs the workspace the query sizes
+    big = _square(N=2, H=23, W=25, OH=23, OW=25)
+    floats = int(lib.fcn_rconv2d_wgrad_workspace_floats(C.byref(big)))
+    assert floats > 0 and floats % (6 * 9 * 4) == 0 and floats // (6 * 9 * 4) > 1
+    assert _wgrad(big, ws=None)[0] == E_ARG and _wgrad(big, ws=0x80004)[0] == E_ALIGN
+    assert int(lib.fcn_rconv2d_wgrad_workspace_floats(C.byref(_square()))) == 0       # 63 pixels: one split, no workspace
+    assert int(lib.fcn_rconv2d_wgrad_workspace_floats(C.byref(_square(dilation=0)))) == 0
 
 
 def test_the_weight_gradient_refuses_on_the_host():

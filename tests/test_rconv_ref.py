@@ -1,5 +1,5 @@
-"""tests/ref_rconv64.py against torch.nn.functional.conv2d with per-axis stride / padding and its autograd, both in float64 (no GPU):
-the reference the guarded rectangular-convolution tests trust is held to a second, independent statement of the operation first."""
+"""tests/ref_rconv64.py against torch.nn.functional.conv2d with per-axis stride / padding, a dilation and its autograd, both in float64
+(no GPU): the reference the guarded rectangular- and dilated-convolution tests trust is held to a second, independent statement of the operation first."""
 import numpy as np
 import pytest
 import torch
@@ -13,6 +13,11 @@ CASES = [  # n, cin, cout, (h, w), (kh, kw), (ph, pw), (sh, sw), dil
     (1, 4, 6, (5, 6), (1, 3), (0, 1), (1, 1), 1), (1, 4, 6, (5, 6), (3, 1), (1, 0), (1, 1), 1), (2, 3, 5, (11, 9), (3, 5), (0, 2), (2, 1), 1),
     (1, 2, 3, (8, 13), (1, 5), (0, 0), (1, 2), 1), (1, 4, 4, (9, 10), (3, 1), (2, 0), (1, 1), 2), (2, 3, 4, (8, 7), (2, 3), (0, 2), (1, 1), 2),
     (1, 5, 6, (7, 9), (3, 3), (1, 2), (1, 1), 1), (1, 3, 3, (12, 11), (3, 2), (1, 1), (2, 3), 2),
+    # square dilated layers: equal axes, written (k, k), (p, p), (s, s), d
+    (2, 5, 7, (7, 9), (3, 3), (2, 2), (1, 1), 2), (1, 3, 4, (5, 6), (3, 3), (12, 12), (1, 1), 12), (1, 4, 6, (11, 13), (3, 3), (0, 0), (1, 1), 4),
+    (1, 3, 5, (9, 10), (5, 5), (4, 4), (1, 1), 2), (2, 2, 3, (8, 7), (2, 2), (0, 0), (1, 1), 3), (1, 4, 4, (6, 5), (1, 1), (0, 0), (1, 1), 3),
+    (1, 5, 6, (7, 9), (3, 3), (1, 1), (1, 1), 1), (2, 3, 4, (11, 9), (3, 3), (2, 2), (2, 2), 2), (1, 4, 5, (13, 11), (3, 3), (1, 1), (2, 2), 3),
+    (1, 3, 3, (9, 9), (3, 3), (1, 1), (1, 1), 4),
 ]
 
 
@@ -46,10 +51,11 @@ def test_a_square_problem_is_the_dense_reference():
 
 
 @pytest.mark.parametrize("k,pad,d", [((1, 7), (0, 3), 1), ((7, 1), (3, 0), 1), ((3, 1), (2, 0), 2), ((2, 3), (0, 2), 2), ((3, 5), (2, 1), 1),
-                                     ((1, 3), (0, 0), 2), ((3, 3), (1, 2), 1)])
+                                     ((1, 3), (0, 0), 2), ((3, 3), (1, 2), 1),
+                                     ((3, 3), (2, 2), 2), ((3, 3), (1, 1), 4), ((5, 5), (4, 4), 2)])      # square dilated layers
 def test_the_data_gradient_is_the_convolution_with_the_flipped_bank(k, pad, d):
     """What the engine does for a stride-1 layer: dX = rconv(dY, flipped bank, ph' = d (kh-1) - ph, pw' = d (kw-1) - pw, the same d),
-    on a non-square image, with kh != kw or ph != pw."""
+    on a non-square image, with kh != kw or ph != pw - and with equal axes, the square dilated layer."""
     rng = np.random.default_rng(k[0] * 10 + k[1] + d)
     h, w = 9, 11
     wt = rng.standard_normal((6, 4) + k)
@@ -66,3 +72,13 @@ def test_magnitude_forms_bound_the_values():
     dy = rng.standard_normal((1, 4, 7, 8))
     assert np.all(R.dgrad_mag(dy, wt, (0, 2), (1, 1), 1, 7, 8) >= np.abs(R.dgrad(dy, wt, (0, 2), (1, 1), 1, 7, 8)))
     assert np.all(R.wgrad_mag(x, dy, 1, 5, (0, 2), (1, 1), 1)[0] >= np.abs(R.wgrad(x, dy, 1, 5, (0, 2), (1, 1), 1)[0]))
+
+
+def test_magnitude_forms_bound_the_values_of_a_square_dilated_layer():
+    """k3 d2 p2 on 7 x 7, equal axes."""
+    rng = np.random.default_rng(5)
+    x, wt, b = rng.standard_normal((1, 3, 7, 7)), rng.standard_normal((4, 3, 3, 3)), rng.standard_normal(4)
+    assert np.all(R.conv2d_mag(x, wt, b, (2, 2), (1, 1), 2) >= np.abs(R.conv2d(x, wt, b, (2, 2), (1, 1), 2)))
+    dy = rng.standard_normal((1, 4, 7, 7))
+    assert np.all(R.dgrad_mag(dy, wt, (2, 2), (1, 1), 2, 7, 7) >= np.abs(R.dgrad(dy, wt, (2, 2), (1, 1), 2, 7, 7)))
+    assert np.all(R.wgrad_mag(x, dy, 3, 3, (2, 2), (1, 1), 2)[0] >= np.abs(R.wgrad(x, dy, 3, 3, (2, 2), (1, 1), 2)[0]))

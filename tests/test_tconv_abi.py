@@ -16,7 +16,7 @@ def test_symbols_are_exported_and_bound():
     lib = L.load()
     for n in NAMES:
         assert hasattr(lib, n) and n in L.PROTOTYPES, n
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
     assert int(lib.fcn_tconv2d_num_configs()) >= 1
 
 

@@ -18,7 +18,7 @@ def test_symbols_are_exported_and_bound():
     lib = L.load()
     for n in NAMES:
         assert hasattr(lib, n) and n in L.PROTOTYPES, n
-    assert lib.fcn_abi_version() == 1
+    assert lib.fcn_abi_version() == 2
 
 
 def test_prototypes_match_the_header():
