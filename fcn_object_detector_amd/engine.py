@@ -32,7 +32,7 @@ from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, bn_global_stats, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation, layer_geometry
+from .netspec import Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation, layer_geometry
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -326,6 +326,18 @@ class BnChain:
     mids: List[str] = field(default_factory=list)
     save: Optional["DeviceBuffer"] = None
     global_stats: bool = False
+
+
+@dataclass(eq=False)
+class ArgChain:
+    """An ArgMax and what one launch takes in with it (csrc/argmax.hip): an Interp and / or a Softmax directly in front, each read by
+    the next link alone.  x: the blob the launch reads, y: the ArgMax top, mids: the tops in between, which the launch never writes."""
+    x: str
+    y: str
+    argmax: Optional[Layer] = None
+    interp: Optional[Layer] = None
+    softmax: Optional[Layer] = None
+    mids: List[str] = field(default_factory=list)
 
 
 def ranges_hit(a: Sequence[Range], b: Sequence[Range]) -> bool:
@@ -754,6 +766,65 @@ class Engine:
         self._bn_chains[first.name] = ch
         return ops
 
+    def _argmax_chain_at(self, l: Layer, skip: set) -> Optional["ArgChain"]:
+        """The chain [Interp ->] [Softmax ->] ArgMax that starts at layer l, or None when l (an Interp or a Softmax) starts none.  A link
+        joins where the blob in front of it has it as its only reader, has one producer, is no output of the net and no view of another
+        blob: the fused launch never writes it.  An Interp joins only in front of top_k 1 (the fused pass keeps one pair per pixel).
+        Without `fuse` an ArgMax stands alone.  Absorbed layers join `skip`, like _relu_after's."""
+        ch, cur = ArgChain(l.bottoms[0], ""), l
+        while cur.type != "ArgMax":
+            if not self.fuse or len(cur.bottoms) != 1 or len(cur.tops) != 1 or cur.tops[0] == cur.bottoms[0]:
+                return None
+            if cur.type == "Interp" and ch.interp is None and ch.softmax is None:
+                ch.interp = cur
+            elif cur.type == "Softmax" and ch.softmax is None and int(cur.sub("softmax_param").get("axis", 1)) == 1 \
+                    and len(self.shapes[cur.bottoms[0]]) in (2, 4):
+                ch.softmax = cur
+            else:
+                return None
+            top = cur.tops[0]
+            cons = self.consumers.get(top, [])
+            if len(cons) != 1 or top in self.outputs or len(self.producers.get(top, [])) != 1 or top in self.alias:
+                return None
+            ch.mids.append(top)
+            cur = cons[0]
+        ch.argmax, ch.y = cur, cur.tops[0]
+        if ch.interp is not None and argmax_form(cur, self.shapes[cur.bottoms[0]])[0] != 1:
+            return None
+        skip.update(q.name for q in (ch.softmax, ch.argmax) if q is not None and q is not l)
+        return ch
+
+    def _fwd_argmax(self, ch: "ArgChain") -> List[Op]:
+        """ArgMax as ONE launch, alone or with the Interp and / or the Softmax in front of it.  The top is float32 in both engines; the
+        launch reads floats or halves.  The tops in the middle of a chain own a buffer that the launch leaves alone: read_blob() fills
+        it on demand with the layers' own launches."""
+        lib, B, l = L.load(), self.blobs, ch.argmax
+        xb, yb = B[ch.x], B[ch.y]
+        top_k, out_max_val, legacy = argmax_form(l, self.shapes[l.bottoms[0]])
+        flags = (L.ARGMAX_SOFTMAX if ch.softmax is not None else 0) | ((L.ARGMAX_PAIRS if legacy else L.ARGMAX_VALUES) if out_max_val else 0)
+        if yb.esize != 4 or xb.nchw is None:
+            raise NotImplementedError("ArgMax %s: the top %s must be float32 and the bottom a 4-d or 2-d blob" % (l.name, ch.y))
+        half = xb.esize == 2
+        if half and (xb.coffset % 8 or xb.cstride % 8 or yb.coffset % 4 or yb.cstride % 4):
+            raise NotImplementedError("f16 engine: ArgMax %s on a channel window that is not 16-byte aligned" % l.name)
+        name = "+".join(q.name for q in (ch.interp, ch.softmax, ch.argmax) if q is not None)
+        n, c, h, w = xb.nchw
+        if ch.interp is not None:
+            oh, ow, pad_beg, pad_end = interp_size(ch.interp, h, w)
+            fn = lib.fcn_interp_argmax_fwd_f16 if half else lib.fcn_interp_argmax_fwd_f32
+            run = lambda st: L.check(fn(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset, pad_beg, pad_end, oh, ow,
+                                        yb.cstride, yb.coffset, flags, st))
+            byts = float(xb.esize) * n * (h + pad_beg + pad_end) * (w + pad_beg + pad_end) * c
+        else:
+            fn = lib.fcn_argmax_fwd_f16 if half else lib.fcn_argmax_fwd_f32
+            run = lambda st: L.check(fn(xb.buf.ptr, yb.buf.ptr, xb.pixels, c, xb.cstride, xb.coffset, top_k, yb.cstride, yb.coffset, flags, st))
+            byts = float(xb.esize) * xb.pixels * c
+        lazy: List[Op] = []
+        for q, m in zip([q for q in (ch.interp, ch.softmax) if q is not None], ch.mids):
+            lazy = lazy + self._emit_simple(q)
+            self._lazy_blob_ops[m] = lazy
+        return [Op("argmax", name, run, 0.0, byts + 4.0 * yb.pixels * yb.channels)]
+
     def _collect_tasks(self) -> List[Task]:
         """Layer list -> tasks with read/write sets: one per convolution (a descriptor for the grouped launches) and one per
         other layer that launches anything (its ops)."""
@@ -813,6 +884,11 @@ class Engine:
                 continue
             if t == "Power" and l.tops[0] in self.shift:
                 continue      # folded into the consumer convolutions' loaders
+            if t in ("Interp", "Softmax", "ArgMax"):
+                ch = self._argmax_chain_at(l, skip)
+                if ch is not None:
+                    tasks.append(OpTask(ch.argmax, self._fwd_argmax(ch), reads=[self._range(ch.x)], writes=[self._range(ch.y)]))
+                    continue
             ops = self._emit_simple(l)
             read = l.bottoms[:1] if t == "Crop" else l.bottoms      # a Crop's second bottom is a shape, not data
             tasks.append(OpTask(l, ops, reads=[self._range(b) for b in read], writes=[self._range(tp) for tp in l.tops],

@@ -177,6 +177,9 @@ IP_MAX_ROWS = 32               # FCN_IP_MAX_ROWS: rows the InnerProduct streamin
 IP_WEIGHTS_NT = 256            # FCN_IP_WEIGHTS_NT
 CONV_IMAGE_ONES = 128      # half image whose channels 3 and 4 are the constant 1 (the folded Power shift): see include/fcnhip.h
 ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
+ARGMAX_MAX_TOPK = 32           # FCN_ARGMAX_MAX_TOPK
+ARGMAX_WAVE_BYTES, ARGMAX_WAVE_PIXELS, ARGMAX_WAVE_MIN_C = 512, 8192, 32      # FCN_ARGMAX_WAVE_*: where a wave takes a pixel (csrc/argmax.hip)
+ARGMAX_VALUES, ARGMAX_PAIRS, ARGMAX_SOFTMAX = 1, 2, 4
 SOLVER_KINDS = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADADELTA": 4, "ADAM": 5}      # FCN_SOLVER_*
 REG_L2, REG_L1 = 0, 1
 RECT_ROUND_NEAREST_EVEN, RECT_ROUND_TRUNCATE = 0, 1
@@ -332,6 +335,10 @@ PROTOTYPES = {
     "fcn_interp_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_interp_fwd_f16": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_interp_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_argmax_fwd_f32": (_i, [_vp, _vp] + [_i] * 8 + [_vp]),
+    "fcn_argmax_fwd_f16": (_i, [_vp, _vp] + [_i] * 8 + [_vp]),
+    "fcn_interp_argmax_fwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
+    "fcn_interp_argmax_fwd_f16": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_unpool_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_unpool_fwd_f16": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     "fcn_unpool_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),

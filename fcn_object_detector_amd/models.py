@@ -396,7 +396,13 @@ def _voc_crop(w: _Writer, name: str, bottom: str, like: str, offset: int) -> Non
     w.layer(name, "Crop", [bottom, like], [name], "  crop_param {\n    axis: 2\n    offset: %d\n  }" % offset)
 
 
-def _voc_fcn(variant: int, phase: str, num_classes: int, shape: Sequence[int], width_div: int, fc_div: Optional[int], fillers: bool) -> str:
+def _label_map(w: _Writer, score: str) -> None:
+    """The label map behind a deploy net's scores or probabilities, as SegNet's web-demo prototxt ends: ArgMax over the channel axis."""
+    w.layer("argmax", "ArgMax", [score], ["argmax"], "  argmax_param {\n    axis: 1\n  }")
+
+
+def _voc_fcn(variant: int, phase: str, num_classes: int, shape: Sequence[int], width_div: int, fc_div: Optional[int], fillers: bool,
+             argmax: bool = False) -> str:
     if phase not in ("TRAIN", "TEST"):
         raise ValueError("phase must be 'TRAIN' or 'TEST'")
     n, c, h, wd = (int(v) for v in shape)
@@ -440,31 +446,34 @@ def _voc_fcn(variant: int, phase: str, num_classes: int, shape: Sequence[int], w
             _voc_crop(w, "score", "upscore8", "data", 31)
     if phase == "TRAIN":
         w.layer("loss", "SoftmaxWithLoss", ["score", "label"], ["loss"], "  loss_param {\n    ignore_label: 255\n    normalize: false\n  }")
+    elif argmax:
+        _label_map(w, "score")
     return w.text()
 
 
 def voc_fcn32s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
-               fc_div: Optional[int] = None, fillers: bool = False) -> str:
+               fc_div: Optional[int] = None, fillers: bool = False, argmax: bool = False) -> str:
     """The published FCN-32s: VGG16 (conv1_1 with pad 100) to pool5, fc6 (k7) / fc7 (k1) as convolutions with ReLU and Dropout,
     score_fr, a x32 Deconvolution (k64 s32, no bias, lr_mult 0) and score = Crop(upscore, data) at offset 19.  TRAIN adds the label
     input and SoftmaxWithLoss (normalize: false, ignore_label: 255); TEST ends at `score`.  width_div / fc_div divide the VGG widths
-    and the 4096 of fc6 / fc7 (tests).  The published files carry no fillers (the nets are initialised by net surgery);
+    and the 4096 of fc6 / fc7 (tests).  argmax=True ends the TEST net in the label map `argmax` (ArgMax, axis 1) behind `score`; the
+    other two variants take it alike.  The published files carry no fillers (the nets are initialised by net surgery);
     fillers=True writes xavier / constant 0.1 into the convolutions and the bilinear filler into the upsampling layers."""
-    return _voc_fcn(32, phase, num_classes, shape, width_div, fc_div, fillers)
+    return _voc_fcn(32, phase, num_classes, shape, width_div, fc_div, fillers, argmax)
 
 
 def voc_fcn16s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
-               fc_div: Optional[int] = None, fillers: bool = False) -> str:
+               fc_div: Optional[int] = None, fillers: bool = False, argmax: bool = False) -> str:
     """The published FCN-16s: as voc_fcn32s to score_fr, then upscore2 (k4 s2), score_pool4 on pool4 cropped to it at offset 5, their
     sum, upscore16 (k32 s16) and score = Crop(upscore16, data) at offset 27."""
-    return _voc_fcn(16, phase, num_classes, shape, width_div, fc_div, fillers)
+    return _voc_fcn(16, phase, num_classes, shape, width_div, fc_div, fillers, argmax)
 
 
 def voc_fcn8s(phase: str = "TEST", num_classes: int = 21, shape: Sequence[int] = (1, 3, 500, 500), width_div: int = 1,
-              fc_div: Optional[int] = None, fillers: bool = False) -> str:
+              fc_div: Optional[int] = None, fillers: bool = False, argmax: bool = False) -> str:
     """The published FCN-8s: as voc_fcn16s to fuse_pool4, then upscore_pool4 (k4 s2), score_pool3 on pool3 cropped to it at offset 9,
     their sum, upscore8 (k16 s8) and score = Crop(upscore8, data) at offset 31."""
-    return _voc_fcn(8, phase, num_classes, shape, width_div, fc_div, fillers)
+    return _voc_fcn(8, phase, num_classes, shape, width_div, fc_div, fillers, argmax)
 
 
 # ----------------------------------------------------------------------
@@ -754,13 +763,15 @@ def _deeplab_vgg(w: _Writer, phase: str, batch: int, size: int, width_div: int, 
     return prev
 
 
-def _deeplab_tail(w: _Writer, phase: str, score: str, interp: bool = False) -> None:
+def _deeplab_tail(w: _Writer, phase: str, score: str, interp: bool = False, argmax: bool = False) -> None:
     """Loss (and, in TEST, Accuracy) on the score map.  interp, under the published names: DEPLOY ends in fc8_interp, the score map at
     the image's size (Interp, zoom_factor 8); TRAIN / TEST read label_shrink, every 8th pixel of the image-sized label (Interp,
     shrink_factor 8: positions that fall on label pixels, so the class ids and the 255s arrive as they are)."""
     if phase == "DEPLOY":
         if interp:
             w.layer("fc8_interp", "Interp", [score], ["fc8_interp"], "  interp_param {\n    zoom_factor: 8\n  }")
+        if argmax:      # the label map behind the DEPLOY tail
+            _label_map(w, "fc8_interp" if interp else score)
         return
     label = "label"
     if interp:
@@ -772,13 +783,14 @@ def _deeplab_tail(w: _Writer, phase: str, score: str, interp: bool = False) -> N
 
 
 def deeplab_largefov(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
-                     fc6_dilation: int = 12, interp: bool = False) -> str:
+                     fc6_dilation: int = 12, interp: bool = False, argmax: bool = False) -> str:
     """DeepLab-LargeFOV on VGG16 with the published names: the stride-8 body (_deeplab_vgg), pool5a (AVE 3x3 / s1 / pad 1), fc6 3x3 with
     1024 outputs at dilation 12 (pad 12), fc7 1x1 (ReLU, Dropout 0.5 behind both) and fc8_voc12 (lr_mult 10 / 20).  TRAIN and TEST end
     in SoftmaxWithLoss with ignore_label 255 (TEST adds Accuracy) on a `label` input of the score map's size; DEPLOY ends at
     fc8_voc12.  interp=True adds the published Interp layers (_deeplab_tail): DEPLOY ends in fc8_interp at the image's size, and the
     `label` input of TRAIN / TEST has the image's size and is shrunk by label_shrink; size must then be 1 modulo 8.  The published
-    ImageSegData layer is not emitted.  width_div / fc_div divide the VGG widths and the 1024."""
+    ImageSegData layer is not emitted.  argmax=True ends the DEPLOY net in the label map `argmax` (ArgMax, axis 1) behind its last
+    blob.  width_div / fc_div divide the VGG widths and the 1024."""
     _check_phase(phase)
     w = _Writer()
     w.raw('name: "DeepLab-LargeFOV"')
@@ -788,15 +800,15 @@ def deeplab_largefov(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 2
     _dl_conv(w, "fc6", feat, fc, 3, fc6_dilation, fc6_dilation, relu="relu6", drop="drop6")
     _dl_conv(w, "fc7", "fc6", fc, 1, relu="relu7", drop="drop7")
     _dl_conv(w, "fc8_voc12", "fc7", num_classes, 1, lr=(10.0, 20.0), std=0.01)
-    _deeplab_tail(w, phase, "fc8_voc12", interp)
+    _deeplab_tail(w, phase, "fc8_voc12", interp, argmax)
     return w.text()
 
 
 def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, width_div: int = 1, fc_div: int = 1, size: int = 321,
-                 rates: Sequence[int] = (6, 12, 18, 24), interp: bool = False) -> str:
+                 rates: Sequence[int] = (6, 12, 18, 24), interp: bool = False, argmax: bool = False) -> str:
     """The DeepLab-v2 VGG16 head (atrous spatial pyramid pooling): behind pool5 one branch per rate r, fc6_i 3x3 with 1024 outputs at
     dilation r (pad r), fc7_i 1x1 (ReLU, Dropout 0.5 behind both), fc8_voc12_i; the branches' scores are summed by the Eltwise
-    fc8_voc12.  Phases, label, interp and width_div / fc_div as deeplab_largefov."""
+    fc8_voc12.  Phases, label, interp, argmax and width_div / fc_div as deeplab_largefov."""
     _check_phase(phase)
     w = _Writer()
     w.raw('name: "DeepLab-v2-ASPP"')
@@ -808,7 +820,7 @@ def deeplab_aspp(phase: str = "DEPLOY", batch: int = 1, num_classes: int = 21, w
         _dl_conv(w, "fc7_%d" % i, "fc6_%d" % i, fc, 1, relu="relu7_%d" % i, drop="drop7_%d" % i)
         scores.append(_dl_conv(w, "fc8_voc12_%d" % i, "fc7_%d" % i, num_classes, 1, lr=(10.0, 20.0), std=0.01))
     w.layer("fc8_voc12", "Eltwise", scores, ["fc8_voc12"], "  eltwise_param { operation: SUM }")
-    _deeplab_tail(w, phase, "fc8_voc12", interp)
+    _deeplab_tail(w, phase, "fc8_voc12", interp, argmax)
     return w.text()
 
 
@@ -1097,10 +1109,13 @@ def _sn_inputs(w: _Writer, phase: str, batch: int, hw: Tuple[int, int]) -> None:
         w.layer("label", "Input", [], ["label"], "  input_param { shape { dim: %d dim: 1 dim: %d dim: %d } }" % (batch, hw[0], hw[1]))
 
 
-def _sn_tail(w: _Writer, phase: str, score: str) -> None:
-    """prob (Softmax; DEPLOY) or loss (SoftmaxWithLoss, ignore_label 255; TRAIN and TEST) with accuracy in TEST."""
+def _sn_tail(w: _Writer, phase: str, score: str, argmax: bool = False) -> None:
+    """prob (Softmax; DEPLOY) or loss (SoftmaxWithLoss, ignore_label 255; TRAIN and TEST) with accuracy in TEST.  argmax: DEPLOY ends
+    in the label map `argmax` behind prob."""
     if phase == "DEPLOY":
         w.layer("prob", "Softmax", [score], ["prob"])
+        if argmax:
+            _label_map(w, "prob")
         return
     if phase == "TEST":
         w.layer("accuracy", "Accuracy", [score, "label"], ["accuracy"], "  accuracy_param { ignore_label: 255 }")
@@ -1111,7 +1126,7 @@ def _halved(hw: Tuple[int, int]) -> Tuple[int, int]:
     return (hw[0] + 1) // 2, (hw[1] + 1) // 2      # 2 x 2 / stride 2 in Caffe's ceil mode
 
 
-def segnet_basic(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1) -> str:
+def segnet_basic(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1, argmax: bool = False) -> str:
     """SegNet-Basic: four encoder stages conv<i> 7x7 (64) + BatchNorm + ReLU + pool<i> 2x2 / 2 with the mask pool<i>_mask, four decoder
     stages upsample<i> (by pool<i>_mask) + conv_decode<i> 7x7 (64) + BatchNorm without a ReLU, and the 1x1 conv_classifier.  DEPLOY ends
     in prob (Softmax); TRAIN and TEST in loss (SoftmaxWithLoss over an (N, 1, H, W) `label`, ignore_label 255), TEST with accuracy.
@@ -1120,7 +1135,8 @@ def segnet_basic(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=
     prob are the published net's, as far as remembered.  `<conv>_bn` is a BatchNorm here (the fork's type is BN, which holds the scale and
     shift as well) and `<conv>_scale` is this project's; the published input LRN (norm) is not emitted, and the loss is not weighted
     by class frequencies.  An Upsample carries `scale: 2`, or upsample_h / upsample_w where the pooling's bottom has an odd extent.
-    width_div divides the 64; size is the image edge or (height, width)."""
+    width_div divides the 64; size is the image edge or (height, width).  argmax=True ends the DEPLOY net in `argmax`, the label map
+    behind prob (ArgMax, axis 1), as the published web-demo prototxt does."""
     _check_phase(phase)
     hw, c = _hw(size), max(64 // width_div, 1)
     w = _Writer()
@@ -1135,14 +1151,14 @@ def segnet_basic(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=
         x = _sn_upsample(w, "upsample%d" % i, x, "pool%d_mask" % i, planes[i - 1])
         x = _sn_conv(w, "conv_decode%d" % i, x, c, 7, phase, None)
     x = _sn_conv(w, "conv_classifier", x, classes, 1, phase, None, bn=False)
-    _sn_tail(w, phase, x)
+    _sn_tail(w, phase, x, argmax)
     return w.text()
 
 
 SEGNET_DECODER = ((5, (512, 512, 512)), (4, (512, 512, 256)), (3, (256, 256, 128)), (2, (128, 64)), (1, (64, 0)))      # widths of conv<b>_<n>_D .. conv<b>_1_D (0: the classes)
 
 
-def segnet(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1) -> str:
+def segnet(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 480), width_div: int = 1, argmax: bool = False) -> str:
     """SegNet: the 13 convolutions of VGG16 (3x3, pad 1) as the encoder, each with BatchNorm + ReLU, all five poolings 2x2 / 2 with a
     mask; the mirrored decoder upsample<b> (by pool<b>_mask) + conv<b>_<n>_D .. conv<b>_1_D, each with BatchNorm + ReLU but the last,
     conv1_1_D, which gives the class scores.  Ends as segnet_basic.
@@ -1171,7 +1187,7 @@ def segnet(phase: str = "DEPLOY", classes: int = 11, batch: int = 1, size=(360, 
                 x = _sn_conv(w, "conv1_1_D", x, classes, 3, phase, None, bn=False)
             else:
                 x = _sn_conv(w, "conv%d_%d_D" % (blk, i), x, wd(width_), 3, phase, "relu%d_%d_D" % (blk, i))
-    _sn_tail(w, phase, x)
+    _sn_tail(w, phase, x, argmax)
     return w.text()
 
 

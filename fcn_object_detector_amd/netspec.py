@@ -229,6 +229,33 @@ def upsample_size(l: "Layer", h: int, w: int) -> Tuple[int, int]:
     return oh, ow
 
 
+ARGMAX_MAX_TOPK = 32      # FCN_ARGMAX_MAX_TOPK of include/fcnhip.h
+
+
+def argmax_form(l: "Layer", shape: Shape) -> Tuple[int, bool, bool]:
+    """Caffe's ArgMaxLayer on a bottom of `shape`: (top_k, out_max_val, legacy).  With axis 1 (-3 on a 4-d blob) the top is the bottom
+    with top_k channels - the indices, or with out_max_val the values.  legacy: no axis, Caffe's form over everything behind the batch
+    axis, taken only where that is the channels alone (H * W == 1): the top is (N, 1, top_k), or (N, 2, top_k) with out_max_val - the
+    indices, then the values.  Everything else is refused by layer name."""
+    p = l.sub("argmax_param")
+    if len(l.bottoms) != 1 or len(shape) not in (2, 4) or len(l.tops) != 1:
+        raise ValueError("layer %s: ArgMax takes one 4-d or 2-d bottom and has one top, got bottoms %s" % (l.name, l.bottoms))
+    if l.tops[0] == l.bottoms[0]:
+        raise ValueError("layer %s: ArgMax cannot run in place" % l.name)
+    top_k, axis = int(p.get("top_k", 1)), p.get("axis")
+    n, c, h, w = as_nchw(shape)
+    if axis is not None and int(axis) not in ((1, -3) if len(shape) == 4 else (1, -1)):
+        raise NotImplementedError("layer %s: ArgMax over axis %d of a %d-d blob (only the channel axis)" % (l.name, int(axis), len(shape)))
+    if axis is None and h * w != 1:
+        raise NotImplementedError("layer %s: ArgMax without an axis over the %d x %d x %d blob of an image (Caffe's legacy form ranks C * H * W "
+                                  "values; only H * W == 1 - a classifier's scores - or axis: 1)" % (l.name, c, h, w))
+    if top_k < 1 or top_k > c:
+        raise ValueError("layer %s: top_k %d is outside [1, %d]" % (l.name, top_k, c))
+    if top_k > ARGMAX_MAX_TOPK:
+        raise NotImplementedError("layer %s: ArgMax with top_k %d (at most %d)" % (l.name, top_k, ARGMAX_MAX_TOPK))
+    return top_k, bool(p.get("out_max_val", False)), axis is None
+
+
 def as_nchw(shape: Shape) -> Optional[Tuple[int, int, int, int]]:
     """A blob's shape as the NHWC machinery sees it: a 4-d blob as it is, an (N, C) blob (the top of an InnerProduct) as N pixels of C
     channels (H = W = 1); None for anything else.  Engine.Blob.nchw and the channel-axis layers (Concat, Slice) share this rule."""
@@ -518,6 +545,14 @@ class NetSpec:
                     raise ValueError("layer %s: Interp cannot run in place" % l.name)
                 oh, ow, _, _ = interp_size(l, bots[0][2], bots[0][3])
                 shapes[l.tops[0]] = (bots[0][0], bots[0][1], oh, ow)
+            elif t == "ArgMax":
+                if len(bots) != 1:
+                    raise ValueError("layer %s: ArgMax takes one bottom, got %d" % (l.name, len(bots)))
+                top_k, out_max_val, legacy = argmax_form(l, bots[0])
+                if legacy:
+                    shapes[l.tops[0]] = (bots[0][0], 2 if out_max_val else 1, top_k)
+                else:
+                    shapes[l.tops[0]] = (bots[0][0], top_k) + tuple(bots[0][2:])
             elif t == "Upsample":
                 if len(bots) != 2 or any(len(b) != 4 for b in bots) or len(l.tops) != 1:
                     raise ValueError("layer %s: Upsample takes two 4-d bottoms (the blob and the pooling mask) and has one top, got %s" % (l.name, bots))

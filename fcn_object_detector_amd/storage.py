@@ -166,14 +166,19 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
             continue
         wide = (not f16 or len(shp) not in (2, 4) or name in outputs or name in data_tops      # inputs stay float32 (Power(-127) quirk)
                 or any(q.type == "Power" and q.bottoms[0] in data_tops for q in producers.get(name, []))
-                or any(q.type == "Sigmoid" for q in consumers.get(name, [])) or any(q.type == "Sigmoid" for q in producers.get(name, [])))
+                or any(q.type == "Sigmoid" for q in consumers.get(name, [])) or any(q.type in ("Sigmoid", "ArgMax") for q in producers.get(name, [])))
         esize[name] = 4 if wide else 2
     if f16:
+        for l in spec.layers:      # labels and ranks are float32: nothing of the half-float path reads them
+            if l.type == "ArgMax" and consumers.get(l.tops[0]):
+                q = consumers[l.tops[0]][0]
+                raise NotImplementedError("f16 engine: layer %s (%s) reads %s, the float32 top of ArgMax %s" % (q.name, q.type, l.tops[0], l.name))
         for name in shapes:
             if esize[name] == 4 and len(shapes[name]) in (2, 4) and name not in data_tops:
-                # (Softmax, Deconvolution, Interp and Upsample read halves and store float32: the out_f32 forms of their half kernels)
+                # (Softmax, Deconvolution, Interp and Upsample read halves and store float32: the out_f32 forms of their half kernels; the
+                # top of an ArgMax is float32 in both engines, as Caffe's is)
                 bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct",
-                                                                                 "Interp", "DepthwiseConvolution", "Upsample")]
+                                                                                 "Interp", "DepthwiseConvolution", "Upsample", "ArgMax")]
                 if bad:
                     raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 
@@ -273,6 +278,9 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
         # an SSD head's 3-d blobs - (N, P, C) scores, (1, 2, P * 4) priors - are rows of P * C floats per image, like their 2-d twins
         if (l.type in ("Reshape", "PriorBox") or l.tops[:1] and l.tops[0] in spec.prior_blobs
                 or l.type == "Softmax" and l.bottoms[0] in rows) and len(shapes.get(l.tops[0], ())) == 3:
+            rows.add(l.tops[0])
+        # the legacy ArgMax top (N, 1 or 2, top_k) is a row per image: the indices, then - with out_max_val - the values
+        if l.type == "ArgMax" and len(shapes.get(l.tops[0], ())) == 3:
             rows.add(l.tops[0])
 
     # roots own a buffer; every other blob resolves through its chain of parents to a channel window of one

@@ -1046,6 +1046,40 @@ int  fcn_comm_init(fcn_comm_t* comm, const char* h_id128, int world, int rank);
 int  fcn_comm_allreduce_sum_f32(fcn_comm_t comm, float* buf, size_t count, fcn_stream_t s);
 int  fcn_comm_destroy(fcn_comm_t comm);
 
+/* ---- ArgMax (Caffe's ArgMaxLayer over the channel axis), alone and fused behind Interp and / or Softmax (csrc/argmax.hip).  x is a
+ *      (pixels, C, x_cstride, x_coffset) NHWC view of float32 or halves; y is ALWAYS float32, as Caffe's top is: top_k channels per pixel
+ *      (2 * top_k with FCN_ARGMAX_PAIRS) at y_coffset of y_cstride.  Caffe sorts (value, index) pairs with std::greater: rank 0 is the
+ *      largest value, and of equal values the LARGER INDEX comes first.  Only channels x_coffset .. x_coffset + C - 1 are compared: pad
+ *      channels and neighbouring windows may be loaded (inside the pixel's stride) and never win.  A NaN never takes a rank.  No atomics:
+ *      the same call gives the same bits; every launch can be captured.  Two launch shapes: a lane per pixel over the window's 16-byte
+ *      segments (segmentation tails: few channels, many pixels), and a wave per pixel with a fixed butterfly over (value, index) pairs
+ *      (classifier rows).  The wave form runs where a pixel's window holds more than FCN_ARGMAX_WAVE_BYTES bytes, and where at least
+ *      FCN_ARGMAX_WAVE_MIN_C channels meet at most FCN_ARGMAX_WAVE_PIXELS pixels (every pixel's wave resident at once: 256 CUs x 32).
+ *      Contract, checked before the first HIP call: null pointers, non-positive extents, top_k < 1 or > C, a window outside its pixel,
+ *      unknown flags or VALUES together with PAIRS FCN_E_ARG; top_k > FCN_ARGMAX_MAX_TOPK FCN_E_UNSUPPORTED; alignment as
+ *      fcn_interp_fwd_*: float32 x and y on 4-byte pointers with any stride (16-byte loads where x allows), half x on a 16-byte pointer
+ *      with stride and offset in multiples of 8 halves and y on one with multiples of 4 floats, else FCN_E_ALIGN.  Floor: the bytes of x. ---- */
+#define FCN_ARGMAX_MAX_TOPK 32
+#define FCN_ARGMAX_WAVE_BYTES  512   /* a window above this many bytes (128 floats, 256 halves): a wave per pixel */
+#define FCN_ARGMAX_WAVE_PIXELS 8192  /* up to this many pixels ...                                                  */
+#define FCN_ARGMAX_WAVE_MIN_C  32    /* ... of at least this many channels: a wave per pixel as well                */
+#define FCN_ARGMAX_VALUES  1   /* y holds the k largest values, not their indices (Caffe: axis set + out_max_val) */
+#define FCN_ARGMAX_PAIRS   2   /* y holds k indices, then k values (Caffe: no axis + out_max_val) */
+#define FCN_ARGMAX_SOFTMAX 4   /* x holds the scores in front of a fused Softmax: values are probabilities, indices unchanged */
+int  fcn_argmax_fwd_f32(const float* x, float* y, int pixels, int C, int x_cstride, int x_coffset, int top_k, int y_cstride, int y_coffset,
+                        int flags, fcn_stream_t s);
+int  fcn_argmax_fwd_f16(const void* x, float* y, int pixels, int C, int x_cstride, int x_coffset, int top_k, int y_cstride, int y_coffset,
+                        int flags, fcn_stream_t s);
+/* Interp (the geometry and integer cell arithmetic of fcn_interp_fwd_*: cell = num / (n2 - 1), weight = float(num % (n2 - 1)) /
+ * float(n2 - 1), num = o (n1 - 1); the blend in float32 without contraction) and ArgMax in one pass, a lane per output pixel: the
+ * resampled map is never written.  top_k == 1: y takes one float per pixel (index, or value with VALUES), or two (PAIRS: index, value).
+ * Under FCN_ARGMAX_SOFTMAX the value is the probability 1 / sum exp(v - max) over the blended scores.  Contract of fcn_interp_fwd_*
+ * (the half form as with out_f32 1) plus the flags'; 2^31 output pixels or more FCN_E_UNSUPPORTED. */
+int  fcn_interp_argmax_fwd_f32(const float* x, float* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int pad_beg, int pad_end,
+                               int OH, int OW, int y_cstride, int y_coffset, int flags, fcn_stream_t s);
+int  fcn_interp_argmax_fwd_f16(const void* x, float* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int pad_beg, int pad_end,
+                               int OH, int OW, int y_cstride, int y_coffset, int flags, fcn_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
