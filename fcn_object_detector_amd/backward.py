@@ -50,6 +50,7 @@ class BackwardPlanner:
         self.ops: List[Op] = []
         self.ws_floats = 1                                   # workspace of the weight-gradient launches: the largest any of them needs
         self.ip_ws_bytes = 0                                 # ... and of the InnerProduct data gradients, which run beside them (_inner_product)
+        self.ip_wgrad_ws_bytes = 0                           # ... and of the InnerProduct weight gradients above FCN_IP_MAX_ROWS rows (csrc/ip_gemm.hip)
         self.written: Dict[int, List[Tuple[int, int]]] = {}  # gradient buffer -> channel ranges already holding a gradient
         self.writers: Dict[str, List[object]] = {}           # gradient blob -> what wrote it, in order (a dgrad / pooling record or None)
         self.concat_members: Dict[str, List[str]] = {}       # Concat output -> its member blobs
@@ -84,6 +85,7 @@ class BackwardPlanner:
         self._finish_dgrads()
         self.ws = DeviceBuffer(self.ws_floats * 4, zero=False)
         self.ip_ws = DeviceBuffer(self.ip_ws_bytes, zero=False) if self.ip_ws_bytes else None
+        self.ip_wgrad_ws = DeviceBuffer(self.ip_wgrad_ws_bytes, zero=False) if self.ip_wgrad_ws_bytes else None
 
     # ------------------------------------------------------------------ write state of the gradient views
     def state(self, g: Blob) -> str:
@@ -535,8 +537,9 @@ class BackwardPlanner:
 
     # ------------------------------------------------------------------ InnerProduct
     def _inner_product(self, l: Layer) -> None:
-        """The weight-streaming kernels of csrc/inner_product.hip at M <= FCN_IP_MAX_ROWS rows: dW / db from the layer's input rows and
-        dY, dX = dY x bank.  Rows of the bottom and of its gradient are H*W*cstride floats apart and the bank holds zeros in the columns
+        """The weight-streaming kernels of csrc/inner_product.hip at M <= FCN_IP_MAX_ROWS rows, the matrix-core kernels of
+        csrc/ip_gemm.hip above (NetSpec ip_gemm=True; the same operands, op kinds ip_gemm_bwd / wgrad): dW / db from the layer's input
+        rows and dY, dX = dY x bank.  Rows of the bottom and of its gradient are H*W*cstride floats apart and the bank holds zeros in the columns
         of the pad channels, so pad channels of dX and pad columns of dW come out zero: the solver, weight decay and clipping run over
         the packed buffer as it is."""
         gtop = self._arrived(l)
@@ -546,17 +549,28 @@ class BackwardPlanner:
         xb = self.B[l.bottoms[0]]
         m, c, h, w = xb.nchw
         k, n_out = h * w * xb.cstride, gtop.channels
-        if m > L.IP_MAX_ROWS:
-            raise NotImplementedError("InnerProduct %s: a batch of %d rows (the streaming kernels take at most %d)" % (l.name, m, L.IP_MAX_ROWS))
+        gemm = m > L.IP_MAX_ROWS
+        if gemm and not self.spec.ip_gemm:
+            raise NotImplementedError(L.ip_rows_refusal(l.name, m))
+        gemm_ws = int(lib.fcn_ip_gemm_workspace_bytes(m, k, n_out, 4)) if gemm else 0
         if e._conv_layer_meta[l.name].get("relu") and top not in self.relu_done:
             self.relu_bwd_op(l.name, self.B[top], gtop)      # the layer's own in-place ReLU, on dY first
             self.relu_done.add(top)
         if e._learns(l) and l.name not in self.wgrad_done:
             dw = e._grad_view(l.name, 0)
             db = e._grad_view(l.name, 1).ptr if len(e.params_dev[l.name]) > 1 else None
-            op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_inner_product_bwd_weights_f32(
-                xb.buf.ptr, k, gtop.buf.ptr, gtop.cstride, gtop.coffset, dw.ptr, db, m, k, n_out, 0, st)),
-                2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out))
+            if gemm:
+                # a workspace of the weight gradients' own (for all such layers: they run one after the other on the second stream, beside
+                # bwd_data and its slabs)
+                self.ip_wgrad_ws_bytes = max(self.ip_wgrad_ws_bytes, gemm_ws)
+                op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_ip_gemm_bwd_weights_f32(
+                    xb.buf.ptr, k, gtop.buf.ptr, gtop.cstride, gtop.coffset, dw.ptr, db, m, k, n_out, 0,
+                    e._ip_wgrad_ws.ptr if e._ip_wgrad_ws is not None else None, st)),
+                    2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out))
+            else:
+                op = Op("wgrad", l.name, lambda st: L.check(lib.fcn_inner_product_bwd_weights_f32(
+                    xb.buf.ptr, k, gtop.buf.ptr, gtop.cstride, gtop.coffset, dw.ptr, db, m, k, n_out, 0, st)),
+                    2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out))
             self._book_wgrad(op, None, [l.name], [])
         gbot = self.G.get(l.bottoms[0])
         if gbot is None:
@@ -564,10 +578,11 @@ class BackwardPlanner:
         if gbot.coffset or gbot.cstride != xb.cstride or gbot.cstride != _r4(c):      # (storage.param_layout refused the forward's already)
             raise NotImplementedError("InnerProduct %s: the gradient of the bottom %s is a channel window of a wider buffer" % (l.name, l.bottoms[0]))
         # the slabs of bwd_data are NOT the weight gradients' workspace: those launches run on the second stream at the same time
-        self.ip_ws_bytes = max(self.ip_ws_bytes, int(lib.fcn_inner_product_workspace_bytes(m, k, n_out)))
+        self.ip_ws_bytes = max(self.ip_ws_bytes, gemm_ws if gemm else int(lib.fcn_inner_product_workspace_bytes(m, k, n_out)))
         flags = L.CONV_ACCUM if self.state(gbot) == "full" else 0
         wptr = e.params_dev[l.name][0].ptr
-        self.ops.append(Op("inner_product_bwd", l.name, lambda st: L.check(lib.fcn_inner_product_bwd_data_f32(
+        fn = lib.fcn_ip_gemm_bwd_data_f32 if gemm else lib.fcn_inner_product_bwd_data_f32
+        self.ops.append(Op("ip_gemm_bwd" if gemm else "inner_product_bwd", l.name, lambda st: L.check(fn(
             gtop.buf.ptr, gtop.cstride, gtop.coffset, wptr, gbot.buf.ptr, k, m, k, n_out, flags,
             e._ip_ws.ptr if e._ip_ws is not None else None, st)),
             2.0 * m * c * h * w * n_out, 4.0 * (n_out * k + m * k + m * n_out)))

@@ -38,6 +38,9 @@ inline hipStream_t as_stream(fcn_stream_t s) { return reinterpret_cast<hipStream
 // conv_fwd.hip: the per-device 16-byte zero page that masked lanes load (allocated by fcn_init)
 const float* zero_page_for_current_device(int* rc);
 
+// inner_product.hip: db[n] (+)= sum over m of dY[m][n] in row order, one launch (also the bias gradient of ip_gemm.hip)
+int ip_bias_grad(const char* who, const float* dy, float* db, int dy_cstride, int dy_coffset, int M, int N, int accumulate, fcn_stream_t s);
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // grid for HBM-bound grid-stride kernels: one work item per thread while that takes at most 64 Ki blocks (a grid only

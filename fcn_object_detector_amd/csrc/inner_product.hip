@@ -342,7 +342,7 @@ int ip_check(const char* who, const void* a, const void* b, const void* c, int M
     FCN_REQUIRE(a && b && c && M > 0 && K > 0 && N > 0, FCN_E_ARG, "%s: null pointer or non-positive extent", who);
     FCN_REQUIRE(K % E == 0 && aligned16(a) && aligned16(b) && aligned16(c), FCN_E_ALIGN,
                 "%s: K must be a multiple of %d elements, pointers of 16 bytes", who, E);
-    FCN_REQUIRE(M <= FCN_IP_MAX_ROWS, FCN_E_UNSUPPORTED, "%s: %d rows (at most %d: larger batches run as a 1x1 convolution)", who, M,
+    FCN_REQUIRE(M <= FCN_IP_MAX_ROWS, FCN_E_UNSUPPORTED, "%s: %d rows (at most %d: larger batches run through fcn_ip_gemm_*)", who, M,
                 FCN_IP_MAX_ROWS);
     FCN_REQUIRE((long long)N * K < (1ll << 31), FCN_E_UNSUPPORTED, "%s: bank past 2^31 elements", who);
     return 0;
@@ -394,6 +394,13 @@ int bwd_check(const char* who, int M, int K, int N, int dy_cstride, int dy_coffs
 }
 
 }  // namespace
+
+// the serial-over-M column sum, shared with ip_gemm.hip (common.h)
+int fcn::ip_bias_grad(const char* who, const float* dy, float* db, int dy_cstride, int dy_coffset, int M, int N, int accumulate, fcn_stream_t s) {
+    hipLaunchKernelGGL(ip_bias_grad_kernel, dim3(cdiv(N, 256)), dim3(256), 0, as_stream(s), dy, db, dy_cstride, dy_coffset, M, N, accumulate);
+    FCN_LAUNCH_CHECK(who);
+    return 0;
+}
 
 extern "C" {
 
@@ -463,10 +470,7 @@ int fcn_inner_product_bwd_weights_f32(const float* x, int x_rstride, const float
     switch (round_mt(M)) { FCN_IP_BWD(1) FCN_IP_BWD(2) FCN_IP_BWD(4) FCN_IP_BWD(8) FCN_IP_BWD(16) FCN_IP_BWD(32) }
 #undef FCN_IP_BWD
     FCN_LAUNCH_CHECK(who);
-    if (db) {
-        hipLaunchKernelGGL(ip_bias_grad_kernel, dim3(cdiv(N, 256)), dim3(256), 0, as_stream(s), dy, db, dy_cstride, dy_coffset, M, N, accumulate);
-        FCN_LAUNCH_CHECK(who);
-    }
+    if (db) return ip_bias_grad(who, dy, db, dy_cstride, dy_coffset, M, N, accumulate, s);
     return 0;
 }
 

@@ -1757,7 +1757,8 @@ class Engine:
         return out
 
     def _fwd_inner_product(self, l: Layer, relu: bool) -> List[Op]:
-        """InnerProduct at up to FCN_IP_MAX_ROWS rows: the weight-streaming kernels (csrc/inner_product.hip).  The bottom's rows are
+        """InnerProduct.  At up to FCN_IP_MAX_ROWS rows: the weight-streaming kernels (csrc/inner_product.hip); above, for a NetSpec
+        built with ip_gemm=True: the same call on the matrix-core kernels of csrc/ip_gemm.hip.  The bottom's rows are
         the input vectors as they lie in memory, the bank was packed in that order at upload; the top is N pixels of num_output
         channels, written at its channel offset (a member of a Concat of (N, C) blobs in place: _plan_buffers aliases it)."""
         lib = L.load()
@@ -1765,26 +1766,28 @@ class Engine:
         m, c, h, w = xb.nchw
         n_out = yb.channels
         k = h * w * xb.cstride
-        if m > L.IP_MAX_ROWS:
-            raise NotImplementedError("InnerProduct %s: a batch of %d rows (the streaming kernels take at most %d)" % (l.name, m, L.IP_MAX_ROWS))
+        gemm = m > L.IP_MAX_ROWS
+        if gemm and not self.spec.ip_gemm:
+            raise NotImplementedError(L.ip_rows_refusal(l.name, m))
         if xb.esize == 4 and yb.esize != 4:
             raise NotImplementedError("f16 engine: InnerProduct %s reads float32 and writes halves" % l.name)
         devs = self.params_dev[l.name]
         bias = devs[1].ptr if len(devs) > 1 else None
-        nbytes = int(lib.fcn_inner_product_fwd_workspace_bytes(m, k, n_out, xb.esize))
+        nbytes = int(lib.fcn_ip_gemm_workspace_bytes(m, k, n_out, xb.esize) if gemm else lib.fcn_inner_product_fwd_workspace_bytes(m, k, n_out, xb.esize))
         ws = DeviceBuffer(nbytes, zero=False) if nbytes else None
         if ws is not None:
             self._keep.append(ws)
         wsp = ws.ptr if ws is not None else None
         # non-temporal weight loads: the bank is read once per forward; launched alone behind a 512 MiB memset that policy took
         # 0.5 - 0.9 of the default's time, replayed back to back about the same (not measured inside a net)
-        flags = (L.CONV_RELU if relu else 0) | L.IP_WEIGHTS_NT
+        # (the GEMM has no such flag: its tiles of the bank are read again by the workgroups of the other row tiles)
+        flags = (L.CONV_RELU if relu else 0) | (0 if gemm else L.IP_WEIGHTS_NT)
         if xb.esize == 2:
-            fn, flags = lib.fcn_inner_product_fwd_f16, flags | (L.CONV_OUT_F32 if yb.esize == 4 else 0)
+            fn, flags = (lib.fcn_ip_gemm_fwd_f16 if gemm else lib.fcn_inner_product_fwd_f16), flags | (L.CONV_OUT_F32 if yb.esize == 4 else 0)
         else:
-            fn = lib.fcn_inner_product_fwd_f32
+            fn = lib.fcn_ip_gemm_fwd_f32 if gemm else lib.fcn_inner_product_fwd_f32
         wptr = devs[0].ptr
-        return [Op("inner_product", l.name, lambda st: L.check(fn(xb.buf.ptr, k, wptr, bias, yb.buf.ptr, yb.cstride, yb.coffset, m, k, n_out,
+        return [Op("ip_gemm" if gemm else "inner_product", l.name, lambda st: L.check(fn(xb.buf.ptr, k, wptr, bias, yb.buf.ptr, yb.cstride, yb.coffset, m, k, n_out,
                                                                   flags, wsp, st)),
                    2.0 * m * c * h * w * n_out, float(xb.esize) * (n_out * k + m * k) + float(yb.esize) * m * n_out)]
 

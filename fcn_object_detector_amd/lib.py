@@ -175,6 +175,12 @@ CODE_CORNER, CODE_CENTER_SIZE = 1, 2
 CONV_RELU, CONV_SIGMOID2, CONV_ACCUM, CONV_OUT_F32, CONV_F16, CONV_OUT_F16, CONV_MASK = 1, 2, 4, 8, 16, 32, 64
 IP_MAX_ROWS = 32               # FCN_IP_MAX_ROWS: rows the InnerProduct streaming kernels take
 IP_WEIGHTS_NT = 256            # FCN_IP_WEIGHTS_NT
+
+
+def ip_rows_refusal(layer: str, rows: int) -> str:
+    """What both engines and the backward planner say of an InnerProduct above IP_MAX_ROWS rows in a NetSpec built without ip_gemm=True."""
+    return ("InnerProduct %s: a batch of %d rows (the streaming kernels take at most %d): the matrix-core kernels take any row count for "
+            "a NetSpec built with ip_gemm=True (caffe.Net, the solvers and the caffe tool pass it)" % (layer, rows, IP_MAX_ROWS))
 CONV_IMAGE_ONES = 128      # half image whose channels 3 and 4 are the constant 1 (the folded Power shift): see include/fcnhip.h
 ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
 ARGMAX_MAX_TOPK = 32           # FCN_ARGMAX_MAX_TOPK
@@ -350,6 +356,11 @@ PROTOTYPES = {
     "fcn_inner_product_fwd_f16": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
     "fcn_inner_product_bwd_data_f32": (_i, [_vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "fcn_inner_product_bwd_weights_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 4 + [_vp]),
+    "fcn_ip_gemm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fcn_ip_gemm_fwd_f32": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "fcn_ip_gemm_fwd_f16": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "fcn_ip_gemm_bwd_data_f32": (_i, [_vp, _i, _i, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
+    "fcn_ip_gemm_bwd_weights_f32": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp]),
     "fcn_batchnorm_workspace_bytes": (_sz, [_i, _i]),
     "fcn_batchnorm_stats_f32": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "fcn_batchnorm_apply_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),

@@ -1407,3 +1407,68 @@ def rfcn_resnet(phase: str = "DEPLOY", depth: int = 50, classes: int = 21, size=
         w.layer(ave, "Pooling", [pooled], [top], "  pooling_param { pool: AVE kernel_size: 7 stride: 7 }")
     w.layer("cls_prob", "Softmax", ["cls_score"], ["cls_prob"])
     return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# Faster R-CNN (Ren, He, Girshick, Sun: "Faster R-CNN: Towards Real-Time Object Detection with Region Proposal Networks") on VGG16: the
+# test net of the py-faster-rcnn release, layer and blob names as remembered
+# ----------------------------------------------------------------------
+
+def faster_rcnn_vgg16(phase: str = "DEPLOY", classes: int = 21, size=(600, 1000), width_div: int = 1, fc_div: int = 1, batch: int = 1,
+                      post_nms_topn: int = 300, pre_nms_topn: int = 6000, fillers: bool = True) -> str:
+    """The Faster R-CNN test net on VGG16 (published names): conv1_1 .. conv5_3 with relu<b>_<i> and the 2x2 / 2 poolings pool1 .. pool4
+    (no pool5: conv5_3 is the stride-16 feature map).  RPN over conv5_3: rpn_conv/3x3 (512) with rpn_relu/3x3, rpn_cls_score (2 x 9) and
+    rpn_bbox_pred (4 x 9), the softmax chain rpn_cls_score_reshape -> rpn_cls_prob -> rpn_cls_prob_reshape, and `proposal` over
+    (rpn_cls_prob_reshape, rpn_bbox_pred, im_info) with the top rois.  Region stage: roi_pool5 (ROIPooling 7 x 7, spatial_scale 0.0625)
+    over (conv5_3, rois), fc6 and fc7 (4096, relu6 / drop6, relu7 / drop7), cls_score (classes) and bbox_pred (4 x classes) over fc7,
+    cls_prob.  Inputs: data (batch, 3, h, w) and im_info (1, 3).  `size` is the image edge or (height, width).
+
+    fc6 runs over all post_nms_topn rows of roi_pool5 - 300 in the published net, far above the 32 rows of the weight-streaming
+    InnerProduct kernels: the net needs a NetSpec built with ip_gemm=True (caffe.Net and the caffe tool pass it).
+
+    With the default pre / post_nms_topn the proposal layer is written as the published file writes it, a Python layer naming
+    rpn.proposal_layer.ProposalLayer with param_str "'feat_stride': 16"; with others as `type: "Proposal"` with a proposal_param.  This
+    project's own: width_div (the body's and the RPN's widths), fc_div (the 4096 of fc6 / fc7), the two topn arguments (small test nets),
+    and the lr_mult 1 / 2 param blocks on every learnable layer (the published test file has none).  DEPLOY only: TRAIN and TEST need
+    AnchorTarget / ProposalTarget, SmoothL1Loss and a backward pass through ROIPooling, which are not built."""
+    _check_phase(phase)
+    if phase != "DEPLOY":
+        raise NotImplementedError("Faster R-CNN %s net: AnchorTarget / ProposalTarget, SmoothL1Loss and the backward pass of ROIPooling are "
+                                  "not built - only the DEPLOY net" % phase)
+    if batch != 1:
+        raise NotImplementedError("faster_rcnn_vgg16: batch %d (the Proposal layer takes one image a forward)" % batch)
+    h, wdt = _hw(size)
+    wd = lambda c: max(c // width_div, 1)
+    fc = max(4096 // fc_div, 1)
+    w = _Writer()
+    w.raw('name: "VGG_ILSVRC_16_layers"')
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, h, wdt))
+    w.layer("im_info", "Input", [], ["im_info"], "  input_param { shape { dim: 1 dim: 3 } }")
+    prev = "data"
+    for blk, convs, width_ in VGG16:
+        for i in range(1, convs + 1):
+            prev = _dl_conv(w, "conv%d_%d" % (blk, i), prev, wd(width_), 3, 1, relu="relu%d_%d" % (blk, i))
+        if blk < 5:
+            w.layer("pool%d" % blk, "Pooling", [prev], ["pool%d" % blk], "  pooling_param { pool: MAX kernel_size: 2 stride: 2 }")
+            prev = "pool%d" % blk
+    _dl_conv(w, "rpn_conv/3x3", "conv5_3", wd(512), 3, 1, relu="rpn_relu/3x3", std=0.01)
+    _dl_conv(w, "rpn_cls_score", "rpn_conv/3x3", 18, 1, std=0.01)
+    _dl_conv(w, "rpn_bbox_pred", "rpn_conv/3x3", 36, 1, std=0.01)
+    w.layer("rpn_cls_score_reshape", "Reshape", ["rpn_cls_score"], ["rpn_cls_score_reshape"], "  reshape_param { shape { dim: 0 dim: 2 dim: -1 dim: 0 } }")
+    w.layer("rpn_cls_prob", "Softmax", ["rpn_cls_score_reshape"], ["rpn_cls_prob"])
+    w.layer("rpn_cls_prob_reshape", "Reshape", ["rpn_cls_prob"], ["rpn_cls_prob_reshape"], "  reshape_param { shape { dim: 0 dim: 18 dim: -1 dim: 0 } }")
+    bottoms = ["rpn_cls_prob_reshape", "rpn_bbox_pred", "im_info"]
+    if (pre_nms_topn, post_nms_topn) == (6000, 300):
+        w.layer("proposal", "Python", bottoms, ["rois"], "  python_param {\n    module: 'rpn.proposal_layer'\n    layer: 'ProposalLayer'\n"
+                "    param_str: \"'feat_stride': 16\"\n  }")
+    else:
+        w.layer("proposal", "Proposal", bottoms, ["rois"], "  proposal_param {\n    feat_stride: 16\n    pre_nms_topn: %d\n    post_nms_topn: %d\n  }"
+                % (pre_nms_topn, post_nms_topn))
+    w.layer("roi_pool5", "ROIPooling", ["conv5_3", "rois"], ["roi_pool5"], "  roi_pooling_param {\n    pooled_w: 7\n    pooled_h: 7\n"
+            "    spatial_scale: 0.0625\n  }")
+    _cn_fc(w, "fc6", "roi_pool5", fc, 0.005, 0.1, "relu6", "drop6")
+    _cn_fc(w, "fc7", "fc6", fc, 0.005, 0.1, "relu7", "drop7")
+    _cn_fc(w, "cls_score", "fc7", classes, 0.01, 0.0)
+    _cn_fc(w, "bbox_pred", "fc7", 4 * classes, 0.001, 0.0)
+    w.layer("cls_prob", "Softmax", ["cls_score"], ["cls_prob"])
+    return w.text() if fillers else _strip_fillers(w.text())

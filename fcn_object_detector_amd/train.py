@@ -245,7 +245,7 @@ class TrainEngine(Engine):
     def _build_backward(self) -> None:
         plan = BackwardPlanner(self)
         plan.run()
-        self.bwd_ops, self._ws, self._ip_ws = plan.ops, plan.ws, plan.ip_ws
+        self.bwd_ops, self._ws, self._ip_ws, self._ip_wgrad_ws = plan.ops, plan.ws, plan.ip_ws, plan.ip_wgrad_ws
         self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
             self.tuner.wgrad_cfgs(self.bwd_ops)

@@ -853,7 +853,7 @@ int  fcn_pool_mask_to_nchw_f32(const int32_t* idx, float* dst, int N, int PH, in
  *      d_workspace may be NULL) and run a second small launch; all launches are capturable.
  *      Contract: null pointers (x, w, y, dy, dx, dw; the workspace where one is needed), non-positive extents, a row stride below K, a
  *      slice outside its pixel, unknown flags FCN_E_ARG; pointers off 16 bytes, K or a stride that is not a multiple of 16 bytes (4 floats
- *      / 8 halves) FCN_E_ALIGN; M > FCN_IP_MAX_ROWS (run the layer as a 1x1 convolution over M pixels: the bank is its OHWI bank), N * K
+ *      / 8 halves) FCN_E_ALIGN; M > FCN_IP_MAX_ROWS (those row counts run through fcn_ip_gemm_* below, on the same operands), N * K
  *      or a view past 2^31 elements FCN_E_UNSUPPORTED.  Every check precedes the first HIP call. ---- */
 #define FCN_IP_MAX_ROWS 32
 #define FCN_IP_WEIGHTS_NT 256   /* forward flag: the loads of w carry the non-temporal hint (a bank read once, from cold caches) */
@@ -874,6 +874,37 @@ int  fcn_inner_product_bwd_data_f32(const float* dy, int dy_cstride, int dy_coff
 /* dW[n][k] (+)= sum_m dY[m][n] * x[m][k];  db[n] (+)= sum_m dY[m][n] (db may be NULL);  accumulate 1 adds (iter_size) */
 int  fcn_inner_product_bwd_weights_f32(const float* x, int x_rstride, const float* dy, int dy_cstride, int dy_coffset,
                                        float* dw, float* db, int M, int K, int N, int accumulate, fcn_stream_t s);
+
+/* ---- InnerProduct at any row count on the matrix cores (csrc/ip_gemm.hip): the same four products on the same operands as the block
+ *      above - rows of x with a stride, the bank [N][K], y / dY as a channel window of wider pixels, bias may be NULL, ReLU in the
+ *      forward epilogue - as an LDS-tiled GEMM (v_mfma_f32_32x32x2_f32 / v_mfma_f32_32x32x16_f16, float32 accumulation and bias).  Any
+ *      M >= 1 is legal; engines send M > FCN_IP_MAX_ROWS here and M <= FCN_IP_MAX_ROWS to the streaming kernels, whose results these do
+ *      not reproduce bit for bit (another order of summation).  One kernel serves all three products: forward reduces over K, bwd_data
+ *      over N, bwd_weights over M; elements of a reduction past its end are zeros in registers and are never loaded (what lies behind
+ *      the K elements of a row of x is never read), rows past M or N are never stored, and nothing outside [y_coffset, y_coffset + N)
+ *      of a y pixel, [0, K) of a dX row or the N x K of dW is written.  No atomics: a shape with too few 64 x 64 output tiles to fill
+ *      the chip has its reduction cut into slices - a function of (M, K, N, esize) alone - which leave float32 partial tiles in
+ *      d_workspace; a second small launch adds them in slice order and applies bias, ReLU and accumulate.  The same call gives the same
+ *      bits.  fcn_ip_gemm_workspace_bytes(M, K, N, esize) (esize 4: float32, all three products; 2: the half-float forward; anything
+ *      else, or a non-positive extent: 0) is what any one call needs; 0: none is needed and d_workspace may be NULL.  Calls that run at
+ *      the same time (the weight gradient on a second stream beside bwd_data) need a workspace each.
+ *      Contract: as the block above without the row limit - null pointers (the workspace where one is needed), non-positive extents, a
+ *      row stride below K, a slice outside its pixel, unknown flags FCN_E_ARG; pointers off 16 bytes, K or a stride that is not a
+ *      multiple of 16 bytes FCN_E_ALIGN; N * K or a view past 2^31 elements FCN_E_UNSUPPORTED.  Every check precedes the first HIP
+ *      call; all launches are capturable. ---- */
+size_t fcn_ip_gemm_workspace_bytes(int M, int K, int N, int esize);
+/* flags: FCN_CONV_RELU */
+int  fcn_ip_gemm_fwd_f32(const float* x, int x_rstride, const float* w, const float* bias, float* y, int y_cstride, int y_coffset,
+                         int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* x, w and y hold half floats; flags: FCN_CONV_RELU | FCN_CONV_OUT_F32 (y is float32) */
+int  fcn_ip_gemm_fwd_f16(const void* x, int x_rstride, const void* w, const float* bias, void* y, int y_cstride, int y_coffset,
+                         int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* dX[m][k] (+)= sum_n dY[m][n] * w[n][k];  flags: FCN_CONV_ACCUM adds the finished sum into dX (one rounded add per element) */
+int  fcn_ip_gemm_bwd_data_f32(const float* dy, int dy_cstride, int dy_coffset, const float* w, float* dx, int dx_rstride,
+                              int M, int K, int N, int flags, void* d_workspace, fcn_stream_t s);
+/* dW[n][k] (+)= sum_m dY[m][n] * x[m][k];  db[n] (+)= sum_m dY[m][n] in row order (db may be NULL);  accumulate 1 adds (iter_size) */
+int  fcn_ip_gemm_bwd_weights_f32(const float* x, int x_rstride, const float* dy, int dy_cstride, int dy_coffset,
+                                 float* dw, float* db, int M, int K, int N, int accumulate, void* d_workspace, fcn_stream_t s);
 
 /* ---- BatchNorm / Scale (Caffe BatchNormLayer, ScaleLayer over the channel axis) on NHWC views (csrc/batchnorm.hip).
  *      Views are the usual (pixels, C, cstride, coffset); a lane owns one 16-byte channel group of a pixel (4 floats / 8 halves).  Only
