@@ -6,7 +6,7 @@ tool cannot run without): point CAFFE_ROOT at <repo>/fcn_object_detector_amd and
 
     caffe train --solver=solver.prototxt [--weights=a.caffemodel[,b.caffemodel]] [--snapshot=x.solverstate] [--gpu=0|0,1,..|all]
     caffe test --model=train_val.prototxt --weights=a.caffemodel [--iterations=50] [--gpu=0]
-    caffe time --model=deploy.prototxt [--iterations=50] [--gpu=0]
+    caffe time --model=deploy.prototxt [--iterations=50] [--gpu=0]      (FCN_DTYPE=f16: the half-float engine)
     caffe device_query [--gpu=0]
 
 With more than one GPU the tool starts one process per GPU (data parallel, gradients summed over RCCL); it can
@@ -152,8 +152,8 @@ def cmd_time(flags):
     iters = int(flags.get("iterations", 50))
     device = gpu_list(flags.get("gpu"))[0]
     L.call("fcn_init", device)
-    spec = NetSpec(proto.parse_file(flags["model"]), "TEST", depthwise=True, ip_gemm=True)
-    eng = Engine(spec, data_shapes={}, params=None, device=device)
+    spec = NetSpec(proto.parse_file(flags["model"]), "TEST", depthwise=True, ip_gemm=True, rconv_f16=True)
+    eng = Engine(spec, data_shapes={}, params=None, device=device, dtype=os.environ.get("FCN_DTYPE", "f32"))      # (as caffe.Net reads it)
     rng = np.random.default_rng(0)
     for nm in eng.inputs:
         eng.host_array(nm)[...] = rng.random(eng.shapes[nm], dtype=np.float32) * 255

@@ -17,6 +17,11 @@
 // the current chunk's MFMAs.  A tap that falls outside the image contributes staged zeros.  16 KiB of LDS.  One launch covers every
 // problem of a plan: grid = (pixel blocks x Cout blocks of the largest problem, 1, problems).
 //
+// Forward in halves (rconv_f16_kernel, fcn_rconv2d_prepare_f16 / fcn_rconv2d_f16): the same tile, loader roles and LDS
+// layout over NHWC halves and the bank [Cout][kh][kw][round8(Cin)]; a 64-byte LDS row holds 32 input channels, a lane's 16-byte
+// fragment is the 8 consecutive k that v_mfma_f32_32x32x16_f16 takes: two MFMAs per chunk and wave.  Float32 sums, one rounding to
+// half (or a float32 result), bias and ReLU only: inference.
+//
 // Weight gradient (rconv_wgrad_kernel): per tap, dw[co][tap][ci] = sum over pixels of dy[pixel][co] * x[pixel under the tap][ci]: a
 // workgroup computes 64 Cout x 64 Cin of one tap over one split of the pixels, 16 pixels per staged chunk.  16 KiB of LDS.  With one
 // split the result goes straight to dw; otherwise every split writes its own slab of the workspace and rconv_wgrad_finish_kernel adds
@@ -38,6 +43,12 @@ constexpr int RC_THREADS = 256;
 constexpr int RW_BP = 16;       // weight gradient: pixels per staged chunk
 constexpr int RW_MAX_SPLITS = 64;
 constexpr int RC_CONFIGS = 1;   // tile configurations: 64 pixels x 64 channels x 16 k
+constexpr int RH_BK = 32;       // halves: input channels per staged chunk (the same 64-byte LDS row)
+constexpr int RH_CONFIGS = 1;   // halves: 64 pixels x 64 channels x 32 k
+constexpr int RH_CFG_BASE = FCN_RCONV_CFG_F16;      // fcn_rconv_plan.cfg of a half plan counts from here: a plan names its element type
+
+typedef _Float16 v4h __attribute__((ext_vector_type(4)));
+typedef int v2i __attribute__((ext_vector_type(2)));
 
 struct RConvP {
     const float* x;
@@ -171,6 +182,165 @@ __global__ __launch_bounds__(RC_THREADS) void rconv_f32_kernel(const RConvP* __r
     }
 }
 
+// The forward in halves (fcn_rconv2d_f16): the tile, the loader roles, the swizzled 64-byte LDS rows and the one barrier per chunk of
+// rconv_f32_kernel.  A row now holds 32 input channels, a thread's 16-byte load is 8 halves, and a lane's 16-byte fragment is the 8
+// consecutive k of its row that v_mfma_f32_32x32x16_f16 takes (lane half fh: k 8 fh .. 8 fh + 7 of the instruction's 16): two MFMAs
+// per chunk and wave.  RConvP's x / w / y point to halves here (y to floats under FCN_CONV_OUT_F32) and Cin4 holds round8(Cin).
+__global__ __launch_bounds__(RC_THREADS) void rconv_f16_kernel(const RConvP* __restrict__ probs) {
+    const RConvP& p = probs[blockIdx.z];
+    const int M = p.M;
+    const int mblk = blockIdx.x / p.nblk_n, nblk = blockIdx.x - mblk * p.nblk_n;
+    if (mblk * RC_BM >= M) return;
+
+    __shared__ __attribute__((aligned(16))) f16_t sW[2][RC_BN * RH_BK];
+    __shared__ __attribute__((aligned(16))) f16_t sA[2][RC_BM * RH_BK];
+
+    const f16_t* xh = reinterpret_cast<const f16_t*>(p.x);
+    const f16_t* wh = reinterpret_cast<const f16_t*>(p.w);
+    const int Cin8 = p.Cin4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- loader roles: row (a filter of the bank tile / a pixel of the activation tile) and 16-byte segment of the chunk
+    const int lrow = tid >> 2, lseg = tid & 3;
+    const int l_co = nblk * RC_BN + lrow;
+    const int l_m = mblk * RC_BM + lrow;
+    int l_n = 0, l_y0 = 0, l_x0 = 0;      // image, input row / column under tap (0, 0)
+    const bool l_mok = l_m < M;
+    if (l_mok) {
+        const int ox = l_m % p.OW;
+        const int t = l_m / p.OW;
+        l_y0 = (t % p.OH) * p.stride_h - p.pad_h;
+        l_x0 = ox * p.stride_w - p.pad_w;
+        l_n = t / p.OH;
+    }
+    const int lds_slot = lrow * RH_BK + ((lseg ^ swz<4>(lrow)) << 3);
+    const int nchunk = (Cin8 + RH_BK - 1) / RH_BK;
+    const int total = p.kh * p.kw * nchunk;
+
+    const v8h zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    v8h regW = zero8, regA = zero8;
+    int it_r = 0, it_q = 0, it_c = 0;      // the chunk the NEXT fetch() loads
+    auto fetch = [&]() {
+        const int ci = it_c * RH_BK + lseg * 8;
+        const int iy = l_y0 + it_r * p.dil, ix = l_x0 + it_q * p.dil;
+        regW = zero8;
+        regA = zero8;
+        if (ci < Cin8) {
+            if (l_co < p.Cout) regW = *(const v8h*)(wh + ((size_t)(l_co * p.kh + it_r) * p.kw + it_q) * Cin8 + ci);
+            if (l_mok && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) {
+                regA = *(const v8h*)(xh + ((size_t)(l_n * p.H + iy) * p.W + ix) * p.x_cstride + ci);
+                // channels Cin .. Cin8-1 of a pixel are padding: never multiplied, whatever they hold
+#pragma unroll
+                for (int e = 1; e < 8; ++e)
+                    if (ci + e >= p.Cin) regA[e] = (f16_t)0.f;
+            }
+        }
+        if (++it_c == nchunk) {
+            it_c = 0;
+            if (++it_q == p.kw) { it_q = 0; ++it_r; }
+        }
+    };
+
+    // ---- MFMA roles
+    const int wm = wave & 1, wn = wave >> 1;
+    const int fr = lane & 31, fh = lane >> 5;
+    const int rowW = wm * 32 + fr, rowA = wn * 32 + fr;
+    int offW[2], offA[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {      // MFMA j contracts k 16 j .. 16 j + 15 of the chunk: slots 2 j and 2 j + 1, one per lane half
+        offW[j] = rowW * RH_BK + (((2 * j + fh) ^ swz<4>(rowW)) << 3);
+        offA[j] = rowA * RH_BK + (((2 * j + fh) ^ swz<4>(rowA)) << 3);
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+
+    fetch();
+#pragma unroll 1
+    for (int it = 0; it < total; ++it) {
+        const int buf = it & 1;
+        *(v8h*)&sW[buf][lds_slot] = regW;
+        *(v8h*)&sA[buf][lds_slot] = regA;
+        if (it + 1 < total) fetch();
+        __syncthreads();      // (two buffers, one barrier per chunk: as in rconv_f32_kernel)
+        v8h wf[2], af[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            wf[j] = *(const v8h*)&sW[buf][offW[j]];
+            af[j] = *(const v8h*)&sA[buf][offA[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[j], af[j], acc, 0, 0, 0);
+    }
+
+    // ---- epilogue: the result layout of rconv_f32_kernel - lane = pixel, registers 4g .. 4g+3 = channels 8g + 4 fh .. +3 of the wave's 32
+    const int m = mblk * RC_BM + wn * 32 + fr;
+    if (m >= M) return;
+    const size_t pix = (size_t)m;
+    const bool do_relu = (p.flags & FCN_CONV_RELU) != 0, out32 = (p.flags & FCN_CONV_OUT_F32) != 0;
+    float* dst32 = reinterpret_cast<float*>(p.y) + pix * p.y_cstride + p.y_coffset;
+    f16_t* dst16 = reinterpret_cast<f16_t*>(p.y) + pix * p.y_cstride + p.y_coffset;
+    // bias and ReLU on the lane's own four runs of four channels
+    const int cbase = nblk * RC_BN + wm * 32;
+    v4f v[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int co = cbase + 8 * g + 4 * fh;
+        v[g] = v4f{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (p.bias && co + e < p.Cout) v[g][e] += p.bias[co + e];
+            if (do_relu) v[g][e] = fmaxf(v[g][e], 0.f);
+        }
+    }
+    if (!out32 && ((p.y_cstride | p.y_coffset) & 7) == 0 && ((unsigned)(size_t)p.y & 15) == 0) {
+        // 16-byte stores of halves: the two lanes of a pixel (fh = 0, 1; the same m, so both are here) trade runs - of the 16 channels
+        // of runs 2 gp and 2 gp + 1, lane fh = 0 ends up with the first eight and lane fh = 1 with the last eight
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+            const v4f a = v[2 * gp], b = v[2 * gp + 1];
+            const v4h own0 = {(f16_t)a[0], (f16_t)a[1], (f16_t)a[2], (f16_t)a[3]};      // round to nearest even, once
+            const v4h own1 = {(f16_t)b[0], (f16_t)b[1], (f16_t)b[2], (f16_t)b[3]};
+            const v2i send = __builtin_bit_cast(v2i, fh ? own0 : own1);
+            const v2i got = {__shfl_xor(send[0], 32), __shfl_xor(send[1], 32)};
+            const v4h recv = __builtin_bit_cast(v4h, got);
+            const v4h lo = fh ? recv : own0, hi = fh ? own1 : recv;
+            const v8h out = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            const int co8 = cbase + 16 * gp + 8 * fh;
+            if (co8 + 7 < p.Cout) {
+                *(v8h*)(dst16 + co8) = out;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (co8 + e < p.Cout) dst16[co8 + e] = out[e];
+            }
+        }
+        return;
+    }
+    // otherwise a run of four channels is one store where it is aligned as a whole: 16 bytes of floats, 8 bytes of halves
+    const bool vec_ok = ((p.y_cstride | p.y_coffset) & 3) == 0 && ((unsigned)(size_t)p.y & (out32 ? 15 : 7)) == 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int co = cbase + 8 * g + 4 * fh;
+        if (co >= p.Cout) continue;
+        const int run = min(4, p.Cout - co);
+        if (vec_ok && run == 4) {
+            if (out32) {
+                *(v4f*)(dst32 + co) = v[g];
+            } else {
+                const v4h h = {(f16_t)v[g][0], (f16_t)v[g][1], (f16_t)v[g][2], (f16_t)v[g][3]};      // round to nearest even, once
+                *(v4h*)(dst16 + co) = h;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e >= run) break;
+                if (out32) dst32[co + e] = v[g][e];
+                else dst16[co + e] = (f16_t)v[g][e];      // a 2-byte store: the half that shares the word is not touched
+            }
+        }
+    }
+}
+
 struct RWgradP {
     const float* x;
     const float* dy;
@@ -295,7 +465,8 @@ __global__ __launch_bounds__(256) void rconv_wgrad_finish_kernel(const float* __
 }
 
 // wgrad = true: the descriptor of fcn_rconv2d_wgrad_f32 (w, bias, y2 and flags are not looked at; y names dY)
-int validate(const fcn_rconv_desc& d, bool wgrad) {
+// half = true: the descriptor of fcn_rconv2d_prepare_f16 (x, w and y point to halves, y to floats under FCN_CONV_OUT_F32)
+int validate(const fcn_rconv_desc& d, bool wgrad, bool half = false) {
     FCN_REQUIRE(d.x && d.y && (wgrad || d.w), FCN_E_ARG, "rconv: null x/w/y");
     FCN_REQUIRE(d.N > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.kh > 0 && d.kw > 0 && d.stride_h > 0 && d.stride_w > 0 &&
                     d.pad_h >= 0 && d.pad_w >= 0,
@@ -303,11 +474,15 @@ int validate(const fcn_rconv_desc& d, bool wgrad) {
                 "rconv: non-positive extent");
     FCN_REQUIRE(d.dilation >= 1, FCN_E_UNSUPPORTED, "rconv: dilation %d below 1", d.dilation);
     FCN_REQUIRE(d.kh * (long long)d.kw <= 4096, FCN_E_UNSUPPORTED, "rconv: kernel window %dx%d too large", d.kh, d.kw);
-    const int ci4 = (d.Cin + 3) & ~3;
-    FCN_REQUIRE(d.x_cstride % 4 == 0 && d.x_cstride >= ci4, FCN_E_ALIGN, "rconv: x_cstride (%d) must be a multiple of 4 holding Cin (%d) padded to 4",
-                d.x_cstride, d.Cin);
+    const int vec = half ? 8 : 4;      // elements of a 16-byte load
+    const int ci4 = (d.Cin + vec - 1) & ~(vec - 1);
+    FCN_REQUIRE(d.x_cstride % vec == 0 && d.x_cstride >= ci4, FCN_E_ALIGN, "rconv: x_cstride (%d) must be a multiple of %d holding Cin (%d) padded to %d",
+                d.x_cstride, vec, d.Cin, vec);
     FCN_REQUIRE(((uintptr_t)d.x & 15) == 0 && (wgrad || ((uintptr_t)d.w & 15) == 0), FCN_E_ALIGN, "rconv: x / w must be 16-byte aligned");
-    FCN_REQUIRE(((uintptr_t)d.y & 3) == 0 && (wgrad || !d.bias || ((uintptr_t)d.bias & 3) == 0), FCN_E_ALIGN, "rconv: y / bias must be 4-byte aligned");
+    if (half && !(d.flags & FCN_CONV_OUT_F32))
+        FCN_REQUIRE(((uintptr_t)d.y & 1) == 0 && (!d.bias || ((uintptr_t)d.bias & 3) == 0), FCN_E_ALIGN, "rconv: y must be 2-byte, bias 4-byte aligned");
+    else
+        FCN_REQUIRE(((uintptr_t)d.y & 3) == 0 && (wgrad || !d.bias || ((uintptr_t)d.bias & 3) == 0), FCN_E_ALIGN, "rconv: y / bias must be 4-byte aligned");
     const long long eh = (long long)d.dilation * (d.kh - 1) + 1, ew = (long long)d.dilation * (d.kw - 1) + 1;
     const long long nh = (long long)d.H + 2ll * d.pad_h - eh, nw = (long long)d.W + 2ll * d.pad_w - ew;
     FCN_REQUIRE(nh >= 0 && nw >= 0, FCN_E_ARG, "rconv: the window (%lldx%lld) exceeds the padded image", eh, ew);
@@ -315,7 +490,10 @@ int validate(const fcn_rconv_desc& d, bool wgrad) {
                 "rconv: OH/OW (%d,%d) is not (H + 2 pad - (dil (k-1) + 1)) / stride + 1 per axis = (%lld,%lld)", d.OH, d.OW, nh / d.stride_h + 1,
                 nw / d.stride_w + 1);
     FCN_REQUIRE(d.y_coffset >= 0 && d.y_cstride >= d.y_coffset + d.Cout, FCN_E_ARG, "rconv: output slice exceeds y_cstride");
-    if (!wgrad) {
+    if (half) {      // the training epilogues stay float32
+        FCN_REQUIRE((d.flags & ~(FCN_CONV_RELU | FCN_CONV_OUT_F32)) == 0 && !d.y2, FCN_E_UNSUPPORTED,
+                    "rconv: flags 0x%x outside FCN_CONV_RELU | FCN_CONV_OUT_F32, or y2 set (half floats: forward only)", d.flags);
+    } else if (!wgrad) {
         FCN_REQUIRE((d.flags & ~(FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK)) == 0, FCN_E_UNSUPPORTED,
                     "rconv: flags 0x%x outside FCN_CONV_RELU | FCN_CONV_ACCUM | FCN_CONV_MASK (float32 only)", d.flags);
         if (d.flags & FCN_CONV_MASK)
@@ -324,7 +502,7 @@ int validate(const fcn_rconv_desc& d, bool wgrad) {
     }
     FCN_REQUIRE((long long)d.N * d.H * d.W * d.x_cstride < (1ll << 31) && (long long)d.N * d.OH * d.OW * d.y_cstride < (1ll << 31) &&
                     (long long)d.kh * d.kw * d.Cout * ci4 < (1ll << 31) &&
-                    (wgrad || !(d.flags & FCN_CONV_MASK) || (long long)d.N * d.OH * d.OW * d.y2_cstride < (1ll << 31)),
+                    (wgrad || half || !(d.flags & FCN_CONV_MASK) || (long long)d.N * d.OH * d.OW * d.y2_cstride < (1ll << 31)),
                 FCN_E_UNSUPPORTED, "rconv: tensor too large for 32-bit element offsets");
     return 0;
 }
@@ -363,19 +541,20 @@ using namespace fcn;
 extern "C" {
 
 int fcn_rconv2d_num_configs(void) { return RC_CONFIGS; }
+int fcn_rconv2d_num_configs_f16(void) { return RH_CONFIGS; }
 
 size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n) {
     (void)h_descs;
     return n > 0 ? (size_t)n * sizeof(RConvP) : 0;
 }
 
-int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out) {
+static int rconv_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out, bool half) {
     FCN_REQUIRE(h_descs && h_out && n > 0, FCN_E_ARG, "rconv prepare: null descriptors / plan or n <= 0");
     FCN_REQUIRE(n <= 65535, FCN_E_UNSUPPORTED, "rconv prepare: more than 65535 problems");
-    FCN_REQUIRE(cfg_request >= -1 && cfg_request < RC_CONFIGS, FCN_E_ARG, "rconv prepare: unknown configuration %d", cfg_request);
+    FCN_REQUIRE(cfg_request >= -1 && cfg_request < (half ? RH_CONFIGS : RC_CONFIGS), FCN_E_ARG, "rconv prepare: unknown configuration %d", cfg_request);
     long long gx = 0, total = 0;
     for (int i = 0; i < n; ++i) {
-        const int rc = validate(h_descs[i], false);
+        const int rc = validate(h_descs[i], false, half);
         if (rc) return rc;
         const long long tx = tiles_x(h_descs[i]);
         gx = tx > gx ? tx : gx;
@@ -383,6 +562,7 @@ int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace,
     }
     FCN_REQUIRE(gx < (1ll << 31) && total < (1ll << 31), FCN_E_UNSUPPORTED, "rconv prepare: too many tiles for one launch");
     FCN_REQUIRE(d_workspace, FCN_E_ARG, "rconv prepare: null workspace");
+    FCN_REQUIRE(!half || ((uintptr_t)d_workspace & 15) == 0, FCN_E_ALIGN, "rconv prepare: the workspace must be 16-byte aligned");
     std::vector<RConvP> ps((size_t)n);
     for (int i = 0; i < n; ++i) {
         const fcn_rconv_desc& d = h_descs[i];
@@ -391,18 +571,26 @@ int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace,
         p.N = d.N; p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.x_cstride = d.x_cstride; p.Cout = d.Cout; p.kh = d.kh; p.kw = d.kw;
         p.pad_h = d.pad_h; p.pad_w = d.pad_w; p.stride_h = d.stride_h; p.stride_w = d.stride_w; p.dil = d.dilation; p.OH = d.OH; p.OW = d.OW;
         p.y_cstride = d.y_cstride; p.y_coffset = d.y_coffset; p.y2_cstride = d.y2_cstride; p.y2_coffset = d.y2_coffset; p.flags = d.flags;
-        p.Cin4 = (d.Cin + 3) & ~3;
+        p.Cin4 = half ? (d.Cin + 7) & ~7 : (d.Cin + 3) & ~3;
         p.nblk_n = (d.Cout + RC_BN - 1) / RC_BN;
         p.M = d.N * d.OH * d.OW;
     }
     FCN_HIP(hipMemcpy(d_workspace, ps.data(), ps.size() * sizeof(RConvP), hipMemcpyHostToDevice));
     h_out->d_probs = d_workspace;
     h_out->n = n;
-    h_out->cfg = 0;
+    h_out->cfg = half ? RH_CFG_BASE : 0;
     h_out->grid_x = (int32_t)gx;
     h_out->grid_y = 1;
     h_out->total_tiles = (int32_t)total;
     return 0;
+}
+
+int fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out) {
+    return rconv_prepare(h_descs, n, d_workspace, cfg_request, h_out, false);
+}
+
+int fcn_rconv2d_prepare_f16(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out) {
+    return rconv_prepare(h_descs, n, d_workspace, cfg_request, h_out, true);
 }
 
 int fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s) {
@@ -411,6 +599,16 @@ int fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s) {
     hipLaunchKernelGGL(rconv_f32_kernel, dim3((unsigned)h_plan->grid_x, 1u, (unsigned)h_plan->n), dim3(RC_THREADS), 0, as_stream(s),
                        (const RConvP*)h_plan->d_probs);
     FCN_LAUNCH_CHECK("rconv_f32_kernel");
+    return 0;
+}
+
+int fcn_rconv2d_f16(const fcn_rconv_plan* h_plan, fcn_stream_t s) {
+    FCN_REQUIRE(h_plan && h_plan->d_probs && h_plan->n > 0 && h_plan->grid_x > 0 && h_plan->grid_y == 1 && h_plan->n <= 65535 &&
+                    h_plan->cfg >= RH_CFG_BASE && h_plan->cfg < RH_CFG_BASE + RH_CONFIGS,
+                FCN_E_ARG, "rconv: the plan was not filled by fcn_rconv2d_prepare_f16");
+    hipLaunchKernelGGL(rconv_f16_kernel, dim3((unsigned)h_plan->grid_x, 1u, (unsigned)h_plan->n), dim3(RC_THREADS), 0, as_stream(s),
+                       (const RConvP*)h_plan->d_probs);
+    FCN_LAUNCH_CHECK("rconv_f16_kernel");
     return 0;
 }
 

@@ -129,6 +129,11 @@ class RectGeom(namedtuple("RectGeom", "n cin h w cout oh ow kh kw sh sw ph pw d"
     def bytes(self) -> float:
         return 4.0 * (self.n * self.cin * self.h * self.w + self.n * self.cout * self.oh * self.ow + self.cout * self.cin * self.kh * self.kw + self.cout)
 
+    def bytes_as(self, xsize: int, ysize: int) -> float:
+        """`bytes` with x and the bank in elements of xsize bytes, y in elements of ysize bytes (the bias stays float32)."""
+        return float(xsize * (self.n * self.cin * self.h * self.w + self.cout * self.cin * self.kh * self.kw) +
+                     ysize * self.n * self.cout * self.oh * self.ow + 4 * self.cout)
+
     def swapped(self) -> "RectGeom":
         """The same layer seen from its output: input and output trade places (the data-gradient pass)."""
         return self._replace(cin=self.cout, h=self.oh, w=self.ow, cout=self.cin, oh=self.h, ow=self.w)
@@ -1155,30 +1160,38 @@ class Engine:
     def _rconv_task(self, li: int, l: Layer, skip: set) -> OpTask:
         """A Convolution whose axes differ in kernel, pad or stride (dilated or not), or a square one with dilation > 1 (the case with
         equal axes): a problem of csrc/rconv.hip, never of the tiled family or the tuner.  The bank is the layer's parameter blob where
-        it lies; an in-place ReLU behind the layer rides in the epilogue."""
+        it lies; an in-place ReLU behind the layer rides in the epilogue.  In a half-float engine whose NetSpec was built with
+        rconv_f16=True the bottom and the bank hold halves, the bias is float32 and the top holds halves or float32 (a net output);
+        without the keyword a half-float engine refuses the layer."""
         rect, dil, ng = is_rectangular(l), layer_dilation(l), self._conv_groups(l)
         who = "rectangular Convolution %s (%dx%d stride %dx%d pad %dx%d)" % (l.name, *layer_geometry(l)) if rect else \
             "Convolution %s with dilation %d" % (l.name, dil)
-        if self.f16:
+        if self.f16 and not self.spec.rconv_f16:
             raise NotImplementedError("f16 engine: %s has no half-float kernel" % who)
         if ng > 1:
             raise NotImplementedError("%s: group %d" % (who, ng) if rect else "Convolution %s: group %d together with dilation %d" % (l.name, ng, dil))
         g = self._rgeom(l)
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        if xb.coffset % 4 or xb.cstride % 4:
+        if self.f16 and xb.esize == 4:
+            raise NotImplementedError("f16 engine: %s reads the float32 blob %s" % (who, l.bottoms[0]))
+        eps = 16 // xb.esize
+        if xb.coffset % eps or xb.cstride % eps:
             raise NotImplementedError("%s Convolution %s: input view is not 16-byte aligned" % ("rectangular" if rect else "dilated", l.name))
         relu = self._relu_after(li, l, skip)      # (the ReLU half of _fused_after: fcn_rconv_desc has no second output for a Sigmoid)
         self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
         pd = self.params_dev[l.name]
-        d = rconv_desc(xb, yb, g, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, L.CONV_RELU if relu else 0)
+        flags = (L.CONV_RELU if relu else 0) | (L.CONV_OUT_F32 if xb.esize == 2 and yb.esize == 4 else 0)
+        d = rconv_desc(xb, yb, g, pd[0].ptr, pd[1].ptr if len(pd) > 1 else None, flags)
         return OpTask(l, [], reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])], rconv=d)
 
     def _emit_rconvs(self, items: List[OpTask]) -> None:
         """The dilated and rectangular convolutions of one level: the square dilated ones that read the same bottom (the four branches
         of an ASPP head) share ONE fcn_rconv2d_prepare plan and launch, op kind "dconv", the label shows the dilations; so do the
         rectangular ones (the 1x3 / 3x1 pair of an 8-grid Inception module), op kind "rconv", the label shows the kernels.  Square
-        launches come first.  FLOPs are booked as 2 N OH OW Cin Cout kh kw."""
+        launches come first.  FLOPs are booked as 2 N OH OW Cin Cout kh kw.  A half-float engine prepares and launches through
+        fcn_rconv2d_prepare_f16 / fcn_rconv2d_f16 and books its halves as 2 bytes."""
         lib = L.load()
+        prepare, fn = ("fcn_rconv2d_prepare_f16", lib.fcn_rconv2d_f16) if self.f16 else ("fcn_rconv2d_prepare", lib.fcn_rconv2d_f32)
         groups: Dict[Tuple[bool, Range], List[OpTask]] = {}
         for it in items:
             groups.setdefault((is_rectangular(it.layer), it.reads[0]), []).append(it)
@@ -1186,13 +1199,16 @@ class Engine:
             arr = (L.RConvDesc * len(chunk))(*[it.rconv for it in chunk])
             ws = DeviceBuffer(int(lib.fcn_rconv2d_workspace_bytes(arr, len(chunk))), zero=False)
             plan = L.RConvPlan()
-            L.call("fcn_rconv2d_prepare", arr, len(chunk), ws.ptr, -1, C.byref(plan))
+            L.call(prepare, arr, len(chunk), ws.ptr, -1, C.byref(plan))
             self._keep.extend([arr, ws, plan])
             geoms = [self._rgeom(it.layer) for it in chunk]
             shows = ",".join("%dx%d" % (g.kh, g.kw) for g in geoms) if rect else "d" + ",".join(str(g.d) for g in geoms)
             label = "%s [%s %dwg]" % ("+".join(it.layer.name for it in chunk), shows, plan.total_tiles)
-            self.ops.append(Op("rconv" if rect else "dconv", label, lambda st, p=plan: L.check(lib.fcn_rconv2d_f32(C.byref(p), st)),
-                               sum(g.flops for g in geoms), sum(g.bytes for g in geoms)))
+            byts = sum(g.bytes for g in geoms)
+            if self.f16:
+                byts = sum(g.bytes_as(self.blobs[it.layer.bottoms[0]].esize, self.blobs[it.layer.tops[0]].esize) for g, it in zip(geoms, chunk))
+            self.ops.append(Op("rconv" if rect else "dconv", label, lambda st, p=plan: L.check(fn(C.byref(p), st)),
+                               sum(g.flops for g in geoms), byts))
 
     def _emit_group(self, chunk: List[ConvTask], fused: List[OpTask], tail: Optional[dict]) -> None:
         """One grouped launch of `chunk` (at most 16 convolutions of one level); `fused` MAX poolings ride in it."""

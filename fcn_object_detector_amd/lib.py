@@ -327,6 +327,9 @@ PROTOTYPES = {
     "fcn_rconv2d_workspace_bytes": (_sz, [C.POINTER(RConvDesc), _i]),
     "fcn_rconv2d_prepare": (_i, [C.POINTER(RConvDesc), _i, _vp, _i, C.POINTER(RConvPlan)]),
     "fcn_rconv2d_f32": (_i, [C.POINTER(RConvPlan), _vp]),
+    "fcn_rconv2d_num_configs_f16": (_i, []),
+    "fcn_rconv2d_prepare_f16": (_i, [C.POINTER(RConvDesc), _i, _vp, _i, C.POINTER(RConvPlan)]),
+    "fcn_rconv2d_f16": (_i, [C.POINTER(RConvPlan), _vp]),
     "fcn_rconv2d_wgrad_workspace_floats": (_sz, [C.POINTER(RConvDesc)]),
     "fcn_rconv2d_wgrad_f32": (_i, [C.POINTER(RConvDesc), _vp, _vp, _vp, _vp]),
     "fcn_dwconv2d_num_configs": (_i, []),

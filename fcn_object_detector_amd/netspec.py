@@ -292,19 +292,23 @@ LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropy
 class NetSpec:
     """Phase-filtered layer list + blob/parameter shapes."""
 
-    def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False):
+    def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False, rconv_f16: bool = False):
         """depthwise: a Convolution with group == bottom channels == num_output > 1 is a depthwise convolution (is_depthwise), the
         same thing as a layer of type DepthwiseConvolution - the way the published MobileNet prototxts write it.  Off by default:
         a bare NetSpec keeps refusing such a layer where its parameters are laid out (storage.conv_groups).  The public entry points
         (caffe.Net, caffe.get_solver, `caffe train / test / time`) pass True.
         ip_gemm: an InnerProduct over more than FCN_IP_MAX_ROWS (32) rows runs through the matrix-core kernels of csrc/ip_gemm.hip.
         Off by default for the same reason: a bare NetSpec keeps refusing such a layer by name where it is planned (both engines and the
-        backward planner); the same public entry points pass True.  At up to 32 rows the keyword changes nothing."""
+        backward planner); the same public entry points pass True.  At up to 32 rows the keyword changes nothing.
+        rconv_f16: in a half-float engine a dilated or rectangular Convolution runs through the half-float kernel of csrc/rconv.hip
+        (fcn_rconv2d_f16).  Off by default, again: a bare NetSpec keeps refusing such a layer by name in a half-float engine; the public
+        entry points that build a TEST-phase net pass True.  A float32 engine never looks at the keyword."""
         if phase not in ("TRAIN", "TEST"):
             raise ValueError("phase must be 'TRAIN' or 'TEST'")
         self.phase = phase
         self.depthwise = bool(depthwise)
         self.ip_gemm = bool(ip_gemm)
+        self.rconv_f16 = bool(rconv_f16)
         self.name = str(msg.get("name", ""))
         self.layers: List[Layer] = [Layer(m) for m in msg.getall("layer") if _phase_included(m, phase)]
         if msg.getall("layers"):
@@ -337,8 +341,8 @@ class NetSpec:
         self.roi_blobs: Dict[str, Layer] = {}
 
     @classmethod
-    def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False) -> "NetSpec":
-        return cls(proto.parse_file(path), phase, depthwise, ip_gemm)
+    def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False) -> "NetSpec":
+        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16)
 
     def is_depthwise(self, l: Layer) -> bool:
         """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose

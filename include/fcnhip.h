@@ -697,6 +697,25 @@ size_t fcn_rconv2d_workspace_bytes(const fcn_rconv_desc* h_descs, int n);
 int    fcn_rconv2d_prepare(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out);
 /* one pure kernel launch for all problems of the plan: capturable */
 int    fcn_rconv2d_f32(const fcn_rconv_plan* h_plan, fcn_stream_t s);
+/* The forward in half floats (inference; training stays float32), the contract above with these differences.  The SAME descriptor:
+ * its x, w and y point to IEEE halves (declared float* - pass the addresses), y to float32 under FCN_CONV_OUT_F32; bias is float32
+ * or NULL.  x: NHWC halves, x_cstride a multiple of 8 and >= round8(Cin), 16-byte aligned; channels Cin .. round8(Cin)-1 of a pixel
+ * are padding and are never multiplied.  w: [Cout][kh][kw][round8(Cin)] halves where the layer's parameter blob lies, 16-byte
+ * aligned.  Sums are float32 on the matrix cores (v_mfma_f32_32x32x16_f16); a half result is rounded to nearest even once from the
+ * float32 sum (after bias and ReLU).  flags: FCN_CONV_RELU | FCN_CONV_OUT_F32; every other flag and a non-NULL y2 are
+ * FCN_E_UNSUPPORTED.  y needs 2-byte alignment (4-byte under FCN_CONV_OUT_F32) and any y_cstride >= y_coffset + Cout.  Halves go out
+ * in 16-byte stores (eight channels) when y is 16-byte aligned and y_cstride / y_coffset are multiples of 8, in 8-byte stores (four
+ * channels) when y is 8-byte aligned with multiples of 4, else in 2-byte stores; float32 results as in the float32 kernel.  A last
+ * partial run goes out in scalar stores: a half that shares a 32-bit word with the slice's first or last half is not touched.  The workspace (fcn_rconv2d_workspace_bytes) must be 16-byte aligned (FCN_E_ALIGN).  One launch for all problems
+ * of a plan, every output element written by exactly one lane, no atomics: the same bits on every run.
+ * A plan records its element type in `cfg`: fcn_rconv2d_prepare numbers its configurations from 0, fcn_rconv2d_prepare_f16 from
+ * FCN_RCONV_CFG_F16, and each launch refuses the other's plan with FCN_E_ARG. */
+#define FCN_RCONV_CFG_F16 256
+/* number of half-float tile configurations (cfg_request: -1 or 0 .. count-1); one today: 64 pixels x 64 channels x 32 k */
+int    fcn_rconv2d_num_configs_f16(void);
+int    fcn_rconv2d_prepare_f16(const fcn_rconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_rconv_plan* h_out);
+/* one pure kernel launch for all problems of the plan: capturable */
+int    fcn_rconv2d_f16(const fcn_rconv_plan* h_plan, fcn_stream_t s);
 /* Weight / bias gradient, the contract of fcn_conv2d_wgrad_f32: `d` describes the FORWARD problem, d->y / y_cstride / y_coffset name dY
  * (d->w, d->bias, d->y2 and d->flags are ignored).  dw is [Cout][kh][kw][round4(Cin)], 16-byte aligned, and is OVERWRITTEN; its pad
  * columns Cin .. round4(Cin)-1 are written as exact zeros (the solver, clipping and weight decay run over the packed buffer as it is).
