@@ -1511,14 +1511,14 @@ class Engine:
         """Crop: the window of bottom 0 at crop_param's offsets, in the size of bottom 1 - which lends its shape and is never read."""
         lib = L.load()
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        if xb.esize != yb.esize:
+        if xb.esize != yb.esize and not (xb.esize == 2 and yb.esize == 4):      # (halves into a float32 net output: the converting kernel)
             raise NotImplementedError("f16 engine: Crop %s copies between half and float32 blobs" % l.name)
         _, (_, oc, oy, ox) = crop_window(l, xb.shape, self.blobs[l.bottoms[1]].shape)
         n, _, h, w = xb.shape
         _, c, oh, ow = yb.shape
-        fn = lib.fcn_crop_fwd_f16 if xb.esize == 2 else lib.fcn_crop_fwd_f32
+        fn = lib.fcn_crop_fwd_f32 if xb.esize == 4 else lib.fcn_crop_fwd_f16 if yb.esize == 2 else lib.fcn_crop_fwd_f16_f32
         return [Op("crop", l.name, lambda st: L.check(fn(xb.buf.ptr, yb.buf.ptr, n, h, w, c, xb.cstride, xb.coffset + oc, oy, ox, oh, ow,
-                                                         yb.cstride, yb.coffset, st)), 0.0, 2.0 * xb.esize * yb.pixels * c)]
+                                                         yb.cstride, yb.coffset, st)), 0.0, float(xb.esize + yb.esize) * yb.pixels * c)]
 
     def _fwd_interp(self, l: Layer, halves: List[str]) -> List[Op]:
         """Interp: bilinear resampling of the bottom's effective window (interp_param's pads crop) to the top's size.  Halves are read
@@ -1818,6 +1818,8 @@ class Engine:
             # group 1: the transposed convolution on the matrix cores.  Its bank is re-packed from the blob in front of every
             # launch (one small launch): the blob may have been stepped by a solver, set through net.params or belong to
             # another engine (share_params) since the last forward.
+            if self.param_segs[(l.name, 0)].esize == 2:
+                return self._fwd_tconv_f16(l, g, xb, yb, wdev, bdev)
             if xb.coffset % 4 or xb.cstride % 4:
                 raise NotImplementedError("Deconvolution %s: input view is not 16-byte aligned" % l.name)
             bank = DeviceBuffer(max(int(lib.fcn_tconv_bank_floats(c, co, k, k)), 4) * 4, zero=True)
@@ -1837,6 +1839,27 @@ class Engine:
         return [Op("deconv", l.name, lambda st: L.check(fn(
             xb.ptr, wdev, bdev, yb.buf.ptr, g.n, g.h, g.w, c, xb.cstride, k, g.s, g.pad, g.oh, g.ow, yb.cstride, yb.coffset, *out_f32, st)),
             2.0 * yb.pixels * c * (k / g.s) ** 2, float(xb.esize * xb.pixels + yb.esize * yb.pixels) * c)]
+
+    def _fwd_tconv_f16(self, l: Layer, g: ConvGeom, xb: Blob, yb: Blob, wdev: int, bdev: Optional[int]) -> List[Op]:
+        """A group-1 Deconvolution of a half-float engine whose NetSpec was built with tconv_f16=True (storage.param_layout laid its
+        blob out in halves): the bottom and the bank hold halves, the bias is float32, the top holds halves or float32 (a net output).
+        The bank is re-packed in front of every launch, as in float32."""
+        lib = L.load()
+        c, co, k = g.cin, g.cout, g.k
+        if xb.esize != 2:
+            raise NotImplementedError("f16 engine: Deconvolution %s reads the float32 blob %s" % (l.name, l.bottoms[0]))
+        if xb.coffset % 8 or xb.cstride % 8:
+            raise NotImplementedError("Deconvolution %s: input view is not 16-byte aligned" % l.name)
+        bank = DeviceBuffer(max(int(lib.fcn_tconv_bank_halves(c, co, k, k)), 8) * 2, zero=True)
+        d = tconv_desc(xb, yb, g, bank.ptr, bdev, L.CONV_OUT_F32 if yb.esize == 4 else 0)
+        tws = DeviceBuffer(int(lib.fcn_tconv2d_workspace_bytes(C.byref(d), 1)), zero=False)
+        plan = L.TConvPlan()
+        L.call("fcn_tconv2d_prepare_f16", C.byref(d), 1, tws.ptr, -1, C.byref(plan))
+        self._keep.extend([bank, d, tws, plan])
+        return [Op("tconv_pack", l.name, lambda st: L.check(lib.fcn_tconv_bank_pack_f16(wdev, bank.ptr, c, co, _ra(co, 2), k, k, st)),
+                   0.0, 4.0 * c * co * k * k),
+                Op("tconv", l.name, lambda st: L.check(lib.fcn_tconv2d_f16(C.byref(plan), st)),
+                   2.0 * g.n * g.h * g.w * c * co * k * k, 2.0 * xb.pixels * c + float(yb.esize) * yb.pixels * co)]
 
     # ------------------------------------------------------------------ host <-> device
     def _stage(self, name: str) -> DeviceBuffer:

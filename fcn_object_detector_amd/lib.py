@@ -322,6 +322,11 @@ PROTOTYPES = {
     "fcn_tconv2d_f32": (_i, [C.POINTER(TConvPlan), _vp]),
     "fcn_tconv_bank_floats": (_sz, [_i, _i, _i, _i]),
     "fcn_tconv_bank_pack_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fcn_tconv2d_num_configs_f16": (_i, []),
+    "fcn_tconv2d_prepare_f16": (_i, [C.POINTER(TConvDesc), _i, _vp, _i, C.POINTER(TConvPlan)]),
+    "fcn_tconv2d_f16": (_i, [C.POINTER(TConvPlan), _vp]),
+    "fcn_tconv_bank_halves": (_sz, [_i, _i, _i, _i]),
+    "fcn_tconv_bank_pack_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fcn_channel_sum_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "fcn_rconv2d_num_configs": (_i, []),
     "fcn_rconv2d_workspace_bytes": (_sz, [C.POINTER(RConvDesc), _i]),
@@ -340,6 +345,7 @@ PROTOTYPES = {
     "fcn_dwconv2d_wgrad_f32": (_i, [C.POINTER(DwConvDesc), _vp, _vp, _vp, _i, _vp]),
     "fcn_crop_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_fwd_f16": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
+    "fcn_crop_fwd_f16_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_crop_bwd_f32": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),
     "fcn_interp_fwd_f32": (_i, [_vp, _vp] + [_i] * 12 + [_vp]),
     "fcn_interp_fwd_f16": (_i, [_vp, _vp] + [_i] * 13 + [_vp]),

@@ -292,7 +292,8 @@ LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropy
 class NetSpec:
     """Phase-filtered layer list + blob/parameter shapes."""
 
-    def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False, rconv_f16: bool = False):
+    def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False, rconv_f16: bool = False,
+                 tconv_f16: bool = False):
         """depthwise: a Convolution with group == bottom channels == num_output > 1 is a depthwise convolution (is_depthwise), the
         same thing as a layer of type DepthwiseConvolution - the way the published MobileNet prototxts write it.  Off by default:
         a bare NetSpec keeps refusing such a layer where its parameters are laid out (storage.conv_groups).  The public entry points
@@ -302,13 +303,17 @@ class NetSpec:
         backward planner); the same public entry points pass True.  At up to 32 rows the keyword changes nothing.
         rconv_f16: in a half-float engine a dilated or rectangular Convolution runs through the half-float kernel of csrc/rconv.hip
         (fcn_rconv2d_f16).  Off by default, again: a bare NetSpec keeps refusing such a layer by name in a half-float engine; the public
-        entry points that build a TEST-phase net pass True.  A float32 engine never looks at the keyword."""
+        entry points that build a TEST-phase net pass True.  A float32 engine never looks at the keyword.
+        tconv_f16: in a half-float engine a group-1 Deconvolution over a half bottom runs through the half-float kernel of
+        csrc/tconv.hip (fcn_tconv2d_f16) and its blob is a bank of halves.  Off by default, passed by the same entry points, never looked
+        at by a float32 engine: the rule of rconv_f16."""
         if phase not in ("TRAIN", "TEST"):
             raise ValueError("phase must be 'TRAIN' or 'TEST'")
         self.phase = phase
         self.depthwise = bool(depthwise)
         self.ip_gemm = bool(ip_gemm)
         self.rconv_f16 = bool(rconv_f16)
+        self.tconv_f16 = bool(tconv_f16)
         self.name = str(msg.get("name", ""))
         self.layers: List[Layer] = [Layer(m) for m in msg.getall("layer") if _phase_included(m, phase)]
         if msg.getall("layers"):
@@ -341,8 +346,9 @@ class NetSpec:
         self.roi_blobs: Dict[str, Layer] = {}
 
     @classmethod
-    def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False) -> "NetSpec":
-        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16)
+    def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False,
+                  tconv_f16: bool = False) -> "NetSpec":
+        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16)
 
     def is_depthwise(self, l: Layer) -> bool:
         """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose

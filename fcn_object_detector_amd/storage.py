@@ -175,10 +175,10 @@ def plan_blobs(spec: NetSpec, shapes: Dict[str, Tuple[int, ...]], inputs: Sequen
                 raise NotImplementedError("f16 engine: layer %s (%s) reads %s, the float32 top of ArgMax %s" % (q.name, q.type, l.tops[0], l.name))
         for name in shapes:
             if esize[name] == 4 and len(shapes[name]) in (2, 4) and name not in data_tops:
-                # (Softmax, Deconvolution, Interp and Upsample read halves and store float32: the out_f32 forms of their half kernels; the
-                # top of an ArgMax is float32 in both engines, as Caffe's is)
+                # (Softmax, Deconvolution, Interp, Upsample and Crop read halves and store float32: the out_f32 forms of their half kernels;
+                # the top of an ArgMax is float32 in both engines, as Caffe's is)
                 bad = [q.type for q in producers.get(name, []) if q.type not in ("Convolution", "Sigmoid", "Power", "Softmax", "Deconvolution", "InnerProduct",
-                                                                                 "Interp", "DepthwiseConvolution", "Upsample", "ArgMax")]
+                                                                                 "Interp", "DepthwiseConvolution", "Upsample", "ArgMax", "Crop")]
                 if bad:
                     raise NotImplementedError("f16 engine: float32 blob %s is produced by %s" % (name, bad))
 
@@ -337,6 +337,7 @@ class ParamSeg:
     kind: str                            # CONV: OHWI, Cin padded to whole 16-byte segments of the bottom's elements
     #                                      INNER_PRODUCT: [num_output][H*W*cstride], the columns in the order of a row of the NHWC bottom
     #                                      DECONV (group 1): [Cin][kh][kw][Cout padded to 4], an OHWI bank of Cin outputs over Cout inputs
+    #                                      (halves, Cout padded to 8, in a half-float engine whose NetSpec has tconv_f16)
     #                                      DEPTHWISE: [kh][kw][C padded to whole 16-byte segments of the bottom's elements], always float32
     #                                      PLAIN: as it is (biases, the depthwise Deconvolution's filters)
     offset: int                          # in 4-byte words (= floats in the f32 engine, where the solver and RCCL index the buffer)
@@ -346,7 +347,7 @@ class ParamSeg:
     lr_mult: float
     decay_mult: float
     nbytes: int
-    esize: int                           # 4, or 2: a bank of halves (half-float engine, CONV / INNER_PRODUCT over a half bottom)
+    esize: int                           # 4, or 2: a bank of halves (half-float engine, CONV / INNER_PRODUCT / DECONV over a half bottom)
     bottom: Optional[Tuple[int, int, int, int]] = None      # INNER_PRODUCT: c, h, w, cstride of the bottom
 
 
@@ -389,8 +390,15 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
                 elif g != 1:
                     raise NotImplementedError("Deconvolution %s: group %d with %d -> %d channels (only group 1 and group == channels == num_output)"
                                               % (l.name, g, c, co))
-                elif f16:
+                elif f16 and not spec.tconv_f16:
                     raise NotImplementedError("f16 engine: layer type Deconvolution with group 1 (%s) has no half-float kernel" % l.name)
+                elif f16:
+                    # the half-float transposed convolution (csrc/tconv.hip, fcn_tconv2d_f16): inference over a half bottom, a bank of halves
+                    if spec.phase == "TRAIN":
+                        raise NotImplementedError("f16 engine: Deconvolution %s with group 1 in a TRAIN net (half-float training)" % l.name)
+                    if views[l.bottoms[0]].esize != 2:
+                        raise NotImplementedError("f16 engine: Deconvolution %s reads the float32 blob %s" % (l.name, l.bottoms[0]))
+                    kind, shape, esize = DECONV, (c, kh, kw, _ra(cog, 2)), 2
                 else:
                     kind, shape = DECONV, (c, kh, kw, _r4(cog))
             elif i == 0 and l.type not in ("BatchNorm", "Scale", "Normalize"):      # (their blobs are per-channel vectors as they are: PLAIN)

@@ -639,6 +639,32 @@ int    fcn_tconv2d_f32(const fcn_tconv_plan* h_plan, fcn_stream_t s);
  * group-1 Deconvolution blob (Ca = Cin, Cb = Cout, w_cstride = round4(Cout)).  fcn_tconv_bank_floats(): floats of `packed`. */
 size_t fcn_tconv_bank_floats(int Ca, int Cb, int kh, int kw);
 int    fcn_tconv_bank_pack_f32(const float* w, float* packed, int Ca, int Cb, int w_cstride, int kh, int kw, fcn_stream_t s);
+/* The transposed convolution in half floats (inference; the data gradient of a strided convolution stays float32), the contract above
+ * with these differences.  The SAME descriptor: its a, w and b point to IEEE halves (declared float* - pass the addresses), b to
+ * float32 under FCN_CONV_OUT_F32; bias is float32 or NULL.  a: NHWC halves, a_cstride a multiple of 8 and >= round8(Ca), 16-byte
+ * aligned; channels Ca .. round8(Ca)-1 of a pixel are padding and are never multiplied, whatever they hold.  w: the bank packed by
+ * fcn_tconv_bank_pack_f16, [kh][kw][Cb][round8(Ca)] halves, 16-byte aligned.  Sums are float32 on the matrix cores
+ * (v_mfma_f32_32x32x16_f16); a half result is rounded to nearest even once from the float32 sum (after bias and ReLU).  flags:
+ * FCN_CONV_RELU | FCN_CONV_OUT_F32; every other flag (FCN_CONV_ACCUM, FCN_CONV_MASK) and a non-NULL y2 are FCN_E_UNSUPPORTED.  b needs
+ * 2-byte alignment (4-byte under FCN_CONV_OUT_F32) and any b_cstride >= b_coffset + Cb.  Halves go out in 16-byte stores (eight
+ * channels) when b is 16-byte aligned and b_cstride / b_coffset are multiples of 8, in 8-byte stores (four channels) when b is 8-byte
+ * aligned with multiples of 4, else in 2-byte stores; float32 results as in the float32 kernel.  A last partial run goes out in scalar
+ * stores: a half that shares a 32-bit word with the slice's first or last half is not touched.  One launch for all phases and problems
+ * of a plan, every output element written by exactly one lane, no atomics: the same bits on every run.
+ * Two tile configurations: 0 = 64 lattice pixels x 64 channels, 1 = 128 lattice pixels x 32 channels; one holds for the whole plan.
+ * cfg_request -1 takes 1 when no problem of the plan has more than 32 output channels (a score layer has 21) and 0 otherwise.
+ * A plan records its element type in `cfg`: fcn_tconv2d_prepare numbers its configurations from 0, fcn_tconv2d_prepare_f16 from
+ * FCN_TCONV_CFG_F16, and each launch refuses the other's plan with FCN_E_ARG.  The workspace is that of fcn_tconv2d_workspace_bytes. */
+#define FCN_TCONV_CFG_F16 256
+int    fcn_tconv2d_num_configs_f16(void);
+int    fcn_tconv2d_prepare_f16(const fcn_tconv_desc* h_descs, int n, void* d_workspace, int cfg_request, fcn_tconv_plan* h_out);
+/* one pure kernel launch for all problems and phases of the plan: capturable */
+int    fcn_tconv2d_f16(const fcn_tconv_plan* h_plan, fcn_stream_t s);
+/* the bank in halves: packed[(r*kw + q)*Cb + cb][ca] = w[ca][r][q][cb], zero for Ca <= ca < round8(Ca).  w is [Ca][kh][kw][w_cstride]
+ * halves (cb contiguous): the device layout of a group-1 Deconvolution blob over a half bottom (w_cstride = round8(Cout)); 2-byte
+ * aligned, packed 16-byte aligned.  fcn_tconv_bank_halves(): halves of `packed`. */
+size_t fcn_tconv_bank_halves(int Ca, int Cb, int kh, int kw);
+int    fcn_tconv_bank_pack_f16(const void* w, void* packed, int Ca, int Cb, int w_cstride, int kh, int kw, fcn_stream_t s);
 /* db[c] = sum over pixels of dy[pixel*cstride + coffset + c], c < C: the bias gradient of a Deconvolution (the weight-gradient kernel
  * sums ITS y, which after the role swap is the layer's input).  One workgroup per channel, fixed order: bit-reproducible. */
 int    fcn_channel_sum_f32(const float* dy, float* db, int pixels, int C, int cstride, int coffset, fcn_stream_t s);
@@ -796,6 +822,10 @@ int  fcn_crop_fwd_f32(const float* x, float* y, int N, int H, int W, int C, int 
                       int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
 int  fcn_crop_fwd_f16(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int off_y, int off_x,
                       int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
+/* the window copy, converting: x holds halves (x_cstride a multiple of 8), y float32 (y_cstride a multiple of 4) - the final score map of
+ * a half-float FCN net, a float32 net output.  Exact.  16 bytes of halves per lane when x_coffset is a multiple of 8 and y_coffset of 4 */
+int  fcn_crop_fwd_f16_f32(const void* x, void* y, int N, int H, int W, int C, int x_cstride, int x_coffset, int off_y, int off_x,
+                          int OH, int OW, int y_cstride, int y_coffset, fcn_stream_t s);
 /* accumulate 0: ONE launch writes channels dx_coffset .. dx_coffset + C - 1 of every pixel of dX - dY inside the window, zeros outside
  * (no memset in front).  accumulate 1: dX += dY inside the window and nothing outside it is touched (a blob with several consumers).
  * There is no half-float twin: the half-float engine is inference only. */
