@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Tuple
 from . import lib as L
 from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation
+from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad, layer_dilation, scale_gate_form
 
 
 @dataclass
@@ -51,6 +51,7 @@ class BackwardPlanner:
         self.ws_floats = 1                                   # workspace of the weight-gradient launches: the largest any of them needs
         self.ip_ws_bytes = 0                                 # ... and of the InnerProduct data gradients, which run beside them (_inner_product)
         self.ip_wgrad_ws_bytes = 0                           # ... and of the InnerProduct weight gradients above FCN_IP_MAX_ROWS rows (csrc/ip_gemm.hip)
+        self.gate_ws_bytes = 0                               # ... and of the gate gradients of the gated Scale layers (csrc/gate.hip)
         self.written: Dict[int, List[Tuple[int, int]]] = {}  # gradient buffer -> channel ranges already holding a gradient
         self.writers: Dict[str, List[object]] = {}           # gradient blob -> what wrote it, in order (a dgrad / pooling record or None)
         self.concat_members: Dict[str, List[str]] = {}       # Concat output -> its member blobs
@@ -67,7 +68,7 @@ class BackwardPlanner:
         # layer types that look at the plan state themselves ...
         self.emitters = {"Convolution": self._convolution, "DepthwiseConvolution": self._convolution, "InnerProduct": self._inner_product, "Eltwise": self._eltwise, "Deconvolution": self._deconvolution,
                          "Sigmoid": self._sigmoid, "ReLU": self._relu, "Slice": self._slice, "Concat": self._concat,
-                         "BatchNorm": self._batchnorm, "Scale": self._batchnorm,
+                         "BatchNorm": self._batchnorm, "Scale": lambda l: (self._scale_gate if is_scale_gate(l) else self._batchnorm)(l),
                          "L1Loss": self._loss, "EuclideanLoss": self._loss, "SoftmaxWithLoss": self._loss,
                          "Accuracy": nothing,      # a metric: no gradient, no entry in loss_blobs
                          **{t: nothing for t in DATA_TYPES}}
@@ -86,6 +87,7 @@ class BackwardPlanner:
         self.ws = DeviceBuffer(self.ws_floats * 4, zero=False)
         self.ip_ws = DeviceBuffer(self.ip_ws_bytes, zero=False) if self.ip_ws_bytes else None
         self.ip_wgrad_ws = DeviceBuffer(self.ip_wgrad_ws_bytes, zero=False) if self.ip_wgrad_ws_bytes else None
+        self.gate_ws = DeviceBuffer(self.gate_ws_bytes, zero=False) if self.gate_ws_bytes else None
 
     # ------------------------------------------------------------------ write state of the gradient views
     def state(self, g: Blob) -> str:
@@ -768,6 +770,37 @@ class BackwardPlanner:
         if learns:      # (the apply launch reads the two sums where the reduce launch left them: the exchange must not sum them before)
             self.ops[-1].layers = [ch.scale.name]
         self.mark(gbot)
+
+    # ------------------------------------------------------------------ gated Scale (the multiplier is a blob of the net)
+    def _scale_gate(self, l: Layer) -> None:
+        """Backward of a Scale with two bottoms (x, gate) - engine._scale_gate_op; TRAIN engines never fuse it: dx (+)= dY * gate[n, c] into
+        G[x] and dgate[n, c] (+)= sum over the image's pixels of dY * x into G[gate], each accumulating where its view already holds a
+        gradient and left out where that bottom needs none.  The data gradient comes first: in an SE block the global pooling's backward
+        then accumulates into G[x].  One workspace, sized here, serves every gate gradient of the net (they run one after the other on
+        the main stream)."""
+        gtop = self._arrived(l)
+        if gtop is None:
+            return
+        e, lib, B = self.e, self.lib, self.B
+        xb, gb = B[l.bottoms[0]], B[l.bottoms[1]]
+        n, ppi, c = scale_gate_form(l, [e.shapes[b] for b in l.bottoms], self.spec.phase)
+        gx, gg = self.G.get(l.bottoms[0]), self.G.get(l.bottoms[1])
+        for v in (gtop, gx, xb):
+            if v is not None and (v.coffset % 4 or v.cstride % 4):
+                raise NotImplementedError("backward of Scale %s: the view of %s is not 16-byte aligned" % (l.name, v.name))
+        if gx is not None:
+            acc_x = 1 if self.state(gx) == "full" else 0      # (a name of its own: the launch reads it when it runs, after the gate's is set)
+            self.ops.append(Op("scale_gate_bwd", l.name + ":" + l.bottoms[0], lambda st: L.check(lib.fcn_scale_gate_bwd_data_f32(
+                gtop.buf.ptr, gb.ptr, gx.buf.ptr, n, ppi, c, gtop.cstride, gtop.coffset, gb.cstride, gx.cstride, gx.coffset, acc_x, st)),
+                1.0 * n * ppi * c, 4.0 * (2 + acc_x) * n * ppi * c))
+            self.mark(gx)
+        if gg is not None:
+            acc_g = 1 if self.state(gg) == "full" else 0
+            self.gate_ws_bytes = max(self.gate_ws_bytes, int(lib.fcn_scale_gate_workspace_bytes(n, ppi, c)))
+            self.ops.append(Op("scale_gate_bwd", l.name + ":" + l.bottoms[1], lambda st: L.check(lib.fcn_scale_gate_bwd_gate_f32(
+                gtop.buf.ptr, xb.buf.ptr, gg.ptr, n, ppi, c, gtop.cstride, gtop.coffset, xb.cstride, xb.coffset, gg.cstride, acc_g,
+                e._gate_ws.ptr, st)), 2.0 * n * ppi * c, 8.0 * n * ppi * c))
+            self.mark(gg)
 
     # ------------------------------------------------------------------ one bottom, one top, one launch dY -> dX
     def _one_bottom(self, l: Layer) -> None:

@@ -32,7 +32,8 @@ from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
-from .netspec import Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, kernel_stride_pad, layer_dilation, layer_geometry
+from .netspec import (Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
+                      layer_dilation, layer_geometry, scale_gate_form)
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -771,6 +772,67 @@ class Engine:
         self._bn_chains[first.name] = ch
         return ops
 
+    @staticmethod
+    def _gate_residual(sc: Layer, elt: Layer) -> str:
+        """The bottom of the Eltwise `elt` that is not the top of the gated Scale `sc`."""
+        return elt.bottoms[1] if elt.bottoms[0] == sc.tops[0] else elt.bottoms[0]
+
+    def _gate_fusion(self, li: int, l: Layer) -> Optional[Layer]:
+        """The Eltwise that takes the gated Scale l into its launch, y = relu?(x * g + r), or None.  TEST-phase engines with `fuse` only.
+        The Scale top is read by exactly one layer, an Eltwise SUM of two different bottoms with coefficients 1; it has one producer, is
+        no output of the net and no view of another blob (the fused launch never writes it: read_blob() fills it on demand); no layer
+        behind the Scale writes x or the gate; and x, the residual and the Eltwise top are windows the kernel takes.  The fused task stands
+        at the Eltwise's place in the order (_collect_tasks), where the residual has been written."""
+        top, B = l.tops[0], self.blobs
+        if not self.fuse or self.spec.phase != "TEST":
+            return None
+        cons = self.consumers.get(top, [])
+        if len(cons) != 1 or top in self.outputs or len(self.producers.get(top, [])) != 1 or top in self.alias or top in l.bottoms:
+            return None
+        elt = cons[0]
+        p = elt.sub("eltwise_param")
+        if elt.type != "Eltwise" or str(p.get("operation", "SUM")) != "SUM" or len(elt.bottoms) != 2 or elt.bottoms.count(top) != 1 \
+                or any(float(c) != 1.0 for c in p.getall("coeff")) or len(elt.tops) != 1:
+            return None
+        # nothing behind the Scale may write x or the gate - the Eltwise in place over x included: the fused launch reads them at the
+        # Eltwise's place in the order, and read_blob() computes the Scale top from them after the forward pass
+        if any(b in q.tops for q in self.spec.layers[li + 1:] for b in l.bottoms):
+            return None
+        xb, rb, yb = B[l.bottoms[0]], B[self._gate_residual(l, elt)], B[elt.tops[0]]
+        grp = 16 // xb.esize
+        if any(v.esize != xb.esize or v.nchw is None or v.coffset % grp or v.cstride % grp for v in (xb, rb, yb)):
+            return None
+        self._gate_fused[elt.name] = l
+        return elt
+
+    def _scale_gate_op(self, l: Layer, elt: Optional[Layer], relu: Optional[str]) -> Op:
+        """One launch of csrc/gate.hip: y = x * gate[n, c] for the gated Scale l alone (its top), or - with the Eltwise `elt` that
+        _gate_fusion found - y = relu?(x * gate[n, c] + r) into the Eltwise top, `relu` the ReLU layer in place behind it.  x, r and y are
+        floats or halves alike; the gate is float32 in both engines (the top of a Sigmoid: storage.plan_blobs keeps it so)."""
+        lib, B = L.load(), self.blobs
+        xb, gb = B[l.bottoms[0]], B[l.bottoms[1]]
+        yb = B[elt.tops[0] if elt is not None else l.tops[0]]
+        rb = B[self._gate_residual(l, elt)] if elt is not None else None
+        n, ppi, c = scale_gate_form(l, [self.shapes[b] for b in l.bottoms], self.spec.phase)
+        if self.f16 and l.bottoms[1] in self.inputs:
+            raise NotImplementedError("f16 engine: Scale %s takes its multiplier %s from an input of the net" % (l.name, l.bottoms[1]))
+        if gb.esize != 4:
+            raise NotImplementedError("f16 engine: Scale %s: the multiplier %s is stored as halves (the kernel reads a float32 gate: the top of "
+                                      "a Sigmoid is one)" % (l.name, l.bottoms[1]))
+        if gb.nchw is None or gb.nchw[0] != n or gb.nchw[1] != c:
+            raise NotImplementedError("Scale %s: the multiplier %s is no (N, C) blob on the device" % (l.name, l.bottoms[1]))
+        grp = 16 // xb.esize
+        for v in (xb, yb) + ((rb,) if rb is not None else ()):
+            if v.esize != xb.esize or v.nchw is None or v.coffset % grp or v.cstride % grp:
+                raise NotImplementedError("Scale %s: %s is stored in another element type than %s, or is a channel window that is not 16-byte "
+                                          "aligned" % (l.name, v.name, xb.name))
+        fn = lib.fcn_scale_gate_fwd_f16 if xb.esize == 2 else lib.fcn_scale_gate_fwd_f32
+        rp, rcs, rco = (rb.buf.ptr, rb.cstride, rb.coffset) if rb is not None else (None, 0, 0)
+        name = l.name if elt is None else "+".join([l.name, elt.name] + ([relu] if relu else []))
+        return Op("scale_gate", name, lambda st: L.check(fn(
+            xb.buf.ptr, gb.ptr, rp, yb.buf.ptr, n, ppi, c, xb.cstride, xb.coffset, gb.cstride, rcs, rco, yb.cstride, yb.coffset, int(bool(relu)), st)),
+            (2.0 if rb is not None else 1.0) * n * ppi * c, float(xb.esize) * (3.0 if rb is not None else 2.0) * n * ppi * c)
+
     def _argmax_chain_at(self, l: Layer, skip: set) -> Optional["ArgChain"]:
         """The chain [Interp ->] [Softmax ->] ArgMax that starts at layer l, or None when l (an Interp or a Softmax) starts none.  A link
         joins where the blob in front of it has it as its only reader, has one producer, is no output of the net and no view of another
@@ -837,6 +899,7 @@ class Engine:
         skip: set = set()
         tasks: List[Task] = []
         self._conv_flags: Dict[str, int] = {}      # Convolution layer of the tiled family -> the CONV_* flags of its descriptor(s)
+        self._gate_fused: Dict[str, Layer] = {}    # Eltwise layer -> the gated Scale whose launch it joins (_gate_fusion)
         for li, l in enumerate(spec.layers):
             if l.name in skip:
                 continue
@@ -869,6 +932,17 @@ class Engine:
                 relu = self._relu_after(li, l, skip)
                 self._conv_layer_meta[l.name] = dict(relu=relu, sigmoid_top=None)
                 tasks.append(OpTask(l, self._fwd_inner_product(l, relu), reads=[self._range(l.bottoms[0])], writes=[self._range(l.tops[0])]))
+                continue
+            if is_scale_gate(l):      # the multiplier is a blob of the net: csrc/gate.hip, alone or (TEST) with the residual add behind it
+                if self._gate_fusion(li, l) is None:
+                    tasks.append(OpTask(l, [self._scale_gate_op(l, None, None)], reads=[self._range(b) for b in l.bottoms], writes=[self._range(l.tops[0])]))
+                continue
+            if t == "Eltwise" and l.name in self._gate_fused:      # (at the Eltwise's place in the order: its residual is written by now)
+                sc, before = self._gate_fused[l.name], set(skip)
+                relu = next(iter(skip - before)) if self._relu_after(li, l, skip) else None
+                self._lazy_blob_ops[sc.tops[0]] = [self._scale_gate_op(sc, None, None)]
+                tasks.append(OpTask(l, [self._scale_gate_op(sc, l, relu)], reads=[self._range(b) for b in sc.bottoms + [self._gate_residual(sc, l)]],
+                                    writes=[self._range(l.tops[0])]))
                 continue
             if t in ("BatchNorm", "Scale"):
                 ch = self._bn_chain_after(li, l, skip)

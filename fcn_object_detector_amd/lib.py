@@ -376,6 +376,11 @@ PROTOTYPES = {
     "fcn_batchnorm_apply_f16": (_i, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _vp]),
     "fcn_batchnorm_bwd_reduce_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _vp]),
     "fcn_batchnorm_bwd_apply_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp]),
+    "fcn_scale_gate_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fcn_scale_gate_fwd_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),
+    "fcn_scale_gate_fwd_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),
+    "fcn_scale_gate_bwd_data_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "fcn_scale_gate_bwd_gate_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     "fcn_ssd_gather_f32": (_i, [C.POINTER(SsdHead), _i, _i, _vp, _i, _i, _vp]),
     "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
     "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),

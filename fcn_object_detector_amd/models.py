@@ -713,6 +713,94 @@ def resnet152(phase: str = "DEPLOY", **kw) -> str:
 
 
 # ----------------------------------------------------------------------
+# SE-ResNet-50 / 101 / 152 (Hu, Shen, Sun: "Squeeze-and-Excitation Networks"; the SENet release's Caffe names where remembered)
+# ----------------------------------------------------------------------
+
+def _se_fc(w: _Writer, name: str, bottom: str, num_output: int, form: str) -> str:
+    """A squeeze or excite layer over the pooled (N, C, 1, 1) blob, with a bias: an InnerProduct (form "scale") or the release's 1x1
+    Convolution (form "axpy").  Their blobs agree up to the trailing 1, 1."""
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n    bias_filler { type: \"constant\" value: 0 }\n" % (2.0 / num_output) ** 0.5
+    if form == "scale":
+        w.layer(name, "InnerProduct", [bottom], [name], "  inner_product_param {\n    num_output: %d\n%s  }" % (num_output, fill))
+    else:
+        w.layer(name, "Convolution", [bottom], [name], "  convolution_param {\n    num_output: %d\n    kernel_size: 1\n    stride: 1\n%s  }" % (num_output, fill))
+    return name
+
+
+def se_resnet(phase: str = "DEPLOY", depth: int = 50, batch: int = 1, num_classes: int = 1000, width_div: int = 1, size: int = 224,
+              reduction: int = 16, form: str = "scale", fillers: bool = True) -> str:
+    """SE-ResNet-50 / 101 / 152: models.resnet's bottleneck stages with a Squeeze-and-Excitation block behind the last BatchNorm / Scale of
+    every residual branch - global AVE pooling, a squeeze to out // reduction channels with an in-place ReLU, an excite back to out, a
+    Sigmoid, the gate applied to the branch, the Eltwise with the shortcut and the ReLU.
+    form "scale": squeeze and excite are InnerProduct layers, the (N, C) gate is applied by `Scale { axis: 0 }` with two bottoms and an
+    Eltwise SUM follows.  form "axpy": they are 1x1 Convolutions and the release's `Axpy` layer (gate, branch, shortcut) applies the gate
+    and adds the shortcut - the shape of the published files.  Both need a NetSpec built with scale_gate=True (caffe.Net and the caffe
+    tool pass it), and after it has read the Axpy layers both forms have the same layers and blobs by name.
+    Names.  The SENet release's, as remembered: conv1/7x7_s2, pool1/3x3_s2, the convolutions conv<stage>_<block>_1x1_reduce / _3x3 /
+    _1x1_increase / _1x1_proj, the SE layers conv<stage>_<block>_global_pool / _1x1_down / _1x1_down/relu / _1x1_up / _prob, the block
+    output conv<stage>_<block> with conv<stage>_<block>/relu, pool5/7x7_s1, classifier and prob.  The project's own: the BatchNorm, Scale
+    and ReLU layers on the convolutions (models.resnet's bn_<conv> / scale_<conv> / <conv>_relu, not the release's <conv>/bn ...), the
+    gated Scale conv<stage>_<block>/scale of form "scale" (what an Axpy is read as), and a bias on conv1 as in models.resnet.  Phases,
+    width_div and size as in models.resnet; the squeeze width is at least 1."""
+    _check_phase(phase)
+    if depth not in RESNET_BLOCKS:
+        raise ValueError("depth must be one of %s" % sorted(RESNET_BLOCKS))
+    if form not in ("scale", "axpy"):
+        raise ValueError("form must be 'scale' or 'axpy'")
+    if reduction < 1:
+        raise ValueError("reduction must be at least 1")
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "SE-ResNet-%d"' % depth)
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch,)))
+    _rn_conv_bn(w, "", "data", wd(64), 7, 3, 2, phase, True, conv_name="conv1/7x7_s2", bias=True)
+    w.layer("pool1/3x3_s2", "Pooling", ["conv1/7x7_s2"], ["pool1/3x3_s2"], "  pooling_param { pool: MAX kernel_size: 3 stride: 2 }")
+    feat = "pool1/3x3_s2"
+    for stage, count in zip((2, 3, 4, 5), RESNET_BLOCKS[depth]):
+        mid, out = wd(64 << (stage - 2)), wd(256 << (stage - 2))
+        for bi in range(count):
+            tag = "conv%d_%d" % (stage, bi + 1)
+            stride = 2 if bi == 0 and stage > 2 else 1
+            short = feat if bi else _rn_conv_bn(w, "", feat, out, 1, 0, stride, phase, False, conv_name=tag + "_1x1_proj")
+            x = _rn_conv_bn(w, "", feat, mid, 1, 0, stride, phase, True, conv_name=tag + "_1x1_reduce")
+            x = _rn_conv_bn(w, "", x, mid, 3, 1, 1, phase, True, conv_name=tag + "_3x3")
+            x = _rn_conv_bn(w, "", x, out, 1, 0, 1, phase, False, conv_name=tag + "_1x1_increase")
+            w.layer(tag + "_global_pool", "Pooling", [x], [tag + "_global_pool"], "  pooling_param { pool: AVE global_pooling: true }")
+            g = _se_fc(w, tag + "_1x1_down", tag + "_global_pool", max(out // reduction, 1), form)
+            w.layer(g + "/relu", "ReLU", [g], [g])
+            g = _se_fc(w, tag + "_1x1_up", g, out, form)
+            w.layer(tag + "_prob", "Sigmoid", [g], [tag + "_prob"])
+            if form == "scale":
+                w.layer(tag + "/scale", "Scale", [x, tag + "_prob"], [tag + "/scale"], "  scale_param { axis: 0 }")
+                w.layer(tag, "Eltwise", [tag + "/scale", short], [tag])
+            else:
+                w.layer(tag, "Axpy", [tag + "_prob", x, short], [tag])
+            w.layer(tag + "/relu", "ReLU", [tag], [tag])
+            feat = tag
+    w.layer("pool5/7x7_s1", "Pooling", [feat], ["pool5/7x7_s1"], "  pooling_param { pool: AVE global_pooling: true }")
+    _cn_fc(w, "classifier", "pool5/7x7_s1", num_classes, 0.01, 0.0)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["classifier"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["classifier", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["classifier", "label"], ["loss"])
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def se_resnet50(phase: str = "DEPLOY", **kw) -> str:
+    return se_resnet(phase, depth=50, **kw)
+
+
+def se_resnet101(phase: str = "DEPLOY", **kw) -> str:
+    return se_resnet(phase, depth=101, **kw)
+
+
+def se_resnet152(phase: str = "DEPLOY", **kw) -> str:
+    return se_resnet(phase, depth=152, **kw)
+
+
+# ----------------------------------------------------------------------
 # DeepLab-LargeFOV and the DeepLab-v2 ASPP head on VGG16 (Chen, Papandreou, Kokkinos, Murphy, Yuille: "Semantic Image Segmentation with
 # Deep Convolutional Nets and Fully Connected CRFs" / "DeepLab: ... Atrous Convolution, and Fully Connected CRFs"; the published names)
 # ----------------------------------------------------------------------

@@ -19,7 +19,7 @@ Shape = Tuple[int, ...]
 
 
 class Layer:
-    __slots__ = ("name", "type", "bottoms", "tops", "msg", "lr_mult", "decay_mult", "loss_weight", "python_alias")
+    __slots__ = ("name", "type", "bottoms", "tops", "msg", "lr_mult", "decay_mult", "loss_weight", "python_alias", "axpy")
 
     def __init__(self, msg: proto.Msg):
         self.msg = msg
@@ -34,6 +34,7 @@ class Layer:
         # the published Faster R-CNN / R-FCN deploy files write Proposal as a Python layer (rpn.proposal_layer.ProposalLayer): the same
         # built-in layer, its parameters in param_str; no module is imported.  Every other Python layer stays a Python layer
         self.python_alias: bool = region.is_python_proposal(self)
+        self.axpy: Optional[str] = None      # the Axpy layer of the file this layer stands for (NetSpec scale_gate=True), else None
         if self.python_alias:
             self.type = "Proposal"
 
@@ -285,6 +286,63 @@ def bn_global_stats(l: "Layer", phase: str) -> bool:
     return phase == "TEST" if v is None else bool(v)
 
 
+def is_scale_gate(l: "Layer") -> bool:
+    """A Scale whose multiplier is a blob of the net (two bottoms): the gated form of csrc/gate.hip, not a link of a BatchNorm chain."""
+    return l.type == "Scale" and len(l.bottoms) == 2
+
+
+def scale_gate_form(l: "Layer", bots: Sequence[Shape], phase: str) -> Tuple[int, int, int]:
+    """Caffe's ScaleLayer with two bottoms (x, gate) in the one form taken: x is (N, C, H, W) or (N, C), axis is 0 (or its negative
+    equivalent) and the gate's shape equals x.shape[axis : axis + gate.ndim] with two axes - an (N, C) gate; an (N, C, 1, 1) gate is
+    legal only where H = W = 1 (Caffe's own rule).  Returns (N, pixels per image, C).  bias_term, any other axis or gate rank and, in
+    a TRAIN net, the form in place on x (Caffe keeps a copy of x for the backward pass; nothing here does) are refused by layer name."""
+    sp = l.sub("scale_param")
+    x, g = tuple(bots[0]), tuple(bots[1])
+    if l.axpy is not None and len(g) == 4 and g[2:] == (1, 1):
+        g = g[:2]      # (the Axpy layer takes its gate as (N, C, 1, 1): the top of a 1x1 convolution over the pooled blob)
+    if len(l.tops) != 1 or len(x) not in (2, 4):
+        raise ValueError("layer %s: Scale with two bottoms takes a 4-d or 2-d blob and its multiplier and has one top, got %s" % (l.name, list(bots)))
+    if bool(sp.get("bias_term", False)):
+        raise NotImplementedError("layer %s: Scale with two bottoms and bias_term: true (a learned bias beside a multiplier from the net)" % l.name)
+    axis = int(sp.get("axis", 1))
+    if not -len(x) <= axis < len(x):
+        raise ValueError("layer %s: Scale axis %d is outside [%d, %d)" % (l.name, axis, -len(x), len(x)))
+    axis += len(x) if axis < 0 else 0
+    if x[axis:axis + len(g)] != g:
+        raise ValueError("layer %s: the multiplier %s %s does not match axes %d.. of %s %s (Caffe: its shape must equal "
+                         "x.shape[axis : axis + its rank])" % (l.name, l.bottoms[1], g, axis, l.bottoms[0], x))
+    if axis != 0 or not (len(g) == 2 or (len(g) == 4 and x[2:] == (1, 1))):
+        raise NotImplementedError("layer %s: Scale with two bottoms over axis %d with the %d-d multiplier %s %s (only a per-image, per-channel "
+                                  "gate: axis 0 and an (N, C) multiplier, or (N, C, 1, 1) where H = W = 1)" % (l.name, axis, len(g), l.bottoms[1], g))
+    if phase == "TRAIN" and l.tops[0] == l.bottoms[0]:
+        raise NotImplementedError("layer %s: Scale with two bottoms in place on %s in a TRAIN net (the gate's gradient needs x as it was; "
+                                  "give the layer a top of its own)" % (l.name, l.bottoms[0]))
+    if l.tops[0] == l.bottoms[1]:
+        raise ValueError("layer %s: Scale with two bottoms cannot write its top over the multiplier %s" % (l.name, l.bottoms[1]))
+    n, c, h, w = as_nchw(x)
+    return n, h * w, c
+
+
+def _lower_axpy(m: proto.Msg) -> List["Layer"]:
+    """The SENet release's Axpy layer (bottoms: gate, x, residual; top = gate * x + residual, the gate (N, C, 1, 1) or (N, C)) as the two
+    layers it stands for: a gated Scale `<name>/scale` of (x, gate) over axis 0 with the top `<top>/scale`, and an Eltwise SUM `<name>`
+    of that blob and the residual with the layer's top.  No new layer type reaches the planners."""
+    name, bots, tops = str(m.get("name", "")), [str(b) for b in m.getall("bottom")], [str(t) for t in m.getall("top")]
+    if len(bots) != 3 or len(tops) != 1:
+        raise ValueError("layer %s: Axpy takes three bottoms (the gate, the blob, the residual) and has one top, got %s -> %s" % (name, bots, tops))
+    mid = tops[0] + "/scale"
+    sc, el, sp = proto.Msg(), proto.Msg(), proto.Msg()
+    sp.add("axis", 0)
+    for k, v in (("name", name + "/scale"), ("type", "Scale"), ("bottom", bots[1]), ("bottom", bots[0]), ("top", mid), ("scale_param", sp)):
+        sc.add(k, v)
+    for k, v in (("name", name), ("type", "Eltwise"), ("bottom", mid), ("bottom", bots[2]), ("top", tops[0])):
+        el.add(k, v)
+    out = [Layer(sc), Layer(el)]
+    for l in out:
+        l.axpy = name
+    return out
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 
@@ -293,7 +351,7 @@ class NetSpec:
     """Phase-filtered layer list + blob/parameter shapes."""
 
     def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False, rconv_f16: bool = False,
-                 tconv_f16: bool = False):
+                 tconv_f16: bool = False, scale_gate: bool = False):
         """depthwise: a Convolution with group == bottom channels == num_output > 1 is a depthwise convolution (is_depthwise), the
         same thing as a layer of type DepthwiseConvolution - the way the published MobileNet prototxts write it.  Off by default:
         a bare NetSpec keeps refusing such a layer where its parameters are laid out (storage.conv_groups).  The public entry points
@@ -306,7 +364,12 @@ class NetSpec:
         entry points that build a TEST-phase net pass True.  A float32 engine never looks at the keyword.
         tconv_f16: in a half-float engine a group-1 Deconvolution over a half bottom runs through the half-float kernel of
         csrc/tconv.hip (fcn_tconv2d_f16) and its blob is a bank of halves.  Off by default, passed by the same entry points, never looked
-        at by a float32 engine: the rule of rconv_f16."""
+        at by a float32 engine: the rule of rconv_f16.
+        scale_gate: a Scale with two bottoms (x, gate) over axis 0 - the multiplier a per-image, per-channel (N, C) blob of the net, the gate of
+        a Squeeze-and-Excitation block - is accepted and runs through csrc/gate.hip (scale_gate_form), and the SENet release's Axpy layer
+        (gate, x, residual) is read as the two layers it stands for: such a Scale `<name>/scale` with the top `<top>/scale`, and an Eltwise SUM
+        `<name>` of that blob and the residual.  Off by default, once more: a bare NetSpec keeps refusing the two-bottom Scale by name (and
+        knows no Axpy type); the same public entry points pass True.  A net without such a layer is planned the same either way."""
         if phase not in ("TRAIN", "TEST"):
             raise ValueError("phase must be 'TRAIN' or 'TEST'")
         self.phase = phase
@@ -314,8 +377,10 @@ class NetSpec:
         self.ip_gemm = bool(ip_gemm)
         self.rconv_f16 = bool(rconv_f16)
         self.tconv_f16 = bool(tconv_f16)
+        self.scale_gate = bool(scale_gate)
         self.name = str(msg.get("name", ""))
-        self.layers: List[Layer] = [Layer(m) for m in msg.getall("layer") if _phase_included(m, phase)]
+        self.layers: List[Layer] = [l for m in msg.getall("layer") if _phase_included(m, phase)
+                                    for l in (_lower_axpy(m) if self.scale_gate and str(m.get("type", "")) == "Axpy" else [Layer(m)])]
         if msg.getall("layers"):
             raise NotImplementedError("V1 'layers' prototxt syntax is not used by the reference")
         self.input_shapes: Dict[str, Shape] = {}
@@ -347,8 +412,8 @@ class NetSpec:
 
     @classmethod
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False,
-                  tconv_f16: bool = False) -> "NetSpec":
-        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16)
+                  tconv_f16: bool = False, scale_gate: bool = False) -> "NetSpec":
+        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16, scale_gate)
 
     def is_depthwise(self, l: Layer) -> bool:
         """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose
@@ -536,8 +601,14 @@ class NetSpec:
             elif t == "Scale":
                 # Caffe's ScaleLayer with the multiplier as a learned blob over the channel axis: (C,) gamma and, with bias_term, (C,) beta
                 sp = l.sub("scale_param")
+                if len(bots) == 2 and not self.scale_gate:
+                    raise NotImplementedError("layer %s: Scale with two bottoms (the multiplier as a blob of the net): a per-image, "
+                                              "per-channel gate over axis 0 is taken by a NetSpec built with scale_gate=True (caffe.Net, the "
+                                              "solvers and the caffe tool pass it)" % l.name)
                 if len(bots) == 2:
-                    raise NotImplementedError("layer %s: Scale with two bottoms (the multiplier as a blob of the net)" % l.name)
+                    scale_gate_form(l, bots, self.phase)     # (no parameter blobs: the multiplier is the second bottom)
+                    shapes[l.tops[0]] = bots[0]
+                    continue
                 if len(bots) != 1 or len(bots[0]) not in (2, 4) or len(l.tops) != 1:
                     raise ValueError("layer %s: Scale takes one 4-d or 2-d bottom and has one top, got %s" % (l.name, bots))
                 if int(sp.get("axis", 1)) != 1 or int(sp.get("num_axes", 1)) != 1:

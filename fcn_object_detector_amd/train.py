@@ -246,6 +246,7 @@ class TrainEngine(Engine):
         plan = BackwardPlanner(self)
         plan.run()
         self.bwd_ops, self._ws, self._ip_ws, self._ip_wgrad_ws = plan.ops, plan.ws, plan.ip_ws, plan.ip_wgrad_ws
+        self._gate_ws = plan.gate_ws      # the gate gradients of the gated Scale layers (backward._scale_gate); None without one
         self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
             self.tuner.wgrad_cfgs(self.bwd_ops)

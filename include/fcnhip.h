@@ -994,6 +994,32 @@ int  fcn_batchnorm_bwd_apply_f32(const float* dy, const float* xhat, const float
                                  const float* save, const float* blob_var, const float* blob_factor, float eps, const float* gamma,
                                  const float* sum_dy, const float* sum_dyx, int accumulate, fcn_stream_t s);
 
+/* ---- Gated Scale (Caffe ScaleLayer with two bottoms over axis 0; with the residual, the SENet release's Axpy) on NHWC views
+ *      (csrc/gate.hip): a per-image, per-channel multiplier taken from a blob of the net.  N images of ppi pixels each lie one behind
+ *      the other in every view; the gate is float32, N rows of C values g_rstride >= C floats apart (4-byte aligned, read element by
+ *      element, once per lane - never per pixel).  Views, groups and pad channels follow fcn_batchnorm_apply_*: a lane owns one 16-byte
+ *      channel group of a pixel (4 floats / 8 halves), whole groups are LOADED (strides and offsets are multiples of the group), only
+ *      channels coffset .. coffset + C - 1 are ever written.
+ *      Contract of all four: null pointers, non-positive extents, a slice outside its pixel, g_rstride < C FCN_E_ARG; a stride or offset
+ *      that is no multiple of the group, x / r / y / dy / dx / workspace off 16 bytes, the gate off 4 bytes FCN_E_ALIGN; more than 65535
+ *      images or N * ppi >= 2^31 FCN_E_UNSUPPORTED.  Every check precedes the first HIP call; all launches are capturable. ---- */
+/* y = relu?(x * gate[n, c] (+ r)): r may be NULL (its stride and offset are then ignored), relu applies after the add.  y may be x or r. */
+int  fcn_scale_gate_fwd_f32(const float* x, const float* gate, const float* r, float* y, int N, int ppi, int C, int x_cstride, int x_coffset,
+                            int g_rstride, int r_cstride, int r_coffset, int y_cstride, int y_coffset, int relu, fcn_stream_t s);
+/* inference twin: x, r and y hold halves (groups of 8), the gate stays float32, arithmetic in float32, one rounding to half */
+int  fcn_scale_gate_fwd_f16(const void* x, const float* gate, const void* r, void* y, int N, int ppi, int C, int x_cstride, int x_coffset,
+                            int g_rstride, int r_cstride, int r_coffset, int y_cstride, int y_coffset, int relu, fcn_stream_t s);
+/* dx (+)= dy * gate[n, c]; accumulate 1 adds into dx.  dx may be dy. */
+int  fcn_scale_gate_bwd_data_f32(const float* dy, const float* gate, float* dx, int N, int ppi, int C, int dy_cstride, int dy_coffset,
+                                 int g_rstride, int dx_cstride, int dx_coffset, int accumulate, fcn_stream_t s);
+/* dgate[n, c] (+)= sum over the pixels of image n of dy * x, rows of dgate g_rstride floats apart.  No atomics: one workgroup folds a
+ * slab of one image's pixels, the partial sums lie in d_workspace (fcn_scale_gate_workspace_bytes(N, ppi, C) bytes) and a second launch
+ * folds them per (image, channel) in a fixed order (lane l of a wave folds slabs l, l + 64, .. ascending, then the lanes fold by
+ * halves).  One launch pair covers all images; the same call gives the same bits. */
+int  fcn_scale_gate_bwd_gate_f32(const float* dy, const float* x, float* dgate, int N, int ppi, int C, int dy_cstride, int dy_coffset,
+                                 int x_cstride, int x_coffset, int g_rstride, int accumulate, void* d_workspace, fcn_stream_t s);
+size_t fcn_scale_gate_workspace_bytes(int N, int ppi, int C);
+
 /* ---- SSD detection head (Caffe-SSD's Permute + Flatten + Concat, Normalize and DetectionOutput; csrc/ssd.hip).  Float32, inference.
  *      Common contract: every output element has exactly one writer lane (no float atomics anywhere), so a second launch on the same
  *      inputs gives the same bytes; nothing outside the named outputs and the workspace is written; every refusal is made on the host
