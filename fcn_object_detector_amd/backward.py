@@ -52,6 +52,7 @@ class BackwardPlanner:
         self.ip_ws_bytes = 0                                 # ... and of the InnerProduct data gradients, which run beside them (_inner_product)
         self.ip_wgrad_ws_bytes = 0                           # ... and of the InnerProduct weight gradients above FCN_IP_MAX_ROWS rows (csrc/ip_gemm.hip)
         self.gate_ws_bytes = 0                               # ... and of the gate gradients of the gated Scale layers (csrc/gate.hip)
+        self.act_ws_bytes = 0                                # ... and of the parameter gradients of PReLU and Bias layers (csrc/act.hip)
         self.written: Dict[int, List[Tuple[int, int]]] = {}  # gradient buffer -> channel ranges already holding a gradient
         self.writers: Dict[str, List[object]] = {}           # gradient blob -> what wrote it, in order (a dgrad / pooling record or None)
         self.concat_members: Dict[str, List[str]] = {}       # Concat output -> its member blobs
@@ -77,6 +78,9 @@ class BackwardPlanner:
                            "Deconvolution": self._depthwise_deconv, "Sigmoid": self._sigmoid_plain, "ReLU": self._relu_plain,
                            "Crop": self._crop, "Interp": self._interp, "Upsample": self._upsample,
                            "Power": lambda l, gtop, gbot, acc: None}      # input transform: nothing upstream learns
+        # ... and the one-bottom activations of csrc/act.hip, which _one_bottom consults where one_bottom has no entry: the same
+        # (layer, dY, dX, accumulate), except that dX is None where only the layer's own blob wants a gradient
+        self.activations = {"PReLU": self._act, "TanH": self._act, "Bias": self._act}
 
     def run(self) -> None:
         self._find_concat_relu()
@@ -88,6 +92,7 @@ class BackwardPlanner:
         self.ip_ws = DeviceBuffer(self.ip_ws_bytes, zero=False) if self.ip_ws_bytes else None
         self.ip_wgrad_ws = DeviceBuffer(self.ip_wgrad_ws_bytes, zero=False) if self.ip_wgrad_ws_bytes else None
         self.gate_ws = DeviceBuffer(self.gate_ws_bytes, zero=False) if self.gate_ws_bytes else None
+        self.act_ws = DeviceBuffer(self.act_ws_bytes, zero=False) if self.act_ws_bytes else None
 
     # ------------------------------------------------------------------ write state of the gradient views
     def state(self, g: Blob) -> str:
@@ -806,15 +811,53 @@ class BackwardPlanner:
     def _one_bottom(self, l: Layer) -> None:
         gtop = self._arrived(l)
         gbot = self.G.get(l.bottoms[0]) if gtop is not None and l.bottoms else None
-        if gbot is None:
+        act = self.activations.get(l.type) if l.type not in self.one_bottom else None
+        if gbot is None and (act is None or gtop is None):      # (a PReLU or Bias may learn where its bottom needs no gradient)
             return
         # an in-place layer (bottom == top: drop6 / drop7 of the published FCN nets, an unfused in-place Sigmoid, ReLU or LRN) rewrites dY
         # as dX - there is nothing to accumulate into, whatever the layer type; `+=` into its own dY would be dY + f(dY)
-        acc = 1 if self.state(gbot) == "full" and gbot is not gtop else 0
-        emit = self.one_bottom.get(l.type)
+        acc = 1 if gbot is not None and self.state(gbot) == "full" and gbot is not gtop else 0
+        emit = self.one_bottom.get(l.type) or act
         if emit is None:
             raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
         emit(l, gtop, gbot, acc)
+
+    def _act(self, l: Layer, gtop: Blob, gbot: Optional[Blob], acc: int) -> None:
+        """PReLU, TanH and Bias (csrc/act.hip, engine._fwd_act).  Where the layer's blob learns, the parameter-gradient launch comes first
+        - in place the data launch rewrites the dY it reads - and overwrites that blob's segment of the flat gradient buffer; the data
+        launch dX (+)= f'(ref) dY follows and is left out where the bottom needs no gradient.  ref is the layer's input for a PReLU (the
+        copy the forward launch kept where the layer ran in place) and its output for a TanH.  One workspace, sized here, serves every
+        parameter gradient of the net (they run one after the other on the main stream)."""
+        e, lib, B, t = self.e, self.lib, self.B, l.type
+        xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+        pix, c, mode = xb.pixels, xb.channels, L.ACT_MODES[t]
+        for v in (gtop, gbot, xb, yb):
+            if v is not None and (v.coffset % 4 or v.cstride % 4):
+                raise NotImplementedError("backward of %s %s: the view of %s is not 16-byte aligned" % (t, l.name, v.name))
+        ref = (None, 0, 0)
+        if t == "PReLU":
+            aux = e.aux_dev.get(l.name)
+            if aux is None and l.tops[0] == l.bottoms[0]:
+                raise RuntimeError("PReLU %s ran in place and kept no copy of its input for the backward pass" % l.name)
+            ref = (aux.ptr, _r4(c), 0) if aux is not None else (xb.buf.ptr, xb.cstride, xb.coffset)
+        elif t == "TanH":
+            ref = (yb.buf.ptr, yb.cstride, yb.coffset)
+        param = e.params_dev[l.name][0].ptr if t == "PReLU" else None      # (the data gradient of a Bias reads no parameter)
+        shared = int(t == "PReLU" and tuple(self.spec.param_shapes[l.name][0]) == ())
+        if t != "TanH" and e._learns(l) and l.name not in self.wgrad_done:
+            dparam = e._grad_view(l.name, 0).ptr
+            self.act_ws_bytes = max(self.act_ws_bytes, int(lib.fcn_act_workspace_bytes(pix, c)))
+            self.ops.append(Op("act_bwd_param", l.name, lambda st: L.check(lib.fcn_act_bwd_param_f32(
+                gtop.buf.ptr, ref[0], dparam, pix, c, gtop.cstride, gtop.coffset, ref[1], ref[2], mode, shared, e._act_ws.ptr, st)),
+                2.0 * pix * c, (8.0 if t == "PReLU" else 4.0) * pix * c))
+            self.ops[-1].layers = [l.name]
+            self.wgrad_done.add(l.name)
+        if gbot is None:
+            return
+        self.ops.append(Op("act_bwd", l.name, lambda st: L.check(lib.fcn_act_bwd_data_f32(
+            gtop.buf.ptr, ref[0], gbot.buf.ptr, pix, c, gtop.cstride, gtop.coffset, ref[1], ref[2], gbot.cstride, gbot.coffset, mode, param,
+            shared, acc, st)), 1.0 * pix * c, 4.0 * ((2 if t == "Bias" else 3) + acc) * pix * c))
+        self.mark(gbot)
 
     def _pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
         pp = l.sub("pooling_param")

@@ -32,7 +32,7 @@ from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
-from .netspec import (Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
+from .netspec import (ACT_TYPES, Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
                       layer_dilation, layer_geometry, scale_gate_form)
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
@@ -1560,8 +1560,11 @@ class Engine:
         """The launches of one layer that is not a convolution."""
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample"):
+        acts = ACT_TYPES if self.spec.activations else ()      # (csrc/act.hip: only a NetSpec built with activations=True has them)
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample") + acts:
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
+        if t in acts:
+            return self._fwd_act(l, halves)
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
@@ -1731,6 +1734,34 @@ class Engine:
             pw, sc, sh = float(p.get("power", 1.0)), float(p.get("scale", 1.0)), float(p.get("shift", 0.0))
             fn = lambda st: L.check(lib.fcn_power_fwd_f32(xb.ptr, yb.ptr, count, pw, sc, sh, st))
         return [Op(t.lower(), l.name, fn, 0.0, 8.0 * count)]
+
+    def _fwd_act(self, l: Layer, halves: List[str]) -> List[Op]:
+        """PReLU, TanH and Bias as one launch of csrc/act.hip, on whole buffers and on 16-byte-aligned channel windows alike (the kernel
+        keeps to its window), floats or halves with float32 parameters.  A TRAIN engine keeps the input of an in-place PReLU to which a
+        gradient comes (its bottom needs one, or its slopes learn) in aux_dev - Caffe's bottom_memory_ - filled by the same launch."""
+        lib, t = L.load(), l.type
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.nchw is None or xb.shape != yb.shape:
+            raise NotImplementedError("%s %s on a blob that is neither 4-d nor 2-d" % (t, l.name))
+        if xb.esize != yb.esize:
+            raise NotImplementedError("f16 engine: %s %s between half and float32 blobs" % (t, l.name))
+        grp = 16 // xb.esize
+        if xb.coffset % grp or yb.coffset % grp or xb.cstride % grp or yb.cstride % grp:
+            raise NotImplementedError("%s %s: a channel window that is not 16-byte aligned" % (t, l.name))
+        pix, c, mode = xb.pixels, xb.channels, L.ACT_MODES[t]
+        param = self.params_dev[l.name][0].ptr if t != "TanH" else None
+        shared = int(t == "PReLU" and tuple(self.spec.param_shapes[l.name][0]) == ())
+        if xb.esize == 2:
+            return [Op("act", l.name, lambda st: L.check(lib.fcn_act_fwd_f16(
+                xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, mode, param, shared, st)), 1.0 * pix * c, 4.0 * pix * c)]
+        keep = None
+        need = getattr(self, "need_grad", None)
+        if self.spec.phase == "TRAIN" and t == "PReLU" and l.tops[0] == l.bottoms[0] and (need is None or l.tops[0] in need):
+            keep = self.aux_dev[l.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
+        kp = keep.ptr if keep is not None else None
+        return [Op("act", l.name, lambda st: L.check(lib.fcn_act_fwd_f32(
+            xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, param, shared, st)),
+            1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]
 
     def _fwd_dropout(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()

@@ -184,6 +184,8 @@ def ip_rows_refusal(layer: str, rows: int) -> str:
 CONV_IMAGE_ONES = 128      # half image whose channels 3 and 4 are the constant 1 (the folded Power shift): see include/fcnhip.h
 ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
 ARGMAX_MAX_TOPK = 32           # FCN_ARGMAX_MAX_TOPK
+ACT_PRELU, ACT_TANH, ACT_BIAS = 0, 1, 2      # FCN_ACT_*: the modes of csrc/act.hip
+ACT_MODES = {"PReLU": ACT_PRELU, "TanH": ACT_TANH, "Bias": ACT_BIAS}
 ARGMAX_WAVE_BYTES, ARGMAX_WAVE_PIXELS, ARGMAX_WAVE_MIN_C = 512, 8192, 32      # FCN_ARGMAX_WAVE_*: where a wave takes a pixel (csrc/argmax.hip)
 ARGMAX_VALUES, ARGMAX_PAIRS, ARGMAX_SOFTMAX = 1, 2, 4
 SOLVER_KINDS = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADADELTA": 4, "ADAM": 5}      # FCN_SOLVER_*
@@ -381,6 +383,11 @@ PROTOTYPES = {
     "fcn_scale_gate_fwd_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),
     "fcn_scale_gate_bwd_data_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "fcn_scale_gate_bwd_gate_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
+    "fcn_act_workspace_bytes": (_sz, [_i, _i]),
+    "fcn_act_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _i, _vp]),
+    "fcn_act_fwd_f16": (_i, [_vp, _vp] + [_i] * 7 + [_vp, _i, _vp]),
+    "fcn_act_bwd_data_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp, _i, _i, _vp]),
+    "fcn_act_bwd_param_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp]),
     "fcn_ssd_gather_f32": (_i, [C.POINTER(SsdHead), _i, _i, _vp, _i, _i, _vp]),
     "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
     "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),

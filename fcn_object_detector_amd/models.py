@@ -1560,3 +1560,213 @@ def faster_rcnn_vgg16(phase: str = "DEPLOY", classes: int = 21, size=(600, 1000)
     _cn_fc(w, "bbox_pred", "fc7", 4 * classes, 0.001, 0.0)
     w.layer("cls_prob", "Softmax", ["cls_score"], ["cls_prob"])
     return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# MTCNN (Zhang et al. 2016: P-Net / R-Net / O-Net) and ENet (Paszke et al. 2016): the two published families whose activation is PReLU.
+# Both need a NetSpec built with activations=True (caffe.Net, the solvers and the caffe tool pass it).
+# ----------------------------------------------------------------------
+
+def _prelu(w: _Writer, name: str, blob: str) -> None:
+    """PReLU `<name>` in place on `blob`: one slope per channel, Caffe's default filler (constant 0.25), decay_mult 0."""
+    w.layer(name, "PReLU", [blob], [blob], "  param { lr_mult: 1 decay_mult: 0 }")
+
+
+def _mt_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, prelu: Optional[str] = None) -> str:
+    w.layer(name, "Convolution", [bottom], [name], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  convolution_param {\n    num_output: %d\n    kernel_size: %d\n    weight_filler { type: \"xavier\" }\n"
+            "    bias_filler { type: \"constant\" value: 0 }\n  }" % (num_output, k))
+    if prelu:
+        _prelu(w, prelu, name)
+    return name
+
+
+def _mt_pool(w: _Writer, name: str, bottom: str, k: int) -> str:
+    w.layer(name, "Pooling", [bottom], [name], "  pooling_param { pool: MAX kernel_size: %d stride: 2 }" % k)
+    return name
+
+
+def mtcnn_grid(net: str, size) -> Tuple[int, int]:
+    """Extents of the blob in front of the heads (P-Net: of the heads' maps) for an input of `size`, pooling in Caffe's ceil mode."""
+    convs = {"pnet": ((3, 2), (3, 0), (3, 0)), "rnet": ((3, 3), (3, 3), (2, 0)), "onet": ((3, 3), (3, 3), (3, 2), (2, 0))}[net]
+    out = []
+    for v in _hw(size):
+        for k, pool in convs:
+            v = v - k + 1
+            if pool:
+                v = -(-(v - pool) // 2) + 1
+        out.append(v)
+    return out[0], out[1]
+
+
+def mtcnn(net: str = "pnet", phase: str = "DEPLOY", batch: int = 1, size=None) -> str:
+    """The three nets of MTCNN.  P-Net (12 x 12, fully convolutional - any `size` in DEPLOY): conv1 3x3x10, PReLU1, pool1 MAX 2x2 / 2,
+    conv2 3x3x16, PReLU2, conv3 3x3x32, PReLU3, the 1x1 heads conv4-1 (2, Softmax prob1) and conv4-2 (4 box offsets).  R-Net (24 x 24):
+    conv1 3x3x28, pool1 3x3 / 2, conv2 3x3x48, pool2 3x3 / 2, conv3 2x2x64, InnerProduct conv4 (128), heads conv5-1 (2, prob1) and conv5-2
+    (4).  O-Net (48 x 48): conv1 3x3x32, pool1 3x3 / 2, conv2 3x3x64, pool2 3x3 / 2, conv3 3x3x64, pool3 2x2 / 2, conv4 2x2x128,
+    InnerProduct conv5 (256), Dropout drop5, prelu5, heads conv6-1 (2, prob1), conv6-2 (4) and conv6-3 (10 landmark coordinates).  A
+    PReLU, one slope per channel, follows every convolution and the first InnerProduct, in place.
+
+    Names: conv*, pool*, PReLU1 .. PReLU3 (P-Net), prelu1 .. prelu5 (R-Net, O-Net), drop5, conv4-1 .. conv6-3 and prob1 are the published
+    deploy files', as far as remembered.  The TRAIN / TEST forms are this project's (the release has deploy files only): Input `label`
+    (one class per position of the class head), `roi` (the box targets, the box head's shape) and for O-Net `pts`, SoftmaxWithLoss
+    `cls_loss` on the class head and EuclideanLoss `roi_loss` (O-Net: and `pts_loss`) on the others.  `size` is the image edge or
+    (height, width); R-Net and O-Net end in InnerProduct layers and take their own size only."""
+    _check_phase(phase)
+    if net not in ("pnet", "rnet", "onet"):
+        raise ValueError("net must be 'pnet', 'rnet' or 'onet'")
+    own = {"pnet": 12, "rnet": 24, "onet": 48}[net]
+    hw = _hw(own if size is None else size)
+    if net != "pnet" and hw != (own, own):
+        raise ValueError("%s takes %d x %d images (it ends in InnerProduct layers)" % (net, own, own))
+    if phase != "DEPLOY" and net == "pnet" and hw != (own, own):
+        raise ValueError("pnet trains on 12 x 12 crops; another size is for the DEPLOY form")
+    if min(mtcnn_grid(net, hw)) < 1:
+        raise ValueError("%s needs images of at least %d x %d" % (net, own, own))
+    w = _Writer()
+    w.raw('name: "%s"' % {"pnet": "PNet", "rnet": "RNet", "onet": "ONet"}[net])
+    w.layer("data", "Input", [], ["data"], "  input_param { shape { dim: %d dim: 3 dim: %d dim: %d } }" % (batch, hw[0], hw[1]))
+    if net == "pnet":
+        x = _mt_conv(w, "conv1", "data", 10, 3, "PReLU1")
+        x = _mt_pool(w, "pool1", x, 2)
+        x = _mt_conv(w, "conv2", x, 16, 3, "PReLU2")
+        x = _mt_conv(w, "conv3", x, 32, 3, "PReLU3")
+        heads = [_mt_conv(w, "conv4-1", x, 2, 1), _mt_conv(w, "conv4-2", x, 4, 1)]
+    else:
+        widths = (28, 48, 64) if net == "rnet" else (32, 64, 64, 128)
+        x = _mt_pool(w, "pool1", _mt_conv(w, "conv1", "data", widths[0], 3, "prelu1"), 3)
+        x = _mt_pool(w, "pool2", _mt_conv(w, "conv2", x, widths[1], 3, "prelu2"), 3)
+        if net == "rnet":
+            x = _mt_conv(w, "conv3", x, widths[2], 2, "prelu3")
+            fc, act, head = "conv4", "prelu4", "conv5"
+        else:
+            x = _mt_pool(w, "pool3", _mt_conv(w, "conv3", x, widths[2], 3, "prelu3"), 2)
+            x = _mt_conv(w, "conv4", x, widths[3], 2, "prelu4")
+            fc, act, head = "conv5", "prelu5", "conv6"
+        _cn_fc(w, fc, x, 128 if net == "rnet" else 256, 0.0, 0.0, filler="xavier", drop="drop5" if net == "onet" else None, ratio=0.25)
+        _prelu(w, act, fc)
+        heads = [head + "-%d" % (i + 1) for i in range(2 if net == "rnet" else 3)]
+        for nm, n_out in zip(heads, (2, 4, 10)):
+            _cn_fc(w, nm, fc, n_out, 0.0, 0.0, filler="xavier")
+    if phase == "DEPLOY":
+        w.layer("prob1", "Softmax", [heads[0]], ["prob1"])
+        return w.text()
+    gh, gw = mtcnn_grid(net, hw)
+    shape = (lambda c: (batch, c, gh, gw)) if net == "pnet" else (lambda c: (batch, c))
+    targets = list(zip(("label", "roi", "pts"), (1, 4, 10)))[:len(heads)]
+    for nm, c in targets:
+        shp = shape(c) if not (nm == "label" and net != "pnet") else (batch,)
+        w.layer(nm, "Input", [], [nm], "  input_param { shape { %s } }" % " ".join("dim: %d" % d for d in shp))
+    w.layer("cls_loss", "SoftmaxWithLoss", [heads[0], "label"], ["cls_loss"])
+    for hd, (nm, _c_) in list(zip(heads, targets))[1:]:
+        w.layer(nm + "_loss", "EuclideanLoss", [hd, nm], [nm + "_loss"], "  loss_weight: 0.5")
+    return w.text()
+
+
+def _en_conv(w: _Writer, name: str, bottom: str, num_output: int, kernel, phase: str, pad=0, stride: int = 1, dilation: int = 1,
+             deconv: bool = False, bn: bool = True, prelu: bool = True, bias: bool = False) -> str:
+    """Convolution (or, with `deconv`, Deconvolution) `<name>`, without a bias unless `bias`; with `bn` BatchNorm `<name>/bn` and Scale
+    `<name>/scale` (bias_term: true), with `prelu` PReLU `<name>/prelu`, all in place on its top; returns the top."""
+    kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
+    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    geo = "    num_output: %d\n" % num_output
+    geo += "    kernel_size: %d\n" % kh if kh == kw else "    kernel_h: %d\n    kernel_w: %d\n" % (kh, kw)
+    if ph or pw:
+        geo += "    pad: %d\n" % ph if (kh, ph) == (kw, pw) else "    pad_h: %d\n    pad_w: %d\n" % (ph, pw)
+    if stride != 1:
+        geo += "    stride: %d\n" % stride
+    if dilation != 1:
+        geo += "    dilation: %d\n" % dilation
+    if not bias:
+        geo += "    bias_term: false\n"
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / (kh * kw * num_output)) ** 0.5
+    w.layer(name, "Deconvolution" if deconv else "Convolution", [bottom], [name],
+            "  param { lr_mult: 1 decay_mult: 1 }\n%s  convolution_param {\n%s%s  }" % ("  param { lr_mult: 2 decay_mult: 0 }\n" if bias else "", geo, fill))
+    if bn:
+        stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+        w.layer(name + "/bn", "BatchNorm", [name], [name], stats)
+        w.layer(name + "/scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
+    if prelu:
+        _prelu(w, name + "/prelu", name)
+    return name
+
+
+def _en_bottleneck(w: _Writer, tag: str, x: str, cin: int, cout: int, kind, phase: str, ratio: float, mask: Optional[str] = None,
+                   hw: Optional[Tuple[int, int]] = None) -> str:
+    """One ENet bottleneck `<tag>`: 1x1 reduce to cout / 4, at least 2 (`down`: a 2x2 / 2 convolution), the main convolution (`regular` 3x3, an int
+    d: 3x3 with dilation d, `asym`: 5x1 then 1x5, `down`: 3x3, `up`: a 2x2 / 2 Deconvolution), 1x1 expand, Dropout, Eltwise SUM with the
+    shortcut (`down`: MAX pooling 2x2 / 2 with the mask `<tag>/pool_mask`, then a 1x1 convolution that widens; `up`: a 1x1 convolution,
+    then Upsample by `mask` to `hw`) and PReLU.  Returns the top, `<tag>`."""
+    mid = max(cout // 4, 2)      # (never one channel: a Deconvolution of one channel into one reads as a depthwise one, which does not learn)
+    b = _en_conv(w, tag + "/reduce", x, mid, 2 if kind == "down" else 1, phase, stride=2 if kind == "down" else 1)
+    if kind == "asym":
+        b = _en_conv(w, tag + "/conv_a", b, mid, (5, 1), phase, pad=(2, 0), bn=False, prelu=False)
+        b = _en_conv(w, tag + "/conv", b, mid, (1, 5), phase, pad=(0, 2))
+    elif kind == "up":
+        b = _en_conv(w, tag + "/conv", b, mid, 2, phase, stride=2, deconv=True)
+    else:
+        d = kind if isinstance(kind, int) else 1
+        b = _en_conv(w, tag + "/conv", b, mid, 3, phase, pad=d, dilation=d)
+    b = _en_conv(w, tag + "/expand", b, cout, 1, phase, prelu=False)
+    w.layer(tag + "/drop", "Dropout", [b], [b], "  dropout_param { dropout_ratio: %g }" % ratio)
+    s = x
+    if kind == "down":
+        w.layer(tag + "/pool", "Pooling", [x], [tag + "/pool", tag + "/pool_mask"], "  pooling_param { pool: MAX kernel_size: 2 stride: 2 }")
+        s = _en_conv(w, tag + "/short", tag + "/pool", cout, 1, phase, prelu=False)
+    elif kind == "up":
+        s = _en_conv(w, tag + "/short", x, cout, 1, phase, prelu=False)
+        s = _sn_upsample(w, tag + "/unpool", s, mask, hw)
+    w.layer(tag, "Eltwise", [b, s], [tag])
+    _prelu(w, tag + "/prelu", tag)
+    return tag
+
+
+ENET_STAGE = ("regular", 2, "asym", 4, "regular", 8, "asym", 16)      # bottlenecks x.1 .. x.8 of stages 2 and 3 (an int: the dilation)
+
+
+def enet(phase: str = "DEPLOY", classes: int = 19, batch: int = 1, size=(512, 1024), width_div: int = 1, argmax: bool = False) -> str:
+    """ENet in the layers this project has.  `initial`: a 3x3 / 2 convolution to 13 channels beside a 2x2 / 2 MAX pooling of the image,
+    Concat to 16, BatchNorm + Scale + PReLU.  Stage 1: a downsampling bottleneck and four regular ones (64 channels); stage 2: a
+    downsampling one and regular, dilated 2, asymmetric 5, dilated 4, regular, dilated 8, asymmetric 5, dilated 16 (128); stage 3: those
+    eight again; stage 4: an upsampling bottleneck and two regular ones (64); stage 5: an upsampling one and a regular one (16);
+    `fullconv`, a 2x2 / 2 Deconvolution to `classes`.  Every convolution of a bottleneck carries BatchNorm + Scale, the first two a PReLU
+    as well; a plain Dropout (0.01 in stage 1, 0.1 after it) closes the branch; a PReLU follows the sum.
+
+    Where the paper pads the pooled shortcut of a downsampling bottleneck with zero channels, a 1x1 convolution + BatchNorm + Scale widens it
+    here (Caffe has no zero-padding layer); the paper's SpatialDropout is a plain Dropout; the decoder's shortcuts are a 1x1 convolution +
+    BatchNorm + Scale, then an Upsample by the mask of the matching downsampling bottleneck.  ALL layer and blob names are this project's:
+    `initial`, `b<stage>_<index>` with `/reduce`, `/conv` (`/conv_a` for the 5x1 half), `/expand`, `/drop`, `/short`, `/pool`,
+    `/pool_mask`, `/unpool` and `<conv>/bn`, `/scale`, `/prelu`.  Ends as models.segnet: prob (DEPLOY, with argmax=True the label map
+    `argmax` behind it), or loss (SoftmaxWithLoss, ignore_label 255) with accuracy in TEST.  width_div divides the widths; size is the
+    image edge or (height, width), multiples of 8."""
+    _check_phase(phase)
+    hw = _hw(size)
+    if hw[0] % 8 or hw[1] % 8:
+        raise ValueError("enet takes images whose extents are multiples of 8, got %d x %d" % hw)
+    c16, c64, c128 = max(16 // width_div, 4), max(64 // width_div, 4), max(128 // width_div, 4)
+    w = _Writer()
+    w.raw('name: "ENet"')
+    _sn_inputs(w, phase, batch, hw)
+    _en_conv(w, "initial/conv", "data", c16 - 3, 3, phase, pad=1, stride=2, bn=False, prelu=False, bias=True)
+    w.layer("initial/pool", "Pooling", ["data"], ["initial/pool"], "  pooling_param { pool: MAX kernel_size: 2 stride: 2 }")
+    w.layer("initial", "Concat", ["initial/conv", "initial/pool"], ["initial"])
+    stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+    w.layer("initial/bn", "BatchNorm", ["initial"], ["initial"], stats)
+    w.layer("initial/scale", "Scale", ["initial"], ["initial"], "  scale_param { bias_term: true }")
+    _prelu(w, "initial/prelu", "initial")
+    h2, h4 = (hw[0] // 2, hw[1] // 2), (hw[0] // 4, hw[1] // 4)
+    x = _en_bottleneck(w, "b1_0", "initial", c16, c64, "down", phase, 0.01)
+    for i in range(1, 5):
+        x = _en_bottleneck(w, "b1_%d" % i, x, c64, c64, "regular", phase, 0.01)
+    x = _en_bottleneck(w, "b2_0", x, c64, c128, "down", phase, 0.1)
+    for stage in (2, 3):
+        for i, kind in enumerate(ENET_STAGE):
+            x = _en_bottleneck(w, "b%d_%d" % (stage, i + 1), x, c128, c128, kind, phase, 0.1)
+    x = _en_bottleneck(w, "b4_0", x, c128, c64, "up", phase, 0.1, "b2_0/pool_mask", h4)
+    for i in (1, 2):
+        x = _en_bottleneck(w, "b4_%d" % i, x, c64, c64, "regular", phase, 0.1)
+    x = _en_bottleneck(w, "b5_0", x, c64, c16, "up", phase, 0.1, "b1_0/pool_mask", h2)
+    x = _en_bottleneck(w, "b5_1", x, c16, c16, "regular", phase, 0.1)
+    x = _en_conv(w, "fullconv", x, classes, 2, phase, stride=2, deconv=True, bn=False, prelu=False, bias=True)
+    _sn_tail(w, phase, x, argmax)
+    return w.text()

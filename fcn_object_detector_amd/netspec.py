@@ -343,6 +343,27 @@ def _lower_axpy(m: proto.Msg) -> List["Layer"]:
     return out
 
 
+ACT_TYPES = ("PReLU", "TanH", "Bias")      # the one-bottom activations of csrc/act.hip (NetSpec activations=True)
+
+
+def act_param_shape(l: "Layer", bots: Sequence[Shape]) -> Shape:
+    """The learned blob of a PReLU (Caffe's PReLULayer: the slopes, (C,), or () - one value - with channel_shared) or of a Bias (Caffe's
+    BiasLayer in its one-bottom form over the channel axis: (C,)).  One bottom, 4-d or 2-d, channels on shape[1]; everything else is
+    refused by layer name."""
+    if len(l.bottoms) == 2 and l.type == "Bias":
+        raise NotImplementedError("layer %s: Bias with two bottoms (the bias as a blob of the net)" % l.name)
+    if len(bots) != 1 or len(bots[0]) not in (2, 4) or len(l.tops) != 1:
+        raise ValueError("layer %s: %s takes one 4-d or 2-d bottom and has one top, got %s" % (l.name, l.type, list(bots)))
+    c = bots[0][1]
+    if l.type == "PReLU":
+        return () if bool(l.sub("prelu_param").get("channel_shared", False)) else (c,)
+    bp = l.sub("bias_param")
+    if int(bp.get("axis", 1)) != 1 or int(bp.get("num_axes", 1)) != 1:
+        raise NotImplementedError("layer %s: Bias over axis %d, num_axes %d (only the channel axis: axis 1, num_axes 1)"
+                                  % (l.name, int(bp.get("axis", 1)), int(bp.get("num_axes", 1))))
+    return (c,)
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 
@@ -351,7 +372,7 @@ class NetSpec:
     """Phase-filtered layer list + blob/parameter shapes."""
 
     def __init__(self, msg: proto.Msg, phase: str = "TEST", depthwise: bool = False, ip_gemm: bool = False, rconv_f16: bool = False,
-                 tconv_f16: bool = False, scale_gate: bool = False):
+                 tconv_f16: bool = False, scale_gate: bool = False, *, activations: bool = False):
         """depthwise: a Convolution with group == bottom channels == num_output > 1 is a depthwise convolution (is_depthwise), the
         same thing as a layer of type DepthwiseConvolution - the way the published MobileNet prototxts write it.  Off by default:
         a bare NetSpec keeps refusing such a layer where its parameters are laid out (storage.conv_groups).  The public entry points
@@ -369,7 +390,12 @@ class NetSpec:
         a Squeeze-and-Excitation block - is accepted and runs through csrc/gate.hip (scale_gate_form), and the SENet release's Axpy layer
         (gate, x, residual) is read as the two layers it stands for: such a Scale `<name>/scale` with the top `<top>/scale`, and an Eltwise SUM
         `<name>` of that blob and the residual.  Off by default, once more: a bare NetSpec keeps refusing the two-bottom Scale by name (and
-        knows no Axpy type); the same public entry points pass True.  A net without such a layer is planned the same either way."""
+        knows no Axpy type); the same public entry points pass True.  A net without such a layer is planned the same either way.
+        activations (keyword only): PReLU (prelu_param { filler channel_shared }: one learned blob (C,), or () with channel_shared), Bias
+        (bias_param { axis: 1 num_axes: 1 filler }: one learned blob (C,)) and TanH are accepted and run through csrc/act.hip in both
+        inference engines and train in float32.  Off by default, as the others are: a bare NetSpec keeps refusing PReLU and Bias by name
+        and hands TanH to an engine that refuses it; the same public entry points pass True.  A net without one of the three is planned
+        the same either way."""
         if phase not in ("TRAIN", "TEST"):
             raise ValueError("phase must be 'TRAIN' or 'TEST'")
         self.phase = phase
@@ -378,6 +404,7 @@ class NetSpec:
         self.rconv_f16 = bool(rconv_f16)
         self.tconv_f16 = bool(tconv_f16)
         self.scale_gate = bool(scale_gate)
+        self.activations = bool(activations)
         self.name = str(msg.get("name", ""))
         self.layers: List[Layer] = [l for m in msg.getall("layer") if _phase_included(m, phase)
                                     for l in (_lower_axpy(m) if self.scale_gate and str(m.get("type", "")) == "Axpy" else [Layer(m)])]
@@ -412,8 +439,8 @@ class NetSpec:
 
     @classmethod
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False,
-                  tconv_f16: bool = False, scale_gate: bool = False) -> "NetSpec":
-        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16, scale_gate)
+                  tconv_f16: bool = False, scale_gate: bool = False, activations: bool = False) -> "NetSpec":
+        return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16, scale_gate, activations=activations)
 
     def is_depthwise(self, l: Layer) -> bool:
         """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose
@@ -587,6 +614,12 @@ class NetSpec:
                 if len(l.tops) > 1:
                     shapes[l.tops[1]] = (bots[0][1],)
             elif t in ("ReLU", "Sigmoid", "Power", "LRN", "Dropout", "Softmax", "TanH"):
+                shapes[l.tops[0]] = bots[0]
+            elif t in ("PReLU", "Bias"):
+                if not self.activations:
+                    raise NotImplementedError("layer type %r (layer %s): taken by a NetSpec built with activations=True (caffe.Net, the "
+                                              "solvers and the caffe tool pass it)" % (t, l.name))
+                self.param_shapes[l.name] = [act_param_shape(l, bots)]
                 shapes[l.tops[0]] = bots[0]
             elif t == "BatchNorm":
                 # Caffe's BatchNormLayer over the channel axis: blobs (C,) mean sum, (C,) variance sum, (1,) scale factor - statistics,
@@ -789,6 +822,12 @@ def fill_params(spec: NetSpec, seed: int = 0) -> Dict[str, List[np.ndarray]]:
             if len(shapes) > 1:
                 blobs.append(fill_blob(shapes[1], p.get("bias_filler"), rng))
             out[l.name] = blobs
+            continue
+        if l.type in ("PReLU", "Bias"):      # PReLULayer: filler defaults to constant 0.25; BiasLayer: to constant 0
+            f = l.sub("prelu_param" if l.type == "PReLU" else "bias_param").get("filler")
+            if f is None and l.type == "PReLU":
+                f = proto.parse_text("type: \"constant\" value: 0.25")
+            out[l.name] = [fill_blob(shapes[0], f, rng)]
             continue
         if l.type == "Normalize":      # NormalizeLayer: scale_filler defaults to constant 1
             f = l.sub("norm_param").get("scale_filler")

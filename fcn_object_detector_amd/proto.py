@@ -338,7 +338,7 @@ def write_caffemodel(path: str, layers: List[Tuple[str, str, List[np.ndarray]]],
         lay += _ld(2, ltype.encode("utf-8"))
         for b in blobs:
             arr = np.ascontiguousarray(b, dtype="<f4")
-            shape = b"".join(_enc_varint(int(d)) for d in arr.shape)
+            shape = b"".join(_enc_varint(int(d)) for d in np.shape(b))      # (of b: a 0-d blob - a shared PReLU slope - keeps Caffe's empty shape)
             blob = _ld(7, _ld(1, shape)) + _ld(5, arr.tobytes())
             lay += _ld(7, blob)
         out += _ld(100, bytes(lay))

@@ -401,7 +401,7 @@ def param_layout(spec: NetSpec, views, f16: bool, skip: Sequence[str] = ()) -> T
                     kind, shape, esize = DECONV, (c, kh, kw, _ra(cog, 2)), 2
                 else:
                     kind, shape = DECONV, (c, kh, kw, _r4(cog))
-            elif i == 0 and l.type not in ("BatchNorm", "Scale", "Normalize"):      # (their blobs are per-channel vectors as they are: PLAIN)
+            elif i == 0 and l.type not in ("BatchNorm", "Scale", "Normalize", "PReLU", "Bias"):      # (their blobs are per-channel vectors as they are: PLAIN)
                 raise NotImplementedError(l.type)
             count = int(np.prod(shape))
             lr, decay = float(l.lr_mult[i] if i < len(l.lr_mult) else 1.0), float(l.decay_mult[i] if i < len(l.decay_mult) else 1.0)

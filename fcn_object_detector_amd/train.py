@@ -247,6 +247,7 @@ class TrainEngine(Engine):
         plan.run()
         self.bwd_ops, self._ws, self._ip_ws, self._ip_wgrad_ws = plan.ops, plan.ws, plan.ip_ws, plan.ip_wgrad_ws
         self._gate_ws = plan.gate_ws      # the gate gradients of the gated Scale layers (backward._scale_gate); None without one
+        self._act_ws = plan.act_ws        # the parameter gradients of PReLU and Bias layers (backward._act); None without one
         self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
         if self.autotune:
             self.tuner.wgrad_cfgs(self.bwd_ops)

@@ -1020,6 +1020,38 @@ int  fcn_scale_gate_bwd_gate_f32(const float* dy, const float* x, float* dgate, 
                                  int x_cstride, int x_coffset, int g_rstride, int accumulate, void* d_workspace, fcn_stream_t s);
 size_t fcn_scale_gate_workspace_bytes(int N, int ppi, int C);
 
+/* ---- One-bottom activations with or without a learned per-channel parameter (Caffe PReLULayer, TanHLayer, BiasLayer over the channel
+ *      axis) on NHWC views (csrc/act.hip).  Views, groups and pad channels follow fcn_batchnorm_apply_* and fcn_scale_gate_*: a lane owns
+ *      one 16-byte channel group of a pixel (4 floats / 8 halves), whole groups are LOADED (strides and offsets are multiples of the
+ *      group), only channels coffset .. coffset + C - 1 are ever written.  `param` is float32 in both element types: C values, or ONE
+ *      value with param_shared (Caffe's channel_shared); it is read once per lane, never per pixel, and is NULL for TanH.
+ *      Contract of all four: null operands, non-positive extents, an unknown mode, a slice outside its pixel, a missing parameter
+ *      FCN_E_ARG; a stride or offset that is no multiple of the group, x / y / keep / dy / ref / dx / workspace off 16 bytes, param /
+ *      dparam off 4 bytes FCN_E_ALIGN.  Every check precedes the first HIP call; all launches are capturable. ---- */
+enum { FCN_ACT_PRELU = 0, FCN_ACT_TANH = 1, FCN_ACT_BIAS = 2 };
+/* PReLU: y = x > 0 ? x : param[c] * x.  TanH: y = tanh(x).  Bias: y = x + param[c].  y may be x.  keep may be NULL; otherwise it is a
+ * buffer of its own, keep_cstride >= C floats per pixel (a multiple of 4) with the view's channels at 0, and receives x unchanged in the
+ * same launch (Caffe's bottom_memory_ of an in-place PReLU; laid out as xhat is for fcn_batchnorm_apply_f32). */
+int  fcn_act_fwd_f32(const float* x, float* y, float* keep, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                     int keep_cstride, int mode, const float* param, int param_shared, fcn_stream_t s);
+/* inference twin: x and y hold halves (groups of 8), param stays float32, arithmetic in float32, one rounding to half; no keep */
+int  fcn_act_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset, int mode,
+                     const float* param, int param_shared, fcn_stream_t s);
+/* PReLU: ref is the layer's INPUT x (the kept copy where the layer ran in place), dx (+)= x > 0 ? dy : param[c] * dy.  TanH: ref is the
+ * layer's OUTPUT y, dx (+)= dy * (1 - y * y).  Bias: ref is NULL (its stride and offset are ignored), dx (+)= dy.  accumulate 1 adds
+ * into dx; dx may be dy when accumulate is 0. */
+int  fcn_act_bwd_data_f32(const float* dy, const float* ref, float* dx, int pixels, int C, int dy_cstride, int dy_coffset, int ref_cstride,
+                          int ref_coffset, int dx_cstride, int dx_coffset, int mode, const float* param, int param_shared, int accumulate,
+                          fcn_stream_t s);
+/* PReLU: dparam[c] = sum over the pixels of dy * x * [x <= 0].  Bias: dparam[c] = sum of dy (x may be NULL).  With param_shared ONE value:
+ * the per-channel sums folded over the channels in ascending order.  The result is OVERWRITTEN (as fcn_batchnorm_bwd_reduce_f32's sums
+ * are).  No atomics: one workgroup folds a slab of pixels, the partial sums lie in d_workspace (fcn_act_workspace_bytes(pixels, C) bytes)
+ * and a second launch folds them per channel in a fixed order (lane l of a wave folds slabs l, l + 64, .. ascending, then the lanes fold
+ * by halves); the same call gives the same bits.  TanH has no parameter: FCN_E_ARG. */
+int  fcn_act_bwd_param_f32(const float* dy, const float* x, float* dparam, int pixels, int C, int dy_cstride, int dy_coffset, int x_cstride,
+                           int x_coffset, int mode, int param_shared, void* d_workspace, fcn_stream_t s);
+size_t fcn_act_workspace_bytes(int pixels, int C);
+
 /* ---- SSD detection head (Caffe-SSD's Permute + Flatten + Concat, Normalize and DetectionOutput; csrc/ssd.hip).  Float32, inference.
  *      Common contract: every output element has exactly one writer lane (no float atomics anywhere), so a second launch on the same
  *      inputs gives the same bytes; nothing outside the named outputs and the workspace is written; every refusal is made on the host
