@@ -152,7 +152,7 @@ def cmd_time(flags):
     iters = int(flags.get("iterations", 50))
     device = gpu_list(flags.get("gpu"))[0]
     L.call("fcn_init", device)
-    spec = NetSpec(proto.parse_file(flags["model"]), "TEST", depthwise=True, ip_gemm=True, rconv_f16=True, tconv_f16=True, scale_gate=True, activations=True)
+    spec = NetSpec.public(proto.parse_file(flags["model"]), "TEST")
     eng = Engine(spec, data_shapes={}, params=None, device=device, dtype=os.environ.get("FCN_DTYPE", "f32"))      # (as caffe.Net reads it)
     rng = np.random.default_rng(0)
     for nm in eng.inputs:

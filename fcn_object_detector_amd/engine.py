@@ -376,13 +376,44 @@ class Engine:
                  params: Optional[Dict[str, List[np.ndarray]]] = None, device: int = 0,
                  fuse: bool = True, group_convs: bool = True, autotune: bool = True, dtype: str = "f32",
                  tune_from: Optional["Engine"] = None, tune_max_lds_kb: Optional[int] = None,
-                 share_params: Optional["Engine"] = None, score_outputs: bool = False, replica: Optional[int] = None):
+                 share_params: Optional["Engine"] = None, score_outputs: bool = False, replica: Optional[int] = None, **state):
         """replica: this engine is replica number `replica` of a frame pipeline and takes a replica stream (default: the next
         number of an enclosing `replica_streams()` context, else a plain stream).
         share_params: Net::ShareTrainedLayersWith - every parameter layer whose name the given engine also has reads that
         engine's flat parameter buffer in place (no copy; a solver step is visible to the next forward of this engine).
         score_outputs: the engine is built for scoring (Solver::Test, `caffe test`): every forward also adds each output blob
-        to a device accumulator (score_begin() / forward_score() / score_read())."""
+        to a device accumulator (score_begin() / forward_score() / score_read()).
+        state: what a subclass's _init_state takes besides (a TrainEngine's solver and comm)."""
+        self._init_state(spec, data_shapes, dtype=dtype, fuse=fuse, group_convs=group_convs, autotune=autotune, share_params=share_params,
+                         score_outputs=score_outputs, **state)
+        self.device = device
+        L.call("fcn_init", device)
+        sp = C.c_void_p()
+        self.replica = replica if replica is not None else _take_replica_index()
+        if self.replica is None:
+            L.call("fcn_stream_create", C.byref(sp))
+        else:
+            L.call("fcn_stream_create_replica", C.byref(sp), int(self.replica))
+        self.stream = int(sp.value)
+        yes = C.c_int(0)
+        L.call("fcn_stream_is_prioritized", self.stream, C.byref(yes))
+        self.stream_prioritized = bool(yes.value)      # False on a replica: the runtime refused, its queue is shared again
+        # autotuner: only tile configurations whose workgroup holds at most this much LDS (engines that share the GPU with
+        # other streams: small footprints let workgroups of concurrent launches fit on a CU side by side)
+        max_lds = int(tune_max_lds_kb if tune_max_lds_kb is not None else os.environ.get("FCN_TUNE_MAX_LDS_KB", "160")) * 1024
+        # tune_from: a replica of the same net, whose plan is reused instead of timing again
+        self.tuner = T.Tuner(self.stream, T.key_suffix(self.shapes.get(self.inputs[0], ()) if self.inputs else None, self.f16, max_lds),
+                             spec.phase == "TEST", max_lds, tune_from._chosen_cfgs if tune_from is not None else None)
+        self._plan_buffers()
+        self._alloc_params(params)
+        self._build_ops()
+        self.tuner.release()      # (a TrainEngine tunes its backward plan after this, and releases again)
+
+    def _init_state(self, spec: NetSpec, data_shapes: Optional[Dict[str, Tuple[int, ...]]] = None, *, dtype: str = "f32", fuse: bool = True,
+                    group_convs: bool = True, autotune: bool = True, share_params: Optional["Engine"] = None, score_outputs: bool = False) -> None:
+        """The host-side state every planner reads, declared once: the argument checks, the inferred shapes, and an empty value for each
+        dict, list, set and handle that __init__, the planners and close() use.  No device call, no buffer, no tuner: __init__ makes
+        those after it, and a test that plans without a GPU (tests/plan_stub.py) starts from here."""
         if dtype not in ("f32", "f16"):
             raise ValueError("dtype must be 'f32' or 'f16'")
         if share_params is not None and (dtype != "f32" or share_params.f16):
@@ -396,21 +427,10 @@ class Engine:
             raise NotImplementedError("the half-float path is inference only (BASELINE configs[4])")
         self.dtype, self.f16 = dtype, dtype == "f16"      # f16: activations / weights stored as halves, f32 accumulation
         self.spec = spec
-        self.device = device
         self.fuse = fuse
         self.group_convs = group_convs
         self.autotune = autotune
-        L.call("fcn_init", device)
-        sp = C.c_void_p()
-        self.replica = replica if replica is not None else _take_replica_index()
-        if self.replica is None:
-            L.call("fcn_stream_create", C.byref(sp))
-        else:
-            L.call("fcn_stream_create_replica", C.byref(sp), int(self.replica))
-        self.stream = int(sp.value)
-        yes = C.c_int(0)
-        L.call("fcn_stream_is_prioritized", self.stream, C.byref(yes))
-        self.stream_prioritized = bool(yes.value)      # False on a replica: the runtime refused, its queue is shared again
+        self.stream = None
         self.lock = threading.RLock()
         self.shapes = spec.infer(data_shapes)
         self.blobs: Dict[str, Blob] = {}
@@ -435,16 +455,6 @@ class Engine:
         self.inputs = spec.data_tops()
         # (a pooling mask that no Upsample consumes is no output: it is not an activation blob; read_blob() still returns it)
         self.outputs = [b for b in spec.output_blobs() if b in self.shapes and b not in spec.mask_blobs]
-        # autotuner: only tile configurations whose workgroup holds at most this much LDS (engines that share the GPU with
-        # other streams: small footprints let workgroups of concurrent launches fit on a CU side by side)
-        max_lds = int(tune_max_lds_kb if tune_max_lds_kb is not None else os.environ.get("FCN_TUNE_MAX_LDS_KB", "160")) * 1024
-        # tune_from: a replica of the same net, whose plan is reused instead of timing again
-        self.tuner = T.Tuner(self.stream, T.key_suffix(self.shapes.get(self.inputs[0], ()) if self.inputs else None, self.f16, max_lds),
-                             spec.phase == "TEST", max_lds, tune_from._chosen_cfgs if tune_from is not None else None)
-        self._plan_buffers()
-        self._alloc_params(params)
-        self._build_ops()
-        self.tuner.release()      # (a TrainEngine tunes its backward plan after this, and releases again)
 
     @property
     def _chosen_cfgs(self) -> Dict[str, object]:
@@ -2448,7 +2458,7 @@ class Engine:
                 self.stream = 0
             # the library's host copies of this engine's prepared groups are keyed by their workspace address: drop them before
             # the addresses can be handed out again
-            for ws in getattr(self, "_group_workspaces", []):
+            for ws in self._group_workspaces:
                 if ws.ptr:
                     lib.fcn_conv2d_group_release(ws.ptr)
                     ws.free()

@@ -366,6 +366,8 @@ def act_param_shape(l: "Layer", bots: Sequence[Shape]) -> Shape:
 
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
+# the opt-in keywords of NetSpec (each off in a bare NetSpec; NetSpec.public turns them on): a new layer family adds its keyword here
+FEATURES = ("depthwise", "ip_gemm", "rconv_f16", "tconv_f16", "scale_gate", "activations")
 
 
 class NetSpec:
@@ -441,6 +443,16 @@ class NetSpec:
     def from_file(cls, path: str, phase: str = "TEST", depthwise: bool = False, *, ip_gemm: bool = False, rconv_f16: bool = False,
                   tconv_f16: bool = False, scale_gate: bool = False, activations: bool = False) -> "NetSpec":
         return cls(proto.parse_file(path), phase, depthwise, ip_gemm, rconv_f16, tconv_f16, scale_gate, activations=activations)
+
+    @staticmethod
+    def public_features(phase: str) -> Dict[str, bool]:
+        """The keywords of FEATURES as the public entry points pass them: everything on, the two half-float ones where the net is a TEST net."""
+        return {k: phase == "TEST" if k in ("rconv_f16", "tconv_f16") else True for k in FEATURES}
+
+    @classmethod
+    def public(cls, msg: proto.Msg, phase: str = "TEST") -> "NetSpec":
+        """The NetSpec of the public entry points (caffe.Net, caffe.get_solver, `caffe train / test / time`): public_features(phase)."""
+        return cls(msg, phase, **cls.public_features(phase))
 
     def is_depthwise(self, l: Layer) -> bool:
         """The layer runs through csrc/dwconv.hip: a DepthwiseConvolution, or - with the `depthwise` keyword - a Convolution whose

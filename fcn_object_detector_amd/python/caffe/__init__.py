@@ -160,11 +160,11 @@ class Net(object):
 
     # ---- construction -------------------------------------------------
     def _setup_python_layers(self) -> None:
-        spec = _NetSpec(self._msg, self._phase, depthwise=True, ip_gemm=True, rconv_f16=self._phase == "TEST", tconv_f16=self._phase == "TEST", scale_gate=True, activations=True)
+        spec = _NetSpec.public(self._msg, self._phase)
         self._py_layers, self._data_shapes = _pylayer.setup_python_layers(spec, TRAIN if self._phase == "TRAIN" else TEST)
 
     def _build(self, initial_params) -> None:
-        spec = _NetSpec(self._msg, self._phase, depthwise=True, ip_gemm=True, rconv_f16=self._phase == "TEST", tconv_f16=self._phase == "TEST", scale_gate=True, activations=True)
+        spec = _NetSpec.public(self._msg, self._phase)
         shapes = dict(self._data_shapes)
         shapes.update(self._user_shapes)
         params = initial_params

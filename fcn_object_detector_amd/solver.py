@@ -109,9 +109,9 @@ class TestNet(object):
     def __init__(self, net_file: str, device: int = 0, autotune: bool = True, share_params: Optional[Engine] = None, params=None):
         self.net_file = net_file
         msg = proto.parse_file(net_file)
-        spec = NetSpec(msg, "TEST", depthwise=True, ip_gemm=True, rconv_f16=True, tconv_f16=True, scale_gate=True, activations=True)
+        spec = NetSpec.public(msg, "TEST")
         self.py_layers, data_shapes = pylayer.setup_python_layers(spec, pylayer.TEST)
-        spec = NetSpec(msg, "TEST", depthwise=True, ip_gemm=True, rconv_f16=True, tconv_f16=True, scale_gate=True, activations=True)
+        spec = NetSpec.public(msg, "TEST")
         spec.infer({**spec.input_shapes, **data_shapes})
         self.engine = eng = Engine(spec, data_shapes, params, device=device, autotune=autotune, share_params=share_params,
                                    score_outputs=True)
@@ -206,9 +206,9 @@ class Solver(object):
         self.log = log if (log is not None and self.rank == 0) else (lambda m: None)
         L.call("fcn_init", self.device)
         msg = proto.parse_file(self.net_file)
-        spec = NetSpec(msg, "TRAIN", depthwise=True, ip_gemm=True, scale_gate=True, activations=True)
+        spec = NetSpec.public(msg, "TRAIN")
         self.py_layers, data_shapes = pylayer.setup_python_layers(spec, pylayer.TRAIN)
-        spec = NetSpec(msg, "TRAIN", depthwise=True, ip_gemm=True, scale_gate=True, activations=True)
+        spec = NetSpec.public(msg, "TRAIN")
         spec.infer({**spec.input_shapes, **data_shapes})
         self.engine = TrainEngine(spec, data_shapes, fill_params(spec, seed=0), device=self.device, solver=self.param, comm=comm,
                                   autotune=autotune)

@@ -154,6 +154,12 @@ class TrainEngine(Engine):
 
     def __init__(self, spec: NetSpec, data_shapes: Dict[str, Tuple[int, ...]], params=None, device: int = 0,
                  solver: Optional[SolverParams] = None, comm=None, autotune: bool = True):
+        super().__init__(spec, data_shapes, params, device, fuse=True, group_convs=True, autotune=autotune, solver=solver, comm=comm)
+        self._alloc_solver_state()
+        self._build_backward()
+
+    def _init_state(self, spec: NetSpec, data_shapes=None, *, solver: Optional[SolverParams] = None, comm=None, **kw) -> None:
+        """Engine._init_state plus the training state: the solver, the gradient blobs and the backward plan's slots (_adopt_backward fills them)."""
         if spec.phase != "TRAIN":
             raise ValueError("TrainEngine needs a TRAIN-phase NetSpec")
         self.solver = solver or SolverParams()
@@ -161,9 +167,9 @@ class TrainEngine(Engine):
         self.grad_blobs: Dict[str, Blob] = {}
         self.bwd_ops: List[Op] = []
         self.iter = 0
-        super().__init__(spec, data_shapes, params, device, fuse=True, group_convs=True, autotune=autotune)
-        self._alloc_solver_state()
-        self._build_backward()
+        self._ws = self._ip_ws = self._ip_wgrad_ws = self._gate_ws = self._act_ws = None
+        self._flip_flat = self._flip_segs_dev = self._tbank = None
+        super()._init_state(spec, data_shapes, **kw)
 
     # ------------------------------------------------------------------ gradient buffers
     def _learns(self, l: Layer) -> bool:
@@ -245,14 +251,18 @@ class TrainEngine(Engine):
     def _build_backward(self) -> None:
         plan = BackwardPlanner(self)
         plan.run()
-        self.bwd_ops, self._ws, self._ip_ws, self._ip_wgrad_ws = plan.ops, plan.ws, plan.ip_ws, plan.ip_wgrad_ws
-        self._gate_ws = plan.gate_ws      # the gate gradients of the gated Scale layers (backward._scale_gate); None without one
-        self._act_ws = plan.act_ws        # the parameter gradients of PReLU and Bias layers (backward._act); None without one
-        self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
+        self._adopt_backward(plan)
         if self.autotune:
             self.tuner.wgrad_cfgs(self.bwd_ops)
         self.tuner.release()
         self._plan_buckets()
+
+    def _adopt_backward(self, plan: BackwardPlanner) -> None:
+        """Take the launches and the workspaces of a finished backward plan."""
+        self.bwd_ops, self._ws, self._ip_ws, self._ip_wgrad_ws = plan.ops, plan.ws, plan.ip_ws, plan.ip_wgrad_ws
+        self._gate_ws = plan.gate_ws      # the gate gradients of the gated Scale layers (backward._scale_gate); None without one
+        self._act_ws = plan.act_ws        # the parameter gradients of PReLU and Bias layers (backward._act); None without one
+        self._flip_flat, self._flip_segs_dev, self._tbank = plan.flip_flat, plan.flip_segs_dev, plan.tbank
 
     def _plan_buckets(self, bucket_floats: int = 1536 * 1024) -> None:
         """Gradient buckets for the overlapped all-reduce: contiguous ranges of the flat gradient buffer (forward layer

@@ -1,77 +1,24 @@
 """PReLU, TanH and Bias (csrc/act.hip) as the forward and backward planners lay them out - without a GPU.
 
-The stub engine of tests/test_gate_plan.py (a NetSpec built with activations=True): Engine / TrainEngine / BackwardPlanner methods run
-with DeviceBuffer replaced by a counter of addresses and the library by one whose entry points return 0 (size queries: 64).  Checked:
+The stub engine of tests/plan_stub.py (a NetSpec built by NetSpec.public's rule, so with activations=True): Engine / TrainEngine /
+BackwardPlanner methods run with DeviceBuffer replaced by a counter of addresses and the library by one whose entry points return 0
+(size queries: 64).  Checked:
 one launch per layer and its operands in both element types; a convolution's or a BatchNorm chain's fusion ends in front of a PReLU; the
 kept copy exists exactly where a gradient comes to an in-place PReLU; windows and the refusals by layer name; the parameter-gradient
 launch before the data launch, each left out where nothing wants it; that a ResNet - a net without one of the three layers - has the
 same launch lists and storage plans with and without the keyword; and that models.mtcnn and models.enet plan completely."""
-import threading
-
 import pytest
 
-from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto
+from fcn_object_detector_amd import models
 from fcn_object_detector_amd import storage as S
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
-
-
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append((name, a))
-            return 64 if name.endswith("_bytes") else 0
-        return fn
+from plan_stub import engine_factory
 
 
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: None)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False, activations=True, backward=True):
-        FakeBuffer.next_ptr = 1 << 20
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=True, ip_gemm=True, rconv_f16=phase == "TEST", tconv_f16=phase == "TEST",
-                       scale_gate=True, activations=activations)
-        cls = T.TrainEngine if phase == "TRAIN" else E.Engine
-        e = cls.__new__(cls)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e._bn_chains, e._bn_ws_bytes, e._group_workspaces = {}, 0, []
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        if phase == "TRAIN" and backward:
-            e.plan = BW.BackwardPlanner(e)
-            e.plan.run()
-            e._act_ws, e._gate_ws, e._bn_ws = e.plan.act_ws, e.plan.gate_ws, FakeBuffer(64)
-        return e
-    return make
+    return engine_factory(monkeypatch, public=True)
 
 
 def fwd_ops(e, kinds=("act",)):

@@ -1,4 +1,4 @@
-"""ArgMax as the forward planner lays it out - without a GPU, on the stub engine of tests/test_rect_plan.py (DeviceBuffer replaced by
+"""ArgMax as the forward planner lays it out - without a GPU, on the stub engine of tests/plan_stub.py (DeviceBuffer replaced by
 a counter of addresses, the library by one whose every entry point returns 0 and records its name).
 
 Checked: the launch list of the three fused forms and the entry point each launch calls; the launch list for each reason not to
@@ -10,7 +10,7 @@ from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd.netspec import NetSpec
-from test_rect_plan import stub      # noqa: F401  (the fixture)
+from plan_stub import engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 HEAD = """
@@ -23,6 +23,11 @@ ARGMAX = 'layer { name: "am" type: "ArgMax" bottom: "%s" top: "am" argmax_param 
 RELU = 'layer { name: "more" type: "ReLU" bottom: "%s" top: "more" }\n'
 
 
+@pytest.fixture
+def stub(monkeypatch):
+    return engine_factory(monkeypatch, backward=False)
+
+
 def launches(e):
     return [(op.kind, op.name) for t in e.tasks if isinstance(t, E.OpTask) for op in t.ops]
 
@@ -30,7 +35,7 @@ def launches(e):
 def called(e, op):
     del e.fake.calls[:]
     op.run(None)
-    return list(e.fake.calls)
+    return e.fake.names()
 
 
 def argmax_op(e):

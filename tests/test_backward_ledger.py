@@ -19,7 +19,7 @@ from fcn_object_detector_amd.engine import Blob
 from fcn_object_detector_amd.netspec import DATA_TYPES, Layer
 import test_gpu_backward_fanout as F
 from test_gpu_backward_fanout import CASES, LEAKY, REFUSALS, VARIANTS
-from test_rect_plan import FakeBuffer, stub  # noqa: F401  (the stub engine of the plan tests: no device, a library that returns 0)
+from plan_stub import engine_factory      # (the stub engine of the plan tests: no device, a library that returns 0)
 
 NO_GRADIENT = {
     **{t: "a data layer: it has no bottom" for t in DATA_TYPES},
@@ -31,6 +31,11 @@ NO_GRADIENT = {
     "Slice": "its tops are views of the bottom, and so are their gradients: no launch (a Slice that copies is refused)",
 }
 REFUSES = {"Dropout": "Dropout into an already written gradient"}
+
+
+@pytest.fixture
+def stub(monkeypatch):
+    return engine_factory(monkeypatch, backward=False)
 
 
 @pytest.fixture
@@ -113,7 +118,7 @@ def test_no_fused_mask_is_built_for_a_relu_with_a_slope(stub):
         setattr(e.fake, name, lambda *a, name=name: seen.setdefault(name, []).append(a) or 0)
     plan = BW.BackwardPlanner(e)
     plan.run()
-    e._ws, e._bn_ws, e._ip_ws = plan.ws, FakeBuffer(64), plan.ip_ws
+    e._adopt_backward(plan)
     kinds = [(op.kind, op.name) for op in plan.ops]
     assert [kn for kn in kinds if kn[0] in ("relu_bwd", "maxpool_bwd", "bn_bwd_apply")] == [
         ("relu_bwd", "t_relu"), ("bn_bwd_apply", "t"), ("maxpool_bwd", "m"), ("relu_bwd", "lr0")]

@@ -1,20 +1,15 @@
 """Dilated Convolution as the forward and backward planners lay it out - without a GPU.
 
-As tests/test_grouped_conv_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by
+As tests/test_grouped_conv_plan.py: Engine / TrainEngine / BackwardPlanner methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by
 a counter of addresses and the library by one whose every entry point returns 0; what is checked is the arithmetic of the
 descriptors (pointers, extents, pad' = dil (k-1) - pad, flags), which launches share a plan, how the weight gradient is booked, and
 that every refusal names its layer."""
-import ctypes as C
-import threading
-
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import proto
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from plan_stub import FakeBuffer, engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 NET = """
@@ -34,56 +29,9 @@ TRAIN_NET = (NET % ('input: "target" input_shape { dim: 2 dim: 5 dim: 8 dim: 10 
                     'layer { name: "loss" type: "EuclideanLoss" bottom: "b3" bottom: "target" top: "loss" }')).replace("EXTRA", "")
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append(name)
-            return 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    copies, lib = [], FakeLib()
-
-    def call(name, *a):
-        lib.calls.append(name)
-        if name == "fcn_memcpy_h2d_async":
-            copies.append((int(a[0]), C.string_at(a[1], a[2])))
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", call)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False):
-        spec = NetSpec(proto.parse_text(text), phase)
-        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.copies, e.fake = {}, None, threading.RLock(), copies, lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False)
 
 
 def test_forward_tasks_and_the_shared_launch(stub):
@@ -109,13 +57,13 @@ def test_forward_tasks_and_the_shared_launch(stub):
     assert lv["a2"] == lv["a4"] == lv["c0"] + 1 and lv["b3"] > lv["sum"] > lv["a2"]
     del e.fake.calls[:]
     e._emit_rconvs([dt["a2"], dt["a4"]])
-    assert e.fake.calls.count("fcn_rconv2d_prepare") == 1 and len(e.ops) == 1
+    assert e.fake.names().count("fcn_rconv2d_prepare") == 1 and len(e.ops) == 1
     op = e.ops[0]
     assert op.kind == "dconv" and op.name.startswith("a2+a4 [d2,4 ")
     assert op.flops == 2 * (2.0 * 2 * 12 * 14 * 6 * 8 * 9)                               # 2 N OH OW Cin Cout k k, each
     assert op.bytes == 4.0 * (2 * (2 * 6 * 168 + 2 * 8 * 168 + 8 * 6 * 9) + 8 + 8)
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_rconv2d_f32"
+    assert e.fake.names()[-1] == "fcn_rconv2d_f32"
     e._emit_rconvs([dt["b3"]])
     assert len(e.ops) == 2 and e.ops[1].flops == 2.0 * 2 * 4 * 5 * 8 * 5 * 9
 
@@ -148,7 +96,7 @@ def test_backward_plan_of_dilated_layers(stub):
     assert (d.w, d.kh, d.kw, d.stride_h, d.stride_w, d.dilation, d.pad_h, d.pad_w, d.flags) == \
         (plan.flip_flat.ptr + 4 * 2 * 6 * 9 * 8, 3, 3, 1, 1, 3, 3 * 2 - 1, 3 * 2 - 1, 0)      # pad' = dil (k-1) - pad
     wop.run(None)
-    assert e.fake.calls[-1] == "fcn_rconv2d_wgrad_f32"
+    assert e.fake.names()[-1] == "fcn_rconv2d_wgrad_f32"
     # a2 (fused ReLU: its mask first) and a4 both write the gradient of c0: the second one accumulates
     plan._eltwise(by["sum"])
     n0 = len(plan.ops)
@@ -163,7 +111,7 @@ def test_backward_plan_of_dilated_layers(stub):
     plan._convolution(by["c0"])
     del e.fake.calls[:]
     plan._finish_dgrads()
-    assert e.fake.calls.count("fcn_rconv2d_prepare") == 3
+    assert e.fake.names().count("fcn_rconv2d_prepare") == 3
     dl = last.descs[0]
     assert dl.flags == L.CONV_ACCUM | L.CONV_MASK and (dl.y2, dl.y2_cstride, dl.y2_coffset) == (B["c0"].buf.ptr, B["c0"].cstride, B["c0"].coffset)
     assert first.descs[0].flags == 0 and ("relu_bwd", "c0") not in [(op.kind, op.name) for op in plan.ops]

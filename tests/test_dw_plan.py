@@ -1,22 +1,19 @@
 """Depthwise Convolution as the forward and backward planners lay it out - without a GPU.
 
-As tests/test_rect_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by a counter
+As tests/test_rect_plan.py: Engine / TrainEngine / BackwardPlanner methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a counter
 of addresses and the library by one whose every entry point returns 0; what is checked is the arithmetic of the descriptors (pointers,
 extents, flags), the level and the read / write ranges of the task, how the weight gradient is booked, that every refusal names its
 layer - and that nets without a depthwise layer plan exactly the same with NetSpec(depthwise=True) as without it."""
-import ctypes as C
 import json
-import threading
 
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto
+from fcn_object_detector_amd import models
 from fcn_object_detector_amd import storage as S
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from plan_stub import FakeBuffer, engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 NET = """
@@ -37,58 +34,9 @@ TRAIN_NET = NET % ('input: "target" input_shape { dim: 2 dim: 5 dim: 6 dim: 7 }'
                    'layer { name: "loss" type: "EuclideanLoss" bottom: "pw" bottom: "target" top: "loss" }')
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append(name)
-            return 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    copies, lib = [], FakeLib()
-
-    def call(name, *a):
-        lib.calls.append(name)
-        if name == "fcn_memcpy_h2d_async":
-            copies.append((int(a[0]), C.string_at(a[1], a[2])))
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", call)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False, depthwise=True):
-        FakeBuffer.next_ptr = 1 << 20
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=depthwise)
-        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.copies, e.fake = {}, None, threading.RLock(), copies, lib
-        e._bn_chains, e._bn_ws_bytes = {}, 0
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False, depthwise=True)
 
 
 def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
@@ -115,7 +63,7 @@ def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
         assert op.bytes == 4.0 * (2 * 12 * 14 * 6 + 2 * oh * ow * 6 + kh * kw * 6 + 6)       # 4 (N H W C + N OH OW C + kh kw C + C)
         del e.fake.calls[:]
         op.run(None)
-        assert e.fake.calls == ["fcn_dwconv2d_fwd_f32"]
+        assert e.fake.names() == ["fcn_dwconv2d_fwd_f32"]
     assert len(e.params_dev["dwb"]) == 1
     # the bank as uploaded: tap-major, the channels of one tap contiguous, pad channels zero
     import numpy as np
@@ -126,12 +74,12 @@ def test_a_depthwise_layer_is_one_op_task_with_its_descriptor(stub):
     lv = dict(zip([t.layer.name for t in e.tasks], E.task_levels(e.tasks)))
     assert lv["dwa"] == lv["dwb"] == lv["c0"] + 1 and lv["pw"] > lv["sum"] > lv["dwa"]
     # the whole plan: the two launches and nothing of the other convolution families for them
-    e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+    e.tuner = None
     del e.fake.calls[:]
     e._build_ops()
     assert [op.name for op in e.ops if op.kind == "dwconv"] == ["dwa [3x3]", "dwb [3x5]"]
-    assert "fcn_rconv2d_prepare" not in e.fake.calls and e.fake.calls.count("fcn_conv2d_group_prepare") + \
-        e.fake.calls.count("fcn_conv2d_group_prepare_fused") == 2
+    assert "fcn_rconv2d_prepare" not in e.fake.names() and e.fake.names().count("fcn_conv2d_group_prepare") + \
+        e.fake.names().count("fcn_conv2d_group_prepare_fused") == 2
 
 
 def test_the_half_engine_runs_the_half_kernel_on_a_float32_bank(stub):
@@ -146,7 +94,7 @@ def test_the_half_engine_runs_the_half_kernel_on_a_float32_bank(stub):
     assert e.param_segs[("dwa", 1)].esize == 4 and e.param_segs[("pw", 0)].esize == 2
     del e.fake.calls[:]
     dt["dwa"].ops[0].run(None)
-    assert e.fake.calls == ["fcn_dwconv2d_fwd_f16"]
+    assert e.fake.names() == ["fcn_dwconv2d_fwd_f16"]
     # a depthwise layer that is the net's output stores float32
     out = stub(TEST_NET.split('layer { name: "rdwa"')[0], f16=True)
     t = [t for t in out.tasks if isinstance(t, E.OpTask) and t.dwconv is not None][0]
@@ -175,7 +123,7 @@ def test_backward_plan_of_depthwise_layers(stub):
     assert wop.flops == 2.0 * 2 * 6 * 7 * 6 * 15 and wop.bytes == 4.0 * (2 * 12 * 14 * 6 + 2 * 6 * 7 * 6 + 15 * 6 + 6)
     del e.fake.calls[:]
     wop.run(None)
-    assert e.fake.calls == ["fcn_dwconv2d_wgrad_f32"]
+    assert e.fake.names() == ["fcn_dwconv2d_wgrad_f32"]
     first, last = plan.writers["c0"]
     assert first.launch is None and first.targets == ["c0"] and isinstance(first.descs[0], L.DwConvDesc)
     # the descriptor is the FORWARD problem: x names dX (the gradient view of c0), y names dY, the bank is the layer's own
@@ -188,13 +136,12 @@ def test_backward_plan_of_depthwise_layers(stub):
     # c0's own ReLU mask is folded into the LAST pass that writes its gradient, as for a dense pass
     plan._convolution(by["c0"])
     del e.fake.calls[:]
-    e._group_workspaces = []
     plan._finish_dgrads()
-    assert [c for c in e.fake.calls if "prepare" in c] == ["fcn_conv2d_group_prepare"]      # pw's dense pass; a depthwise gather has nothing to prepare
+    assert [c for c in e.fake.names() if "prepare" in c] == ["fcn_conv2d_group_prepare"]      # pw's dense pass; a depthwise gather has nothing to prepare
     assert dl.flags == L.CONV_ACCUM | L.CONV_MASK and (dl.y2, dl.y2_cstride, dl.y2_coffset) == (B["c0"].buf.ptr, B["c0"].cstride, B["c0"].coffset)
     assert first.descs[0].flags == 0 and ("relu_bwd", "c0") not in [(op.kind, op.name) for op in plan.ops]
     last.op.run(None)
-    assert e.fake.calls[-1] == "fcn_dwconv2d_dgrad_f32"
+    assert e.fake.names()[-1] == "fcn_dwconv2d_dgrad_f32"
     assert "rdwa" in e._fused_relu_layers()
 
 
@@ -248,4 +195,4 @@ def test_nets_without_a_depthwise_layer_plan_the_same_with_the_keyword(stub, nam
     assert all(t.dwconv is None for t in keyed.tasks if isinstance(t, E.OpTask)), name
     assert json.dumps(plan_signature(keyed)) == sig_plain, name
     assert keyed.param_layout == plain.param_layout and keyed.param_count == plain.param_count, name
-    assert not any(c.startswith("fcn_dwconv2d") for c in keyed.fake.calls), name
+    assert not any(c.startswith("fcn_dwconv2d") for c in keyed.fake.names()), name

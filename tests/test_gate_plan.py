@@ -1,71 +1,22 @@
 """The gated Scale (csrc/gate.hip) as the forward and backward planners lay it out - without a GPU.
 
-The stub engine of tests/test_rect_plan.py (its FakeBuffer / FakeLib idea, with a NetSpec built with scale_gate=True): Engine /
+The stub engine of tests/plan_stub.py (a NetSpec built by NetSpec.public's rule, so with scale_gate=True): Engine /
 TrainEngine / BackwardPlanner methods run with DeviceBuffer replaced by a counter of addresses and the library by one whose entry points
 return 0 (size queries: 64).  Checked: the fused launch list of a TEST engine and its operands, every reason not to fuse, the TRAIN
 forward unfused, the backward op order of one SE block, the half-float plan (gate float32, top halves), and that a ResNet - a net
 without a two-bottom Scale or an Axpy - has the same launch lists and storage plans with and without the keyword."""
-import threading
-
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
-from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto
+from fcn_object_detector_amd import models
 from fcn_object_detector_amd import storage as S
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
-
-
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append((name, a))
-            return 64 if name.endswith("_bytes") else 0
-        return fn
+from plan_stub import engine_factory
 
 
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: None)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False, scale_gate=True, fuse=True):
-        FakeBuffer.next_ptr = 1 << 20
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=True, ip_gemm=True, scale_gate=scale_gate)
-        cls = T.TrainEngine if phase == "TRAIN" else E.Engine
-        e = cls.__new__(cls)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, fuse, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e._bn_chains, e._bn_ws_bytes, e._group_workspaces = {}, 0, []
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, public=True, backward=False)
 
 
 # one SE block on a 12-channel branch: a convolution (the branch), global pooling, squeeze, excite, Sigmoid, the gate, the residual add
@@ -182,7 +133,7 @@ def test_the_train_forward_is_unfused_and_the_backward_order_of_one_block(stub):
     assert [op.kind for t in e.tasks if isinstance(t, E.OpTask) and t.layer.name == "out" for op in t.ops] == ["eltwise"]
     plan = BW.BackwardPlanner(e)
     plan.run()
-    e._ws, e._ip_ws, e._ip_wgrad_ws, e._gate_ws = plan.ws, plan.ip_ws, plan.ip_wgrad_ws, plan.gate_ws
+    e._adopt_backward(plan)
     kinds = [(op.kind, op.name) for op in plan.ops if op.kind in ("scale_gate_bwd", "avepool_bwd", "sigmoid_bwd", "eltwise_bwd")]
     assert kinds == [("eltwise_bwd", "out:sc"), ("eltwise_bwd", "out:short"), ("scale_gate_bwd", "sc:x"), ("scale_gate_bwd", "sc:gate"),
                      ("sigmoid_bwd", "gate"), ("avepool_bwd", "pool")]
@@ -266,7 +217,7 @@ def test_se_resnet_plans_one_fused_launch_per_block(stub, form):
 def bwd_gate_calls(e):
     plan = BW.BackwardPlanner(e)
     plan.run()
-    e._ws, e._ip_ws, e._ip_wgrad_ws, e._gate_ws = plan.ws, plan.ip_ws, plan.ip_wgrad_ws, plan.gate_ws
+    e._adopt_backward(plan)
     ops = [op for op in plan.ops if op.kind == "scale_gate_bwd"]
     return [op.name for op in ops], {op.name: a for op, (_n, a) in zip(ops, run(e, ops))}, plan
 

@@ -1,12 +1,10 @@
 """Grouped Convolution as the planners lay it out, and the text of the CaffeNet / GOTURN / BVLC GoogLeNet writers - without a GPU.
 
-The planner cases run Engine / TrainEngine / BackwardPlanner methods on a stub object (`__new__`, given what the methods read) with
+The planner cases run Engine / TrainEngine / BackwardPlanner methods on the stub engine of tests/plan_stub.py with
 DeviceBuffer replaced by a counter of addresses and the library by one whose every entry point returns 0: what is checked is pure
 arithmetic - the g descriptors of a grouped layer (pointers, offsets, extents), its g flip segments, its g weight-gradient items -
 against the layout rule written out by hand below (storage.conv_groups: group i's bank is rows i*Cout/g .. of [Cout][kh][kw][Cin/g])."""
-import ctypes as C
 import hashlib
-import threading
 
 import pytest
 
@@ -15,8 +13,8 @@ from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd import models, proto
 from fcn_object_detector_amd import storage as S
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from fcn_object_detector_amd.netspec import NetSpec
+from plan_stub import engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 NET = """
@@ -34,51 +32,9 @@ TRAIN_NET = NET % ('input: "target" input_shape { dim: 2 dim: 32 dim: 6 dim: 6 }
                    'layer { name: "loss" type: "EuclideanLoss" bottom: "gs" bottom: "target" top: "loss" }')
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __getattr__(self, name):
-        return lambda *a: 0
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    """make(text, phase, f16) -> an engine stub whose buffers, parameters and forward tasks are planned; .copies: what was 'uploaded'."""
-    copies = []
-
-    def call(name, *a):
-        if name == "fcn_memcpy_h2d_async":
-            copies.append((int(a[0]), C.string_at(a[1], a[2])))
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", call)
-    monkeypatch.setattr(L, "load", lambda: FakeLib())
-
-    def make(text, phase="TEST", f16=False):
-        msg = proto.parse_text(text)
-        spec = NetSpec(msg, phase)
-        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.copies = {}, None, threading.RLock(), copies
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False)
 
 
 @pytest.mark.parametrize("f16", [False, True])

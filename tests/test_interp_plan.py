@@ -1,18 +1,13 @@
 """The Interp layer as the forward and backward planners lay it out - without a GPU.
 
-As tests/test_dilation_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by a
+As tests/test_dilation_plan.py: Engine / TrainEngine / BackwardPlanner methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a
 counter of addresses and the library by one whose every entry point returns 0 and keeps its arguments; what is checked is which entry
 point an op calls with which geometry, the bytes it books, the accumulate flag of a fan-in, and that a label path gets no backward op."""
-import threading
-
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
-from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import proto
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from plan_stub import FakeBuffer, engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 TEST_NET = """
@@ -41,52 +36,9 @@ layer { name: "loss" type: "SoftmaxWithLoss" bottom: "c0" bottom: "label_shrink"
 """.replace("FILL", FILL)
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls, self.args = [], {}
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append(name)
-            self.args[name] = a
-            return 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: lib.calls.append(name))
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False):
-        spec = NetSpec(proto.parse_text(text), phase)
-        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False)
 
 
 def interp_op(e, name):
@@ -103,7 +55,7 @@ def test_the_forward_op(stub):
     assert (op.kind, op.name, op.flops) == ("interp", "up", 0.0)
     assert op.bytes == 4.0 * 2 * 9 * 11 * 6 + 4.0 * 2 * 33 * 41 * 6               # the effective input once, the output once
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_interp_fwd_f32"
+    assert e.fake.names()[-1] == "fcn_interp_fwd_f32"
     assert e.fake.args["fcn_interp_fwd_f32"] == (x.buf.ptr, y.buf.ptr, 2, 12, 14, 6, 8, 0, -1, -2, 33, 41, 8, 0, None)
     t = [t for t in e.tasks if t.layer.name == "up"][0]
     assert t.reads == [e._range("c0")] and t.writes == [e._range("up")]
@@ -116,7 +68,7 @@ def test_the_half_float_engine_takes_an_interp_that_writes_the_float32_output(st
     op = interp_op(e, "up")
     assert op.bytes == 2.0 * 2 * 9 * 11 * 6 + 4.0 * 2 * 33 * 41 * 6
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_interp_fwd_f16"
+    assert e.fake.names()[-1] == "fcn_interp_fwd_f16"
     assert e.fake.args["fcn_interp_fwd_f16"] == (x.buf.ptr, y.buf.ptr, 2, 12, 14, 6, 8, 0, -1, -2, 33, 41, 8, 0, 1, None)
     # between two half blobs: halves out
     mid = TEST_NET + 'layer { name: "c2" type: "Convolution" bottom: "up" top: "c2" convolution_param { num_output: 4 kernel_size: 1 FILL } }'.replace("FILL", FILL)

@@ -1,72 +1,24 @@
 """InnerProduct above FCN_IP_MAX_ROWS rows as the forward and backward planners lay it out - without a GPU.
 
-As tests/test_region_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by a counter
+As tests/test_region_plan.py: Engine / TrainEngine / BackwardPlanner methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a counter
 of addresses and the library by one whose entry points return 0 (size queries: 64).  Checked: at 32 rows the plan is the streaming one
 whatever the NetSpec's ip_gemm says (same op kinds, same entry points, same arguments); at 33 rows a bare NetSpec is refused by layer
 name with the words that say how to opt in, and one built with ip_gemm=True plans ip_gemm / ip_gemm_bwd / wgrad ops on the
 fcn_ip_gemm_* entry points with the streaming call's operands, the forward workspace per layer from the new query, bwd_data's through
 e._ip_ws and the weight gradient's a buffer of its own."""
-import threading
-
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
-from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from fcn_object_detector_amd import models
+from plan_stub import engine_factory
 
 RELU, ACCUM, OUT_F32, NT = 1, 4, 8, 256
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append((name, a))
-            return 64 if name.endswith("_bytes") else 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: None)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False, ip_gemm=False):
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=True, ip_gemm=ip_gemm)
-        cls = T.TrainEngine if phase == "TRAIN" else E.Engine
-        e = cls.__new__(cls)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e._bn_chains, e._bn_ws_bytes = {}, 0
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False, depthwise=True)
 
 
 def net(m, train=False):
@@ -152,7 +104,7 @@ def test_33_rows_in_the_half_float_engine(stub):
 def backward_plan(e):
     plan = BW.BackwardPlanner(e)
     plan.run()
-    e._ws, e._ip_ws, e._ip_wgrad_ws = plan.ws, plan.ip_ws, plan.ip_wgrad_ws
+    e._adopt_backward(plan)
     return plan
 
 

@@ -1,18 +1,17 @@
 """Dilated and rectangular Convolution as the half-float forward planner lays them out - without a GPU.
 
-The stub engine of tests/test_rect_plan.py (DeviceBuffer a counter of addresses, the library one whose every entry point returns 0)
-over a NetSpec built with rconv_f16=True: the arithmetic of the descriptors over halves, which launches share a plan and that the half
-entry points are the ones called, every refusal by layer name, that a bare NetSpec refuses as it always did, that the float32 plan of
-the same nets does not depend on the keyword, and that the model writers' nets plan completely."""
-import threading
-
+The stub engine of tests/plan_stub.py (DeviceBuffer a counter of addresses, the library one whose every entry point returns 0), here a
+half-float one over a bare NetSpec built with rconv_f16=True: the arithmetic of the descriptors over halves, which launches share a plan
+and that the half entry points are the ones called, every refusal by layer name, that a bare NetSpec refuses as it always did, that the
+float32 plan of the same nets does not depend on the keyword, and that the model writers' nets plan completely."""
 import pytest
 
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd import models, proto
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
-from test_rect_plan import FILL, FakeBuffer, FakeLib, one, plan_signature
+from fcn_object_detector_amd.netspec import NetSpec
+from plan_stub import engine_factory
+from test_rect_plan import FILL, one, plan_signature
 
 NET = """
 input: "data" input_shape { dim: 2 dim: 3 dim: 12 dim: 14 }
@@ -30,26 +29,7 @@ layer { name: "out" type: "Convolution" bottom: "sum" top: "out" convolution_par
 
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    monkeypatch.setattr(E, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: lib.calls.append(name))
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, f16=True, **spec_kw):
-        FakeBuffer.next_ptr = 1 << 20
-        spec = NetSpec(proto.parse_text(text), "TEST", **spec_kw)
-        e = E.Engine.__new__(E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._bn_chains, e._bn_ws_bytes = {}, 0
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, f16=True)
 
 
 def rconv_tasks(e):
@@ -87,7 +67,7 @@ def test_shared_plans_go_through_the_half_entry_points(stub):
     assert lv["a17"] == lv["a71"] == lv["d2"] == lv["d4"] == lv["c0"] + 1 and lv["out"] > lv["sum"] > lv["a17"]
     del e.fake.calls[:]
     e._emit_rconvs([rt[n] for n in ("a17", "a71", "d2", "d4")])
-    assert e.fake.calls.count("fcn_rconv2d_prepare_f16") == 2 and "fcn_rconv2d_prepare" not in e.fake.calls
+    assert e.fake.names().count("fcn_rconv2d_prepare_f16") == 2 and "fcn_rconv2d_prepare" not in e.fake.names()
     assert [(op.kind, op.name.split(" ")[0]) for op in e.ops] == [("dconv", "d2+d4"), ("rconv", "a17+a71")]      # square launches first
     assert e.ops[0].name.startswith("d2+d4 [d2,4 ") and e.ops[1].name.startswith("a17+a71 [1x7,7x1 ")
     op = e.ops[1]
@@ -95,17 +75,17 @@ def test_shared_plans_go_through_the_half_entry_points(stub):
     assert op.bytes == 2.0 * (2 * (2 * 6 * 168 + 2 * 8 * 168 + 8 * 6 * 7)) + 4.0 * (8 + 8)      # halves; the bias is float32
     for op in e.ops:
         op.run(None)
-        assert e.fake.calls[-1] == "fcn_rconv2d_f16"
+        assert e.fake.names()[-1] == "fcn_rconv2d_f16"
     e._emit_rconvs([rt["out"]])
     assert e.ops[2].kind == "dconv" and e.ops[2].bytes == 2.0 * (2 * 8 * 168 + 5 * 8 * 9) + 4.0 * (2 * 5 * 168 + 5)      # float32 result
     # the whole plan: one launch per kind and shared bottom
     e = stub(NET, rconv_f16=True)
-    e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+    e.tuner = None
     del e.fake.calls[:]
     e._build_ops()
     assert [(op.kind, op.name.split(" ")[0]) for op in e.ops if op.kind in ("rconv", "dconv")] == [("dconv", "d2+d4"), ("rconv", "a17+a71"),
                                                                                                   ("dconv", "out")]
-    assert e.fake.calls.count("fcn_rconv2d_prepare_f16") == 3 and "fcn_rconv2d_prepare" not in e.fake.calls
+    assert e.fake.names().count("fcn_rconv2d_prepare_f16") == 3 and "fcn_rconv2d_prepare" not in e.fake.names()
 
 
 def test_refusals_name_the_layer(stub):
@@ -149,10 +129,10 @@ def test_the_float32_plan_does_not_depend_on_the_keyword(stub):
         sa, sb = plan_signature(a), plan_signature(b)
         assert sa == sb and any(r.get("rconv") for r in sa)
         for e in (a, b):
-            e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+            e.tuner = None
             del e.fake.calls[:]
             e._build_ops()
-            assert "fcn_rconv2d_prepare_f16" not in e.fake.calls and e.fake.calls.count("fcn_rconv2d_prepare") >= 1
+            assert "fcn_rconv2d_prepare_f16" not in e.fake.names() and e.fake.names().count("fcn_rconv2d_prepare") >= 1
         assert [(op.kind, op.name, op.flops, op.bytes) for op in a.ops] == [(op.kind, op.name, op.flops, op.bytes) for op in b.ops]
 
 
@@ -178,7 +158,7 @@ def test_the_writers_nets_plan_completely(stub, name, text, problems, first):
         assert xb.esize == 2 and yb.esize == 2 and not d.flags & L.CONV_OUT_F32, nm
         assert xb.cstride % 8 == 0 and xb.coffset % 8 == 0 and yb.coffset % 8 == 0, nm
         assert e.param_segs[(nm, 0)].esize == 2 and e.param_segs[(nm, 0)].shape[-1] == (d.Cin + 7) // 8 * 8, nm
-    e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+    e.tuner = None
     del e.fake.calls[:]
     e._build_ops()
-    assert e.fake.calls.count("fcn_rconv2d_prepare_f16") >= 1 and "fcn_rconv2d_prepare" not in e.fake.calls
+    assert e.fake.names().count("fcn_rconv2d_prepare_f16") >= 1 and "fcn_rconv2d_prepare" not in e.fake.names()

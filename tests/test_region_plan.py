@@ -1,68 +1,23 @@
 """The region stage as the forward planner lays it out - without a GPU.
 
-As tests/test_ssd_plan.py: Engine methods run on a stub object with DeviceBuffer replaced by a counter of addresses and the library by one
+As tests/test_ssd_plan.py: Engine methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a counter of addresses and the library by one
 whose entry points return 0 (size queries: 64).  Checked: one op per layer of the region stage and none for the two Reshape layers of the
 RPN softmax chain, the arguments of each launch, that the chain's middle blobs own nothing, the order of the ops, the blobs on the ROI
 axis, and the refusals that the planner makes (the half-float engine, a TRAIN net, other Reshape forms, a chain with another reader)."""
-import threading
 
 import numpy as np
 import pytest
 
 import ref_region64 as R
-from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
-
-
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append((name, a))
-            return 64 if name.endswith("_bytes") else 0
-        return fn
+from fcn_object_detector_amd import models
+from plan_stub import engine_factory
 
 
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: None)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False):
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=True)
-        cls = T.TrainEngine if phase == "TRAIN" else E.Engine
-        e = cls.__new__(cls)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e._bn_chains, e._bn_ws_bytes = {}, 0
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False, depthwise=True)
 
 
 KINDS = ("pair_softmax", "proposal", "roi_pool", "psroi_pool")

@@ -1,73 +1,24 @@
 """The SSD head as the forward planner lays it out - without a GPU.
 
-As tests/test_dilation_plan.py: Engine methods run on a stub object with DeviceBuffer replaced by a counter of addresses and the library
+As tests/test_dilation_plan.py: Engine methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a counter of addresses and the library
 by one whose entry points return 0 (size queries: 64).  Checked: one ssd_gather op per Concat with the right heads and columns and no copy
 op, nothing for Permute / Flatten / Reshape / PriorBox, the prior constants against the float64 reference, the order of the ops, the
 capacity of detection_out, and the TRAIN-phase refusal."""
 import ctypes as C
-import threading
 
 import numpy as np
 import pytest
 
 import ref_ssd64 as R
-from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
 from fcn_object_detector_amd import lib as L
-from fcn_object_detector_amd import models, proto, ssd
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
-
-
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append((name, a))
-            return 64 if name.endswith("_bytes") else 0
-        return fn
+from fcn_object_detector_amd import models, ssd
+from plan_stub import engine_factory
 
 
 @pytest.fixture
 def stub(monkeypatch):
-    copies, lib = {}, FakeLib()
-
-    def call(name, *a):
-        if name == "fcn_memcpy_h2d_async":
-            copies[int(a[0])] = C.string_at(a[1], a[2])
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", call)
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST"):
-        spec = NetSpec(proto.parse_text(text), phase, depthwise=True)
-        cls = T.TrainEngine if phase == "TRAIN" else E.Engine
-        e = cls.__new__(cls)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), False, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e._bn_chains, e._bn_ws_bytes = {}, 0
-        e.grad_blobs, e.stream, e.lock, e.copies, e.fake = {}, None, threading.RLock(), copies, lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False, depthwise=True)
 
 
 def ssd_ops(e):
@@ -135,7 +86,7 @@ def test_prior_constants_equal_the_reference(stub):
     assert got.shape == (1, 2, 1408) and got.dtype == np.float32 and np.max(np.abs(got - want)) < 1e-6
     assert np.max(np.abs(e.prior_consts["fc7_mbox_priorbox"] - b)) < 1e-6
     # uploaded once, as they lie: corners, then variances
-    assert e.copies[e.blobs["mbox_priorbox"].buf.ptr] == got.tobytes() and e.read_blob("mbox_priorbox") is got
+    assert e.copied[e.blobs["mbox_priorbox"].buf.ptr] == got.tobytes() and e.read_blob("mbox_priorbox") is got
     # the published steps at 300: 8 and 16
     full = stub(models.ssd300_vgg(width_div=32, heads=2))
     a = R.prior_box(38, 38, 300, 300, [30.0], [60.0], [2.0], variance=(0.1, 0.1, 0.2, 0.2), step=8)

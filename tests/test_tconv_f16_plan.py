@@ -1,6 +1,6 @@
 """The group-1 Deconvolution and the converting Crop as the half-float forward planner lays them out - without a GPU.
 
-The stub engine of tests/test_rconv_f16_plan.py over a NetSpec built with tconv_f16=True, on the published FCN-32s / 16s / 8s nets at 5
+The half-float stub engine of tests/plan_stub.py over a NetSpec built with tconv_f16=True, on the published FCN-32s / 16s / 8s nets at 5
 classes, 64 x 48 and an eighth of the widths: without the keyword each is refused by the name of its first group-1 Deconvolution in
 the words it always was; with it each plans completely - tconv_pack + tconv through the half entry points, descriptors over halves, the
 bank segment in halves, `score` float32 through the converting crop or half in front of ArgMax.  The float32 plan of the same nets does
@@ -14,7 +14,7 @@ from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd import models, proto
 from fcn_object_detector_amd import storage as S
 from fcn_object_detector_amd.netspec import NetSpec
-from test_rconv_f16_plan import stub      # noqa: F401  (the fixture)
+from plan_stub import engine_factory
 from test_rect_plan import FILL, plan_signature
 
 KW = dict(num_classes=5, shape=(1, 3, 64, 48), width_div=8, fillers=True)
@@ -26,8 +26,13 @@ PUBLIC = dict(depthwise=True, ip_gemm=True, rconv_f16=True)
 View = namedtuple("View", "esize")      # what storage.param_layout reads of a bottom's view in these nets
 
 
+@pytest.fixture
+def stub(monkeypatch):
+    return engine_factory(monkeypatch, f16=True)
+
+
 def built(e):
-    e.score_outputs, e.tuner, e._group_workspaces = False, None, []
+    e.tuner = None
     del e.fake.calls[:]
     e._build_ops()
     return e
@@ -52,7 +57,7 @@ def test_the_published_nets_plan_completely(stub, variant, argmax):
     by = {l.name: l for l in e.spec.layers}
     ops = [(op.kind, op.name) for op in e.ops]
     # every group-1 Deconvolution: a bank of halves, re-packed and launched through the half entry points
-    assert e.fake.calls.count("fcn_tconv2d_prepare_f16") == len(deconvs) and "fcn_tconv2d_prepare" not in e.fake.calls
+    assert e.fake.names().count("fcn_tconv2d_prepare_f16") == len(deconvs) and "fcn_tconv2d_prepare" not in e.fake.names()
     descs = [k for k in e._keep if isinstance(k, L.TConvDesc)][-len(deconvs):]      # (of this _build_ops: the fixture has planned once before)
     for (name, k, s), d in zip(deconvs, descs):
         l = by[name]
@@ -69,7 +74,7 @@ def test_the_published_nets_plan_completely(stub, variant, argmax):
         del e.fake.calls[:]
         e.ops[i].run(None)
         e.ops[i + 1].run(None)
-        assert e.fake.calls == ["fcn_tconv_bank_pack_f16", "fcn_tconv2d_f16"]
+        assert e.fake.names() == ["fcn_tconv_bank_pack_f16", "fcn_tconv2d_f16"]
         assert e.ops[i + 1].bytes == 2.0 * xb.pixels * 5 + 2.0 * yb.pixels * 5
     # the tail: the last transposed convolution, the crop to `score`, the label map
     kinds = [k for k, _ in ops]
@@ -79,7 +84,7 @@ def test_the_published_nets_plan_completely(stub, variant, argmax):
     assert up.esize == 2 and score.esize == (2 if argmax else 4) and score.shape == (1, 5, 64, 48)
     del e.fake.calls[:]
     e.ops[last + 1].run(None)
-    assert e.fake.calls == ["fcn_crop_fwd_f16" if argmax else "fcn_crop_fwd_f16_f32"]
+    assert e.fake.names() == ["fcn_crop_fwd_f16" if argmax else "fcn_crop_fwd_f16_f32"]
     assert e.ops[last + 1].bytes == float(2 + score.esize) * 64 * 48 * 5
     if argmax:
         assert e.blobs["argmax"].esize == 4 and e.outputs == ["argmax"]
@@ -109,13 +114,13 @@ def test_the_float32_plan_does_not_depend_on_the_keyword(stub):
         assert [(s.kind, s.shape, s.esize, s.offset) for s in a.param_segs.values()] == [(s.kind, s.shape, s.esize, s.offset) for s in b.param_segs.values()]
         for e in (a, b):
             built(e)
-            assert "fcn_tconv2d_prepare_f16" not in e.fake.calls and e.fake.calls.count("fcn_tconv2d_prepare") == len(NETS[variant][1])
+            assert "fcn_tconv2d_prepare_f16" not in e.fake.names() and e.fake.names().count("fcn_tconv2d_prepare") == len(NETS[variant][1])
         assert [(op.kind, op.name, op.flops, op.bytes) for op in a.ops] == [(op.kind, op.name, op.flops, op.bytes) for op in b.ops]
         for op in a.ops:
             if op.kind in ("tconv_pack", "tconv", "crop"):
                 del a.fake.calls[:]
                 op.run(None)
-                assert a.fake.calls[0] in ("fcn_tconv_bank_pack_f32", "fcn_tconv2d_f32", "fcn_crop_fwd_f32")
+                assert a.fake.names()[0] in ("fcn_tconv_bank_pack_f32", "fcn_tconv2d_f32", "fcn_crop_fwd_f32")
 
 
 TINY = """

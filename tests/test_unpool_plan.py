@@ -1,19 +1,16 @@
 """Pooling masks and the Upsample layer as the forward and backward planners lay them out - without a GPU.
 
-As tests/test_interp_plan.py: Engine / TrainEngine / BackwardPlanner methods run on a stub object with DeviceBuffer replaced by a
+As tests/test_interp_plan.py: Engine / TrainEngine / BackwardPlanner methods run on the stub engine of tests/plan_stub.py with DeviceBuffer replaced by a
 counter of addresses and the library by one whose every entry point returns 0 and keeps its arguments; what is checked is which entry
 point an op calls with which geometry and which argmax buffer, the bytes it books, that a masked pooling stays out of the pool + LRN
 fusions, and that the mask gets neither a blob nor a gradient.  The model writers are parsed and inferred at reduced width."""
-import threading
-
 import pytest
 
 from fcn_object_detector_amd import backward as BW
 from fcn_object_detector_amd import engine as E
-from fcn_object_detector_amd import lib as L
 from fcn_object_detector_amd import models, proto
-from fcn_object_detector_amd import train as T
-from fcn_object_detector_amd.netspec import NetSpec, fill_params
+from fcn_object_detector_amd.netspec import NetSpec
+from plan_stub import engine_factory
 
 FILL = 'weight_filler { type: "xavier" } bias_filler { type: "constant" value: 0.1 }'
 BODY = """
@@ -33,52 +30,9 @@ HEAD = 'input: "data" input_shape { dim: 2 dim: 8 dim: 13 dim: 15 }\n'
 UP = 'layer { name: "up1" type: "Upsample" bottom: "BOT" bottom: "pool1_mask" top: "up1" upsample_param { upsample_h: 13 upsample_w: 15 } }\n'
 
 
-class FakeBuffer:
-    next_ptr = 1 << 20
-
-    def __init__(self, nbytes, zero=True):
-        self.ptr, self.nbytes = FakeBuffer.next_ptr, int(nbytes)
-        FakeBuffer.next_ptr += (int(nbytes) + 4095) // 4096 * 4096 + 4096
-
-    def free(self):
-        pass
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls, self.args = [], {}
-
-    def __getattr__(self, name):
-        def fn(*a):
-            self.calls.append(name)
-            self.args[name] = a
-            return 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    lib = FakeLib()
-    for mod in (E, BW, T):
-        monkeypatch.setattr(mod, "DeviceBuffer", FakeBuffer)
-    monkeypatch.setattr(L, "call", lambda name, *a: lib.calls.append(name))
-    monkeypatch.setattr(L, "load", lambda: lib)
-
-    def make(text, phase="TEST", f16=False):
-        spec = NetSpec(proto.parse_text(text), phase)
-        e = (T.TrainEngine if phase == "TRAIN" else E.Engine).__new__(T.TrainEngine if phase == "TRAIN" else E.Engine)
-        e.spec, e.shapes, e.f16, e.fuse, e.group_convs, e.autotune = spec, spec.infer(), f16, True, True, False
-        e.inputs, e.outputs = spec.data_tops(), [b for b in spec.output_blobs() if b in e.shapes and b not in spec.mask_blobs]
-        e.blobs, e.params_host, e.params_dev, e.ops, e._keep, e._conv_layer_meta = {}, {}, {}, [], [], {}
-        e._share_from, e.shared_layers, e.aux_dev, e._lazy_blob_ops, e.loss_blobs = None, set(), {}, {}, {}
-        e.grad_blobs, e.stream, e.lock, e.fake = {}, None, threading.RLock(), lib
-        e._plan_buffers()
-        e._alloc_params(fill_params(spec, seed=1))
-        if phase == "TRAIN":
-            e.grad_flat = FakeBuffer(4 * e.param_count)
-        e.tasks = e._collect_tasks()
-        return e
-    return make
+    return engine_factory(monkeypatch, backward=False)
 
 
 def task_of(e, name):
@@ -120,7 +74,7 @@ def test_one_unpool_op_in_the_float32_engine(stub):
     assert (op.kind, op.name, op.flops) == ("unpool", "up1", 0.0)
     assert op.bytes == (4.0 + 4.0) * 2 * 6 * 7 * 8 + 4.0 * 2 * 11 * 14 * 8          # x + idx + y
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_unpool_fwd_f32"
+    assert e.fake.names()[-1] == "fcn_unpool_fwd_f32"
     assert e.fake.args["fcn_unpool_fwd_f32"] == (x.buf.ptr, idx.ptr, y.buf.ptr, 2, 6, 7, 8, 8, 0, 2, 2, 0, 11, 14, 8, 0, None)
     assert [t.layer.name for t in e.tasks if any(o.kind == "unpool" for o in getattr(t, "ops", []))] == ["up1"]
 
@@ -134,13 +88,13 @@ def test_one_unpool_op_in_the_half_engine(stub):
     assert pool.pool_desc is None                                                    # a masked pooling of halves has its own kernel
     pool.ops[0].run(None)
     xb, yb = e.blobs["c0"], e.blobs["pool1"]
-    assert e.fake.calls[-1] == "fcn_maxpool_idx_fwd_f16"
+    assert e.fake.names()[-1] == "fcn_maxpool_idx_fwd_f16"
     assert e.fake.args["fcn_maxpool_idx_fwd_f16"] == (xb.ptr, yb.buf.ptr, idx.ptr, 2, 11, 14, 8, 8, 2, 2, 0, 6, 7, 8, 0, None)
     assert pool.ops[0].bytes == 2.0 * 8 * (2 * 11 * 14 + 2 * 6 * 7) + 4.0 * 2 * 6 * 7 * 8
     op = only_op(e, "up1")
     assert op.kind == "unpool" and op.bytes == (2.0 + 4.0) * 2 * 6 * 7 * 8 + 2.0 * 2 * 11 * 14 * 8
     op.run(None)
-    assert e.fake.calls[-1] == "fcn_unpool_fwd_f16"
+    assert e.fake.names()[-1] == "fcn_unpool_fwd_f16"
     assert e.fake.args["fcn_unpool_fwd_f16"] == (x.buf.ptr, idx.ptr, y.buf.ptr, 2, 6, 7, 8, 8, 0, 2, 2, 0, 11, 14, 8, 0, 0, None)
     # the net's output behind the layer: halves in, float32 out
     e = stub(BODY, f16=True)
@@ -152,7 +106,7 @@ def test_one_unpool_op_in_the_half_engine(stub):
     plain = stub((BODY + SCORE).replace(' top: "pool1_mask"', "").replace('bottom: "pool1_mask" ', "").replace('"Upsample"', '"ReLU"'), f16=True)
     assert "pool1" not in plain.aux_dev
     task_of(plain, "pool1").ops[0].run(None)
-    assert plain.fake.calls[-1] == "fcn_maxpool_fwd_f16"
+    assert plain.fake.names()[-1] == "fcn_maxpool_fwd_f16"
 
 
 @pytest.mark.parametrize("f16", [False, True])
