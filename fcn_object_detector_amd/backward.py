@@ -14,7 +14,8 @@ from typing import Dict, List, Optional, Tuple
 from . import lib as L
 from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
-from .netspec import DATA_TYPES, Layer, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad, layer_dilation, scale_gate_form
+from .netspec import (DATA_TYPES, NEURON_TYPES, Layer, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad, layer_dilation,
+                      neuron_params, scale_gate_form)
 
 
 @dataclass
@@ -81,6 +82,8 @@ class BackwardPlanner:
         # ... and the one-bottom activations of csrc/act.hip, which _one_bottom consults where one_bottom has no entry: the same
         # (layer, dY, dX, accumulate), except that dX is None where only the layer's own blob wants a gradient
         self.activations = {"PReLU": self._act, "TanH": self._act, "Bias": self._act}
+        # ... and those of csrc/neuron.hip (no learned blob), which _one_bottom consults after the two tables above
+        self.neurons = {t: self._neuron for t in NEURON_TYPES}
 
     def run(self) -> None:
         self._find_concat_relu()
@@ -817,7 +820,7 @@ class BackwardPlanner:
         # an in-place layer (bottom == top: drop6 / drop7 of the published FCN nets, an unfused in-place Sigmoid, ReLU or LRN) rewrites dY
         # as dX - there is nothing to accumulate into, whatever the layer type; `+=` into its own dY would be dY + f(dY)
         acc = 1 if gbot is not None and self.state(gbot) == "full" and gbot is not gtop else 0
-        emit = self.one_bottom.get(l.type) or act
+        emit = self.one_bottom.get(l.type) or act or self.neurons.get(l.type)
         if emit is None:
             raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
         emit(l, gtop, gbot, acc)
@@ -857,6 +860,31 @@ class BackwardPlanner:
         self.ops.append(Op("act_bwd", l.name, lambda st: L.check(lib.fcn_act_bwd_data_f32(
             gtop.buf.ptr, ref[0], gbot.buf.ptr, pix, c, gtop.cstride, gtop.coffset, ref[1], ref[2], gbot.cstride, gbot.coffset, mode, param,
             shared, acc, st)), 1.0 * pix * c, 4.0 * ((2 if t == "Bias" else 3) + acc) * pix * c))
+        self.mark(gbot)
+
+    def _neuron(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        """ELU, ReLU6, Clip, AbsVal, BNLL and Swish (csrc/neuron.hip, engine._fwd_neuron): one launch dX (+)= f'(ref) dY.  ref is the layer's
+        output for ELU, ReLU6, Clip and BNLL - in place they need no copy -, its input for AbsVal (never in place) and for Swish (the copy
+        the forward launch kept where the layer ran in place)."""
+        e, lib, B, t = self.e, self.lib, self.B, l.type
+        xb, yb = B[l.bottoms[0]], B[l.tops[0]]
+        pix, c = xb.pixels, xb.channels
+        mode, a, b = neuron_params(l)
+        for v in (gtop, gbot, xb, yb):
+            if v.coffset % 4 or v.cstride % 4:
+                raise NotImplementedError("backward of %s %s: the view of %s is not 16-byte aligned" % (t, l.name, v.name))
+        if t == "Swish":
+            aux = e.aux_dev.get(l.name)
+            if aux is None and l.tops[0] == l.bottoms[0]:
+                raise RuntimeError("Swish %s ran in place and kept no copy of its input for the backward pass" % l.name)
+            ref = (aux.ptr, _r4(c), 0) if aux is not None else (xb.buf.ptr, xb.cstride, xb.coffset)
+        elif t == "AbsVal":
+            ref = (xb.buf.ptr, xb.cstride, xb.coffset)
+        else:
+            ref = (yb.buf.ptr, yb.cstride, yb.coffset)
+        self.ops.append(Op("neuron_bwd", l.name, lambda st: L.check(lib.fcn_neuron_bwd_f32(
+            gtop.buf.ptr, ref[0], gbot.buf.ptr, pix, c, gtop.cstride, gtop.coffset, ref[1], ref[2], gbot.cstride, gbot.coffset, mode, a, b,
+            acc, st)), 1.0 * pix * c, 4.0 * (3 + acc) * pix * c))
         self.mark(gbot)
 
     def _pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:

@@ -32,8 +32,8 @@ from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
-from .netspec import (ACT_TYPES, Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
-                      layer_dilation, layer_geometry, scale_gate_form)
+from .netspec import (ACT_TYPES, NEURON_TYPES, Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
+                      layer_dilation, layer_geometry, neuron_params, scale_gate_form)
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -1571,10 +1571,12 @@ class Engine:
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
         acts = ACT_TYPES if self.spec.activations else ()      # (csrc/act.hip: only a NetSpec built with activations=True has them)
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample") + acts:
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample") + acts + NEURON_TYPES:
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         if t in acts:
             return self._fwd_act(l, halves)
+        if t in NEURON_TYPES:
+            return self._fwd_neuron(l, halves)
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
@@ -1771,6 +1773,34 @@ class Engine:
         kp = keep.ptr if keep is not None else None
         return [Op("act", l.name, lambda st: L.check(lib.fcn_act_fwd_f32(
             xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, param, shared, st)),
+            1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]
+
+    def _fwd_neuron(self, l: Layer, halves: List[str]) -> List[Op]:
+        """ELU, ReLU6, Clip, AbsVal, BNLL and Swish as one launch of csrc/neuron.hip, on whole buffers and on 16-byte-aligned channel
+        windows alike (the kernel keeps to its window), floats or halves.  A TRAIN engine keeps the input of an in-place Swish to which a
+        gradient comes in aux_dev, filled by the same launch - what _fwd_act does for an in-place PReLU; the other in-place layers read
+        their gradient from the top and keep nothing."""
+        lib, t = L.load(), l.type
+        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
+        if xb.nchw is None or xb.shape != yb.shape:
+            raise NotImplementedError("%s %s on a blob that is neither 4-d nor 2-d" % (t, l.name))
+        if xb.esize != yb.esize:
+            raise NotImplementedError("f16 engine: %s %s between half and float32 blobs" % (t, l.name))
+        grp = 16 // xb.esize
+        if xb.coffset % grp or yb.coffset % grp or xb.cstride % grp or yb.cstride % grp:
+            raise NotImplementedError("%s %s: a channel window that is not 16-byte aligned" % (t, l.name))
+        pix, c = xb.pixels, xb.channels
+        mode, a, b = neuron_params(l)
+        if xb.esize == 2:
+            return [Op("neuron", l.name, lambda st: L.check(lib.fcn_neuron_fwd_f16(
+                xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, mode, a, b, st)), 1.0 * pix * c, 4.0 * pix * c)]
+        keep = None
+        need = getattr(self, "need_grad", None)
+        if self.spec.phase == "TRAIN" and t == "Swish" and l.tops[0] == l.bottoms[0] and (need is None or l.tops[0] in need):
+            keep = self.aux_dev[l.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
+        kp = keep.ptr if keep is not None else None
+        return [Op("neuron", l.name, lambda st: L.check(lib.fcn_neuron_fwd_f32(
+            xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, a, b, st)),
             1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]
 
     def _fwd_dropout(self, l: Layer, halves: List[str]) -> List[Op]:

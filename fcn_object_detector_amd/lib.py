@@ -186,6 +186,8 @@ ELT_PROD, ELT_SUM, ELT_MAX = 0, 1, 2
 ARGMAX_MAX_TOPK = 32           # FCN_ARGMAX_MAX_TOPK
 ACT_PRELU, ACT_TANH, ACT_BIAS = 0, 1, 2      # FCN_ACT_*: the modes of csrc/act.hip
 ACT_MODES = {"PReLU": ACT_PRELU, "TanH": ACT_TANH, "Bias": ACT_BIAS}
+NEURON_ELU, NEURON_CLIP, NEURON_ABSVAL, NEURON_BNLL, NEURON_SWISH = 0, 1, 2, 3, 4      # FCN_NEURON_*: the modes of csrc/neuron.hip
+NEURON_MODES = {"ELU": NEURON_ELU, "ReLU6": NEURON_CLIP, "Clip": NEURON_CLIP, "AbsVal": NEURON_ABSVAL, "BNLL": NEURON_BNLL, "Swish": NEURON_SWISH}
 ARGMAX_WAVE_BYTES, ARGMAX_WAVE_PIXELS, ARGMAX_WAVE_MIN_C = 512, 8192, 32      # FCN_ARGMAX_WAVE_*: where a wave takes a pixel (csrc/argmax.hip)
 ARGMAX_VALUES, ARGMAX_PAIRS, ARGMAX_SOFTMAX = 1, 2, 4
 SOLVER_KINDS = {"SGD": 0, "NESTEROV": 1, "ADAGRAD": 2, "RMSPROP": 3, "ADADELTA": 4, "ADAM": 5}      # FCN_SOLVER_*
@@ -388,6 +390,9 @@ PROTOTYPES = {
     "fcn_act_fwd_f16": (_i, [_vp, _vp] + [_i] * 7 + [_vp, _i, _vp]),
     "fcn_act_bwd_data_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp, _i, _i, _vp]),
     "fcn_act_bwd_param_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp]),
+    "fcn_neuron_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_f, _f, _vp]),
+    "fcn_neuron_fwd_f16": (_i, [_vp, _vp] + [_i] * 7 + [_f, _f, _vp]),
+    "fcn_neuron_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_f, _f, _i, _vp]),
     "fcn_ssd_gather_f32": (_i, [C.POINTER(SsdHead), _i, _i, _vp, _i, _i, _vp]),
     "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
     "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),

@@ -1054,9 +1054,10 @@ def inception_v3(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, wid
 # depthwise=True (caffe.Net and the solvers pass it).
 # ----------------------------------------------------------------------
 
-def _mb_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, stride: int, phase: str, relu: Optional[str], group: int = 1) -> str:
+def _mb_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, stride: int, phase: str, relu: Optional[str], group: int = 1,
+             act: str = "ReLU") -> str:
     """Convolution `<name>` (bias_term: false, pad k // 2; group > 1: depthwise) with BatchNorm `<name>/bn` and Scale `<name>/scale`
-    (bias_term: true) in place on its top and, with `relu`, a ReLU of that name; returns the top."""
+    (bias_term: true) in place on its top and, with `relu`, a layer of that name and of type `act` (ReLU, ReLU6, Swish); returns the top."""
     geo = "    num_output: %d\n    bias_term: false\n    pad: %d\n    kernel_size: %d\n" % (num_output, k // 2, k)
     if group > 1:
         geo += "    group: %d\n    engine: CAFFE\n" % group
@@ -1068,13 +1069,16 @@ def _mb_conv(w: _Writer, name: str, bottom: str, num_output: int, k: int, stride
     w.layer(name + "/bn", "BatchNorm", [name], [name], stats)
     w.layer(name + "/scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
     if relu:
-        w.layer(relu, "ReLU", [name], [name])
+        w.layer(relu, act, [name], [name])
     return name
 
 
-def _mb_tail(w: _Writer, phase: str, feat: str, classes: int) -> None:
-    """pool6 (global AVE), the 1x1 convolution classifier fc7 and prob (DEPLOY) / loss over an (N, 1, 1, 1) `label`, accuracy in TEST."""
+def _mb_tail(w: _Writer, phase: str, feat: str, classes: int, dropout: float = 0.0) -> None:
+    """pool6 (global AVE), with `dropout` an in-place Dropout drop6 of that ratio, the 1x1 convolution classifier fc7 and prob (DEPLOY) /
+    loss over an (N, 1, 1, 1) `label`, accuracy in TEST."""
     w.layer("pool6", "Pooling", [feat], ["pool6"], "  pooling_param { pool: AVE global_pooling: true }")
+    if dropout:
+        w.layer("drop6", "Dropout", ["pool6"], ["pool6"], "  dropout_param { dropout_ratio: %g }" % dropout)
     w.layer("fc7", "Convolution", ["pool6"], ["fc7"], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
             "  convolution_param {\n    num_output: %d\n    kernel_size: 1\n    weight_filler { type: \"gaussian\" std: 0.01 }\n"
             "    bias_filler { type: \"constant\" value: 0 }\n  }" % classes)
@@ -1114,13 +1118,13 @@ def mobilenet_v1(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, wid
     return w.text() if fillers else _strip_fillers(w.text())
 
 
-def _mb2_block(w: _Writer, tag: str, x: str, cin: int, cout: int, t: int, stride: int, phase: str) -> str:
+def _mb2_block(w: _Writer, tag: str, x: str, cin: int, cout: int, t: int, stride: int, phase: str, act: str = "ReLU") -> str:
     """One inverted residual of MobileNet v2: 1x1 `<tag>/expand` to t * cin (left out at t == 1) + ReLU, depthwise 3x3 `<tag>/dwise` at
-    `stride` + ReLU, the linear 1x1 `<tag>/linear` to cout; with stride 1 and cin == cout the Eltwise sum `block_<tag>` with the input."""
+    `stride` + ReLU (`act`: ReLU or ReLU6, both layers), the linear 1x1 `<tag>/linear` to cout; with stride 1 and cin == cout the Eltwise sum `block_<tag>` with the input."""
     y, mid = x, cin * t
     if t != 1:
-        y = _mb_conv(w, "conv%s/expand" % tag, y, mid, 1, 1, phase, "relu%s/expand" % tag)
-    y = _mb_conv(w, "conv%s/dwise" % tag, y, mid, 3, stride, phase, "relu%s/dwise" % tag, group=mid)
+        y = _mb_conv(w, "conv%s/expand" % tag, y, mid, 1, 1, phase, "relu%s/expand" % tag, act=act)
+    y = _mb_conv(w, "conv%s/dwise" % tag, y, mid, 3, stride, phase, "relu%s/dwise" % tag, group=mid, act=act)
     y = _mb_conv(w, "conv%s/linear" % tag, y, cout, 1, 1, phase, None)
     if stride == 1 and cin == cout:
         w.layer("block_%s" % tag, "Eltwise", [x, y], ["block_%s" % tag], "  eltwise_param { operation: SUM }")
@@ -1128,11 +1132,14 @@ def _mb2_block(w: _Writer, tag: str, x: str, cin: int, cout: int, t: int, stride
     return y
 
 
-def mobilenet_v2(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224, fillers: bool = True) -> str:
+def mobilenet_v2(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224, fillers: bool = True,
+                 relu6: bool = False) -> str:
     """MobileNet v2: the structure of the paper (no published prototxt was at hand).  conv1 3x3 / 2 (32), the seven stages (t, c, n, s) =
     (1,16,1,1), (6,24,2,2), (6,32,3,2), (6,64,4,2), (6,96,3,1), (6,160,3,2), (6,320,1,1) of inverted residuals - 17 depthwise layers,
     linear bottlenecks, 10 Eltwise sums - the 1x1 convolution conv9 to 1280, pool6 (global AVE), the 1x1 classifier fc7 and the ends of
-    mobilenet_v1.  Plain ReLU, as the common Caffe port has it (the paper's ReLU6 is not a layer of this project).
+    mobilenet_v1.  Plain ReLU by default, as the common Caffe port has it; relu6=True writes the paper's ReLU6 - `type: "ReLU6"`, the
+    MobileNet forks' layer (csrc/neuron.hip) - in the same places under the same names: behind conv1, every expand and depthwise
+    convolution and conv9, 35 layers.
 
     Names: the spelling `conv<stage>_<block>/expand`, `/dwise`, `/linear`, `block_<stage>_<block>`, pool6 and fc7 is the common Caffe
     port's; the numbering (stage 2 .. 8 of the paper's table, block 1 .. n) and conv9, `<conv>/bn`, `<conv>/scale` and the ReLUs are this
@@ -1142,12 +1149,73 @@ def mobilenet_v2(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, wid
     w = _Writer()
     w.raw('name: "MobileNet-v2"')
     _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, 1, 1)))
-    x, c = _mb_conv(w, "conv1", "data", wd(32), 3, 2, phase, "relu1"), wd(32)
+    act = "ReLU6" if relu6 else "ReLU"
+    x, c = _mb_conv(w, "conv1", "data", wd(32), 3, 2, phase, "relu1", act=act), wd(32)
     for stage, (t, width, n, s) in enumerate(MOBILENET_V2, 2):
         for b in range(n):
-            x, c = _mb2_block(w, "%d_%d" % (stage, b + 1), x, c, wd(width), t, s if b == 0 else 1, phase), wd(width)
-    x = _mb_conv(w, "conv9", x, wd(1280), 1, 1, phase, "relu9")
+            x, c = _mb2_block(w, "%d_%d" % (stage, b + 1), x, c, wd(width), t, s if b == 0 else 1, phase, act), wd(width)
+    x = _mb_conv(w, "conv9", x, wd(1280), 1, 1, phase, "relu9", act=act)
     _mb_tail(w, phase, x, classes)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
+# EfficientNet-B0 (Tan, Le: "EfficientNet: Rethinking Model Scaling for Convolutional Neural Networks"): MBConv blocks - MobileNet v2's
+# inverted residuals with a Squeeze-and-Excitation gate on the depthwise branch - and Swish (BVLC master's layer, csrc/neuron.hip).
+# ----------------------------------------------------------------------
+
+EFFICIENTNET_B0 = ((1, 16, 1, 1, 3), (6, 24, 2, 2, 3), (6, 40, 2, 2, 5), (6, 80, 3, 2, 3), (6, 112, 3, 1, 5), (6, 192, 4, 2, 5),
+                   (6, 320, 1, 1, 3))      # (expand, channels, repeats, stride, kernel) of the paper's table
+
+
+def _mbconv_block(w: _Writer, tag: str, x: str, cin: int, cout: int, t: int, stride: int, k: int, phase: str) -> str:
+    """One MBConv block: 1x1 `<tag>/expand` to t * cin (left out at t == 1) + Swish, depthwise k x k `<tag>/dwise` at `stride` + Swish, the
+    SE gate as se_resnet(form="scale") writes it - global AVE pooling `<tag>/se_pool`, InnerProduct `<tag>/se_reduce` to max(cin // 4, 1)
+    + Swish on the (N, s) blob, InnerProduct `<tag>/se_expand`, Sigmoid `<tag>/se_prob`, the two-bottom `Scale { axis: 0 }` `<tag>/se_scale`
+    on the depthwise branch -, the linear 1x1 `<tag>/project` to cout; with stride 1 and cin == cout the Eltwise sum `block_<tag>`."""
+    y, mid = x, cin * t
+    if t != 1:
+        y = _mb_conv(w, "conv%s/expand" % tag, y, mid, 1, 1, phase, "swish%s/expand" % tag, act="Swish")
+    y = _mb_conv(w, "conv%s/dwise" % tag, y, mid, k, stride, phase, "swish%s/dwise" % tag, group=mid, act="Swish")
+    se = "conv%s/se_" % tag
+    w.layer(se + "pool", "Pooling", [y], [se + "pool"], "  pooling_param { pool: AVE global_pooling: true }")
+    g = _se_fc(w, se + "reduce", se + "pool", max(cin // 4, 1), "scale")
+    w.layer("swish%s/se" % tag, "Swish", [g], [g])
+    g = _se_fc(w, se + "expand", g, mid, "scale")
+    w.layer(se + "prob", "Sigmoid", [g], [se + "prob"])
+    w.layer(se + "scale", "Scale", [y, se + "prob"], [se + "scale"], "  scale_param { axis: 0 }")
+    y = _mb_conv(w, "conv%s/project" % tag, se + "scale", cout, 1, 1, phase, None)
+    if stride == 1 and cin == cout:
+        w.layer("block_%s" % tag, "Eltwise", [x, y], ["block_%s" % tag], "  eltwise_param { operation: SUM }")
+        y = "block_%s" % tag
+    return y
+
+
+def efficientnet_b0(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224, fillers: bool = True) -> str:
+    """EfficientNet-B0: the structure of the paper in this project's layers (no published prototxt was at hand, so every name is this
+    project's own, in the spelling of models.mobilenet_v2: conv1, conv<stage>_<block>/expand, /dwise, /se_pool, /se_reduce, /se_expand,
+    /se_prob, /se_scale, /project, block_<stage>_<block>, conv9, pool6, drop6, fc7; `<conv>/bn`, `<conv>/scale`, the Swish layers
+    swish1, swish<stage>_<block>/expand, /dwise, /se and swish9).  The stem conv1 3x3 / 2 (32), the seven MBConv stages (expand,
+    channels, repeats, stride, kernel) = (1,16,1,1,3), (6,24,2,2,3), (6,40,2,2,5), (6,80,3,2,3), (6,112,3,1,5), (6,192,4,2,5),
+    (6,320,1,1,3) - 16 depthwise layers, 9 Eltwise sums -, the 1x1 convolution conv9 to 1280, pool6 (global AVE), Dropout 0.2, the
+    classifier fc7 and the ends of mobilenet_v1.  BatchNorm + Scale behind every convolution but the SE layers; `Swish` in place behind
+    conv1, every expand and depthwise convolution, every SE squeeze and conv9: 49 layers.  The squeeze width is the block's input
+    channels // 4, at least 1.
+    Not reproduced: drop-connect (stochastic depth) on the residual branches, and the release's TensorFlow "SAME" padding - at stride 2
+    it pads the far edges only; this is Caffe's symmetric pad = k // 2, so a weight file converted from the release does not give the
+    release's numbers.  Needs a NetSpec with depthwise=True and scale_gate=True (caffe.Net, the solvers and the caffe tool pass them).
+    width_div divides every convolution width, size is the image edge."""
+    _check_phase(phase)
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    w.raw('name: "EfficientNet-B0"')
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, 1, 1)))
+    x, c = _mb_conv(w, "conv1", "data", wd(32), 3, 2, phase, "swish1", act="Swish"), wd(32)
+    for stage, (t, width, n, s, k) in enumerate(EFFICIENTNET_B0, 2):
+        for b in range(n):
+            x, c = _mbconv_block(w, "%d_%d" % (stage, b + 1), x, c, wd(width), t, s if b == 0 else 1, k, phase), wd(width)
+    x = _mb_conv(w, "conv9", x, wd(1280), 1, 1, phase, "swish9", act="Swish")
+    _mb_tail(w, phase, x, classes, dropout=0.2)
     return w.text() if fillers else _strip_fillers(w.text())
 
 

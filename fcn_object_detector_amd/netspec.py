@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import proto, region, ssd
+from .lib import NEURON_MODES
 
 Shape = Tuple[int, ...]
 
@@ -364,6 +365,43 @@ def act_param_shape(l: "Layer", bots: Sequence[Shape]) -> Shape:
     return (c,)
 
 
+# the one-bottom activations of csrc/neuron.hip: no learned blob, no opt-in keyword - every NetSpec takes them
+NEURON_TYPES = ("ELU", "ReLU6", "Clip", "AbsVal", "BNLL", "Swish")
+
+
+def neuron_params(l: "Layer") -> Tuple[int, float, float]:
+    """(mode, a, b) of fcn_neuron_*: a is alpha (ELU, elu_param, default 1), beta (Swish, swish_param, default 1) or lo (Clip), b is hi
+    (Clip); ReLU6 - the MobileNet forks' type, no parameters - is Clip with 0 and 6; both are 0 where the mode ignores them.  Refused by
+    layer name: a second bottom or top, AbsVal in place (Caffe's own CHECK), ELU with a negative alpha (the sign of y would no longer
+    tell the sign of x, which the gradient reads from y), Clip without both bounds (required fields of clip_param) or with min >= max."""
+    t = l.type
+    if len(l.bottoms) != 1 or len(l.tops) != 1:
+        raise ValueError("layer %s: %s takes one bottom and has one top, got %d and %d" % (l.name, t, len(l.bottoms), len(l.tops)))
+    a = b = 0.0
+    if t == "ELU":
+        a = float(l.sub("elu_param").get("alpha", 1.0))
+        if not a >= 0.0:
+            raise NotImplementedError("layer %s: ELU with alpha %g (a negative alpha is not supported: the gradient is read from the top)"
+                                      % (l.name, a))
+    elif t == "Swish":
+        a = float(l.sub("swish_param").get("beta", 1.0))
+    elif t == "ReLU6":
+        a, b = 0.0, 6.0
+    elif t == "Clip":
+        cp = l.sub("clip_param")
+        if cp.get("min") is None or cp.get("max") is None:
+            raise ValueError("layer %s: Clip needs clip_param { min max }, both" % l.name)
+        a, b = float(cp.get("min")), float(cp.get("max"))
+        if not a < b:
+            raise ValueError("layer %s: Clip with min %g >= max %g" % (l.name, a, b))
+    elif t == "AbsVal":
+        if l.tops[0] == l.bottoms[0]:
+            raise ValueError("layer %s: AbsVal does not allow in-place computation (the gradient needs the bottom's sign)" % l.name)
+    elif t != "BNLL":
+        raise ValueError("layer %s: %s is none of %s" % (l.name, t, list(NEURON_TYPES)))
+    return NEURON_MODES[t], a, b
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 # the opt-in keywords of NetSpec (each off in a bare NetSpec; NetSpec.public turns them on): a new layer family adds its keyword here
@@ -626,6 +664,11 @@ class NetSpec:
                 if len(l.tops) > 1:
                     shapes[l.tops[1]] = (bots[0][1],)
             elif t in ("ReLU", "Sigmoid", "Power", "LRN", "Dropout", "Softmax", "TanH"):
+                shapes[l.tops[0]] = bots[0]
+            elif t in NEURON_TYPES:
+                neuron_params(l)      # (its refusals, by layer name)
+                if len(bots) != 1 or len(bots[0]) not in (2, 4):
+                    raise ValueError("layer %s: %s takes one 4-d or 2-d bottom, got %s" % (l.name, t, list(bots)))
                 shapes[l.tops[0]] = bots[0]
             elif t in ("PReLU", "Bias"):
                 if not self.activations:

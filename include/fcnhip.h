@@ -1052,6 +1052,32 @@ int  fcn_act_bwd_param_f32(const float* dy, const float* x, float* dparam, int p
                            int x_coffset, int mode, int param_shared, void* d_workspace, fcn_stream_t s);
 size_t fcn_act_workspace_bytes(int pixels, int C);
 
+/* ---- One-bottom activations without a learned parameter (Caffe ELULayer, ClipLayer - with 0 and 6 the MobileNet forks' ReLU6 -,
+ *      AbsValLayer, BNLLLayer, SwishLayer) on NHWC views (csrc/neuron.hip).  Views, groups and pad channels follow fcn_act_*: a lane owns
+ *      one 16-byte channel group of a pixel (4 floats / 8 halves), whole groups are LOADED (strides and offsets are multiples of the
+ *      group), only channels coffset .. coffset + C - 1 are ever written.  `a` is alpha (ELU), beta (Swish) or lo (Clip), `b` is hi
+ *      (Clip); both are ignored by the other modes.  Float32 arithmetic in both element types (expm1f / log1pf, not expf - 1).
+ *      Contract of all three: null operands, non-positive extents, an unknown mode, a slice outside its pixel, a < 0 for ELU, a >= b
+ *      for Clip FCN_E_ARG; a stride or offset that is no multiple of the group, x / y / keep / dy / ref / dx off 16 bytes FCN_E_ALIGN.
+ *      Every check precedes the first HIP call; all launches are capturable.  No LDS, no atomics, one writer per element: the same
+ *      call gives the same bits. ---- */
+enum { FCN_NEURON_ELU = 0, FCN_NEURON_CLIP = 1, FCN_NEURON_ABSVAL = 2, FCN_NEURON_BNLL = 3, FCN_NEURON_SWISH = 4 };
+/* ELU: y = x > 0 ? x : a * expm1(x).  Clip: y = min(max(x, a), b).  AbsVal: y = |x|.  BNLL: y = x > 0 ? x + log1p(exp(-x)) : log1p(exp(x)).
+ * Swish: y = x / (1 + exp(-a x)).  y may be x.  keep may be NULL; otherwise it is a buffer of its own, keep_cstride >= C floats per pixel
+ * (a multiple of 4) with the view's channels at 0, and receives x unchanged in the same launch (the input of an in-place Swish for its
+ * backward pass; laid out as fcn_act_fwd_f32's keep). */
+int  fcn_neuron_fwd_f32(const float* x, float* y, float* keep, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                        int keep_cstride, int mode, float a, float b, fcn_stream_t s);
+/* inference twin: x and y hold halves (groups of 8), arithmetic in float32, one rounding to half; no keep.  A last, partial group is
+ * stored as 32-bit pairs and, where C is odd, one half: the pad half that shares its word is not written. */
+int  fcn_neuron_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride, int x_coffset, int y_cstride, int y_coffset, int mode, float a,
+                        float b, fcn_stream_t s);
+/* ref is the layer's OUTPUT y for ELU (dx (+)= dy * (y > 0 ? 1 : y + a)), Clip (dy * [a < y < b], both strict) and BNLL (dy * -expm1(-y)),
+ * and its INPUT x for AbsVal (dy * sign(x), sign(0) = 0) and Swish (dy * (a y + s (1 - a y)), s = sigmoid(a x) and y = x s recomputed; in
+ * place: the kept copy).  accumulate 1 adds into dx; dx may be dy when accumulate is 0. */
+int  fcn_neuron_bwd_f32(const float* dy, const float* ref, float* dx, int pixels, int C, int dy_cstride, int dy_coffset, int ref_cstride,
+                        int ref_coffset, int dx_cstride, int dx_coffset, int mode, float a, float b, int accumulate, fcn_stream_t s);
+
 /* ---- SSD detection head (Caffe-SSD's Permute + Flatten + Concat, Normalize and DetectionOutput; csrc/ssd.hip).  Float32, inference.
  *      Common contract: every output element has exactly one writer lane (no float atomics anywhere), so a second launch on the same
  *      inputs gives the same bytes; nothing outside the named outputs and the workspace is written; every refusal is made on the host
