@@ -825,6 +825,21 @@ class BackwardPlanner:
             raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
         emit(l, gtop, gbot, acc)
 
+    def _chan_group_aligned(self, l: Layer, *views: Optional[Blob]) -> None:
+        for v in views:
+            if v is not None and (v.coffset % 4 or v.cstride % 4):
+                raise NotImplementedError("backward of %s %s: the view of %s is not 16-byte aligned" % (l.type, l.name, v.name))
+
+    def _ref_input(self, l: Layer, xb: Blob):
+        """(pointer, cstride, coffset) of the layer's input as its data gradient reads it: the copy that the forward launch kept where
+        the layer ran in place (engine._kept_input), else the bottom's view."""
+        aux = self.e.aux_dev.get(l.name)
+        if aux is not None:
+            return aux.ptr, _r4(xb.channels), 0
+        if l.tops[0] == l.bottoms[0]:
+            raise RuntimeError("%s %s ran in place and kept no copy of its input for the backward pass" % (l.type, l.name))
+        return xb.buf.ptr, xb.cstride, xb.coffset
+
     def _act(self, l: Layer, gtop: Blob, gbot: Optional[Blob], acc: int) -> None:
         """PReLU, TanH and Bias (csrc/act.hip, engine._fwd_act).  Where the layer's blob learns, the parameter-gradient launch comes first
         - in place the data launch rewrites the dY it reads - and overwrites that blob's segment of the flat gradient buffer; the data
@@ -834,15 +849,10 @@ class BackwardPlanner:
         e, lib, B, t = self.e, self.lib, self.B, l.type
         xb, yb = B[l.bottoms[0]], B[l.tops[0]]
         pix, c, mode = xb.pixels, xb.channels, L.ACT_MODES[t]
-        for v in (gtop, gbot, xb, yb):
-            if v is not None and (v.coffset % 4 or v.cstride % 4):
-                raise NotImplementedError("backward of %s %s: the view of %s is not 16-byte aligned" % (t, l.name, v.name))
+        self._chan_group_aligned(l, gtop, gbot, xb, yb)
         ref = (None, 0, 0)
         if t == "PReLU":
-            aux = e.aux_dev.get(l.name)
-            if aux is None and l.tops[0] == l.bottoms[0]:
-                raise RuntimeError("PReLU %s ran in place and kept no copy of its input for the backward pass" % l.name)
-            ref = (aux.ptr, _r4(c), 0) if aux is not None else (xb.buf.ptr, xb.cstride, xb.coffset)
+            ref = self._ref_input(l, xb)
         elif t == "TanH":
             ref = (yb.buf.ptr, yb.cstride, yb.coffset)
         param = e.params_dev[l.name][0].ptr if t == "PReLU" else None      # (the data gradient of a Bias reads no parameter)
@@ -866,18 +876,13 @@ class BackwardPlanner:
         """ELU, ReLU6, Clip, AbsVal, BNLL and Swish (csrc/neuron.hip, engine._fwd_neuron): one launch dX (+)= f'(ref) dY.  ref is the layer's
         output for ELU, ReLU6, Clip and BNLL - in place they need no copy -, its input for AbsVal (never in place) and for Swish (the copy
         the forward launch kept where the layer ran in place)."""
-        e, lib, B, t = self.e, self.lib, self.B, l.type
+        lib, B, t = self.lib, self.B, l.type
         xb, yb = B[l.bottoms[0]], B[l.tops[0]]
         pix, c = xb.pixels, xb.channels
         mode, a, b = neuron_params(l)
-        for v in (gtop, gbot, xb, yb):
-            if v.coffset % 4 or v.cstride % 4:
-                raise NotImplementedError("backward of %s %s: the view of %s is not 16-byte aligned" % (t, l.name, v.name))
+        self._chan_group_aligned(l, gtop, gbot, xb, yb)
         if t == "Swish":
-            aux = e.aux_dev.get(l.name)
-            if aux is None and l.tops[0] == l.bottoms[0]:
-                raise RuntimeError("Swish %s ran in place and kept no copy of its input for the backward pass" % l.name)
-            ref = (aux.ptr, _r4(c), 0) if aux is not None else (xb.buf.ptr, xb.cstride, xb.coffset)
+            ref = self._ref_input(l, xb)
         elif t == "AbsVal":
             ref = (xb.buf.ptr, xb.cstride, xb.coffset)
         else:

@@ -1,73 +1,24 @@
 // BatchNorm / Scale (Caffe BatchNormLayer, ScaleLayer over the channel axis) on NHWC views: the statistics, the fused
 // apply y = relu?(gamma * (x - mean) * invstd + beta) and the two backward launches (per-channel reduce, apply).
 //
-// Work layout of every kernel here: a lane owns ONE 16-byte channel group of a pixel (4 floats / 8 halves), the `tg` lanes next to
-// each other own consecutive groups of the same pixel (tg = 16 where C allows: 256 contiguous bytes per pixel row, whole 128-byte
-// runs), the 256 / tg rows of a workgroup own consecutive pixels.  Per-channel operands (mean, invstd, gamma, beta, the two backward
-// sums) are read once per thread, in its prologue.  A C that is no multiple of the group stores its last group element by
-// element: channels outside coffset .. coffset + C - 1 are never written (the convention of fcn_avepool_bwd_f32); loads of whole
-// groups stay inside the pixel because strides and offsets are multiples of the group.
+// Work layout of every kernel here: that of chan_group.h, whose tile, lane, load / store and fold helpers they use.  Per-channel
+// operands (mean, invstd, gamma, beta, the two backward sums) are read once per thread, in its prologue.
 //
-// Reductions over pixels (statistics, backward sums) never use atomics: a workgroup folds its slab of pixels (rows ascending), the
-// slabs' partial results go to the workspace, and a second launch folds them per channel in a fixed order - lane l of the channel's
-// wave folds slabs l, l + 64, ... ascending, then the lanes fold by halves (32, 16, .. 1).  The same call gives the same bits.
-// The variance is centred: a slab's M2 = sum (x - slab mean)^2 from a second pass over the slab (which the first pass left in the
-// caches), and slabs combine by Chan's parallel formula  M2 = M2a + M2b + (mean_b - mean_a)^2 * na * nb / (na + nb).
-#include "common.h"
-
-#include <hip/hip_fp16.h>
+// Reductions over pixels (statistics, backward sums) go through chan_group.h's slabs and fixed-order folds, without atomics: the same
+// call gives the same bits.  The variance is centred: a slab's M2 = sum (x - slab mean)^2 from a second pass over the slab (which the
+// first pass left in the caches), and slabs combine by Chan's parallel formula  M2 = M2a + M2b + (mean_b - mean_a)^2 * na * nb / (na + nb).
+#include "chan_group.h"
 
 namespace fcn {
 namespace {
 
-constexpr int BN_THREADS = 256;
-constexpr int BN_MAX_SLABS = 1024;
-
-struct BnTile {
-    int tg;        // channel groups side by side in a workgroup (power of two, <= 16)
-    int rows;      // pixels side by side: BN_THREADS / tg
-    int gx;        // workgroups along the channel groups
-    int slabs;     // slabs of pixels (reductions) ...
-    int slab_px;   // ... of this many pixels each (the last one shorter)
-};
-
-inline BnTile bn_tile(int pixels, int C, int epg) {
-    BnTile t;
-    const int cg = (C + epg - 1) / epg;
-    t.tg = 1;
-    while (t.tg < cg && t.tg < 16) t.tg <<= 1;
-    t.rows = BN_THREADS / t.tg;
-    t.gx = (cg + t.tg - 1) / t.tg;
-    int want = 2048 / t.gx;
-    if (want < 1) want = 1;
-    if (want > BN_MAX_SLABS) want = BN_MAX_SLABS;
-    t.slab_px = (pixels + want - 1) / want;
-    if (t.slab_px < t.rows) t.slab_px = t.rows;      // every row of a workgroup gets a pixel
-    t.slabs = (pixels + t.slab_px - 1) / t.slab_px;
-    return t;
-}
-
-inline int bn_apply_gy(const BnTile& t, int pixels) {
-    long long gy = ((long long)pixels + t.rows - 1) / t.rows;
-    long long cap = 16384 / t.gx;
-    if (cap < 1) cap = 1;
-    return (int)(gy < cap ? gy : cap);
-}
-
-__device__ inline float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-// fold of the 256 / tg rows of a workgroup, rows ascending, by the row-0 thread of each group column; the result is broadcast
-__device__ inline float4 bn_fold_rows(float4 v, float4* red, float4* bcast, int tid, int tg, int gl, int row, int rows) {
+// chan_group.h's fold of a workgroup's rows, broadcast to all of them
+__device__ inline float4 bn_fold_rows(float4 v, float4* red, float4* bcast, const CgLane& l, int tg) {
     __syncthreads();      // (red / bcast may still be read from the fold before)
-    red[tid] = v;
+    v = cg_fold_rows(v, red, l, tg);
+    if (l.row == 0) bcast[l.gl] = v;
     __syncthreads();
-    if (row == 0) {
-        float4 s = red[gl];
-        for (int r = 1; r < rows; ++r) s = f4_add(s, red[r * tg + gl]);
-        bcast[gl] = s;
-    }
-    __syncthreads();
-    return bcast[gl];
+    return bcast[l.gl];
 }
 
 // Chan et al.: (n, mean, M2) of a set joined with (nb, mb, qb) of the next one
@@ -85,38 +36,37 @@ __device__ inline void bn_chan(float& n, float& mean, float& m2, float nb, float
 
 // ---------------------------------------------------------------------------------------------------------------- statistics
 // grid (gx, slabs): workspace[(2 * slab + 0) * C4 + c] = slab mean, [(2 * slab + 1) * C4 + c] = slab M2
-__global__ __launch_bounds__(BN_THREADS) void bn_stats_slab_kernel(const float* __restrict__ x, int pixels, int C, int cstride, int coffset,
+__global__ __launch_bounds__(CG_THREADS) void bn_stats_slab_kernel(const float* __restrict__ x, int pixels, int C, int cstride, int coffset,
                                                                     int tg, int slab_px, float* __restrict__ ws, int C4) {
-    __shared__ float4 red[BN_THREADS];
+    __shared__ float4 red[CG_THREADS];
     __shared__ float4 bcast[16];
-    const int tid = threadIdx.x, gl = tid % tg, row = tid / tg, rows = BN_THREADS / tg;
-    const int g = blockIdx.x * tg + gl;
-    const bool live = 4 * g < C;
+    const CgLane l = cg_lane<4>(tg, C);
+    const bool live = l.nv > 0;
     const int p0 = blockIdx.y * slab_px;
     const int p1 = min(pixels, p0 + slab_px);
-    const float* xp = x + coffset + 4 * (live ? g : 0);
+    const float* xp = x + coffset + (live ? l.c0 : 0);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live)
-        for (int p = p0 + row; p < p1; p += rows) s = f4_add(s, *reinterpret_cast<const float4*>(xp + (size_t)p * cstride));
-    s = bn_fold_rows(s, red, bcast, tid, tg, gl, row, rows);
+        for (int p = p0 + l.row; p < p1; p += l.rows) s = cg_add(s, *reinterpret_cast<const float4*>(xp + (size_t)p * cstride));
+    s = bn_fold_rows(s, red, bcast, l, tg);
     const float inv_n = 1.0f / (float)(p1 - p0);
     const float4 mean = make_float4(s.x * inv_n, s.y * inv_n, s.z * inv_n, s.w * inv_n);
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live)
-        for (int p = p0 + row; p < p1; p += rows) {
+        for (int p = p0 + l.row; p < p1; p += l.rows) {
             const float4 v = *reinterpret_cast<const float4*>(xp + (size_t)p * cstride);
             const float dx = v.x - mean.x, dy = v.y - mean.y, dz = v.z - mean.z, dw = v.w - mean.w;
-            q = f4_add(q, make_float4(dx * dx, dy * dy, dz * dz, dw * dw));
+            q = cg_add(q, make_float4(dx * dx, dy * dy, dz * dz, dw * dw));
         }
-    q = bn_fold_rows(q, red, bcast, tid, tg, gl, row, rows);
-    if (live && row == 0) {
-        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y) * C4 + 4 * g) = mean;
-        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y + 1) * C4 + 4 * g) = q;
+    q = bn_fold_rows(q, red, bcast, l, tg);
+    if (live && l.row == 0) {
+        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y) * C4 + l.c0) = mean;
+        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y + 1) * C4 + l.c0) = q;
     }
 }
 
 // one wave per channel, four channels per workgroup
-__global__ __launch_bounds__(BN_THREADS) void bn_stats_final_kernel(const float* __restrict__ ws, int slabs, int slab_px, int pixels, int C, int C4,
+__global__ __launch_bounds__(CG_THREADS) void bn_stats_final_kernel(const float* __restrict__ ws, int slabs, int slab_px, int pixels, int C, int C4,
                                                                      float* __restrict__ b_mean, float* __restrict__ b_var,
                                                                      float* __restrict__ b_factor, float maf, float eps, float* __restrict__ save) {
     const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -167,16 +117,14 @@ __device__ inline BnOps bn_channel(int c, int C, const float* save, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------------------- apply
-__global__ __launch_bounds__(BN_THREADS) void bn_apply_f32_kernel(const float* x, float* y, float* __restrict__ xhat, int pixels, int C, int xcs, int xco,
+__global__ __launch_bounds__(CG_THREADS) void bn_apply_f32_kernel(const float* x, float* y, float* __restrict__ xhat, int pixels, int C, int xcs, int xco,
                                                                    int ycs, int yco, int hcs, const float* __restrict__ save,
                                                                    const float* __restrict__ b_mean, const float* __restrict__ b_var,
                                                                    const float* __restrict__ b_factor, float eps, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, int relu, int tg) {
-    const int tid = threadIdx.x, gl = tid % tg, row = tid / tg, rows = BN_THREADS / tg;
-    const int g = blockIdx.x * tg + gl;
-    const int c0 = 4 * g;
-    if (c0 >= C) return;
-    const int nv = min(4, C - c0);
+    const CgLane l = cg_lane<4>(tg, C);
+    if (l.nv <= 0) return;
+    const int c0 = l.c0, nv = l.nv;
     float mean[4], inv[4], ga[4], be[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -189,40 +137,29 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_f32_kernel(const float* x
             if (beta) be[j] = beta[c0 + j];
         }
     }
-    for (long long p = (long long)blockIdx.y * rows + row; p < pixels; p += (long long)gridDim.y * rows) {
-        const float4 v4 = *reinterpret_cast<const float4*>(x + (size_t)p * xcs + xco + c0);
-        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-        float h[4], o[4];
+    for (long long p = cg_first(l); p < pixels; p += cg_step(l)) {
+        float v[4], h[4], o[4];
+        cg_load(x + (size_t)p * xcs + xco + c0, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             h[j] = (v[j] - mean[j]) * inv[j];
             o[j] = ga[j] * h[j] + be[j];
             if (relu) o[j] = o[j] > 0.f ? o[j] : 0.f;
         }
-        float* yp = y + (size_t)p * ycs + yco + c0;
-        float* hp = xhat ? xhat + (size_t)p * hcs + c0 : nullptr;
-        if (nv == 4) {
-            *reinterpret_cast<float4*>(yp) = make_float4(o[0], o[1], o[2], o[3]);
-            if (hp) *reinterpret_cast<float4*>(hp) = make_float4(h[0], h[1], h[2], h[3]);
-        } else {
-            for (int j = 0; j < nv; ++j) {
-                yp[j] = o[j];
-                if (hp) hp[j] = h[j];
-            }
-        }
+        cg_store(y + (size_t)p * ycs + yco + c0, o, nv);
+        if (xhat) cg_store(xhat + (size_t)p * hcs + c0, h, nv);
     }
 }
 
-// halves in, halves out, float32 operands and arithmetic; a lane owns 8 channels
-__global__ __launch_bounds__(BN_THREADS) void bn_apply_f16_kernel(const __half* x, __half* y, int pixels, int C, int xcs, int xco, int ycs, int yco,
+// halves in, halves out, float32 operands and arithmetic; a lane owns 8 channels.  With its 32 operand registers the kernel is the one
+// here that the compiler would let grow past 64 VGPRs (74: 6 waves per SIMD); asked for 8 it needs 54, without scratch.
+__global__ __launch_bounds__(CG_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void bn_apply_f16_kernel(const __half* x, __half* y, int pixels, int C, int xcs, int xco, int ycs, int yco,
                                                                    const float* __restrict__ b_mean, const float* __restrict__ b_var,
                                                                    const float* __restrict__ b_factor, float eps, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, int relu, int tg) {
-    const int tid = threadIdx.x, gl = tid % tg, row = tid / tg, rows = BN_THREADS / tg;
-    const int g = blockIdx.x * tg + gl;
-    const int c0 = 8 * g;
-    if (c0 >= C) return;
-    const int nv = min(8, C - c0);
+    const CgLane l = cg_lane<8>(tg, C);
+    if (l.nv <= 0) return;
+    const int c0 = l.c0, nv = l.nv;
     float mean[8], inv[8], ga[8], be[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -235,89 +172,72 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_f16_kernel(const __half* 
             if (beta) be[j] = beta[c0 + j];
         }
     }
-    for (long long p = (long long)blockIdx.y * rows + row; p < pixels; p += (long long)gridDim.y * rows) {
-        union { uint4 u; __half h[8]; } in, out;
-        in.u = *reinterpret_cast<const uint4*>(x + (size_t)p * xcs + xco + c0);
+    for (long long p = cg_first(l); p < pixels; p += cg_step(l)) {
+        const CgH8 in = cg_load_h8(x + (size_t)p * xcs + xco + c0);
+        CgH8 out;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float o = ga[j] * ((__half2float(in.h[j]) - mean[j]) * inv[j]) + be[j];
             if (relu) o = o > 0.f ? o : 0.f;
             out.h[j] = __float2half_rn(o);
         }
-        __half* yp = y + (size_t)p * ycs + yco + c0;
-        if (nv == 8)
-            *reinterpret_cast<uint4*>(yp) = out.u;
-        else
-            for (int j = 0; j < nv; ++j) yp[j] = out.h[j];
+        cg_store_h8(y + (size_t)p * ycs + yco + c0, out, nv);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward
 // grid (gx, slabs): workspace[(2 * slab + 0) * C4 + c] = sum dy', [(2 * slab + 1) * C4 + c] = sum dy' * xhat over the slab
-__global__ __launch_bounds__(BN_THREADS) void bn_bwd_slab_kernel(const float* __restrict__ dy, const float* __restrict__ xhat, const float* __restrict__ y,
+__global__ __launch_bounds__(CG_THREADS) void bn_bwd_slab_kernel(const float* __restrict__ dy, const float* __restrict__ xhat, const float* __restrict__ y,
                                                                   int pixels, int C, int dcs, int dco, int hcs, int hco, int ycs, int yco, int tg,
                                                                   int slab_px, float* __restrict__ ws, int C4) {
-    __shared__ float4 red[BN_THREADS];
+    __shared__ float4 red[CG_THREADS];
     __shared__ float4 bcast[16];
-    const int tid = threadIdx.x, gl = tid % tg, row = tid / tg, rows = BN_THREADS / tg;
-    const int g = blockIdx.x * tg + gl;
-    const bool live = 4 * g < C;
-    const int c0 = 4 * (live ? g : 0);
+    const CgLane l = cg_lane<4>(tg, C);
+    const bool live = l.nv > 0;
+    const int c0 = l.c0;
     const int p0 = blockIdx.y * slab_px;
     const int p1 = min(pixels, p0 + slab_px);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f), t = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live)
-        for (int p = p0 + row; p < p1; p += rows) {
+        for (int p = p0 + l.row; p < p1; p += l.rows) {
             float4 d = *reinterpret_cast<const float4*>(dy + (size_t)p * dcs + dco + c0);
             const float4 h = *reinterpret_cast<const float4*>(xhat + (size_t)p * hcs + hco + c0);
             if (y) {
                 const float4 a = *reinterpret_cast<const float4*>(y + (size_t)p * ycs + yco + c0);
                 d.x = a.x > 0.f ? d.x : 0.f; d.y = a.y > 0.f ? d.y : 0.f; d.z = a.z > 0.f ? d.z : 0.f; d.w = a.w > 0.f ? d.w : 0.f;
             }
-            s = f4_add(s, d);
-            t = f4_add(t, make_float4(d.x * h.x, d.y * h.y, d.z * h.z, d.w * h.w));
+            s = cg_add(s, d);
+            t = cg_add(t, make_float4(d.x * h.x, d.y * h.y, d.z * h.z, d.w * h.w));
         }
-    s = bn_fold_rows(s, red, bcast, tid, tg, gl, row, rows);
-    t = bn_fold_rows(t, red, bcast, tid, tg, gl, row, rows);
-    if (live && row == 0) {
-        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y) * C4 + 4 * g) = s;
-        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y + 1) * C4 + 4 * g) = t;
+    s = bn_fold_rows(s, red, bcast, l, tg);
+    t = bn_fold_rows(t, red, bcast, l, tg);
+    if (live && l.row == 0) {
+        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y) * C4 + c0) = s;
+        *reinterpret_cast<float4*>(ws + (size_t)(2 * blockIdx.y + 1) * C4 + c0) = t;
     }
 }
 
-__global__ __launch_bounds__(BN_THREADS) void bn_bwd_final_kernel(const float* __restrict__ ws, int slabs, int C, int C4, float* __restrict__ sum_dy,
+__global__ __launch_bounds__(CG_THREADS) void bn_bwd_final_kernel(const float* __restrict__ ws, int slabs, int C, int C4, float* __restrict__ sum_dy,
                                                                    float* __restrict__ sum_dyx) {
     const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= C) return;
-    float a = 0.f, b = 0.f;
-    for (int s = lane; s < slabs; s += 64) {
-        a += ws[(size_t)(2 * s) * C4 + c];
-        b += ws[(size_t)(2 * s + 1) * C4 + c];
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float a2 = __shfl_down(a, off, 64), b2 = __shfl_down(b, off, 64);
-        if (lane < off) {
-            a += a2;
-            b += b2;
-        }
-    }
+    float a[2];
+    cg_fold_slabs(ws + c, slabs, C4, lane, a);
     if (lane == 0) {
-        sum_dy[c] = a;
-        sum_dyx[c] = b;
+        sum_dy[c] = a[0];
+        sum_dyx[c] = a[1];
     }
 }
 
-__global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const float* dy, const float* __restrict__ xhat, const float* __restrict__ y, float* dx,
+__global__ __launch_bounds__(CG_THREADS) void bn_bwd_apply_kernel(const float* dy, const float* __restrict__ xhat, const float* __restrict__ y, float* dx,
                                                                    int pixels, int C, int dcs, int dco, int hcs, int hco, int ycs, int yco, int xcs,
                                                                    int xco, const float* __restrict__ save, const float* __restrict__ b_var,
                                                                    const float* __restrict__ b_factor, float eps, const float* __restrict__ gamma,
                                                                    const float* __restrict__ sum_dy, const float* __restrict__ sum_dyx,
                                                                    int accumulate, int tg) {
-    const int tid = threadIdx.x, gl = tid % tg, row = tid / tg, rows = BN_THREADS / tg;
-    const int g = blockIdx.x * tg + gl;
-    const int c0 = 4 * g;
-    if (c0 >= C) return;
-    const int nv = min(4, C - c0);
+    const CgLane l = cg_lane<4>(tg, C);
+    if (l.nv <= 0) return;
+    const int c0 = l.c0, nv = l.nv;
     const float inv_m = 1.0f / (float)pixels;
     float k[4], a[4], b[4];
 #pragma unroll
@@ -334,39 +254,28 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const float* d
         }
     }
     const bool centred = sum_dy != nullptr;
-    for (long long p = (long long)blockIdx.y * rows + row; p < pixels; p += (long long)gridDim.y * rows) {
-        const float4 d4 = *reinterpret_cast<const float4*>(dy + (size_t)p * dcs + dco + c0);
-        float d[4] = {d4.x, d4.y, d4.z, d4.w};
+    for (long long p = cg_first(l); p < pixels; p += cg_step(l)) {
+        float d[4];
+        cg_load(dy + (size_t)p * dcs + dco + c0, d);
         if (y) {
-            const float4 m4 = *reinterpret_cast<const float4*>(y + (size_t)p * ycs + yco + c0);
-            const float m[4] = {m4.x, m4.y, m4.z, m4.w};
+            float m[4];
+            cg_load(y + (size_t)p * ycs + yco + c0, m);
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[j] = m[j] > 0.f ? d[j] : 0.f;
         }
         float o[4];
         if (centred) {
-            const float4 h4 = *reinterpret_cast<const float4*>(xhat + (size_t)p * hcs + hco + c0);
-            const float h[4] = {h4.x, h4.y, h4.z, h4.w};
+            float h[4];
+            cg_load(xhat + (size_t)p * hcs + hco + c0, h);
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = k[j] * (d[j] - a[j] - h[j] * b[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = k[j] * d[j];
         }
-        float* xp = dx + (size_t)p * xcs + xco + c0;
-        if (nv == 4) {
-            if (accumulate) {
-                const float4 old = *reinterpret_cast<const float4*>(xp);
-                o[0] += old.x; o[1] += old.y; o[2] += old.z; o[3] += old.w;
-            }
-            *reinterpret_cast<float4*>(xp) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int j = 0; j < nv; ++j) xp[j] = accumulate ? xp[j] + o[j] : o[j];
-        }
+        cg_store_acc(dx + (size_t)p * xcs + xco + c0, o, nv, accumulate);
     }
 }
-
-inline bool bn_view_ok(int C, int cstride, int coffset, int epg) { return coffset >= 0 && cstride >= coffset + C && cstride % epg == 0 && coffset % epg == 0; }
 
 }  // namespace
 }  // namespace fcn
@@ -375,7 +284,7 @@ using namespace fcn;
 
 size_t fcn_batchnorm_workspace_bytes(int pixels, int C) {
     if (pixels <= 0 || C <= 0) return 0;
-    const BnTile t = bn_tile(pixels, C, 4);
+    const CgTile t = cg_tile(1, pixels, C, 4);
     return (size_t)t.slabs * 2 * ((C + 3) / 4 * 4) * sizeof(float);
 }
 
@@ -385,17 +294,17 @@ int fcn_batchnorm_stats_f32(const float* x, int pixels, int C, int x_cstride, in
     FCN_REQUIRE(pixels > 0 && C > 0, FCN_E_ARG, "batchnorm_stats: non-positive extent");
     FCN_REQUIRE((blob_mean != nullptr) == (blob_var != nullptr) && (blob_mean != nullptr) == (blob_factor != nullptr), FCN_E_ARG,
                 "batchnorm_stats: the three blobs come together or not at all");
-    FCN_REQUIRE(x_coffset >= 0 && x_cstride >= x_coffset + C, FCN_E_ARG, "batchnorm_stats: channel slice out of range");
-    FCN_REQUIRE(bn_view_ok(C, x_cstride, x_coffset, 4), FCN_E_ALIGN, "batchnorm_stats: channel stride and offset must be multiples of 4 floats");
-    FCN_REQUIRE((((uintptr_t)x | (uintptr_t)d_workspace) & 15) == 0 && ((uintptr_t)save & 3) == 0, FCN_E_ALIGN,
+    FCN_REQUIRE(cg_view_in(C, x_cstride, x_coffset), FCN_E_ARG, "batchnorm_stats: channel slice out of range");
+    FCN_REQUIRE(cg_view_ok(x_cstride, x_coffset, 4), FCN_E_ALIGN, "batchnorm_stats: channel stride and offset must be multiples of 4 floats");
+    FCN_REQUIRE(cg_aligned16(x, d_workspace) && ((uintptr_t)save & 3) == 0, FCN_E_ALIGN,
                 "batchnorm_stats: x and the workspace must be 16-byte aligned");
-    const BnTile t = bn_tile(pixels, C, 4);
+    const CgTile t = cg_tile(1, pixels, C, 4);
     const int C4 = (C + 3) / 4 * 4;
     float* ws = static_cast<float*>(d_workspace);
-    hipLaunchKernelGGL(bn_stats_slab_kernel, dim3(t.gx, t.slabs), dim3(BN_THREADS), 0, as_stream(s), x, pixels, C, x_cstride, x_coffset, t.tg,
+    hipLaunchKernelGGL(bn_stats_slab_kernel, dim3(t.gx, t.slabs), dim3(CG_THREADS), 0, as_stream(s), x, pixels, C, x_cstride, x_coffset, t.tg,
                        t.slab_px, ws, C4);
     FCN_LAUNCH_CHECK("bn_stats_slab_kernel");
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + 3) / 4), dim3(BN_THREADS), 0, as_stream(s), ws, t.slabs, t.slab_px, pixels, C, C4, blob_mean,
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + 3) / 4), dim3(CG_THREADS), 0, as_stream(s), ws, t.slabs, t.slab_px, pixels, C, C4, blob_mean,
                        blob_var, blob_factor, moving_average_fraction, eps, save);
     FCN_LAUNCH_CHECK("bn_stats_final_kernel");
     return 0;
@@ -409,13 +318,13 @@ int fcn_batchnorm_apply_f32(const float* x, float* y, float* xhat, int pixels, i
     FCN_REQUIRE((blob_mean != nullptr) == (blob_var != nullptr) && (blob_mean != nullptr) == (blob_factor != nullptr), FCN_E_ARG,
                 "batchnorm_apply: the three blobs come together or not at all");
     FCN_REQUIRE(!(save && blob_mean), FCN_E_ARG, "batchnorm_apply: statistics from the save area or from the blobs, not both");
-    FCN_REQUIRE(x_coffset >= 0 && y_coffset >= 0 && x_cstride >= x_coffset + C && y_cstride >= y_coffset + C && (!xhat || xhat_cstride >= C),
-                FCN_E_ARG, "batchnorm_apply: channel slice out of range");
-    FCN_REQUIRE(bn_view_ok(C, x_cstride, x_coffset, 4) && bn_view_ok(C, y_cstride, y_coffset, 4) && (!xhat || xhat_cstride % 4 == 0), FCN_E_ALIGN,
+    FCN_REQUIRE(cg_view_in(C, x_cstride, x_coffset) && cg_view_in(C, y_cstride, y_coffset) && (!xhat || xhat_cstride >= C), FCN_E_ARG,
+                "batchnorm_apply: channel slice out of range");
+    FCN_REQUIRE(cg_view_ok(x_cstride, x_coffset, 4) && cg_view_ok(y_cstride, y_coffset, 4) && (!xhat || xhat_cstride % 4 == 0), FCN_E_ALIGN,
                 "batchnorm_apply: channel strides and offsets must be multiples of 4 floats");
-    FCN_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)xhat) & 15) == 0, FCN_E_ALIGN, "batchnorm_apply: x, y and xhat must be 16-byte aligned");
-    const BnTile t = bn_tile(pixels, C, 4);
-    hipLaunchKernelGGL(bn_apply_f32_kernel, dim3(t.gx, bn_apply_gy(t, pixels)), dim3(BN_THREADS), 0, as_stream(s), x, y, xhat, pixels, C, x_cstride,
+    FCN_REQUIRE(cg_aligned16(x, y, xhat), FCN_E_ALIGN, "batchnorm_apply: x, y and xhat must be 16-byte aligned");
+    const CgTile t = cg_tile(1, pixels, C, 4);
+    hipLaunchKernelGGL(bn_apply_f32_kernel, dim3(t.gx, t.gy), dim3(CG_THREADS), 0, as_stream(s), x, y, xhat, pixels, C, x_cstride,
                        x_coffset, y_cstride, y_coffset, xhat_cstride, save, blob_mean, blob_var, blob_factor, eps, gamma, beta, relu, t.tg);
     FCN_LAUNCH_CHECK("bn_apply_f32_kernel");
     return 0;
@@ -428,13 +337,13 @@ int fcn_batchnorm_apply_f16(const void* x, void* y, int pixels, int C, int x_cst
     FCN_REQUIRE(pixels > 0 && C > 0, FCN_E_ARG, "batchnorm_apply_f16: non-positive extent");
     FCN_REQUIRE((blob_mean != nullptr) == (blob_var != nullptr) && (blob_mean != nullptr) == (blob_factor != nullptr), FCN_E_ARG,
                 "batchnorm_apply_f16: the three blobs come together or not at all");
-    FCN_REQUIRE(x_coffset >= 0 && y_coffset >= 0 && x_cstride >= x_coffset + C && y_cstride >= y_coffset + C, FCN_E_ARG,
+    FCN_REQUIRE(cg_view_in(C, x_cstride, x_coffset) && cg_view_in(C, y_cstride, y_coffset), FCN_E_ARG,
                 "batchnorm_apply_f16: channel slice out of range");
-    FCN_REQUIRE(bn_view_ok(C, x_cstride, x_coffset, 8) && bn_view_ok(C, y_cstride, y_coffset, 8), FCN_E_ALIGN,
+    FCN_REQUIRE(cg_view_ok(x_cstride, x_coffset, 8) && cg_view_ok(y_cstride, y_coffset, 8), FCN_E_ALIGN,
                 "batchnorm_apply_f16: channel strides and offsets must be multiples of 8 halves");
-    FCN_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, FCN_E_ALIGN, "batchnorm_apply_f16: x and y must be 16-byte aligned");
-    const BnTile t = bn_tile(pixels, C, 8);
-    hipLaunchKernelGGL(bn_apply_f16_kernel, dim3(t.gx, bn_apply_gy(t, pixels)), dim3(BN_THREADS), 0, as_stream(s), static_cast<const __half*>(x),
+    FCN_REQUIRE(cg_aligned16(x, y), FCN_E_ALIGN, "batchnorm_apply_f16: x and y must be 16-byte aligned");
+    const CgTile t = cg_tile(1, pixels, C, 8);
+    hipLaunchKernelGGL(bn_apply_f16_kernel, dim3(t.gx, t.gy), dim3(CG_THREADS), 0, as_stream(s), static_cast<const __half*>(x),
                        static_cast<__half*>(y), pixels, C, x_cstride, x_coffset, y_cstride, y_coffset, blob_mean, blob_var, blob_factor, eps, gamma,
                        beta, relu, t.tg);
     FCN_LAUNCH_CHECK("bn_apply_f16_kernel");
@@ -446,22 +355,21 @@ int fcn_batchnorm_bwd_reduce_f32(const float* dy, const float* xhat, const float
                                  void* d_workspace, fcn_stream_t s) {
     FCN_REQUIRE(dy && xhat && sum_dy && sum_dyx && d_workspace, FCN_E_ARG, "batchnorm_bwd_reduce: null pointer");
     FCN_REQUIRE(pixels > 0 && C > 0, FCN_E_ARG, "batchnorm_bwd_reduce: non-positive extent");
-    FCN_REQUIRE(dy_coffset >= 0 && xhat_coffset >= 0 && dy_cstride >= dy_coffset + C && xhat_cstride >= xhat_coffset + C &&
-                    (!relu_y || (y_coffset >= 0 && y_cstride >= y_coffset + C)),
+    FCN_REQUIRE(cg_view_in(C, dy_cstride, dy_coffset) && cg_view_in(C, xhat_cstride, xhat_coffset) &&
+                    (!relu_y || cg_view_in(C, y_cstride, y_coffset)),
                 FCN_E_ARG, "batchnorm_bwd_reduce: channel slice out of range");
-    FCN_REQUIRE(bn_view_ok(C, dy_cstride, dy_coffset, 4) && bn_view_ok(C, xhat_cstride, xhat_coffset, 4) &&
-                    (!relu_y || bn_view_ok(C, y_cstride, y_coffset, 4)),
+    FCN_REQUIRE(cg_view_ok(dy_cstride, dy_coffset, 4) && cg_view_ok(xhat_cstride, xhat_coffset, 4) &&
+                    (!relu_y || cg_view_ok(y_cstride, y_coffset, 4)),
                 FCN_E_ALIGN, "batchnorm_bwd_reduce: channel strides and offsets must be multiples of 4 floats");
-    FCN_REQUIRE((((uintptr_t)dy | (uintptr_t)xhat | (uintptr_t)relu_y | (uintptr_t)d_workspace) & 15) == 0 &&
-                    (((uintptr_t)sum_dy | (uintptr_t)sum_dyx) & 3) == 0,
+    FCN_REQUIRE(cg_aligned16(dy, xhat, relu_y, d_workspace) && (((uintptr_t)sum_dy | (uintptr_t)sum_dyx) & 3) == 0,
                 FCN_E_ALIGN, "batchnorm_bwd_reduce: dy, xhat, relu_y and the workspace must be 16-byte aligned");
-    const BnTile t = bn_tile(pixels, C, 4);
+    const CgTile t = cg_tile(1, pixels, C, 4);
     const int C4 = (C + 3) / 4 * 4;
     float* ws = static_cast<float*>(d_workspace);
-    hipLaunchKernelGGL(bn_bwd_slab_kernel, dim3(t.gx, t.slabs), dim3(BN_THREADS), 0, as_stream(s), dy, xhat, relu_y, pixels, C, dy_cstride, dy_coffset,
+    hipLaunchKernelGGL(bn_bwd_slab_kernel, dim3(t.gx, t.slabs), dim3(CG_THREADS), 0, as_stream(s), dy, xhat, relu_y, pixels, C, dy_cstride, dy_coffset,
                        xhat_cstride, xhat_coffset, y_cstride, y_coffset, t.tg, t.slab_px, ws, C4);
     FCN_LAUNCH_CHECK("bn_bwd_slab_kernel");
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 3) / 4), dim3(BN_THREADS), 0, as_stream(s), ws, t.slabs, C, C4, sum_dy, sum_dyx);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 3) / 4), dim3(CG_THREADS), 0, as_stream(s), ws, t.slabs, C, C4, sum_dy, sum_dyx);
     FCN_LAUNCH_CHECK("bn_bwd_final_kernel");
     return 0;
 }
@@ -476,16 +384,16 @@ int fcn_batchnorm_bwd_apply_f32(const float* dy, const float* xhat, const float*
                 "batchnorm_bwd_apply: the two sums come together, and with them xhat");
     FCN_REQUIRE((blob_var != nullptr) == (blob_factor != nullptr) && !(save && blob_var), FCN_E_ARG,
                 "batchnorm_bwd_apply: invstd from the save area or from the variance and factor blobs, not both");
-    FCN_REQUIRE(dy_coffset >= 0 && dx_coffset >= 0 && dy_cstride >= dy_coffset + C && dx_cstride >= dx_coffset + C &&
-                    (!xhat || (xhat_coffset >= 0 && xhat_cstride >= xhat_coffset + C)) && (!relu_y || (y_coffset >= 0 && y_cstride >= y_coffset + C)),
+    FCN_REQUIRE(cg_view_in(C, dy_cstride, dy_coffset) && cg_view_in(C, dx_cstride, dx_coffset) &&
+                    (!xhat || cg_view_in(C, xhat_cstride, xhat_coffset)) && (!relu_y || cg_view_in(C, y_cstride, y_coffset)),
                 FCN_E_ARG, "batchnorm_bwd_apply: channel slice out of range");
-    FCN_REQUIRE(bn_view_ok(C, dy_cstride, dy_coffset, 4) && bn_view_ok(C, dx_cstride, dx_coffset, 4) &&
-                    (!xhat || bn_view_ok(C, xhat_cstride, xhat_coffset, 4)) && (!relu_y || bn_view_ok(C, y_cstride, y_coffset, 4)),
+    FCN_REQUIRE(cg_view_ok(dy_cstride, dy_coffset, 4) && cg_view_ok(dx_cstride, dx_coffset, 4) &&
+                    (!xhat || cg_view_ok(xhat_cstride, xhat_coffset, 4)) && (!relu_y || cg_view_ok(y_cstride, y_coffset, 4)),
                 FCN_E_ALIGN, "batchnorm_bwd_apply: channel strides and offsets must be multiples of 4 floats");
-    FCN_REQUIRE((((uintptr_t)dy | (uintptr_t)xhat | (uintptr_t)relu_y | (uintptr_t)dx) & 15) == 0, FCN_E_ALIGN,
+    FCN_REQUIRE(cg_aligned16(dy, xhat, relu_y, dx), FCN_E_ALIGN,
                 "batchnorm_bwd_apply: dy, xhat, relu_y and dx must be 16-byte aligned");
-    const BnTile t = bn_tile(pixels, C, 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(t.gx, bn_apply_gy(t, pixels)), dim3(BN_THREADS), 0, as_stream(s), dy, xhat, relu_y, dx, pixels, C,
+    const CgTile t = cg_tile(1, pixels, C, 4);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(t.gx, t.gy), dim3(CG_THREADS), 0, as_stream(s), dy, xhat, relu_y, dx, pixels, C,
                        dy_cstride, dy_coffset, xhat_cstride, xhat_coffset, y_cstride, y_coffset, dx_cstride, dx_coffset, save, blob_var, blob_factor,
                        eps, gamma, sum_dy, sum_dyx, accumulate, t.tg);
     FCN_LAUNCH_CHECK("bn_bwd_apply_kernel");

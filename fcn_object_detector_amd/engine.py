@@ -1747,11 +1747,9 @@ class Engine:
             fn = lambda st: L.check(lib.fcn_power_fwd_f32(xb.ptr, yb.ptr, count, pw, sc, sh, st))
         return [Op(t.lower(), l.name, fn, 0.0, 8.0 * count)]
 
-    def _fwd_act(self, l: Layer, halves: List[str]) -> List[Op]:
-        """PReLU, TanH and Bias as one launch of csrc/act.hip, on whole buffers and on 16-byte-aligned channel windows alike (the kernel
-        keeps to its window), floats or halves with float32 parameters.  A TRAIN engine keeps the input of an in-place PReLU to which a
-        gradient comes (its bottom needs one, or its slopes learn) in aux_dev - Caffe's bottom_memory_ - filled by the same launch."""
-        lib, t = L.load(), l.type
+    def _chan_group_views(self, l: Layer):
+        """(xb, yb, pixels, channels) of a one-bottom layer that runs on csrc/chan_group.h's layout (_fwd_act, _fwd_neuron), or the refusal."""
+        t = l.type
         xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
         if xb.nchw is None or xb.shape != yb.shape:
             raise NotImplementedError("%s %s on a blob that is neither 4-d nor 2-d" % (t, l.name))
@@ -1760,17 +1758,30 @@ class Engine:
         grp = 16 // xb.esize
         if xb.coffset % grp or yb.coffset % grp or xb.cstride % grp or yb.cstride % grp:
             raise NotImplementedError("%s %s: a channel window that is not 16-byte aligned" % (t, l.name))
-        pix, c, mode = xb.pixels, xb.channels, L.ACT_MODES[t]
+        return xb, yb, xb.pixels, xb.channels
+
+    def _kept_input(self, l: Layer, pix: int, c: int) -> Optional[int]:
+        """Pointer of the aux_dev copy (pix x round4(c) floats) that the forward launch of an in-place layer fills with its input - Caffe's
+        bottom_memory_ - where this is a TRAIN engine and a gradient comes to the layer; None where nothing is kept."""
+        need = getattr(self, "need_grad", None)
+        if self.spec.phase != "TRAIN" or l.tops[0] != l.bottoms[0] or not (need is None or l.tops[0] in need):
+            return None
+        keep = self.aux_dev[l.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
+        return keep.ptr
+
+    def _fwd_act(self, l: Layer, halves: List[str]) -> List[Op]:
+        """PReLU, TanH and Bias as one launch of csrc/act.hip, on whole buffers and on 16-byte-aligned channel windows alike (the kernel
+        keeps to its window), floats or halves with float32 parameters.  A TRAIN engine keeps the input of an in-place PReLU to which a
+        gradient comes (its bottom needs one, or its slopes learn) in aux_dev, filled by the same launch."""
+        lib, t = L.load(), l.type
+        xb, yb, pix, c = self._chan_group_views(l)
+        mode = L.ACT_MODES[t]
         param = self.params_dev[l.name][0].ptr if t != "TanH" else None
         shared = int(t == "PReLU" and tuple(self.spec.param_shapes[l.name][0]) == ())
         if xb.esize == 2:
             return [Op("act", l.name, lambda st: L.check(lib.fcn_act_fwd_f16(
                 xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, mode, param, shared, st)), 1.0 * pix * c, 4.0 * pix * c)]
-        keep = None
-        need = getattr(self, "need_grad", None)
-        if self.spec.phase == "TRAIN" and t == "PReLU" and l.tops[0] == l.bottoms[0] and (need is None or l.tops[0] in need):
-            keep = self.aux_dev[l.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
-        kp = keep.ptr if keep is not None else None
+        kp = self._kept_input(l, pix, c) if t == "PReLU" else None
         return [Op("act", l.name, lambda st: L.check(lib.fcn_act_fwd_f32(
             xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, param, shared, st)),
             1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]
@@ -1781,24 +1792,12 @@ class Engine:
         gradient comes in aux_dev, filled by the same launch - what _fwd_act does for an in-place PReLU; the other in-place layers read
         their gradient from the top and keep nothing."""
         lib, t = L.load(), l.type
-        xb, yb = self.blobs[l.bottoms[0]], self.blobs[l.tops[0]]
-        if xb.nchw is None or xb.shape != yb.shape:
-            raise NotImplementedError("%s %s on a blob that is neither 4-d nor 2-d" % (t, l.name))
-        if xb.esize != yb.esize:
-            raise NotImplementedError("f16 engine: %s %s between half and float32 blobs" % (t, l.name))
-        grp = 16 // xb.esize
-        if xb.coffset % grp or yb.coffset % grp or xb.cstride % grp or yb.cstride % grp:
-            raise NotImplementedError("%s %s: a channel window that is not 16-byte aligned" % (t, l.name))
-        pix, c = xb.pixels, xb.channels
+        xb, yb, pix, c = self._chan_group_views(l)
         mode, a, b = neuron_params(l)
         if xb.esize == 2:
             return [Op("neuron", l.name, lambda st: L.check(lib.fcn_neuron_fwd_f16(
                 xb.buf.ptr, yb.buf.ptr, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, mode, a, b, st)), 1.0 * pix * c, 4.0 * pix * c)]
-        keep = None
-        need = getattr(self, "need_grad", None)
-        if self.spec.phase == "TRAIN" and t == "Swish" and l.tops[0] == l.bottoms[0] and (need is None or l.tops[0] in need):
-            keep = self.aux_dev[l.name] = DeviceBuffer(pix * _r4(c) * 4, zero=True)
-        kp = keep.ptr if keep is not None else None
+        kp = self._kept_input(l, pix, c) if t == "Swish" else None
         return [Op("neuron", l.name, lambda st: L.check(lib.fcn_neuron_fwd_f32(
             xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, a, b, st)),
             1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]

@@ -8,14 +8,19 @@ a slab is never shorter than those rows (it grows only past 2048 workgroups) - f
 32 at C = 20, 16 at C = 68.  One count on each side of that boundary at every C but 8 (128 | 129, 64 | 65, 32 | 33, 16 | 17), and two
 counts that give more than 64 slabs - the second launch strides the slabs by 64, so slab 64 is the first that a lane adds to one it
 already holds: 1041 pixels at C = 68 (66 slabs) and 4161 at C = 10 (66 slabs).
+ODD_C, for the half-float forward alone: the odd widths of tests/neuron_cases.py at their pixel counts, at which the store of a partial
+group of halves writes a single half beside a pad half of the same 32-bit word.
 
 Operands: x carries EXACT zeros (every fourth element or so: where `x > 0` and `x >= 0` part ways) ; the slopes have both signs and a
 zero, the shared slope is negative (a negative slope makes sign(y) differ from sign(x): a data gradient that looked at y instead of
 the kept x is then wrong); dy and the pre-filled gradients are standard normal."""
 import numpy as np
 
+import neuron_cases
+
 CASES = [(1, 6), (5, 8), (49, 10), (300, 20), (300, 68), (49, 68), (5, 20), (1, 10), (300, 6), (49, 8), (300, 10),
          (128, 6), (129, 6), (64, 10), (65, 10), (32, 20), (33, 20), (16, 68), (17, 68), (1041, 68), (4161, 10)]
+ODD_C = list(neuron_cases.ODD_C)
 SHARED_SLOPE = -0.35
 
 

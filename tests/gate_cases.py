@@ -5,12 +5,17 @@ path), 8 (whole groups), 20 (a partial last group behind whole ones) and 68 (mor
 Slab boundary of the gate gradient, read from gate_tile() of csrc/gate.hip: a workgroup's 256 lanes stand tg = min(16, next power of
 two >= ceil(C / 4)) channel groups wide and 256 / tg pixels high, and a slab is never shorter than those rows (it grows only past 2048
 workgroups) - first_slab(C) pixels: 128 at C = 6 and 8, 32 at C = 20, 16 at C = 68.  So 300 pixels cross a slab boundary at every C
-(3, 3, 10 and 19 slabs), 49 pixels at C = 20 and 68 (2 and 4 slabs), and 1 and 5 pixels never do."""
+(3, 3, 10 and 19 slabs), 49 pixels at C = 20 and 68 (2 and 4 slabs), and 1 and 5 pixels never do.
+ODD_SHAPES, for the half-float forward alone: N = 2 and the odd widths of tests/neuron_cases.py at their pixel counts, at which the store
+of a partial group of halves writes a single half beside a pad half of the same 32-bit word."""
 import numpy as np
+
+import neuron_cases
 
 # (N, H, W, C)
 SHAPES = [(2, 1, 1, 6), (3, 1, 5, 8), (2, 7, 7, 20), (3, 15, 20, 68), (2, 15, 20, 6), (3, 7, 7, 68), (2, 1, 5, 20), (3, 1, 1, 8), (2, 15, 20, 20),
           (3, 7, 7, 8), (2, 15, 20, 8)]
+ODD_SHAPES = [(2, 1, 5, c) if p == 5 else (2, 7, 7, c) for p, c in neuron_cases.ODD_C]
 
 
 def first_slab(c: int) -> int:

@@ -66,7 +66,7 @@ def test_tanh_and_bias_are_what_torch_and_autograd_compute(case):
     assert R.rel_err(R.bwd_param(R.BIAS, dy), tb.grad.numpy()) < 1e-12
 
 
-@CASES
+@pytest.mark.parametrize("case", AC.CASES + AC.ODD_C, ids=AC.case_id)
 def test_the_parameter_of_the_neighbouring_channel_is_caught(case):
     x, a, b, dy, _dx0 = AC.operands(case)
     assert R.rel_err(R.fwd(R.PRELU, x, np.roll(a, 1)), R.fwd(R.PRELU, x, a)) > FAR
@@ -76,7 +76,7 @@ def test_the_parameter_of_the_neighbouring_channel_is_caught(case):
     assert R.rel_err(np.roll(R.bwd_param(R.BIAS, dy), 1), R.bwd_param(R.BIAS, dy)) > FAR
 
 
-@CASES
+@pytest.mark.parametrize("case", AC.CASES + AC.ODD_C, ids=AC.case_id)
 def test_the_shared_slope_taken_per_channel_is_caught(case):
     x, a, _b, dy, _dx0 = AC.operands(case)
     one = np.array([AC.SHARED_SLOPE], np.float32)
@@ -138,7 +138,7 @@ def half_magnitude(mode, x64, p64, shared):
     return np.abs(R.fwd(mode, x64, p64, shared)) if mode == R.PRELU else None
 
 
-@CASES
+@pytest.mark.parametrize("case", AC.CASES + AC.ODD_C, ids=AC.case_id)
 def test_the_half_float_allowances_admit_a_float32_evaluation(case):
     x, a, b, _dy, _dx0 = AC.operands(case)
     xh = x.astype(np.float16)
@@ -163,5 +163,6 @@ def test_the_cases_cover_what_they_claim():
         assert (AC.first_slab(c), c) in AC.CASES and (AC.first_slab(c) + 1, c) in AC.CASES
         assert AC.slabs((AC.first_slab(c), c)) == 1 and AC.slabs((AC.first_slab(c) + 1, c)) == 2
     assert sorted(AC.slabs(c) for c in AC.CASES if AC.slabs(c) > 64) == [66, 66]
+    assert sorted(c for _p, c in AC.ODD_C) == [3, 5, 7, 13] and not set(AC.ODD_C) & set(AC.CASES)
     x, a, _b, _dy, _dx0 = AC.operands(AC.CASES[3])
     assert (a < 0).any() and (a > 0).any() and (a == 0).any() and AC.SHARED_SLOPE < 0 and 0.15 < (x == 0).mean() < 0.35

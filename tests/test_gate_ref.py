@@ -36,7 +36,7 @@ def test_the_reference_is_what_autograd_computes(shape, relu):
     assert R.rel_err(R.gate_bwd_gate(dym, x, dg0), tg.grad.numpy() + dg0) < 1e-13
 
 
-@pytest.mark.parametrize("shape", GC.SHAPES)
+@pytest.mark.parametrize("shape", GC.SHAPES + GC.ODD_SHAPES)
 def test_the_gate_of_image_0_for_every_image_is_caught(shape):
     x, g, r, dy, _dx0, _dg0 = GC.operands(shape)
     wrong = np.broadcast_to(g[:1], g.shape)
@@ -60,3 +60,4 @@ def test_the_cases_cover_what_they_claim():
     assert [GC.first_slab(c) for c in (6, 8, 20, 68)] == [128, 128, 32, 16]
     crossing = [s for s in GC.SHAPES if GC.crosses_a_slab(s)]
     assert {s[3] for s in crossing} == {6, 8, 20, 68} and {s[1] * s[2] for s in crossing} == {49, 300}
+    assert [(s[0], s[1] * s[2], s[3]) for s in GC.ODD_SHAPES] == [(2, 5, 5), (2, 49, 13), (2, 5, 7), (2, 49, 3)]

@@ -6,7 +6,7 @@ After each launch the result is free of poison, the channels outside the window 
 hold it bit for bit, the inputs are unchanged and leaving the test checks every red zone.
 Cases (tests/act_cases.py, which says where the slab boundaries of the parameter gradient lie; tests/test_act_ref.py shows that each
 case can fail): 1, 5, 49, 300 pixels, one count on each side of the slab boundary at C = 6, 10, 20, 68 and two counts of more than 64
-slabs; C = 6, 8, 10, 20, 68; x a window at channel 4 of wider float pixels / 8 of wider half pixels, y a buffer of its own or x itself;
+slabs; C = 6, 8, 10, 20, 68, and in the half-float forward the odd C = 3, 5, 7, 13; x a window at channel 4 of wider float pixels / 8 of wider half pixels, y a buffer of its own or x itself;
 keep present with keep_cstride above round4(C); the slopes per channel (both signs and zero) and shared (negative); accumulate 0 and 1
 into pre-filled gradients; dx aliased to dy.
 float32 results: rel_err < 1e-4 against float64, the project's bound.  Half results, against float64 on the operands rounded to half:
@@ -108,6 +108,13 @@ def test_forward(g, case, half):
                 kept = kd.read((1, 1, p, kcs))
                 assert nchw(kept, c, 0).tobytes() == x.tobytes(), "%s: keep is not x, bit for bit" % what
                 assert slice_untouched(kept, 0, c), "%s: channels of keep behind C were written" % what
+
+
+@pytest.mark.parametrize("case", AC.ODD_C, ids=AC.case_id)
+def test_forward_half_floats_at_odd_widths(g, case):
+    """The last half of a window shares its 32-bit word with a pad channel: every mode and form of test_forward, x a window at channel 8."""
+    assert case[1] % 2 == 1 and windows(case[1], True)[0][1] == 8
+    test_forward(g, case, True)
 
 
 @CASES

@@ -208,13 +208,16 @@ def test_apply(g, shape, sl, mode, scaled):
 
 # halves: multiples of 8 and one C that is not; a window with poisoned channels on both sides
 HALF_SLICES = [(8, 24, 8, 16, 8), (16, 32, 8, 16, 0), (12, 32, 8, 24, 8), (64, 64, 0, 80, 8)]
+# odd C (the last half of the window shares its 32-bit word with a pad channel), at the pixel counts of tests/neuron_cases.py's ODD_C:
+# (n, h, w) and a slice each
+HALF_ODD = [((1, 1, 5), (5, 24, 8, 16, 8)), ((1, 7, 7), (13, 32, 8, 24, 8)), ((1, 1, 5), (7, 24, 8, 16, 0)), ((1, 7, 7), (3, 24, 8, 16, 8))]
 
 
 @pytest.mark.parametrize("mode", ["blobs", "factor0", "none"])
 @pytest.mark.parametrize("c,csx,cox,csy,coy", HALF_SLICES)
-def test_apply_half_floats(g, c, csx, cox, csy, coy, mode):
+def test_apply_half_floats(g, c, csx, cox, csy, coy, mode, shape=(2, 5, 7)):
     rng = np.random.default_rng(34)
-    n, h, w = 2, 5, 7
+    n, h, w = shape
     eps = 1e-3
     x, gamma, beta = apply_case(rng, (n, h, w), c)
     xh = x.astype(np.float16)
@@ -240,6 +243,13 @@ def test_apply_half_floats(g, c, csx, cox, csy, coy, mode):
             got = nchw(runs[0], c, yco)
             assert poison_free(got) and slice_untouched(runs[0], yco, c)
             within(got, want, allow, "apply f16 %s relu=%d inplace=%d c%d" % (mode, relu, inplace, c))
+
+
+@pytest.mark.parametrize("mode", ["blobs", "factor0", "none"])
+@pytest.mark.parametrize("shape,sl", HALF_ODD)
+def test_apply_half_floats_at_odd_widths(g, shape, sl, mode):
+    assert sl[0] % 2 == 1
+    test_apply_half_floats(g, *sl, mode, shape=shape)
 
 
 def bwd_case(rng, shape, c, relu):

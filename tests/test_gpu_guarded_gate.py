@@ -5,7 +5,7 @@ gate row behind its C values and every output start as the poison.  After each l
 outside the window (the pad channels of y / dx: only coffset .. coffset + C - 1 may be written) and the gate rows' tails still hold it
 bit for bit, the inputs are unchanged and leaving the test checks every red zone.
 Cases (tests/gate_cases.py, which also says which of them cross the slab boundary of the gate gradient - 300 pixels at every C, 49 at
-C = 20 and 68 - and tests/test_gate_ref.py shows that each can fail): N = 2, 3; 1, 5, 49, 300 pixels per image; C = 6, 8, 20, 68; x a
+C = 20 and 68 - and tests/test_gate_ref.py shows that each can fail): N = 2, 3; 1, 5, 49, 300 pixels per image; C = 6, 8, 20, 68, and in the half-float forward (N = 2) the odd C = 3, 5, 7, 13; x a
 window at channel 4 of 12-float pixels / 8 of 24-half pixels (wider where C needs it); g_rstride = C + 3; r absent or present with a
 stride of its own; y a buffer of its own, x, or r; relu on and off; accumulate 0 and 1 into pre-filled gradients.
 float32 results: rel_err < 1e-4 against float64, the project's bound.  Half results: against float64 on the operands rounded to half,
@@ -96,6 +96,13 @@ def test_forward(g, shape, half):
                 check_f32(y, y64, what)
             assert slice_untouched(full, co, c), "%s: channels of y outside the window were written" % what
             assert gd.unchanged() and (yd is xd or xd.unchanged()) and (rd is None or yd is rd or rd.unchanged()), "%s: an input was written" % what
+
+
+@pytest.mark.parametrize("shape", GC.ODD_SHAPES, ids=lambda s: "n%d_%dx%d_c%d" % s)
+def test_forward_half_floats_at_odd_widths(g, shape):
+    """The last half of a window shares its 32-bit word with a pad channel: every mode of test_forward, without and with the residual."""
+    assert shape[0] == 2 and shape[3] % 2 == 1
+    test_forward(g, shape, True)
 
 
 @pytest.mark.parametrize("shape", GC.SHAPES, ids=lambda s: "n%d_%dx%d_c%d" % s)
