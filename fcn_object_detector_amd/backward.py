@@ -14,8 +14,8 @@ from typing import Dict, List, Optional, Tuple
 from . import lib as L
 from . import storage as S
 from .engine import Blob, DevView, DeviceBuffer, Op, _r4, conv_desc, dropout_layer_salt, dwconv_desc, rconv_desc, tconv_desc
-from .netspec import (DATA_TYPES, NEURON_TYPES, Layer, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad, layer_dilation,
-                      neuron_params, scale_gate_form)
+from .netspec import (DATA_TYPES, NEURON_TYPES, SHUFFLE_TYPES, Layer, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad, layer_dilation,
+                      neuron_params, scale_gate_form, shuffle_group)
 
 
 @dataclass
@@ -84,6 +84,8 @@ class BackwardPlanner:
         self.activations = {"PReLU": self._act, "TanH": self._act, "Bias": self._act}
         # ... and those of csrc/neuron.hip (no learned blob), which _one_bottom consults after the two tables above
         self.neurons = {t: self._neuron for t in NEURON_TYPES}
+        # ... and the channel shuffle of csrc/shuffle.hip, a fifth table that _one_bottom consults last
+        self.shuffles = {t: self._shuffle for t in SHUFFLE_TYPES}
 
     def run(self) -> None:
         self._find_concat_relu()
@@ -820,7 +822,7 @@ class BackwardPlanner:
         # an in-place layer (bottom == top: drop6 / drop7 of the published FCN nets, an unfused in-place Sigmoid, ReLU or LRN) rewrites dY
         # as dX - there is nothing to accumulate into, whatever the layer type; `+=` into its own dY would be dY + f(dY)
         acc = 1 if gbot is not None and self.state(gbot) == "full" and gbot is not gtop else 0
-        emit = self.one_bottom.get(l.type) or act or self.neurons.get(l.type)
+        emit = self.one_bottom.get(l.type) or act or self.neurons.get(l.type) or self.shuffles.get(l.type)
         if emit is None:
             raise NotImplementedError("backward of layer type %s (%s)" % (l.type, l.name))
         emit(l, gtop, gbot, acc)
@@ -890,6 +892,18 @@ class BackwardPlanner:
         self.ops.append(Op("neuron_bwd", l.name, lambda st: L.check(lib.fcn_neuron_bwd_f32(
             gtop.buf.ptr, ref[0], gbot.buf.ptr, pix, c, gtop.cstride, gtop.coffset, ref[1], ref[2], gbot.cstride, gbot.coffset, mode, a, b,
             acc, st)), 1.0 * pix * c, 4.0 * (3 + acc) * pix * c))
+        self.mark(gbot)
+
+    def _shuffle(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:
+        """ShuffleChannel (csrc/shuffle.hip, engine._fwd_shuffle): the gradient is the inverse permutation, the forward launch with group
+        C / g: dX[i * (C / g) + j] (+)= dY[j * g + i].  No workspace, no kept input."""
+        lib, xb = self.lib, self.B[l.bottoms[0]]
+        pix, c = xb.pixels, xb.channels
+        inv = c // shuffle_group(l, [xb.shape])
+        self._chan_group_aligned(l, gtop, gbot)
+        self.ops.append(Op("shuffle_bwd", l.name, lambda st: L.check(lib.fcn_shuffle_channel_f32(
+            gtop.buf.ptr, gbot.buf.ptr, pix, c, inv, gtop.cstride, gtop.coffset, gbot.cstride, gbot.coffset, acc, st)),
+            0.0, 4.0 * (2 + acc) * pix * c))
         self.mark(gbot)
 
     def _pooling(self, l: Layer, gtop: Blob, gbot: Blob, acc: int) -> None:

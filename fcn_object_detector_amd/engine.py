@@ -32,8 +32,8 @@ from . import region as RG
 from . import ssd as SSD
 from . import storage as S
 from . import tune as T
-from .netspec import (ACT_TYPES, NEURON_TYPES, Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
-                      layer_dilation, layer_geometry, neuron_params, scale_gate_form)
+from .netspec import (ACT_TYPES, NEURON_TYPES, SHUFFLE_TYPES, Layer, NetSpec, argmax_form, bn_global_stats, crop_window, interp_size, is_rectangular, is_scale_gate, kernel_stride_pad,
+                      layer_dilation, layer_geometry, neuron_params, scale_gate_form, shuffle_group)
 from .storage import _r4, _ra, ip_pack_bank, ip_unpack_bank      # noqa: F401  (the bank helpers stay importable from here)
 
 F32 = np.float32
@@ -1571,12 +1571,14 @@ class Engine:
         B, t = self.blobs, l.type
         halves = [b for b in list(l.bottoms) + list(l.tops) if b in B and B[b].esize == 2]
         acts = ACT_TYPES if self.spec.activations else ()      # (csrc/act.hip: only a NetSpec built with activations=True has them)
-        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample") + acts + NEURON_TYPES:
+        if halves and t not in ("Pooling", "LRN", "Eltwise", "Softmax", "Deconvolution", "Dropout", "Concat", "Slice", "Crop", "ReLU", "Interp", "Upsample") + acts + NEURON_TYPES + SHUFFLE_TYPES:
             raise NotImplementedError("f16 engine: layer type %s (%s) has no half-float kernel" % (t, l.name))
         if t in acts:
             return self._fwd_act(l, halves)
         if t in NEURON_TYPES:
             return self._fwd_neuron(l, halves)
+        if t in SHUFFLE_TYPES:
+            return self._fwd_shuffle(l, halves)
         emit = {"Pooling": self._fwd_pooling, "LRN": self._fwd_lrn, "ReLU": self._fwd_pointwise, "Sigmoid": self._fwd_pointwise,
                 "Power": self._fwd_pointwise, "Dropout": self._fwd_dropout, "L1Loss": self._fwd_loss, "EuclideanLoss": self._fwd_loss,
                 "Softmax": self._fwd_softmax, "SoftmaxWithLoss": self._fwd_softmax_loss, "Accuracy": self._fwd_accuracy,
@@ -1801,6 +1803,19 @@ class Engine:
         return [Op("neuron", l.name, lambda st: L.check(lib.fcn_neuron_fwd_f32(
             xb.buf.ptr, yb.buf.ptr, kp, pix, c, xb.cstride, xb.coffset, yb.cstride, yb.coffset, _r4(c), mode, a, b, st)),
             1.0 * pix * c, (8.0 + (4.0 if kp else 0.0)) * pix * c)]
+
+    def _fwd_shuffle(self, l: Layer, halves: List[str]) -> List[Op]:
+        """ShuffleChannel as one launch of csrc/shuffle.hip, y[j * g + i] = x[i * (C / g) + j] at every pixel, on whole buffers and on
+        16-byte-aligned channel windows alike, floats or halves.  The top owns its buffer (storage.plan_blobs never makes it a window of
+        the bottom), so the two windows never overlap; nothing is kept for the backward pass."""
+        lib = L.load()
+        xb, yb, pix, c = self._chan_group_views(l)
+        g = shuffle_group(l, [xb.shape])
+        if xb.esize == 2:
+            return [Op("shuffle", l.name, lambda st: L.check(lib.fcn_shuffle_channel_f16(
+                xb.buf.ptr, yb.buf.ptr, pix, c, g, xb.cstride, xb.coffset, yb.cstride, yb.coffset, st)), 0.0, 4.0 * pix * c)]
+        return [Op("shuffle", l.name, lambda st: L.check(lib.fcn_shuffle_channel_f32(
+            xb.buf.ptr, yb.buf.ptr, pix, c, g, xb.cstride, xb.coffset, yb.cstride, yb.coffset, 0, st)), 0.0, 8.0 * pix * c)]
 
     def _fwd_dropout(self, l: Layer, halves: List[str]) -> List[Op]:
         lib = L.load()

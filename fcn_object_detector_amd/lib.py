@@ -393,6 +393,8 @@ PROTOTYPES = {
     "fcn_neuron_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_f, _f, _vp]),
     "fcn_neuron_fwd_f16": (_i, [_vp, _vp] + [_i] * 7 + [_f, _f, _vp]),
     "fcn_neuron_bwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_f, _f, _i, _vp]),
+    "fcn_shuffle_channel_f32": (_i, [_vp, _vp] + [_i] * 8 + [_vp]),
+    "fcn_shuffle_channel_f16": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
     "fcn_ssd_gather_f32": (_i, [C.POINTER(SsdHead), _i, _i, _vp, _i, _i, _vp]),
     "fcn_normalize_fwd_f32": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp]),
     "fcn_detection_output_workspace_bytes": (_sz, [C.POINTER(DetOutParams)]),

@@ -1220,6 +1220,190 @@ def efficientnet_b0(phase: str = "DEPLOY", batch: int = 1, classes: int = 1000, 
 
 
 # ----------------------------------------------------------------------
+# ShuffleNet v1 (Zhang et al.: "ShuffleNet: An Extremely Efficient Convolutional Neural Network for Mobile Devices") and v2 (Ma et al.:
+# "ShuffleNet V2: Practical Guidelines for Efficient CNN Architecture Design"): grouped 1x1 convolutions, depthwise 3x3 convolutions and
+# the ports' ShuffleChannel layer (csrc/shuffle.hip).  A channel window has to start on 16 bytes (4 floats) here, so only the widths of
+# the papers' tables whose groups and branches are multiples of 4 channels are written; the others are refused with the channel count.
+# ----------------------------------------------------------------------
+
+SHUFFLENET_V1 = {1: 144, 2: 200, 3: 240, 4: 272, 8: 384}      # groups -> width of stage 2 (stages 3 and 4 double it), the paper's table
+SHUFFLENET_V2 = {0.5: (48, 1024), 1.0: (116, 1024), 1.5: (176, 1024), 2.0: (244, 2048)}      # width -> (stage 2, conv5)
+SHUFFLENET_REPEATS = (4, 8, 4)                                   # units of stages 2, 3 and 4, the first of each at stride 2
+DEPTHWISE_TYPES = ("Convolution", "ConvolutionDepthwise")
+
+
+def _shf_conv(w: _Writer, name: str, bottom: str, cin: int, num_output: int, k: int, stride: int, phase: str, relu: bool, group: int = 1,
+              depthwise_type: Optional[str] = None) -> str:
+    """Convolution `<name>` (bias_term: false, pad k // 2) with BatchNorm `<name>_bn` and Scale `<name>_scale` (bias_term: true) in place
+    on its top and, with `relu`, the ReLU `<name>_relu`; returns the top.  group > 1: a grouped convolution, whose groups must be
+    whole 16-byte segments of 4 channels on both sides.  depthwise_type: the layer is depthwise (num_output == cin), written as
+    type "Convolution" with group: C engine: CAFFE or as type "ConvolutionDepthwise" without a group."""
+    geo = "    num_output: %d\n    bias_term: false\n    pad: %d\n    kernel_size: %d\n" % (num_output, k // 2, k)
+    type_ = "Convolution"
+    if depthwise_type is not None:
+        type_ = depthwise_type
+        if depthwise_type == "Convolution":
+            geo += "    group: %d\n    engine: CAFFE\n" % num_output
+    elif group > 1:
+        for what, c in (("input", cin), ("output", num_output)):
+            if c % group or (c // group) % 4:
+                raise ValueError("ShuffleNet: %s has %d %s channels in %d groups: %s channels per group are no whole 16-byte segments "
+                                 "(multiples of 4)" % (name, c, what, group, "%d" % (c // group) if c % group == 0 else "%d / %d" % (c, group)))
+        geo += "    group: %d\n" % group
+    geo += "    stride: %d\n" % stride
+    fan = k * k * (1 if depthwise_type is not None else num_output // group)
+    fill = "    weight_filler { type: \"gaussian\" std: %g }\n" % (2.0 / fan) ** 0.5
+    w.layer(name, type_, [bottom], [name], "  param { lr_mult: 1 decay_mult: 1 }\n  convolution_param {\n%s%s  }" % (geo, fill))
+    stats = "\n".join(["  param { lr_mult: 0 decay_mult: 0 }"] * 3) if phase != "DEPLOY" else "  batch_norm_param { use_global_stats: true }"
+    w.layer(name + "_bn", "BatchNorm", [name], [name], stats)
+    w.layer(name + "_scale", "Scale", [name], [name], "  scale_param { bias_term: true }")
+    if relu:
+        w.layer(name + "_relu", "ReLU", [name], [name])
+    return name
+
+
+def _shf_stem(w: _Writer, name: str, phase: str, batch: int, size: int, c1: int) -> Tuple[str, int]:
+    """Inputs, conv1 3x3 / 2 to c1 channels + BatchNorm, Scale, ReLU, pool1 MAX 3x3 / 2; returns the top and its edge."""
+    w.raw('name: "%s"' % name)
+    _inputs(w, phase, batch, ["data"], size, ("label", (batch, 1, 1, 1)))
+    _shf_conv(w, "conv1", "data", 3, c1, 3, 2, phase, True)
+    w.layer("pool1", "Pooling", ["conv1"], ["pool1"], "  pooling_param { pool: MAX kernel_size: 3 stride: 2 }")
+    h = (size + 2 - 3) // 2 + 1                   # convolution: rounded down
+    return "pool1", -(-(h - 3) // 2) + 1          # pooling: rounded up
+
+
+def _shf_tail(w: _Writer, phase: str, feat: str, classes: int) -> None:
+    """pool_ave (global AVE), the 1x1 convolution classifier fc1000 and prob (DEPLOY) / loss over an (N, 1, 1, 1) `label`, accuracy in TEST."""
+    w.layer("pool_ave", "Pooling", [feat], ["pool_ave"], "  pooling_param { pool: AVE global_pooling: true }")
+    w.layer("fc1000", "Convolution", ["pool_ave"], ["fc1000"], "  param { lr_mult: 1 decay_mult: 1 }\n  param { lr_mult: 2 decay_mult: 0 }\n"
+            "  convolution_param {\n    num_output: %d\n    kernel_size: 1\n    weight_filler { type: \"gaussian\" std: 0.01 }\n"
+            "    bias_filler { type: \"constant\" value: 0 }\n  }" % classes)
+    if phase == "DEPLOY":
+        w.layer("prob", "Softmax", ["fc1000"], ["prob"])
+    else:
+        if phase == "TEST":
+            w.layer("accuracy", "Accuracy", ["fc1000", "label"], ["accuracy"])
+        w.layer("loss", "SoftmaxWithLoss", ["fc1000", "label"], ["loss"])
+
+
+def _check_depthwise_type(depthwise_type: str) -> None:
+    if depthwise_type not in DEPTHWISE_TYPES:
+        raise ValueError("depthwise_type must be one of %s" % list(DEPTHWISE_TYPES))
+
+
+def shufflenet_v1(phase: str = "DEPLOY", groups: int = 3, batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224,
+                  fillers: bool = True, depthwise_type: str = "Convolution") -> str:
+    """ShuffleNet v1 1x: the structure of the paper (no published prototxt was at hand).  conv1 3x3 / 2 (24) + BatchNorm, Scale, ReLU,
+    pool1 MAX 3x3 / 2, stages 2 - 4 of 4, 8 and 4 units at the widths 240 / 480 / 960 (groups = 3), pool_ave (global AVE), the 1x1
+    classifier fc1000 and prob (DEPLOY), loss (SoftmaxWithLoss over an (N, 1, 1, 1) `label`; TRAIN and TEST) and accuracy (TEST).
+    Unit `resx<i>`, i = 1 .. 16: the grouped 1x1 `resx<i>_conv1` to a quarter of the unit's width (not grouped in resx1, whose input has
+    24 channels) + BatchNorm, Scale, ReLU; `shuffle<i>`, ShuffleChannel { group: groups }; the depthwise 3x3 `resx<i>_conv2` + BatchNorm,
+    Scale; the grouped 1x1 `resx<i>_conv3` + BatchNorm, Scale; then at stride 1 the Eltwise SUM `resx<i>_elewise` with the input, at
+    stride 2 - the first unit of a stage - the Concat `resx<i>_concat` of the AVE-pooled input `resx<i>_match_conv` and the branch, which
+    then has the unit's width less the input's; ReLU in place on either.
+    The two branches of a stride-2 unit must agree under Caffe's shape rules, where a convolution rounds down and a pooling up: beside
+    the depthwise `k3 s2 p1` the shortcut is AVE 3x3 / 2 with pad 0 on an even edge and with pad 1 on an odd one (Caffe's AVE pooling
+    divides by the window clipped to the padded blob, so with the pad the border means differ from the paper's).
+    Names: conv1, pool1, resx<i>_conv1 / _conv2 / _conv3, shuffle<i>, resx<i>_match_conv, resx<i>_concat, resx<i>_elewise, pool_ave and
+    fc1000 are those of the common Caffe port as far as remembered; `<conv>_bn`, `<conv>_scale`, the ReLUs `<blob>_relu` and prob are
+    this project's.  A caffemodel from elsewhere maps only where the names agree.
+    groups: only 3 (and 1, without grouped layers, at 144 / 288 / 576) keeps every group of every grouped convolution on whole 16-byte
+    segments; 2, 4 and 8 - groups of 25, 17 and 45 channels - are refused with that count.  width_div divides the stage widths, and above 1 conv1
+    becomes the largest multiple of 4 * groups at or below 24 / width_div (at least one such multiple): with groups = 3 only 1 and 5 divide
+    every group into multiples of 4, anything else is refused the same way.  In halves the net stops at its first grouped convolution, resx1_conv3 with
+    groups of 20 input channels: no whole segments of 8 halves.
+    depthwise_type: "Convolution" writes the depthwise layers with group: C engine: CAFFE (a NetSpec takes them with depthwise=True, as
+    caffe.Net and the solvers pass it), "ConvolutionDepthwise" as the ports' layer of that type."""
+    _check_phase(phase)
+    _check_depthwise_type(depthwise_type)
+    if groups not in SHUFFLENET_V1:
+        raise ValueError("groups must be one of %s" % sorted(SHUFFLENET_V1))
+    w = _Writer()
+    quantum = 4 * groups
+    c = 24 if width_div == 1 else max(24 // width_div // quantum, 1) * quantum
+    x, h = _shf_stem(w, "ShuffleNet-v1-g%d" % groups, phase, batch, size, c)
+    unit = 0
+    for stage, repeats in enumerate(SHUFFLENET_REPEATS):
+        width = max((SHUFFLENET_V1[groups] << stage) // width_div, 1)
+        for b in range(repeats):
+            unit += 1
+            tag, stride = "resx%d" % unit, 2 if b == 0 else 1
+            if width % 4:
+                raise ValueError("ShuffleNet v1: unit %s has %d channels: its bottleneck is no whole number of channels" % (tag, width))
+            mid, out = width // 4, width - c if stride == 2 else width
+            y = _shf_conv(w, tag + "_conv1", x, c, mid, 1, 1, phase, True, group=1 if unit == 1 else groups)
+            w.layer("shuffle%d" % unit, "ShuffleChannel", [y], ["shuffle%d" % unit], "  shuffle_channel_param { group: %d }" % groups)
+            y = _shf_conv(w, tag + "_conv2", "shuffle%d" % unit, mid, mid, 3, stride, phase, False, depthwise_type=depthwise_type)
+            y = _shf_conv(w, tag + "_conv3", y, mid, out, 1, 1, phase, False, group=groups)
+            if stride == 2:
+                w.layer(tag + "_match_conv", "Pooling", [x], [tag + "_match_conv"],
+                        "  pooling_param { pool: AVE kernel_size: 3 stride: 2%s }" % (" pad: 1" if h % 2 else ""))
+                w.layer(tag + "_concat", "Concat", [tag + "_match_conv", y], [tag + "_concat"])
+                x, h = tag + "_concat", (h + 2 - 3) // 2 + 1
+            else:
+                w.layer(tag + "_elewise", "Eltwise", [x, y], [tag + "_elewise"], "  eltwise_param { operation: SUM }")
+                x = tag + "_elewise"
+            w.layer(x + "_relu", "ReLU", [x], [x])
+            c = width
+    _shf_tail(w, phase, x, classes)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+def shufflenet_v2(phase: str = "DEPLOY", width: float = 0.5, batch: int = 1, classes: int = 1000, width_div: int = 1, size: int = 224,
+                  fillers: bool = True, depthwise_type: str = "Convolution") -> str:
+    """ShuffleNet v2 at 0.5x or 1.5x: the structure of the paper (no published prototxt was at hand).  conv1 3x3 / 2 (24) + BatchNorm,
+    Scale, ReLU, pool1 MAX 3x3 / 2, stages 2 - 4 of 4, 8 and 4 units at the widths 48 / 96 / 192 (0.5x) or 176 / 352 / 704 (1.5x), the 1x1
+    convolution conv5 to 1024 + BatchNorm, Scale, ReLU, and the ends of shufflenet_v1 (pool_ave, fc1000, prob / loss / accuracy).
+    Unit `stage<s>_<b>` at stride 1: the Slice `<unit>/slice` cuts the input in halves `<unit>/left` and `<unit>/right`; the right half
+    goes through the 1x1 `<unit>/conv1` + BatchNorm, Scale, ReLU, the depthwise 3x3 `<unit>/dw` + BatchNorm, Scale and the 1x1
+    `<unit>/conv2` + BatchNorm, Scale, ReLU, every one of half the unit's width; the Concat `<unit>/concat` of the left half and that
+    branch; `<unit>/shuffle`, ShuffleChannel { group: 2 }, the unit's top.  At stride 2 - the first unit of a stage - there is no Slice:
+    the left branch is the depthwise 3x3 / 2 `<unit>/left_dw` + BatchNorm, Scale and the 1x1 `<unit>/left_conv` + BatchNorm, Scale, ReLU
+    on the whole input, the right branch starts from the whole input too, and each has half the new width.  Both branches of such a
+    unit are `k3 s2 p1` convolutions, so they agree on every edge; no pooling is needed beside them.
+    Names: conv1, pool1, conv5, pool_ave and fc1000 are the common Caffe port's as far as remembered; every unit's names, `<conv>_bn`,
+    `<conv>_scale` and the ReLUs are this project's own.
+    width: a half of the unit's width is a channel window (the Slice tops), which must start on 16 bytes: 24 / 48 / 96 channels (0.5x) and
+    88 / 176 / 352 (1.5x) do, the 58 of 1.0x and the 122 of 2.0x do not, and those widths are refused with that count.  width_div divides
+    every width and is refused the same way where a half is no multiple of 4 any more (0.5x: 1, 2, 3 and 6).  In halves the net runs
+    where every half is a multiple of 8 (0.5x at width_div 1 and 3, 1.5x at 1): the Slice tops are then windows on 16 bytes of halves.
+    depthwise_type: as in shufflenet_v1."""
+    _check_phase(phase)
+    _check_depthwise_type(depthwise_type)
+    if width not in SHUFFLENET_V2:
+        raise ValueError("width must be one of %s" % sorted(SHUFFLENET_V2))
+    wd = lambda c: max(c // width_div, 1)
+    w = _Writer()
+    stage2, last = SHUFFLENET_V2[width]
+    x, _h = _shf_stem(w, "ShuffleNet-v2-%gx" % width, phase, batch, size, wd(24))
+    c = wd(24)
+    for stage, repeats in enumerate(SHUFFLENET_REPEATS, 2):
+        full = wd(stage2 << (stage - 2))
+        half = full // 2
+        if full % 2 or half % 4:
+            raise ValueError("ShuffleNet v2 %gx: the units of stage %d have %d channels, branches of %s: a branch is a channel window and "
+                             "must be whole 16-byte segments (a multiple of 4 channels)" % (width, stage, full, "%d" % half if full % 2 == 0 else "%d / 2" % full))
+        for b in range(repeats):
+            tag = "stage%d_%d" % (stage, b + 1)
+            if b == 0:
+                y = _shf_conv(w, tag + "/left_dw", x, c, c, 3, 2, phase, False, depthwise_type=depthwise_type)
+                left = _shf_conv(w, tag + "/left_conv", y, c, half, 1, 1, phase, True)
+                right, cr = x, c
+            else:
+                left, right, cr = tag + "/left", tag + "/right", half
+                w.layer(tag + "/slice", "Slice", [x], [left, right], "  slice_param { axis: 1 slice_point: %d }" % half)
+            y = _shf_conv(w, tag + "/conv1", right, cr, half, 1, 1, phase, True)
+            y = _shf_conv(w, tag + "/dw", y, half, half, 3, 2 if b == 0 else 1, phase, False, depthwise_type=depthwise_type)
+            y = _shf_conv(w, tag + "/conv2", y, half, half, 1, 1, phase, True)
+            w.layer(tag + "/concat", "Concat", [left, y], [tag + "/concat"])
+            w.layer(tag + "/shuffle", "ShuffleChannel", [tag + "/concat"], [tag + "/shuffle"], "  shuffle_channel_param { group: 2 }")
+            x, c = tag + "/shuffle", full
+    x = _shf_conv(w, "conv5", x, c, wd(last), 1, 1, phase, True)
+    _shf_tail(w, phase, x, classes)
+    return w.text() if fillers else _strip_fillers(w.text())
+
+
+# ----------------------------------------------------------------------
 # SegNet and SegNet-Basic (Badrinarayanan, Kendall, Cipolla: "SegNet: A Deep Convolutional Encoder-Decoder Architecture for Image
 # Segmentation"): encoders whose MAX poolings keep their indices (a second top, the mask) and decoders that unpool by them (the SegNet
 # fork's Upsample layer).  The fork's `BN` layer is written as BatchNorm + Scale, its class-weighted loss as a plain SoftmaxWithLoss.

@@ -38,6 +38,10 @@ class Layer:
         self.axpy: Optional[str] = None      # the Axpy layer of the file this layer stands for (NetSpec scale_gate=True), else None
         if self.python_alias:
             self.type = "Proposal"
+        # the ShuffleNet ports (and several MobileNet ones) spell the depthwise layer ConvolutionDepthwise: the same layer, the same
+        # convolution_param
+        if self.type == "ConvolutionDepthwise":
+            self.type = "DepthwiseConvolution"
 
     def sub(self, key: str) -> proto.Msg:
         m = self.msg.get(key)
@@ -402,6 +406,26 @@ def neuron_params(l: "Layer") -> Tuple[int, float, float]:
     return NEURON_MODES[t], a, b
 
 
+# the channel shuffle of csrc/shuffle.hip (the ShuffleNet ports' layer): no learned blob, no opt-in keyword - every NetSpec takes it
+SHUFFLE_TYPES = ("ShuffleChannel",)
+
+
+def shuffle_group(l: "Layer", bots: Sequence[Shape]) -> int:
+    """shuffle_channel_param.group (default 1) of a ShuffleChannel over its bottom shapes: y[j * g + i] = x[i * (C / g) + j].  Refused by
+    layer name, as Caffe's own checks do: a second bottom or top, in place, a blob that is neither 4-d nor 2-d, group < 1 and a channel
+    count that group does not divide."""
+    if len(l.bottoms) != 1 or len(l.tops) != 1 or len(bots) != 1:
+        raise ValueError("layer %s: %s takes one bottom and has one top, got %d and %d" % (l.name, l.type, len(l.bottoms), len(l.tops)))
+    if l.tops[0] == l.bottoms[0]:
+        raise ValueError("layer %s: %s does not allow in-place computation (a permutation of the channels)" % (l.name, l.type))
+    if len(bots[0]) not in (2, 4):
+        raise ValueError("layer %s: %s takes one 4-d or 2-d bottom, got %s" % (l.name, l.type, list(bots)))
+    g, c = int(l.sub("shuffle_channel_param").get("group", 1)), bots[0][1]
+    if g < 1 or c % g:
+        raise ValueError("layer %s: %s with group %d over %d channels (group must be at least 1 and divide the channels)" % (l.name, l.type, g, c))
+    return g
+
+
 DATA_TYPES = ("Data", "Python", "Input", "DummyData", "MemoryData", "ImageData", "HDF5Data")
 LOSS_TYPES = ("L1Loss", "EuclideanLoss", "SoftmaxWithLoss", "SigmoidCrossEntropyLoss")
 # the opt-in keywords of NetSpec (each off in a bare NetSpec; NetSpec.public turns them on): a new layer family adds its keyword here
@@ -669,6 +693,9 @@ class NetSpec:
                 neuron_params(l)      # (its refusals, by layer name)
                 if len(bots) != 1 or len(bots[0]) not in (2, 4):
                     raise ValueError("layer %s: %s takes one 4-d or 2-d bottom, got %s" % (l.name, t, list(bots)))
+                shapes[l.tops[0]] = bots[0]
+            elif t in SHUFFLE_TYPES:
+                shuffle_group(l, bots)      # (its refusals, by layer name)
                 shapes[l.tops[0]] = bots[0]
             elif t in ("PReLU", "Bias"):
                 if not self.activations:

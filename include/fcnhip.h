@@ -1078,6 +1078,24 @@ int  fcn_neuron_fwd_f16(const void* x, void* y, int pixels, int C, int x_cstride
 int  fcn_neuron_bwd_f32(const float* dy, const float* ref, float* dx, int pixels, int C, int dy_cstride, int dy_coffset, int ref_cstride,
                         int ref_coffset, int dx_cstride, int dx_coffset, int mode, float a, float b, int accumulate, fcn_stream_t s);
 
+/* ---- Channel shuffle (the ShuffleChannel layer of the ShuffleNet ports) on NHWC views (csrc/shuffle.hip).  With n = C / group, for every
+ *      pixel y[j * group + i] (+)= x[i * n + j], 0 <= i < group, 0 <= j < n: values are moved, never computed (accumulate's add apart).
+ *      The inverse permutation is the same call with group C / group - the layer's data gradient.  group 1 and group C are the identity.
+ *      Views and groups follow fcn_act_*: a lane owns one 16-byte channel group of a pixel of y (4 floats / 8 halves), gathers its source
+ *      channels from the same pixel of x one by one and stores the group whole; a last, partial group is stored in pieces.  Only channels
+ *      x_coffset .. x_coffset + C - 1 of x are read and only channels y_coffset .. y_coffset + C - 1 of y are written.
+ *      Contract of both: null operands, non-positive extents, group < 1 or C % group != 0, a slice outside its pixel FCN_E_ARG; a stride or
+ *      offset that is no multiple of the 16-byte group, x / y off 16 bytes FCN_E_ALIGN; windows of x and y whose byte ranges (first to last
+ *      element) intersect FCN_E_ARG - the layer cannot run in place.  Every check precedes the first HIP call; both launches are
+ *      capturable.  No LDS, no atomics, one writer per element: the same call gives the same bits. ---- */
+/* accumulate 1 adds into y (a gradient view that already holds one); 0 overwrites. */
+int  fcn_shuffle_channel_f32(const float* x, float* y, int pixels, int C, int group, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                             int accumulate, fcn_stream_t s);
+/* inference twin: x and y hold halves (groups of 8); no accumulate.  A last, partial group is stored as 32-bit pairs and, where C is odd,
+ * one half: the pad half that shares its word is not written. */
+int  fcn_shuffle_channel_f16(const void* x, void* y, int pixels, int C, int group, int x_cstride, int x_coffset, int y_cstride, int y_coffset,
+                             fcn_stream_t s);
+
 /* ---- SSD detection head (Caffe-SSD's Permute + Flatten + Concat, Normalize and DetectionOutput; csrc/ssd.hip).  Float32, inference.
  *      Common contract: every output element has exactly one writer lane (no float atomics anywhere), so a second launch on the same
  *      inputs gives the same bytes; nothing outside the named outputs and the workspace is written; every refusal is made on the host
